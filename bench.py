@@ -8,17 +8,23 @@ resident in HBM (reference timed loop: homomorphic_eval.py:350-361, `elapsed / t
 shards by image across ranks (one process per GPU); there is no collective on the data path -- the only
 exchange is one RCCL all_gather of the decrypted-side logits at the end.
 
-Usage:  python bench.py --gpus N --steps K --warmup W [--batch-per-gpu B] [--budget-s S]
+Usage:  python bench.py --gpus N --steps K --warmup W [--batch-per-gpu B] [--budget-s S] [--dump-outputs DIR]
   * N > 1 without WORLD_SIZE in the environment: bench.py starts its own N ranks (child processes of
     `python -m torch.distributed.run`, before anything here touches a GPU) and exits with their code;
     under torch.distributed.run it is one of the ranks.
-  * One encrypted image takes seconds, so K and W are CAPPED by a wall-clock budget (--budget-s, default 450 s from
-    process start, env DCTFHE_BENCH_BUDGET_S): after the first pass the loop keeps as many of the requested passes
-    as fit; the JSON reports the steps / warm-up passes actually run (and `requested`).  When not even a second pass
-    fits (multi-image configs whose pass takes minutes), the first pass -- bracketed like a step -- is the timed step.
+  * K timed steps after W warm-up passes; `ms_per_step` is the wall time of one timed step.  One encrypted image takes
+    seconds, so K and W can be CAPPED by a wall-clock budget from process start (--budget-s S, off by default): after the
+    first pass the loop keeps as many of the requested passes as fit; the JSON reports the steps / warm-up passes actually
+    run (and `requested`).  When not even a second pass fits (multi-image configs whose pass takes minutes), the first
+    pass -- bracketed like a step -- is the timed step.
+  * The inputs are the same from run to run for the same arguments: seeded images, a fixed key seed and fixed per-rank
+    encryption nonces.  --dump-outputs DIR writes what the last timed step computed, as a caller of the encrypted forward
+    receives it (dctfhe.quantized_module: forward_quantized / forward, then the clear classifier), to DIR/<name>.npy:
+    features_quantized (float64, integer-valued), features (float64) and logits (float32), in global image order.
 Prints ONE JSON line on rank 0.
 """
 import argparse
+import hashlib
 import json
 import math
 import os
@@ -46,6 +52,26 @@ VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 4          # wave-instructions per second: 2
 N_CU, SPEC_CLOCK_HZ = 256, 2.4e9
 L1_DELIVERY_BYTES_PER_CLK_CU = 64.0            # a CU's vector L1 returns one 64-byte half line per clock to the registers (a wave's 16 B/lane load: 16 clocks);
                                                # measured here: 60 B/clk in the key phases of the three-level kernel (profiles/r03_exp_phase_clock.log)
+
+
+KEY_SEED = hashlib.sha256(b"dctfhe bench key seed").digest()       # benchmark keys protect synthetic data: fixed for reproducible inputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """arrays: name -> [images, ...] float32 / float64 of the last timed step, written as out_dir/<name>.npy.  Above
+    DUMP_LIMIT_BYTES in all, the same seeded sample of images (sorted, so still in image order) is kept in every array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = min(a.shape[0] for a in arrays.values())
+    per_image = sum(a.nbytes // max(a.shape[0], 1) for a in arrays.values())
+    keep = None
+    if per_image * n > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(seed).choice(n, max(1, DUMP_LIMIT_BYTES // per_image), replace=False))
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a if keep is None else a[keep])
+    return {"dir": out_dir, "arrays": sorted(arrays), "images": int(n if keep is None else keep.size), "sampled": keep is not None}
 
 
 def _dct_batch(n, seed):
@@ -211,8 +237,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch-per-gpu", type=int, default=int(os.environ.get("DCTFHE_BENCH_BATCH", "1")),
                     help="encrypted images per GPU and step (default 1 = the reference's execute-mode case, run_homomorphic_eval.sh:22-23)")
-    ap.add_argument("--budget-s", type=float, default=float(os.environ.get("DCTFHE_BENCH_BUDGET_S", "450")),
-                    help="wall-clock budget from process start; steps/warm-up are capped to fit (0 = no cap)")
+    ap.add_argument("--budget-s", type=float, default=0.0,
+                    help="wall-clock budget from process start; steps/warm-up are capped to fit (default 0 = no cap: exactly --steps timed steps)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--tier-policy", default="exact", choices=["exact", "p_error"],
                     help="exact (the metric): outputs equal the integer circuit; p_error: the reference-style stochastic regime, p_error=0.01 per look-up (speed only)")
@@ -221,6 +247,8 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N > 1 rehearsal on a single-GPU box: every rank evaluates on GPU 0, collectives over gloo (same code path "
                          "otherwise; the numbers mean nothing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (features_quantized, features, logits)")
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher self-test (CPU, gloo): ranks shard a fake batch, all_gather it and rank 0 prints a JSON line; no GPU work")
     args = ap.parse_args()
@@ -291,10 +319,11 @@ def main():
 
     state["phase"] = "keygen"
     t0 = time.time()
-    # one 256-bit key seed for the whole job: rank 0 draws it from the OS and broadcasts it; every rank regenerates the same
-    # client + evaluation keys from it on its own GPU (no key traffic) and encrypts from its own counter range
-    qm.fhe_circuit.keygen(seed=broadcast_seed(os.urandom(32), world, cdev))
-    # (every rank's client handle draws its own 128-bit encryption nonce from the OS: ranks sharing the seed never share masks or noise)
+    # one 256-bit key seed for the whole job, fixed so that the encrypted inputs are the same from run to run: rank 0 broadcasts it
+    # and every rank regenerates the same client + evaluation keys from it on its own GPU (no key traffic)
+    qm.fhe_circuit.keygen(seed=broadcast_seed(KEY_SEED, world, cdev))
+    # every rank encrypts under its own fixed 128-bit nonce: ranks sharing the seed never share masks or noise
+    qm._keys.set_encrypt_nonce(hashlib.sha256(b"dctfhe bench encryption nonce %d" % rank).digest()[:16])
     keygen_s = time.time() - t0
     stats = qm.statistics()
     # seeded classifier with logits centred on the calibration features (clear circuit): labels differ between images
@@ -415,6 +444,15 @@ def main():
         exact = all_true(exact, world, cdev)
     else:
         all_logits = logits
+    dumped = None
+    if args.dump_outputs:
+        all_q = torch.from_numpy(feats_q.astype(np.float64))
+        if world > 1:
+            all_q = gather_in_image_order(all_q.to(cdev), world).cpu()
+        if rank == 0:
+            all_q = all_q.numpy()
+            dumped = dump_outputs(args.dump_outputs, {"features_quantized": all_q, "features": qm.dequantize_output(all_q),
+                                                      "logits": all_logits.numpy().astype(np.float32)})
 
     if rank == 0:
         steps = max(steps_done, 1)
@@ -470,7 +508,7 @@ def main():
                        "pbs_per_image": int(sum(stats.pbs_count)), "bit_steps_per_image": int(stats.bit_steps),
                        "table_lookups_per_image": int(stats.lut_sites), "conv_macs_per_image": int(stats.conv_macs),
                        "max_bit_width": int(stats.max_bit_width), "compile_s": compile_s, "keygen_s": keygen_s,
-                       "key_seed": "32 bytes of os.urandom on rank 0, broadcast; each rank's handle draws its own 128-bit encryption nonce",
+                       "key_seed": "fixed 32-byte seed, broadcast; each rank encrypts under its own fixed 128-bit nonce",
                        "input_upload_s": upload_s, "input_bytes_per_gpu": int(input_bytes), "output_bytes_per_gpu": int(output_bytes),
                        "wire_format": f"compact rows: {in_dim} + 1 words per input ciphertext, {out_dim} + 1 per output (D = {ps.D})",
                        "images_per_s_pcie_inclusive": images / (elapsed + upload_s * steps),
@@ -529,6 +567,8 @@ def main():
             res["cpu_baseline"] = cpu_box["res"]
             if "value" in res["cpu_baseline"]:
                 res["cpu_baseline"]["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         res["reference_published_s_per_image"] = 565.0      # README.md:84, 96-core CPU; an anchor, not a vs_baseline (other hardware)
         print(json.dumps(res), flush=True)
     qm.close()

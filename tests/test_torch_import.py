@@ -6,10 +6,9 @@ tests/golden/torch_import_golden.npz (tools/make_goldens.py, build container) ho
 a seeded input and the reference's float forward output.  Here a twin written for this test (same attribute names, nothing
 copied) must carry the same state-dict naming, and `from_torch_module(twin)` evaluated in float must reproduce the reference
 output: stem, block order, shortcut type, stride placement, BatchNorm statistics, floor-mode pooling.
-Where /root/reference exists (build container only) the reference's own classes are walked unchanged as well."""
-import importlib
+tests/golden/reference_import_golden.npz holds what the boundary made of the reference's own classes, walked unchanged."""
+import hashlib
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ import torch
 import torch.nn as nn
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "torch_import_golden.npz"))
-REF = "/root/reference/dct-cryptonets"
 
 
 class TwinBlock(nn.Module):
@@ -99,35 +97,40 @@ def test_unsupported_trunks_are_refused():
         from_torch_module(nn.Sequential(nn.Conv2d(3, 8, 3, bias=False), nn.BatchNorm2d(8), nn.Sigmoid(), nn.AvgPool2d(2)))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists in the build container only")
+def describe(m):
+    """every array and geometry field of an imported dctfhe.models.ResNetQ as "<dtype>;<shape>;<sha256>", keyed by its path
+    (the layout of tests/golden/reference_import_golden.npz, tools/make_goldens.py:flatten_description)"""
+    out = {"relu1": np.array(m.relu1), "avgpool_kernel": np.array(m.avgpool_kernel), "final_feat_dim": np.array(m.final_feat_dim),
+           "n_blocks": np.array(len(m.blocks))}
+    def conv(tag, c):
+        out[tag + ".weight"], out[tag + ".stride"], out[tag + ".pad"] = c.weight, np.array(c.stride), np.array(c.pad)
+    def bn(tag, b):
+        for f in ("gamma", "beta", "mean", "var", "eps"):
+            out[f"{tag}.{f}"] = np.asarray(getattr(b, f), np.float64)
+    conv("conv1", m.conv1)
+    bn("bn1", m.bn1)
+    for i, b in enumerate(m.blocks):
+        conv(f"blocks.{i}.C1", b.C1), bn(f"blocks.{i}.BN1", b.BN1), conv(f"blocks.{i}.C2", b.C2), bn(f"blocks.{i}.BN2", b.BN2)
+        out[f"blocks.{i}.has_shortcut"] = np.array(b.shortcut is not None)
+        if b.shortcut is not None:
+            conv(f"blocks.{i}.shortcut", b.shortcut), bn(f"blocks.{i}.BNshortcut", b.BNshortcut)
+    return {k: "%s;%s;%s" % (v.dtype, v.shape, hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()) for k, v in out.items()}
+
+
 def test_reference_classes_import_unchanged():
-    """the reference's own `ResNet20(24,16)` object (models/backbone.py:291-302) through the boundary, bit-identical to the twin"""
-    from unittest.mock import MagicMock
+    """the reference's own `ResNet20(24,16)` object (models/backbone.py:291-302) through the boundary, bit-identical to the twin:
+    tests/golden/reference_import_golden.npz holds what from_torch_module / compile_torch_model made of the reference object under
+    the same seeded weights (tools/make_goldens.py)"""
     from dctfhe.quantized_module import compile_torch_model
     from dctfhe.synthetic import synthetic_dct_batch
     from dctfhe.torch_import import from_torch_module, seed_parameters
-    sys.dont_write_bytecode = True
-    added = []
-    for name in ("brevitas", "brevitas.nn", "brevitas.quant"):
-        if name not in sys.modules:
-            sys.modules[name] = MagicMock()
-            added.append(name)
-    sys.path.insert(0, REF)
-    try:
-        bb = importlib.import_module("models.backbone")
-        ref = seed_parameters(bb.ResNet20(in_channels=24, img_size=16), 11).eval()
-        twin = seed_parameters(TWINS["r20_24_16"](), 11).eval()
-        a, b = from_torch_module(ref), from_torch_module(twin)
-        assert np.array_equal(a.conv1.weight, b.conv1.weight) and a.relu1 == b.relu1 and a.avgpool_kernel == b.avgpool_kernel
-        for x, y in zip(a.blocks, b.blocks):
-            assert np.array_equal(x.C2.weight, y.C2.weight) and np.array_equal(x.BN2.var, y.BN2.var) and (x.shortcut is None) == (y.shortcut is None)
-        calib = synthetic_dct_batch(16, seed=7)
-        qa = compile_torch_model(ref, torch.from_numpy(calib), n_bits=5, rounding_threshold_bits=6, p_error=0.01, bit_width=4)
-        qb = compile_torch_model(twin, torch.from_numpy(calib), n_bits=5, rounding_threshold_bits=6, p_error=0.01, bit_width=4)
-        assert qa.compiled.blob == qb.compiled.blob
-    finally:
-        sys.path.remove(REF)
-        for name in added:
-            sys.modules.pop(name, None)
-        for name in [n for n in sys.modules if n == "models" or n.startswith("models.")]:
-            sys.modules.pop(name, None)
+    R = np.load(os.path.join(os.path.dirname(__file__), "golden", "reference_import_golden.npz"))
+    want = {k: str(R[k]) for k in R.files if not k.startswith("blob_")}
+    twin = seed_parameters(TWINS["r20_24_16"](), 11).eval()
+    got = describe(from_torch_module(twin))
+    assert sorted(got) == sorted(want)
+    assert [k for k in want if got[k] != want[k]] == []
+    calib = synthetic_dct_batch(16, seed=7)
+    qb = compile_torch_model(twin, torch.from_numpy(calib), n_bits=5, rounding_threshold_bits=6, p_error=0.01, bit_width=4)
+    assert len(qb.compiled.blob) == int(R["blob_len"])
+    assert hashlib.sha256(qb.compiled.blob).hexdigest() == str(R["blob_sha256"])

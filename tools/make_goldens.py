@@ -11,6 +11,8 @@ that would really call one of them is NOT used as an oracle.  What is captured:
   - the float twin models.backbone.ResNet20/ResNet18: conv output shapes, parameter counts
   - the same twin under seeded weights (dctfhe.torch_import.seed_parameters): state-dict key names/shapes and the float
     forward output on a seeded input
+  - the seeded ResNet20(24,16) walked by dctfhe.torch_import.from_torch_module: the imported description and a digest of
+    the circuit compile_torch_model makes of it
 Outputs are data only (inputs + expected outputs).
 """
 import importlib
@@ -115,7 +117,54 @@ def main():
         ti[f"{tag}_shapes"] = np.array([";".join(map(str, v.shape)) for v in sd.values()])
         ti[f"{tag}_x"], ti[f"{tag}_y"] = x, y.numpy()
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "torch_import_golden.npz"), **ti)
+    reference_import_golden(bb)
     print("goldens written")
+
+
+def flatten_description(m):
+    """every array and geometry field of a dctfhe.models.ResNetQ, keyed by its path, as "<dtype>;<shape>;<sha256 of the bytes>"
+    (the same walk as tests/test_torch_import.py::describe)"""
+    import hashlib
+    out = {"relu1": np.array(m.relu1), "avgpool_kernel": np.array(m.avgpool_kernel), "final_feat_dim": np.array(m.final_feat_dim),
+           "n_blocks": np.array(len(m.blocks))}
+    def conv(tag, c):
+        out[tag + ".weight"], out[tag + ".stride"], out[tag + ".pad"] = c.weight, np.array(c.stride), np.array(c.pad)
+    def bn(tag, b):
+        for f in ("gamma", "beta", "mean", "var", "eps"):
+            out[f"{tag}.{f}"] = np.asarray(getattr(b, f), np.float64)
+    conv("conv1", m.conv1)
+    bn("bn1", m.bn1)
+    for i, b in enumerate(m.blocks):
+        conv(f"blocks.{i}.C1", b.C1), bn(f"blocks.{i}.BN1", b.BN1), conv(f"blocks.{i}.C2", b.C2), bn(f"blocks.{i}.BN2", b.BN2)
+        out[f"blocks.{i}.has_shortcut"] = np.array(b.shortcut is not None)
+        if b.shortcut is not None:
+            conv(f"blocks.{i}.shortcut", b.shortcut), bn(f"blocks.{i}.BNshortcut", b.BNshortcut)
+    return {k: np.array("%s;%s;%s" % (v.dtype, v.shape, hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()))
+            for k, v in out.items()}
+
+
+def reference_import_golden(bb=None):
+    """the reference's own ResNet20(24,16) object under seeded weights, walked by dctfhe.torch_import.from_torch_module, and the
+    circuit compile_torch_model makes of it (tests/test_torch_import.py::test_reference_classes_import_unchanged)"""
+    import hashlib
+    import torch
+    if bb is None:
+        for name in ("brevitas", "brevitas.nn", "brevitas.quant"):
+            if name not in sys.modules:
+                sys.modules[name] = MagicMock()
+        sys.path.insert(0, REF)
+        bb = importlib.import_module("models.backbone")
+    sys.path.insert(0, os.path.join(ROOT, "dct-cryptonets_amd"))
+    from dctfhe.quantized_module import compile_torch_model
+    from dctfhe.synthetic import synthetic_dct_batch
+    from dctfhe.torch_import import from_torch_module, seed_parameters
+    ref = seed_parameters(bb.ResNet20(in_channels=24, img_size=16), 11).eval()
+    g = flatten_description(from_torch_module(ref))
+    calib = synthetic_dct_batch(16, seed=7)
+    q = compile_torch_model(ref, torch.from_numpy(calib), n_bits=5, rounding_threshold_bits=6, p_error=0.01, bit_width=4)
+    g["blob_len"] = np.array(len(q.compiled.blob))
+    g["blob_sha256"] = np.array(hashlib.sha256(q.compiled.blob).hexdigest())
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "reference_import_golden.npz"), **g)
 
 
 if __name__ == "__main__":

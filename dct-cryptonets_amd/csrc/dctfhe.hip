@@ -714,11 +714,183 @@ extern "C" int dctfhe_eval_keys_export(dctfhe_eval_keys* E, void* buf, size_t ca
   }
   return 0;
 }
+// ---- compressed evaluation keys: every mask word is a draw of the client's PUBLIC generator key `pub` (one ChaCha20 block of the secret
+// key, like enc_pub for the inputs), so the blob carries `pub` and the bodies only, and the importer regenerates the masks on the GPU.
+// Layout: EvalBlobHeader (magic 'DEVC', version 1), pub[32], then per tier: its own key-switch key's D*lk bodies (u64, on the
+// 2^-(8 limbs) grid), its bootstrap key's standard-domain body polynomials [blocks][(k+1)l][N] (u64).  Bootstrap-key rows whose gadget
+// term sits in a mask polynomial (p < k) are shipped in body form (k_bsk_gen_bodies): they decompress to the same phase, not the same
+// words.  Key-switch keys and the rows with p = k decompress bit for bit.
+static constexpr uint32_t EVAL_CBLOB_MAGIC = 0x43564544u /* 'DEVC' */, EVAL_CBLOB_VERSION = 1;
+static size_t eval_cblob_size(const dctfhe_params& p) {
+  size_t n = sizeof(EvalBlobHeader) + 32;
+  for (int ti = 0; ti < p.n_tiers; ti++) {
+    const dctfhe_tier& t = p.tiers[ti];
+    if (t.ksk_share < 0) n += (size_t)p.D * t.lk * 8;
+    n += tier_bsk_blocks(t) * (t.k + 1) * t.l * ((size_t)1 << t.logN) * 8;
+  }
+  return n;
+}
+static void key_to_bytes(const rng_key& k, uint8_t* b) {
+  for (int i = 0; i < 8; i++) for (int x = 0; x < 4; x++) b[4 * i + x] = (uint8_t)(k.k[i] >> (8 * x));
+}
+static uint64_t ksk_grid_mask(const dctfhe_tier& t) {
+  const int drop = 64 - 8 * ks_limbs(t);
+  return drop ? ~0ULL << drop : ~0ULL;
+}
+// rows [count][L] from device bodies (k_seeded_expand); checks the geometry the kernel relies on
+static int launch_expand(const rng_key& key, uint64_t stream, uint64_t row0, uint64_t stride, int dim_eff, uint64_t and_mask, const uint64_t* d_bodies,
+                         int nb, size_t count, size_t L, uint64_t* d_out, hipStream_t st) {
+  if (stride < 8 || dim_eff < 1 || (uint64_t)dim_eff > stride || L < (size_t)nb || (size_t)dim_eff > L - nb)
+    return fail("seeded expansion: rows %llu generator words apart, %d mask words, %d body words, stride %zu", (unsigned long long)stride, dim_eff, nb, L);
+  if (count == 0) return 0;
+  const size_t work = std::max(count * ((size_t)(dim_eff + 7) / 8 + 1), count * (L - dim_eff));
+  const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((work + 255) / 256, 16384));
+  hipLaunchKernelGGL(k_seeded_expand, dim3(grid), dim3(256), 0, st, key, stream, row0, stride, dim_eff, and_mask, d_bodies, nb, count, L, d_out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* buf, size_t capacity, size_t* size) {
+  if (!C || !size) return fail("dctfhe_eval_keys_export_compressed: null argument");
+  const dctfhe_params& P = C->p;
+  const size_t need = eval_cblob_size(P);
+  *size = need;
+  if (!buf) return 0;                       // size query
+  if (capacity < need) return fail("dctfhe_eval_keys_export_compressed: buffer of %zu bytes, %zu needed", capacity, need);
+  HIPCHK(hipSetDevice(C->ctx->device));
+  hipStream_t st = C->ctx->stream;
+  EvalBlobHeader h{};
+  h.magic = EVAL_CBLOB_MAGIC; h.version = EVAL_CBLOB_VERSION; h.total_bytes = need; h.params = P;
+  char* q = (char*)buf;
+  memcpy(q, &h, sizeof h); q += sizeof h;
+  key_to_bytes(C->pub, (uint8_t*)q); q += 32;
+  for (int ti = 0; ti < P.n_tiers; ti++) {
+    const dctfhe_tier& t = P.tiers[ti];
+    if (t.ksk_share < 0) {     // the generated key itself (k_ksk_gen), of which only the body column leaves the device
+      const size_t rows = (size_t)P.D * t.lk;
+      DevBuf d_ksk;
+      HIPCHK(d_ksk.alloc(rows * (t.n + 1) * 8));
+      hipLaunchKernelGGL(k_ksk_gen, dim3((unsigned)rows), dim3(256), 0, st, C->d_S, C->d_s, t.n, t.lk, t.betak, ks_limbs(t), t.lwe_sigma, C->pub, C->sec,
+                         (uint64_t)(STREAM_KSK + 2 * ti), d_ksk.as<uint64_t>());
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpy2D(q, 8, d_ksk.as<uint64_t>() + t.n, (size_t)(t.n + 1) * 8, 8, rows, hipMemcpyDeviceToHost));
+      q += rows * 8;
+    }
+    const int N = 1 << t.logN, rows = (t.k + 1) * t.l;
+    const int blocks = (int)tier_bsk_blocks(t);
+    const int chunk = std::max(1, (int)std::min<size_t>(blocks, ((size_t)64 << 20) / ((size_t)rows * N * 8)));
+    const uint8_t* bits = t.unroll == 2 ? C->d_spair[ti] : C->d_s;
+    DevBuf d_b;
+    HIPCHK(d_b.alloc((size_t)chunk * rows * N * 8));
+    SET_LDS_ATTR(k_bsk_gen_bodies, 8192 * 8);
+    for (int i0 = 0; i0 < blocks; i0 += chunk) {
+      const int ni = std::min(chunk, blocks - i0);
+      hipLaunchKernelGGL(k_bsk_gen_bodies, dim3((unsigned)(ni * rows)), dim3(256), (size_t)N * 8, st, bits, C->d_S, i0, t.k, N, t.l, t.beta, t.glwe_sigma,
+                         C->pub, C->sec, (uint64_t)(STREAM_BSK_MASK + 2 * ti), d_b.as<uint64_t>());
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(st));
+      const size_t bytes = (size_t)ni * rows * N * 8;
+      HIPCHK(hipMemcpy(q, d_b.p, bytes, hipMemcpyDeviceToHost));
+      q += bytes;
+    }
+  }
+  return 0;
+}
+
+// a compressed blob's header and pub key, checked against its size
+static int parse_cblob(const void* buf, size_t size, EvalBlobHeader* h, rng_key* pub) {
+  if (size < sizeof(EvalBlobHeader) + 32) return fail("compressed evaluation-key blob too short");
+  memcpy(h, buf, sizeof *h);
+  if (h->magic != EVAL_CBLOB_MAGIC || h->version != EVAL_CBLOB_VERSION) return fail("bad compressed evaluation-key blob magic/version");
+  CHK(check_params(&h->params));
+  if (h->total_bytes != size || eval_cblob_size(h->params) != size)
+    return fail("compressed evaluation-key blob is %zu bytes, its parameters need %zu", size, eval_cblob_size(h->params));
+  *pub = key_from_bytes((const uint8_t*)buf + sizeof *h);
+  return 0;
+}
+// standard-domain bootstrap-key blocks [i0, i0 + ni) of tier ti from their host bodies: masks regenerated, bodies copied in
+static int expand_bsk_chunk(const rng_key& pub, int ti, const dctfhe_tier& t, int i0, int ni, const uint64_t* h_bodies, uint64_t* d_bodies,
+                            uint64_t* d_std, hipStream_t st) {
+  const size_t N = (size_t)1 << t.logN, rows = (size_t)(t.k + 1) * t.l, nrow = (size_t)ni * rows;
+  HIPCHK(hipMemcpyAsync(d_bodies, h_bodies, nrow * N * 8, hipMemcpyHostToDevice, st));
+  CHK(launch_expand(pub, (uint64_t)(STREAM_BSK_MASK + 2 * ti), (uint64_t)i0 * rows, (uint64_t)t.k * N, t.k * (int)N, ~0ULL, d_bodies, (int)N, nrow,
+                    (t.k + 1) * N, d_std, st));
+  return 0;
+}
+static int import_compressed(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_eval_keys** out) {
+  EvalBlobHeader h;
+  rng_key pub;
+  CHK(parse_cblob(buf, size, &h, &pub));
+  std::unique_ptr<dctfhe_eval_keys> E;
+  CHK(eval_alloc(ctx, &h.params, E));
+  hipStream_t st = ctx->stream;
+  const char* q = (const char*)buf + sizeof h + 32;
+  for (int ti = 0; ti < h.params.n_tiers; ti++) {
+    const dctfhe_tier& t = h.params.tiers[ti];
+    TierKeys& tk = E->tiers[ti];
+    if (t.ksk_share < 0) {
+      const size_t rows = (size_t)h.params.D * t.lk;
+      DevBuf d_b;
+      HIPCHK(d_b.alloc(rows * 8));
+      HIPCHK(hipMemcpyAsync(d_b.p, q, rows * 8, hipMemcpyHostToDevice, st));
+      CHK(launch_expand(pub, (uint64_t)(STREAM_KSK + 2 * ti), 0, (uint64_t)t.n + 1, t.n, ksk_grid_mask(t), d_b.as<uint64_t>(), 1, rows, (size_t)t.n + 1,
+                        tk.d_ksk, st));
+      HIPCHK(hipStreamSynchronize(st));
+      q += rows * 8;
+    }
+    const int N = 1 << t.logN, M = N / 2, rows = (t.k + 1) * t.l;
+    const size_t per_bit_polys = (size_t)rows * (t.k + 1);
+    const int blocks = (int)tier_bsk_blocks(t);
+    const int chunk = std::max(1, (int)std::min<size_t>(blocks, ((size_t)64 << 20) / (per_bit_polys * N * 8)));
+    DevBuf d_std, d_b;
+    HIPCHK(d_std.alloc((size_t)chunk * per_bit_polys * N * 8));
+    HIPCHK(d_b.alloc((size_t)chunk * rows * N * 8));
+    for (int i0 = 0; i0 < blocks; i0 += chunk) {
+      const int ni = std::min(chunk, blocks - i0);
+      CHK(expand_bsk_chunk(pub, ti, t, i0, ni, (const uint64_t*)q, d_b.as<uint64_t>(), d_std.as<uint64_t>(), st));
+      CHK(launch_bsk_fourier(t, d_std.as<uint64_t>(), (size_t)ni * per_bit_polys, tk.d_tw, tk.d_bsk + (size_t)i0 * per_bit_polys * M, st));
+      HIPCHK(hipStreamSynchronize(st));      // the next chunk's copy reuses d_b and d_std
+      q += (size_t)ni * rows * N * 8;
+    }
+  }
+  CHK(eval_finish(E.get()));
+  *out = E.release();
+  return 0;
+}
+// test view: the standard-domain bootstrap key of one tier as dctfhe_eval_keys_import rebuilds it from a compressed blob
+extern "C" int dctfhe_eval_keys_decompress_bsk(dctfhe_ctx* ctx, const void* buf, size_t size, int tier, uint64_t* out) {
+  if (!ctx || !buf || !out) return fail("dctfhe_eval_keys_decompress_bsk: null argument");
+  EvalBlobHeader h;
+  rng_key pub;
+  CHK(parse_cblob(buf, size, &h, &pub));
+  if (tier < 0 || tier >= h.params.n_tiers) return fail("tier out of range");
+  const char* q = (const char*)buf + sizeof h + 32;
+  for (int ti = 0; ti < tier; ti++) {
+    const dctfhe_tier& t = h.params.tiers[ti];
+    if (t.ksk_share < 0) q += (size_t)h.params.D * t.lk * 8;
+    q += tier_bsk_blocks(t) * (t.k + 1) * t.l * ((size_t)1 << t.logN) * 8;
+  }
+  const dctfhe_tier& t = h.params.tiers[tier];
+  if (t.ksk_share < 0) q += (size_t)h.params.D * t.lk * 8;
+  HIPCHK(hipSetDevice(ctx->device));
+  const int blocks = (int)tier_bsk_blocks(t);
+  const size_t N = (size_t)1 << t.logN, rows = (size_t)blocks * (t.k + 1) * t.l;
+  DevBuf d_b, d_std;
+  HIPCHK(d_b.alloc(rows * N * 8));
+  HIPCHK(d_std.alloc(rows * (t.k + 1) * N * 8));
+  CHK(expand_bsk_chunk(pub, tier, t, 0, blocks, (const uint64_t*)q, d_b.as<uint64_t>(), d_std.as<uint64_t>(), ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(out, d_std.p, rows * (t.k + 1) * N * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 extern "C" int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_eval_keys** out) {
   if (!ctx || !buf || !out) return fail("dctfhe_eval_keys_import: null argument");
   if (size < sizeof(EvalBlobHeader)) return fail("evaluation-key blob too short");
   EvalBlobHeader h;
   memcpy(&h, buf, sizeof h);
+  if (h.magic == EVAL_CBLOB_MAGIC) return import_compressed(ctx, buf, size, out);
   if (h.magic != 0x4b564544u || h.version != EVAL_BLOB_VERSION) return fail("bad evaluation-key blob magic/version");
   CHK(check_params(&h.params));
   if (h.total_bytes != size || eval_blob_size(h.params) != size) return fail("evaluation-key blob is %zu bytes, its parameters need %zu", size, eval_blob_size(h.params));
@@ -846,6 +1018,46 @@ extern "C" int dctfhe_decrypt_rows(dctfhe_ctx* ctx, dctfhe_client_key* C, const 
 extern "C" int dctfhe_decrypt(dctfhe_ctx* ctx, dctfhe_client_key* C, const uint64_t* cts, size_t count, uint64_t* phases) {
   if (!C) return fail("dctfhe_decrypt: null argument");
   return dctfhe_decrypt_rows(ctx, C, cts, count, C->p.D, phases);
+}
+
+// ---- seeded input ciphertexts: the mask of ciphertext c is the draw (enc_pub, stream, c (D + 1) + j), j < input_dim, and enc_pub is one
+// ChaCha20 block of the handle's secret encryption key -- the client ships (enc_pub, stream, bodies), the server regenerates the masks
+extern "C" int dctfhe_encrypt_seeded(dctfhe_ctx* ctx, dctfhe_client_key* C, const uint64_t* phases, size_t count, uint8_t* mask_key,
+                                     uint64_t* stream_out, uint64_t* bodies) {
+  if (!ctx || !C || !mask_key || !stream_out || (count && (!phases || !bodies))) return fail("dctfhe_encrypt_seeded: null argument");
+  const int D = C->p.D, dim_eff = C->p.input_dim > 0 ? C->p.input_dim : D;
+  key_to_bytes(C->enc_pub, mask_key);
+  if (count == 0) { *stream_out = 0; return 0; }    // nothing drawn: the counter stays, as in dctfhe_encrypt_rows
+  HIPCHK(hipSetDevice(ctx->device));
+  DevBuf d_ph, d_b;
+  HIPCHK(d_ph.alloc(count * 8));
+  HIPCHK(d_b.alloc(count * 8));
+  HIPCHK(hipMemcpyAsync(d_ph.p, phases, count * 8, hipMemcpyHostToDevice, ctx->stream));
+  const uint64_t stream = (uint64_t)STREAM_ENC + ((++C->enc_calls) << 16);      // the step dctfhe_encrypt_rows takes
+  hipLaunchKernelGGL(k_lwe_encrypt_seeded, dim3((unsigned)count), dim3(256), 0, ctx->stream, C->d_S, D, dim_eff, d_ph.as<uint64_t>(), C->p.input_sigma,
+                     C->enc_pub, C->enc_sec, stream, d_b.as<uint64_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(bodies, d_b.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *stream_out = stream;
+  return 0;
+}
+extern "C" int dctfhe_expand_seeded(dctfhe_ctx* ctx, const uint8_t* mask_key, uint64_t stream, int D, int dim_eff, const uint64_t* bodies, size_t count,
+                                    int dim, uint64_t* rows) {
+  if (!ctx || !mask_key || (count && (!bodies || !rows))) return fail("dctfhe_expand_seeded: null argument");
+  if (D < 8 || dim_eff < 1 || dim_eff > D || dim < dim_eff || dim > D)
+    return fail("dctfhe_expand_seeded: D = %d, %d mask words per ciphertext, rows of %d (need 1 <= dim_eff <= dim <= D, D >= 8)", D, dim_eff, dim);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t L = (size_t)dim + 1;
+  DevBuf d_b, d_r;
+  HIPCHK(d_b.alloc(count * 8));
+  HIPCHK(d_r.alloc(count * L * 8));
+  HIPCHK(hipMemcpyAsync(d_b.p, bodies, count * 8, hipMemcpyHostToDevice, ctx->stream));
+  CHK(launch_expand(key_from_bytes(mask_key), stream, 0, (uint64_t)D + 1, dim_eff, ~0ULL, d_b.as<uint64_t>(), 1, count, L, d_r.as<uint64_t>(), ctx->stream));
+  HIPCHK(hipMemcpyAsync(rows, d_r.p, count * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------ device-level building blocks
@@ -1618,6 +1830,25 @@ extern "C" int dctfhe_session_upload_rows(dctfhe_session* s, const uint64_t* cts
   }
   hipLaunchKernelGGL(k_restride, dim3(ew_grid(count * Ls)), dim3(256), 0, st, tmp.as<uint64_t>(), Lh, s->d_tensor[t], Ls, count, std::min(deff, (size_t)dim));
   HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+// seeded inputs: only the bodies cross PCIe (8 bytes per ciphertext); the masks are written straight into the input tensor
+extern "C" int dctfhe_session_upload_seeded(dctfhe_session* s, const uint8_t* mask_key, uint64_t stream, int dim_eff, const uint64_t* bodies,
+                                            size_t count) {
+  if (!s || !mask_key || !bodies) return fail("dctfhe_session_upload_seeded: null argument");
+  if (!s->keys) return fail("dctfhe_session_upload_seeded: a clear-mode session takes phases (dctfhe_session_upload), not ciphertexts");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  const int t = s->circ->input_tensor;
+  hipStream_t st = s->ctx->stream;
+  const size_t Ls = s->t_L[t], deff = s->t_deff[t], n = s->tensor_words[t] / Ls;
+  if (count != n) return fail("dctfhe_session_upload_seeded: %zu ciphertexts, the session takes batch x n_in = %zu", count, n);
+  // the same rule as upload_rows' tail check: the circuit reads only the first deff mask words
+  if (dim_eff < 1 || (size_t)dim_eff > deff) return fail("dctfhe_session_upload_seeded: %d mask words per input; this circuit's input keeps %zu", dim_eff, deff);
+  DevBuf d_b;
+  HIPCHK(d_b.alloc(count * 8));
+  HIPCHK(hipMemcpyAsync(d_b.p, bodies, count * 8, hipMemcpyHostToDevice, st));
+  CHK(launch_expand(key_from_bytes(mask_key), stream, 0, (uint64_t)s->D + 1, dim_eff, ~0ULL, d_b.as<uint64_t>(), 1, count, Ls, s->d_tensor[t], st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }

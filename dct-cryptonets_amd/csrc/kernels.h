@@ -98,6 +98,63 @@ __global__ void k_lwe_encrypt(const uint8_t* __restrict__ S, int D, int dim, int
   if (threadIdx.x == 0) ct[dim] = s + phases[c] + (uint64_t)gauss_torus(sec, stream + 1, c, sigma);
 }
 
+// ---- seeded (compressed) forms: the client ships bodies only, the server regenerates the masks from the public key -------------
+// rnd64 computes a whole ChaCha20 block for one word; these kernels compute each block once and use all eight of its words.  Rows lie
+// `stride` generator indices apart (D + 1 for an LWE ciphertext), so a block may straddle two rows: each block index is mapped back to
+// (row, word) and words from dim_eff on (the gap of a compact row, the body's index) are skipped.
+
+// client: the bodies of k_lwe_encrypt (the same ciphertexts, for equal keys and stream) without writing a mask word.  One workgroup per
+// ciphertext; the partial block shared with the previous row is computed by both rows (one block in dim_eff / 8).
+__global__ void k_lwe_encrypt_seeded(const uint8_t* __restrict__ S, int D, int dim_eff, const uint64_t* __restrict__ phases, double sigma,
+                                     rng_key pub, rng_key sec, uint64_t stream, uint64_t* __restrict__ bodies) {
+  __shared__ uint64_t red[16];
+  const size_t c = blockIdx.x;
+  const uint64_t base = c * (uint64_t)(D + 1), b_lo = base >> 3, b_hi = (base + dim_eff - 1) >> 3;
+  uint64_t part = 0;
+  for (uint64_t b = b_lo + threadIdx.x; b <= b_hi; b += blockDim.x) {
+    uint32_t o[16];
+    chacha20_block(pub, stream, b, o);
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+      const int64_t j = (int64_t)(8 * b + w - base);
+      if (j >= 0 && j < dim_eff && S[j]) part += (uint64_t)o[2 * w] | ((uint64_t)o[2 * w + 1] << 32);
+    }
+  }
+  const uint64_t s = block_reduce_add(part, red);
+  if (threadIdx.x == 0) bodies[c] = s + phases[c] + (uint64_t)gauss_torus(sec, stream + 1, c, sigma);
+}
+
+// server: rows [count][L] from their bodies.  Row c (generator row row0 + c) gets mask word j = rnd64(key, stream, (row0 + c) stride + j)
+// & and_mask for j < dim_eff, zeros up to L - nb, and its nb body words from bodies[c][nb].  Seeded inputs: stride D + 1, nb = 1;
+// key-switch keys: stride n + 1, the grid mask; bootstrap-key rows: stride kN = dim_eff, nb = N.  Needs stride >= 8 (a block touches at
+// most two rows) and dim_eff <= min(stride, L - nb).  Thread = one block; a block shared by two rows belongs to the earlier one, which
+// writes the later row's words too, so every block is computed once.
+__global__ void k_seeded_expand(rng_key key, uint64_t stream, uint64_t row0, uint64_t stride, int dim_eff, uint64_t and_mask,
+                                const uint64_t* __restrict__ bodies, int nb, size_t count, size_t L, uint64_t* __restrict__ out) {
+  const size_t bpr = (size_t)(dim_eff + 7) / 8 + 1, nblk = count * bpr;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nblk; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = i / bpr, k = i % bpr;
+    const uint64_t base = (row0 + c) * stride, b = (base >> 3) + k;
+    if (b > (base + dim_eff - 1) >> 3) continue;
+    if (k == 0 && c > 0 && ((base - stride + dim_eff - 1) >> 3) == b) continue;   // the previous row's last block
+    uint32_t o[16];
+    chacha20_block(key, stream, b, o);
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+      int64_t j = (int64_t)(8 * b + w - base);
+      int64_t cc = (int64_t)c;
+      if (j < 0) { j += (int64_t)stride; cc--; }
+      else if (j >= (int64_t)stride) { j -= (int64_t)stride; cc++; }
+      if (cc >= 0 && cc < (int64_t)count && j < dim_eff) out[(size_t)cc * L + j] = ((uint64_t)o[2 * w] | ((uint64_t)o[2 * w + 1] << 32)) & and_mask;
+    }
+  }
+  const size_t tail = L - (size_t)dim_eff, ntail = count * tail;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ntail; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = i / tail, w = (size_t)dim_eff + i % tail;
+    out[c * L + w] = w >= L - nb ? bodies[c * nb + (w - (L - nb))] : 0;
+  }
+}
+
 __global__ void k_lwe_phase(const uint8_t* __restrict__ S, int dim, const uint64_t* __restrict__ cts, uint64_t* __restrict__ phases) {
   __shared__ uint64_t red[16];
   const size_t c = blockIdx.x;
@@ -188,6 +245,53 @@ __global__ void k_bsk_gen_std(const uint8_t* __restrict__ s_small, const uint8_t
   if (threadIdx.x == 0 && s_small[i]) {
     const int p = r / l, lev = r % l;
     row[(size_t)p * N] += 1ULL << (64 - beta * (lev + 1));
+  }
+}
+
+// the same rows in BODY FORM, bodies only ([ni * rows][N]): the masks stay the pure draws of `pub` (k_seeded_expand rebuilds them), so
+// the s_i * gadget term that k_bsk_gen_std adds to mask polynomial p < k moves into the body as - s_i g S_p (same phase, same noise
+// draw); rows with p = k are k_bsk_gen_std's bodies bit for bit.  Covers the pair secret of unroll 2 like k_bsk_gen_std (s_small = the
+// derived bits).  One block per row; masks drawn a ChaCha block (eight words) per thread into LDS.
+__global__ void k_bsk_gen_bodies(const uint8_t* __restrict__ s_small, const uint8_t* __restrict__ S_glwe, int i0, int k, int N, int l,
+                                 int beta, double sigma, rng_key pub, rng_key sec, uint64_t stream, uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  uint64_t* A = reinterpret_cast<uint64_t*>(smem_raw);
+  const int rows = (k + 1) * l;
+  const int i = i0 + (int)(blockIdx.x / rows), r = (int)(blockIdx.x % rows);
+  const uint64_t grow = (uint64_t)i * rows + r;
+  uint64_t* B = out + (size_t)blockIdx.x * N;
+  for (int c = threadIdx.x; c < N; c += blockDim.x)
+    B[c] = (uint64_t)gauss_torus(sec, stream + 1, grow * (uint64_t)N + c, sigma);
+  for (int j = 0; j < k; j++) {
+    __syncthreads();
+    const uint64_t blk0 = ((grow * (uint64_t)k + j) * (uint64_t)N) >> 3;     // N is a multiple of 8: the polynomial starts a block
+    for (int q = threadIdx.x; q < N / 8; q += blockDim.x) {
+      uint32_t o[16];
+      chacha20_block(pub, stream, blk0 + q, o);
+#pragma unroll
+      for (int w = 0; w < 8; w++) A[8 * q + w] = (uint64_t)o[2 * w] | ((uint64_t)o[2 * w + 1] << 32);
+    }
+    __syncthreads();
+    const uint8_t* Sj = S_glwe + (size_t)j * N;
+    for (int c = threadIdx.x; c < N; c += blockDim.x) {
+      uint64_t acc = 0;
+      for (int m = 0; m < N; m++) {
+        if (!Sj[m]) continue;  // uniform branch
+        const int src = c - m;
+        acc += (src >= 0) ? A[src] : (uint64_t)0 - A[src + N];
+      }
+      B[c] += acc;
+    }
+  }
+  if (!s_small[i]) return;
+  const int p = r / l, lev = r % l;
+  const uint64_t g = 1ULL << (64 - beta * (lev + 1));
+  if (p == k) {
+    if (threadIdx.x == 0) B[0] += g;       // thread 0 owns coefficient 0 in the loops above
+  } else {
+    const uint8_t* Sp = S_glwe + (size_t)p * N;
+    for (int c = threadIdx.x; c < N; c += blockDim.x)
+      if (Sp[c]) B[c] -= g;
   }
 }
 

@@ -46,6 +46,8 @@ EXPORTS = [
     "dctfhe_pbs", "dctfhe_modswitch_center", "dctfhe_round_lut", "dctfhe_conv2d", "dctfhe_add_rows", "dctfhe_affine_rows", "dctfhe_sum_pool_rows", "dctfhe_circuit_load", "dctfhe_circuit_destroy", "dctfhe_params_check", "dctfhe_circuit_validate", "dctfhe_dct_frontend",
     "dctfhe_circuit_stats", "dctfhe_circuit_io", "dctfhe_session_create", "dctfhe_session_destroy",
     "dctfhe_session_upload", "dctfhe_session_run", "dctfhe_session_download", "dctfhe_session_upload_rows", "dctfhe_session_download_rows", "dctfhe_session_dims", "dctfhe_fp64_peak", "dctfhe_bench_pbs",
+    "dctfhe_encrypt_seeded", "dctfhe_expand_seeded", "dctfhe_session_upload_seeded", "dctfhe_eval_keys_export_compressed",
+    "dctfhe_eval_keys_decompress_bsk",
 ]
 
 _lib = None
@@ -115,6 +117,11 @@ def load():
     L.dctfhe_session_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.dctfhe_fp64_peak.argtypes = [vp, C.POINTER(C.c_double)]
     L.dctfhe_bench_pbs.argtypes = [vp, vp, i32, sz, i32, C.POINTER(C.c_double)]
+    L.dctfhe_encrypt_seeded.argtypes = [vp, vp, vp, sz, vp, C.POINTER(u64), vp]
+    L.dctfhe_expand_seeded.argtypes = [vp, C.c_char_p, u64, i32, i32, vp, sz, i32, vp]
+    L.dctfhe_session_upload_seeded.argtypes = [vp, C.c_char_p, u64, i32, vp, sz]
+    L.dctfhe_eval_keys_export_compressed.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    L.dctfhe_eval_keys_decompress_bsk.argtypes = [vp, vp, sz, i32, vp]
     _lib = L
     return L
 

@@ -2,6 +2,7 @@
 import ctypes as C
 import hashlib
 import os
+import struct
 
 import numpy as np
 
@@ -79,6 +80,23 @@ class Context:
         check(self.L.dctfhe_conv2d(self.h, D, ptr(cts), batch, Cin, H, W, ptr(weight), Cout, KH, KW, stride, pad, ptr(out)))
         return out
 
+    def expand_seeded(self, sc, dim=None):
+        """SeededCiphertexts -> rows of dim mask words + body (None: sc.input_dim, the compact wire form of ClientKey.encrypt)"""
+        dim = sc.input_dim if dim is None else int(dim)
+        out = np.empty((sc.bodies.size, dim + 1), np.uint64)
+        check(self.L.dctfhe_expand_seeded(self.h, sc.key, C.c_uint64(sc.stream), sc.D, sc.input_dim, ptr(sc.bodies), sc.bodies.size, dim, ptr(out)))
+        return out
+
+    def decompress_bsk(self, blob, tier):
+        """test view: the standard-domain bootstrap key of `tier` as importing a compressed blob rebuilds it"""
+        blob = _as_u8(blob)
+        p = blob_params(blob)
+        t = p.tiers[tier]
+        blocks = 3 * t.n // 2 if t.unroll == 2 else t.n
+        out = np.empty((blocks, (t.k + 1) * t.l, t.k + 1, 1 << t.logN), np.uint64)
+        check(self.L.dctfhe_eval_keys_decompress_bsk(self.h, ptr(blob), blob.size, tier, ptr(out)))
+        return out
+
     def close(self):
         if self.h:
             self.L.dctfhe_ctx_destroy(self.h)
@@ -96,6 +114,60 @@ def seed_bytes(seed=None):
             raise ValueError("a key seed is exactly 32 bytes")
         return bytes(seed)
     return hashlib.sha256(b"dctfhe deterministic test seed " + str(int(seed)).encode()).digest()
+
+
+def _as_u8(blob):
+    return np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8)
+
+
+def blob_params(blob):
+    """the parameters in an evaluation-key blob's header (magic, version, total_bytes, params: both the full and the compressed form)"""
+    blob = _as_u8(blob)
+    if blob.size < 16 + C.sizeof(Params):
+        raise _lib.DctfheError("evaluation-key blob too short")
+    return Params.from_buffer_copy(blob[16:16 + C.sizeof(Params)].tobytes())
+
+
+class SeededCiphertexts:
+    """Input ciphertexts in SEEDED form (include/dctfhe.h dctfhe_encrypt_seeded): the 32-byte public mask key, the generator stream and
+    one body per ciphertext.  Mask word j < input_dim of ciphertext c is generator word (key, stream, c (D + 1) + j): the server
+    regenerates it (Session.upload_seeded, Context.expand_seeded).  Wire form: to_bytes / from_bytes."""
+
+    MAGIC, VERSION = b"DSCT", 1
+    _HDR = struct.Struct("<4sIQiiQ")          # magic, version, stream, D, input_dim, count; then the key (32 bytes) and count u64 bodies
+
+    def __init__(self, key, stream, D, input_dim, bodies):
+        key = bytes(key)
+        if len(key) != 32:
+            raise ValueError("a mask key is exactly 32 bytes")
+        D, input_dim = int(D), int(input_dim)
+        if not (1 <= input_dim <= D):
+            raise ValueError(f"input_dim {input_dim} outside [1, D = {D}]")
+        self.key, self.stream, self.D, self.input_dim = key, int(stream), D, input_dim
+        self.bodies = np.ascontiguousarray(bodies, np.uint64).reshape(-1)
+
+    def __len__(self):
+        return self.bodies.size
+
+    @property
+    def nbytes(self):
+        return self._HDR.size + 32 + self.bodies.nbytes
+
+    def to_bytes(self):
+        return self._HDR.pack(self.MAGIC, self.VERSION, self.stream, self.D, self.input_dim, self.bodies.size) + self.key + self.bodies.tobytes()
+
+    @classmethod
+    def from_bytes(cls, blob):
+        blob = bytes(blob)
+        H = cls._HDR.size
+        if len(blob) < H + 32:
+            raise ValueError("seeded-ciphertext blob too short")
+        magic, version, stream, D, input_dim, count = cls._HDR.unpack_from(blob)
+        if magic != cls.MAGIC or version != cls.VERSION:
+            raise ValueError("not a seeded-ciphertext blob (magic / version)")
+        if len(blob) != H + 32 + 8 * count:
+            raise ValueError(f"seeded-ciphertext blob of {len(blob)} bytes, its header says {H + 32 + 8 * count}")
+        return cls(blob[H:H + 32], stream, D, input_dim, np.frombuffer(blob, np.uint64, count, H + 32).copy())
 
 
 class ClientKey:
@@ -156,6 +228,22 @@ class ClientKey:
         check(self.L.dctfhe_encrypt_rows(self.ctx.h, self.h, ptr(phases), phases.size, dim, ptr(out)))
         return out
 
+    def encrypt_seeded(self, phases):
+        """-> SeededCiphertexts: what encrypt(phases, self.input_dim) would return at this counter, masks left to the server"""
+        phases = np.ascontiguousarray(phases, np.uint64).reshape(-1)
+        key, stream = C.create_string_buffer(32), C.c_uint64()
+        bodies = np.empty(phases.size, np.uint64)
+        check(self.L.dctfhe_encrypt_seeded(self.ctx.h, self.h, ptr(phases), phases.size, key, C.byref(stream), ptr(bodies)))
+        return SeededCiphertexts(key.raw, stream.value, self.D, self.input_dim, bodies)
+
+    def export_eval_keys_compressed(self):
+        """the evaluation keys as a compressed blob (bodies + the public mask key; EvalKeys.from_blob reads it)"""
+        n = C.c_size_t()
+        check(self.L.dctfhe_eval_keys_export_compressed(self.h, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        check(self.L.dctfhe_eval_keys_export_compressed(self.h, ptr(out), out.size, C.byref(n)))
+        return out
+
     def decrypt(self, cts, dim=None):
         dim = self.D if dim is None else int(dim)
         cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, dim + 1)
@@ -177,11 +265,12 @@ class EvalKeys:
 
     @classmethod
     def from_blob(cls, ctx, blob):
-        """evaluation keys as shipped by a client (EvalKeys.to_blob): the server never sees a secret"""
-        blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else blob, np.uint8)
+        """evaluation keys as shipped by a client, full (EvalKeys.to_blob) or compressed (ClientKey.export_eval_keys_compressed):
+        the server never sees a secret"""
+        blob = _as_u8(blob)
+        params = blob_params(blob)
         h = C.c_void_p()
         check(ctx.L.dctfhe_eval_keys_import(ctx.h, ptr(blob), blob.size, C.byref(h)))
-        params = Params.from_buffer_copy(blob[16:16 + C.sizeof(Params)].tobytes())       # header: magic, version, total_bytes, params
         return cls(ctx, params, h)
 
     def to_blob(self):
@@ -263,7 +352,8 @@ class Keys:
         return self.params.tiers[i]
 
     def __getattr__(self, name):
-        if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter"):
+        if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter",
+                    "encrypt_seeded", "export_eval_keys_compressed"):
             return getattr(self.client, name)
         if name in ("export_ksk", "keyswitch", "modswitch_center", "pbs", "round_lut", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
@@ -321,6 +411,12 @@ class Session:
             check(self.L.dctfhe_session_upload(self.h, ptr(cts)))
         else:
             check(self.L.dctfhe_session_upload_rows(self.h, ptr(cts), int(dim)))
+
+    def upload_seeded(self, sc):
+        """SeededCiphertexts of batch x n_in inputs: the bodies go to the device, the masks are regenerated there"""
+        if self.keys is not None and sc.D != self.keys.D:
+            raise ValueError(f"seeded ciphertexts under D = {sc.D}, the session's keys have D = {self.keys.D}")
+        check(self.L.dctfhe_session_upload_seeded(self.h, sc.key, C.c_uint64(sc.stream), sc.input_dim, ptr(sc.bodies), sc.bodies.size))
 
     def set_noise(self, seed, sigma_per_op):
         """clear-mode sessions: `simulate` with the noise model (sigma per op, fraction of the torus); None switches it off"""

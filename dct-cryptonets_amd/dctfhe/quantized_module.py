@@ -3,7 +3,8 @@
     reference call site                                         here
     compile_brevitas_qat_model(...)  homomorphic_eval.py:276    compile_brevitas_qat_model -> QuantizedModule
     compile_torch_model(...)         homomorphic_eval.py:287    compile_torch_model (same circuit builder)
-    Configuration(...)               homomorphic_eval.py:266    Configuration (progress flags kept, inert)
+    Configuration(...)               homomorphic_eval.py:266    Configuration (progress flags kept, inert; compress_input_ciphertexts,
+                                                                compress_evaluation_keys: seeded inputs / compressed evaluation keys)
     q.fhe_circuit.graph.maximum_integer_bit_width()    :301     FHECircuit.graph.maximum_integer_bit_width()
     q.fhe_circuit.mlir                                 :311     FHECircuit.mlir  (text dump of the compiled circuit)
     q.fhe_circuit.keygen()                             :315     FHECircuit.keygen()  (keys generated on the GPU)
@@ -19,14 +20,19 @@ import numpy as np
 
 from . import compile as cc
 from . import params as P
-from .engine import Circuit, Context, Keys, Session
+from .engine import Circuit, Context, Keys, SeededCiphertexts, Session
 
 
 class Configuration:
     """Stand-in for concrete.fhe.Configuration (reference homomorphic_eval.py:266-273)."""
 
-    def __init__(self, show_progress=False, progress_tag=False, progress_title="", **kwargs):
+    def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
+                 compress_evaluation_keys=False, **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
+        # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
+        # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
+        self.compress_input_ciphertexts = bool(compress_input_ciphertexts)
+        self.compress_evaluation_keys = bool(compress_evaluation_keys)
         self.extra = kwargs
 
 
@@ -53,8 +59,8 @@ class FHECircuit:
         self._o._keygen(seed, force)
 
     # -- client / server split: the owner's methods (QuantizedModule) -----------------------------------------------
-    def export_evaluation_keys(self):
-        return self._o.export_evaluation_keys()
+    def export_evaluation_keys(self, compressed=None):
+        return self._o.export_evaluation_keys(compressed)
 
     def load_evaluation_keys(self, blob):
         return self._o.load_evaluation_keys(blob)
@@ -69,8 +75,9 @@ class FHECircuit:
 
 
 class QuantizedModule:
-    def __init__(self, compiled, device=0, verbose=False, classifier=None):
+    def __init__(self, compiled, device=0, verbose=False, classifier=None, configuration=None):
         self.compiled = compiled
+        self.configuration = configuration if configuration is not None else Configuration()
         self.device = device
         self.verbose = verbose
         self._ctx = None
@@ -109,15 +116,22 @@ class QuantizedModule:
         return self._sessions[key]
 
     # -- client / server split (reference homomorphic_eval.py:313-317 keeps both halves in one process) ------------
-    def export_evaluation_keys(self):
-        """client side: the evaluation keys as a flat uint8 blob to ship to the server (no secret inside)"""
+    def export_evaluation_keys(self, compressed=None):
+        """client side: the evaluation keys as a flat uint8 blob to ship to the server (no secret inside).  compressed (default:
+        Configuration.compress_evaluation_keys): bodies + the public mask key, about a quarter of the size; needs the client key"""
         if self._keys is None:
             self._keygen(None)
+        if compressed is None:
+            compressed = self.configuration.compress_evaluation_keys
+        if compressed:
+            if not isinstance(self._keys, Keys):
+                raise RuntimeError("compressed evaluation keys are made by the client (its secret key); this module holds evaluation keys only")
+            return self._keys.client.export_eval_keys_compressed()
         return self._keys.eval.to_blob()
 
     def load_evaluation_keys(self, blob):
-        """server side: evaluate with keys a client generated elsewhere; this module can then run `evaluate_encrypted`
-        but can neither encrypt nor decrypt"""
+        """server side: evaluate with keys a client generated elsewhere (either blob form: full or compressed); this module can
+        then run `evaluate_encrypted` but can neither encrypt nor decrypt"""
         from .engine import EvalKeys
         ctx = self._context()
         for k in [k for k in self._sessions if k[0] == "execute"]:
@@ -128,9 +142,15 @@ class QuantizedModule:
 
     def evaluate_encrypted(self, cts, batch, dim=None):
         """server side: input ciphertexts [batch * n_in, D+1] -> output ciphertexts [batch * n_out, D+1]; dim: the compact wire
-        form instead -- input rows of dim mask words + body, output rows of Session.dims()[1] mask words + body"""
+        form instead -- input rows of dim mask words + body, output rows of Session.dims()[1] mask words + body.  cts may also be
+        SeededCiphertexts (or their to_bytes() form): the masks are regenerated on the GPU; dim then only selects the output form"""
+        if isinstance(cts, (bytes, bytearray, memoryview)):
+            cts = SeededCiphertexts.from_bytes(cts)
         sess = self._session("execute", batch)
-        sess.upload(cts, dim)
+        if isinstance(cts, SeededCiphertexts):
+            sess.upload_seeded(cts)
+        else:
+            sess.upload(cts, dim)
         sess.run()
         if dim is None:
             return sess.download().reshape(-1, self._keys.D + 1)
@@ -184,11 +204,16 @@ class QuantizedModule:
         if mode == "execute":
             # ciphertexts travel in the compact wire form: a fresh encryption masks input_dim words, an output the ring of the last
             # table tier -- not the D words of the master key (include/dctfhe.h dctfhe_encrypt_rows)
+            # Configuration(compress_input_ciphertexts=True): only the bodies travel (seeded form), the GPU regenerates the masks
             in_dim, out_dim = sess.dims()
+            seeded = self.configuration.compress_input_ciphertexts
             t1 = time.time()
-            cts = self._keys.encrypt(phases.reshape(-1), in_dim)
+            cts = self._keys.encrypt_seeded(phases.reshape(-1)) if seeded else self._keys.encrypt(phases.reshape(-1), in_dim)
             t2 = time.time()
-            sess.upload(cts, in_dim)
+            if seeded:
+                sess.upload_seeded(cts)
+            else:
+                sess.upload(cts, in_dim)
             t3 = time.time()
             timing = sess.run(timing=True)
             t4 = time.time()
@@ -196,7 +221,8 @@ class QuantizedModule:
             t5 = time.time()
             out_ph = self._keys.decrypt(out, out_dim).reshape(B, -1)
             self.last_io = dict(encrypt_s=t2 - t1, upload_s=t3 - t2, run_s=t4 - t3, download_s=t5 - t4, decrypt_s=time.time() - t5,
-                                input_bytes=int(cts.nbytes), output_bytes=int(out.nbytes))
+                                input_bytes=int(cts.nbytes), output_bytes=int(out.nbytes),
+                                upload_bytes=int(cts.bodies.nbytes if seeded else cts.nbytes))
         else:
             sess.upload(phases)
             timing = sess.run(timing=True)
@@ -247,7 +273,7 @@ def compile_brevitas_qat_model(torch_model, torch_inputset, n_bits=5, configurat
         torch_model = torch_import.from_torch_module(torch_model, bit_width=bit_width or 4)
     compiled = cc.compile_model(torch_model, _as_numpy(torch_inputset), rounding_threshold_bits=rtb, n_bits=n_bits,
                                 param_set=param_set, p_error=p_error, rounding_method=method, tier_policy=tier_policy)
-    return QuantizedModule(compiled, device=device, verbose=verbose)
+    return QuantizedModule(compiled, device=device, verbose=verbose, configuration=configuration)
 
 
 def compile_torch_model(torch_model, torch_inputset, n_bits=5, configuration=None, rounding_threshold_bits=6, p_error=None,

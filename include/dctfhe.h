@@ -113,7 +113,18 @@ int dctfhe_eval_keys_destroy(dctfhe_eval_keys* eval);
 /* evaluation-key persistence / shipping to the server: a flat blob (header + parameters, then per tier its key-switch key
  * and its Fourier bootstrap key).  buf == NULL: only *size is written (size query). */
 int dctfhe_eval_keys_export(dctfhe_eval_keys* eval, void* buf, size_t capacity, size_t* size);
+/* import accepts both blob forms: the one above and the compressed one below (told apart by the magic). */
 int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_eval_keys** out);
+/* COMPRESSED evaluation keys (CLIENT side: the bodies need the secret).  Every key mask word is a draw of the client's public generator key
+ * (one ChaCha20 block of the secret one), so the blob holds the header and parameters, that 32-byte key, then per tier the D*lk bodies of
+ * its own key-switch key (u64, on the 2^-(8 limbs) grid) and the standard-domain bodies of its bootstrap key, blocks x (k+1)l x N u64
+ * (blocks = n, or 3n/2 for unroll 2).  dctfhe_eval_keys_import regenerates the masks on the GPU and transforms the bootstrap key as
+ * dctfhe_eval_keys_generate does.  Key-switch keys and the bootstrap-key rows whose gadget term sits in the body (p = k) decompress bit
+ * for bit; the rows p < k are shipped in BODY FORM (a, b - s_i g S_p): the same phase and noise draw, another ciphertext.  About a
+ * quarter of dctfhe_eval_keys_export's size for the default parameters.  buf == NULL: size query. */
+int dctfhe_eval_keys_export_compressed(dctfhe_client_key* client, void* buf, size_t capacity, size_t* size);
+/* test view: the standard-domain bootstrap key [blocks][(k+1)l][k+1][N] of `tier` as import rebuilds it from a compressed blob */
+int dctfhe_eval_keys_decompress_bsk(dctfhe_ctx* ctx, const void* buf, size_t size, int tier, uint64_t* out);
 
 /* test / client views */
 int dctfhe_client_key_export_secret(dctfhe_client_key* client, uint8_t* big_key /* D */, uint8_t* small_key /* n_max */);
@@ -147,6 +158,16 @@ int dctfhe_decrypt_rows(dctfhe_ctx* ctx, dctfhe_client_key* client, const uint64
  * made from one seed (a re-created key, a second process, the ranks of a job) therefore never draw the same mask or noise.
  * set_encrypt_counter moves the position inside the handle's own streams (kept for callers that partition them); set_encrypt_nonce
  * FIXES the nonce -- reproducible experiments and tests only: handles with equal seed, nonce and counter encrypt identically. */
+/* SEEDED input ciphertexts: the client keeps the masks to itself -- they are draws of the handle's public encryption key (one ChaCha20
+ * block of its secret one) -- and ships the 32-byte key, the stream id and one body per ciphertext (8 bytes instead of 8 (input_dim + 1)).
+ * encrypt_seeded takes one step of the call counter like dctfhe_encrypt_rows; for equal nonce and counter the expanded ciphertexts are
+ * bit for bit those of dctfhe_encrypt_rows(dim = input_dim): mask word j < input_dim of ciphertext c is generator word
+ * (mask_key, stream, c (D+1) + j).  expand_seeded is the server's stand-alone expander: rows of dim >= dim_eff mask words + body
+ * (words from dim_eff on zero).  dctfhe_session_upload_seeded writes the masks straight into a session's input tensor. */
+int dctfhe_encrypt_seeded(dctfhe_ctx* ctx, dctfhe_client_key* client, const uint64_t* phases, size_t count, uint8_t mask_key[32] /* out */,
+                          uint64_t* stream /* out */, uint64_t* bodies /* count */);
+int dctfhe_expand_seeded(dctfhe_ctx* ctx, const uint8_t mask_key[32], uint64_t stream, int D, int dim_eff, const uint64_t* bodies, size_t count,
+                         int dim, uint64_t* rows /* count x (dim+1) */);
 int dctfhe_client_key_set_encrypt_counter(dctfhe_client_key* client, uint64_t next_call);
 int dctfhe_client_key_set_encrypt_nonce(dctfhe_client_key* client, const uint8_t nonce[16]);
 
@@ -212,6 +233,9 @@ int dctfhe_session_upload(dctfhe_session* s, const uint64_t* cts_in /* batch x n
  * count as zero, words beyond the input's effective dimension must BE zero (checked).  download: dim >= the output's effective dimension.
  * dctfhe_session_dims reports the two effective dimensions (input: what upload keeps; output: the least download accepts). */
 int dctfhe_session_upload_rows(dctfhe_session* s, const uint64_t* cts_in /* batch x n_in x (dim+1) */, int dim);
+/* seeded inputs (dctfhe_encrypt_seeded): only the bodies are copied to the device; count must be batch x n_in, 1 <= dim_eff <= the input's
+ * effective dimension (in_dim of dctfhe_session_dims); encrypted sessions only.  The stored input equals upload_rows of the expanded rows. */
+int dctfhe_session_upload_seeded(dctfhe_session* s, const uint8_t mask_key[32], uint64_t stream, int dim_eff, const uint64_t* bodies, size_t count);
 int dctfhe_session_download_rows(dctfhe_session* s, uint64_t* cts_out /* batch x n_out x (dim+1) */, int dim);
 int dctfhe_session_dims(dctfhe_session* s, int* in_dim, int* out_dim);
 /* synchronous.  The uploaded input stays resident: run may be called again without a fresh upload (same result). */

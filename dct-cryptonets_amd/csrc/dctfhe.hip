@@ -273,78 +273,39 @@ static int tier_ppt(const dctfhe_tier& t) {
     }                                                                                                \
   } while (0)
 
+// one bootstrap kernel, GR ciphertexts per workgroup
+template <int LN, int K, int L, int P, int GR, int MB = 0>
+static int launch_pbs_as(const pbs_launch& a, hipStream_t st) {
+  const size_t lds = pbs_lds_bytes<LN, K, L, P, MB>(GR);
+  SET_LDS_ATTR((pbs_kernel<LN, K, L, P, GR, MB>), lds);
+  const unsigned grid = (unsigned)((a.count + GR - 1) / GR);
+  hipLaunchKernelGGL((pbs_kernel<LN, K, L, P, GR, MB>), dim3(grid), dim3(pbs_geom<LN, K, L, P, MB>::T * GR), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 static int launch_pbs(const dctfhe_tier& t, const pbs_launch& a, hipStream_t st) {
   if (a.count == 0) return 0;
   // the kernel's L2 warm-up contract (pbs_core.h): callers pad the key by PBS_PF_DIST iterations (eval_alloc does)
   if (a.pf_parts != 0 && a.pf_parts < 8) return fail("bootstrap launch: pf_parts must be 0 or >= 8 (got %d)", a.pf_parts);
-  if (a.bsk_wrap < 0 || (a.bsk_wrap > 0 && t.unroll == 2)) return fail("bootstrap launch: bsk_wrap is a one-bit-kernel experiment switch");
   if (!a.bsk || !a.tw || !a.cts_small || !a.out || !a.dummy || (t.unroll == 2 && !a.wtab)) return fail("bootstrap launch: null operand");
   if (a.w < 0 || a.w > t.logN - 1) return fail("bootstrap launch: table of 2^%d entries does not fit N = 2^%d", a.w, t.logN);
-#define X(LN, K_, L_, P_)                                                                            \
-  if (t.logN == LN && t.k == K_ && t.l == L_ && t.unroll == 1) {                                     \
-    using G = pbs_geom<LN, K_, L_, P_>;                                                              \
-    constexpr int GR = groups_for<LN, K_, L_, P_>();                                                 \
-    const size_t lds = G::TW_BYTES + (size_t)GR * G::GROUP_BYTES;                                 \
-    SET_LDS_ATTR((pbs_kernel<LN, K_, L_, P_, GR>), lds);                                             \
-    const unsigned grid = (unsigned)((a.count + GR - 1) / GR);                                       \
-    hipLaunchKernelGGL((pbs_kernel<LN, K_, L_, P_, GR>), dim3(grid), dim3(G::T * GR), lds, st, a);   \
-    HIPCHK(hipGetLastError());                                                                       \
-    return 0;                                                                                        \
-  }
+#define X(LN, K_, L_, P_) \
+  if (t.logN == LN && t.k == K_ && t.l == L_ && t.unroll == 1) return launch_pbs_as<LN, K_, L_, P_, groups_for<LN, K_, L_, P_>()>(a, st);
   PBS_CASES(X)
 #undef X
-#define X(LN)                                                                                        \
-  if (t.logN == LN && t.k == 1 && t.l == 1 && t.unroll == 2) {                                       \
-    using G = pbs_geom<LN, 1, 1, 8, 1>;                                                              \
-    /* N = 4096: two ciphertexts per 512-thread workgroup share their key lines (28.5 vs 30.8 ms) */  \
-    constexpr int GR = LN == 12 ? 2 : groups_for<LN, 1, 1, 8>();                                     \
-    const size_t lds = G::TW_BYTES + (size_t)GR * G::GROUP_BYTES;                                    \
-    SET_LDS_ATTR((pbs_kernel<LN, 1, 1, 8, GR, 1>), lds);                                             \
-    const unsigned grid = (unsigned)((a.count + GR - 1) / GR);                                       \
-    hipLaunchKernelGGL((pbs_kernel<LN, 1, 1, 8, GR, 1>), dim3(grid), dim3(G::T * GR), lds, st, a);   \
-    HIPCHK(hipGetLastError());                                                                       \
-    return 0;                                                                                        \
-  }
+  // N = 4096: two ciphertexts per 512-thread workgroup share their key lines (28.5 vs 30.8 ms)
+#define X(LN) \
+  if (t.logN == LN && t.k == 1 && t.l == 1 && t.unroll == 2) return launch_pbs_as<LN, 1, 1, 8, (LN == 12 ? 2 : groups_for<LN, 1, 1, 8>()), 1>(a, st);
   PBS_MB_CASES(X)
 #undef X
-  if (t.logN == 11 && t.k == 1 && t.l == 3 && t.unroll == 2) {
-    // the general form of the two-bit rotation (one polynomial at a time, monomial factors rebuilt per gadget row), four
-    // ciphertexts per 512-thread workgroup so that they share their key lines: 74.2 ms per 4096 against 82.3 for the one-bit
-    // chain of the same tier (profiles/r02_exp_ablations.log); its output is 0.7 bit noisier, so the compiler only uses it
-    // where the circuit's budget allows (dctfhe/params.py T4r2)
-    using G = pbs_geom<11, 1, 3, 8, 1>;
-    constexpr int GR = 4;
-    const size_t lds = G::TW_BYTES + (size_t)GR * G::GROUP_BYTES;
-    SET_LDS_ATTR((pbs_kernel<11, 1, 3, 8, GR, 1>), lds);
-    const unsigned grid = (unsigned)((a.count + GR - 1) / GR);
-    hipLaunchKernelGGL((pbs_kernel<11, 1, 3, 8, GR, 1>), dim3(grid), dim3(G::T * GR), lds, st, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (t.logN == 10 && t.k == 2 && t.l == 1 && t.unroll == 2) {
-    // general two-bit rotation for the one-level bit tier (Ba2): one wave per ciphertext, four per workgroup
-    using G = pbs_geom<10, 2, 1, 8, 1>;
-    if (t.key_lds) {
-      // the eight ciphertexts of a 512-thread workgroup share every key tile through an LDS ring filled by LDS-DMA (pbs_core.h, KLDS):
-      // one copy of the key per CU through L1 instead of eight.  Same results; measured no faster than the free-running form below
-      // (47.6 against 47.5 ms per 16 384: profiles/r03_exp_t4r2_ulow_ba2_keylds.log) -- the kernel sits at its instruction-issue
-      // rate at the clock the chip holds, not at the L1 path -- so the catalogue leaves it off.
-      constexpr int GR8 = 8, KL = 4;
-      const size_t lds8 = pbs_lds_bytes<10, 2, 1, 8, 1, KL>(GR8);
-      SET_LDS_ATTR((pbs_kernel<10, 2, 1, 8, GR8, 1, KL>), lds8);
-      const unsigned grid8 = (unsigned)((a.count + GR8 - 1) / GR8);
-      hipLaunchKernelGGL((pbs_kernel<10, 2, 1, 8, GR8, 1, KL>), dim3(grid8), dim3(G::T * GR8), lds8, st, a);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    constexpr int GR = 4;
-    const size_t lds = G::TW_BYTES + (size_t)GR * G::GROUP_BYTES;
-    SET_LDS_ATTR((pbs_kernel<10, 2, 1, 8, GR, 1>), lds);
-    const unsigned grid = (unsigned)((a.count + GR - 1) / GR);
-    hipLaunchKernelGGL((pbs_kernel<10, 2, 1, 8, GR, 1>), dim3(grid), dim3(G::T * GR), lds, st, a);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
+  // the general form of the two-bit rotation (one polynomial at a time, monomial factors rebuilt per gadget row), four
+  // ciphertexts per 512-thread workgroup so that they share their key lines: 74.2 ms per 4096 against 82.3 for the one-bit
+  // chain of the same tier (profiles/r02_exp_ablations.log); its output is 0.7 bit noisier, so the compiler only uses it
+  // where the circuit's budget allows (dctfhe/params.py T4r2)
+  if (t.logN == 11 && t.k == 1 && t.l == 3 && t.unroll == 2) return launch_pbs_as<11, 1, 3, 8, 4, 1>(a, st);
+  // general two-bit rotation for the one-level bit tier (Ba2): one wave per ciphertext, four per workgroup
+  if (t.logN == 10 && t.k == 2 && t.l == 1 && t.unroll == 2) return launch_pbs_as<10, 2, 1, 8, 4, 1>(a, st);
   return fail("no bootstrap kernel instantiated for logN=%d k=%d l=%d unroll=%d", t.logN, t.k, t.l, t.unroll);
 }
 
@@ -435,8 +396,7 @@ static int check_params(const dctfhe_params* p) {
     if (t.k < 1 || t.k > 2 || t.logN < 8 || t.logN > 13) return fail("tier %d: k or logN out of range", i);
     if (t.lk < 1 || t.lk > 63 || t.betak < 1 || t.betak > 8 || t.lk * t.betak > 63) return fail("tier %d: bad key-switch gadget (1 <= betak <= 8, lk >= 1, lk * betak <= 63)", i);
     if (!(t.lwe_sigma >= 0.0) || t.lwe_sigma > 1.0 || !(t.glwe_sigma >= 0.0) || t.glwe_sigma > 1.0) return fail("tier %d: noise parameter out of range", i);
-    if (t.key_lds != 0 && !(t.key_lds == 1 && t.unroll == 2 && t.k == 2 && t.l == 1 && t.logN == 10))
-      return fail("tier %d: key_lds is 0, or 1 on the (k, l, N, unroll) = (2, 1, 1024, 2) tier", i);
+    if (t.reserved != 0) return fail("tier %d: reserved must be 0", i);
     if (!tier_ppt(t)) return fail("tier %d: no kernel for logN=%d k=%d l=%d", i, t.logN, t.k, t.l);
     if (t.ksk_share >= i) return fail("tier %d: ksk_share must name an earlier tier", i);
     if (t.ksk_share >= 0) {

@@ -27,34 +27,6 @@
 #define HD inline __attribute__((always_inline))
 #endif
 
-#ifndef DCTFHE_SHARED_TWIDDLES
-#define DCTFHE_SHARED_TWIDDLES 1
-#endif
-#ifndef DCTFHE_PAIR_STAGGER
-#define DCTFHE_PAIR_STAGGER 0      // experiment switch (fft_forward_n): s_sleep units the younger half of a 512-thread workgroup waits; OFF
-#endif
-
-// Wave-local passes of the NP-polynomial transforms, polynomial by polynomial: {butterflies; scatter; gather} of polynomial u, then of
-// u + 1 -- the LDS unit moves polynomial u while the VALU runs the butterflies of u + 1 (each with a twiddle chain of its own).
-#ifndef DCTFHE_PIPE_LOCAL
-#define DCTFHE_PIPE_LOCAL 0
-#endif
-// Middle passes of the inverse transforms as fused butterflies (fused_idft below): 1 = on
-#ifndef DCTFHE_FUSED_INV
-#define DCTFHE_FUSED_INV 1
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && defined(DCTFHE_PIPE_PIN)
-#define DCTFHE_PIPE_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define DCTFHE_PIPE_SCHED_BARRIER() ((void)0)
-#endif
-// pinning the interleaved order with scheduling barriers measured 8% slower than leaving hipcc free (N = 8192)
-#if defined(__HIP_DEVICE_COMPILE__) && defined(DCTFHE_PIN_FFT_ORDER)
-#define DCTFHE_FFT_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define DCTFHE_FFT_SCHED_BARRIER() ((void)0)
-#endif
-
 namespace dctfhe {
 
 struct cplx { double re, im; };
@@ -285,9 +257,6 @@ struct no_hook { HD void operator()() const {} };
 // its key loads in flight under that pass.
 template <int LOGM, int P, class Sync, class WSync, class Hook = no_hook>
 HD void fft_forward(cplx* v, int t, const cplx* tw, const cplx twist, cplx* exch, Sync&& sync, WSync&& wsync, Hook&& before_last = Hook{}) {
-#if defined(DCTFHE_ABLATE_FFT)   // timing experiments only
-  return;
-#endif
   using G = fft_geom<LOGM, P>;
   constexpr int S = G::S;
   // twist part 1: compile-time factor e^{i pi j T / N} = e^{2 pi i j / (4P)} on register j
@@ -332,16 +301,13 @@ HD void fft_forward(cplx* v, int t, const cplx* tw, const cplx twist, cplx* exch
 //   v[0..P)   in : spectrum at addresses pass_addr<S-1>(t, j);  out: z_n for n = t + T*j, twist removed.
 template <int LOGM, int P, class Sync, class WSync>
 HD void fft_inverse(cplx* v, int t, const cplx* tw, const cplx twist, cplx* exch, Sync&& sync, WSync&& wsync) {
-#if defined(DCTFHE_ABLATE_FFT)
-  return;
-#endif
   using G = fft_geom<LOGM, P>;
   constexpr int S = G::S;
   static_for<0, S>([&](auto Irev) {
     constexpr int i = S - 1 - decltype(Irev)::value;
     constexpr int R = G::radix(i);
     constexpr int W = G::weight(i);
-    constexpr bool FUSED = DCTFHE_FUSED_INV && i > 0 && i < S - 1 && R == P && P == 8;
+    constexpr bool FUSED = i > 0 && i < S - 1 && R == P && P == 8;     // middle passes: fused butterflies (fused_idft)
     if constexpr (i < S - 1 && !FUSED) {
       const cplx b = tw[G::tw_offset(i) + (t % W)];
       {
@@ -382,49 +348,22 @@ HD void fft_inverse(cplx* v, int t, const cplx* tw, const cplx twist, cplx* exch
 // in the same order, as fft_forward / fft_inverse: results are bit-identical to NP separate calls.
 template <int LOGM, int P, int NP, class Sync, class WSync, class Tick = no_tick>
 HD void fft_forward_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist, cplx* exch, Sync&& sync, WSync&& wsync, Tick&& tick = Tick{}) {
-#if defined(DCTFHE_ABLATE_FFT)
-  return;
-#endif
   using G = fft_geom<LOGM, P>;
   constexpr int S = G::S;
   static_for<0, NP>([&](auto U) {
     constexpr int u = decltype(U)::value;
     static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = mul_root64<j*(64 / (4 * P)), +1>(v[u][j]); });
   });
-  [[maybe_unused]] cplx bpre = cmk(1.0, 0.0);      // DCTFHE_PIPE_LOCAL: the next pass's twiddle base, read a pass ahead
   static_for<0, S>([&](auto I) {
     constexpr int i = decltype(I)::value;
     constexpr int R = G::radix(i);
     constexpr int W = G::weight(i);
-    if constexpr (i < S - 1 && W <= 64 && DCTFHE_PIPE_LOCAL) {
-      // this pass's twiddle base was read one pass ahead (bpre) wherever a pass precedes this one: a read issued here would sit BEHIND the
-      // previous pass's last gather in the wave's in-order LDS queue, and the first polynomial's butterflies would wait for all of it
-      cplx b;
-      if constexpr (i > 0) b = bpre; else b = tw[G::tw_offset(i) + (t % W)];
-      const cplx run0 = (i == 0) ? twist : cmk(1.0, 0.0);
-      static_for<0, NP>([&](auto U) {
-        constexpr int u = decltype(U)::value;
-        cplx y[P];
-        small_dft<P, 1, -1>::run(v[u], y);
-        cplx run = run0;
-        if constexpr (i == 0) y[0] = cmul(y[0], run);
-        static_for<1, R>([&](auto K) { constexpr int k = decltype(K)::value; run = cmul(run, b); y[k] = cmul(y[k], run); });
-        cplx* ex = exch + u * G::EXCH_ELEMS;
-        if constexpr (u == 0 && i + 1 < S - 1) bpre = tw[G::tw_offset(i + 1) + (t % G::weight(i + 1))];
-        wsync();
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i + 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
-        wsync();
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i + 1>(pass_addr<LOGM, P, i + 1>(t, j))]; });
-        DCTFHE_PIPE_SCHED_BARRIER();
-      });
-    } else if constexpr (i < S - 1) {
+    if constexpr (i < S - 1) {
       const cplx b = tw[G::tw_offset(i) + (t % W)];
       const cplx run0 = (i == 0) ? twist : cmk(1.0, 0.0);
-      if constexpr (DCTFHE_PIPE_LOCAL && i + 1 < S - 1) bpre = tw[G::tw_offset(i + 1) + (t % G::weight(i + 1))];
       if constexpr (W > 64) tick.template at<0>();        // phase 0: accumulator update, decomposition
       if constexpr (W <= 64) wsync(); else sync();      // nobody still gathers from the buffers about to be written
       if constexpr (W > 64) tick.template at<1>();        // phase 1: waiting at the leading barrier
-#if DCTFHE_SHARED_TWIDDLES
       // butterflies of all NP polynomials, then ONE running twiddle product applied to all of them (the chain costs
       // as much as applying it: 4 f64 instructions per step), then the scatters
       cplx y[NP][P];
@@ -441,48 +380,16 @@ HD void fft_forward_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       static_for<0, NP>([&](auto U) {
         constexpr int u = decltype(U)::value;
         cplx* ex = exch + u * G::EXCH_ELEMS;
-#if defined(DCTFHE_ABLATE_EXCH)
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = y[u][(j + 1) % P]; });
-#else
         static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i + 1>(pass_addr<LOGM, P, i>(t, j))] = y[u][j]; });
-#endif
       });
-#else
-      static_for<0, NP>([&](auto U) {
-        constexpr int u = decltype(U)::value;
-        cplx y[P];
-        small_dft<P, 1, -1>::run(v[u], y);
-        cplx run = run0;
-        if constexpr (i == 0) y[0] = cmul(y[0], run);
-        static_for<1, R>([&](auto K) { constexpr int k = decltype(K)::value; run = cmul(run, b); y[k] = cmul(y[k], run); });
-        cplx* ex = exch + u * G::EXCH_ELEMS;
-#if defined(DCTFHE_ABLATE_EXCH)   // timing experiments only: no LDS traffic, wrong results
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = y[(j + 1) % P]; });
-#else
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i + 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
-#endif
-        DCTFHE_FFT_SCHED_BARRIER();
-      });
-#endif
       if constexpr (W > 64) tick.template at<2>();        // phase 2: butterflies + twiddles + scatter of the cross-wave pass
       if constexpr (W <= 64) wsync(); else sync();
       if constexpr (W > 64) tick.template at<3>();        // phase 3: waiting at the barrier before the gather
-#if defined(__HIP_DEVICE_COMPILE__)
-      // Experiment, off: the two waves of a SIMD (w and w + 4 of a 512-thread workgroup) leave this barrier together and gather, compute
-      // and scatter in the same phase; holding the younger half back by 64-512 cycles de-phases them for the barrier-free stretch that
-      // follows: -0.5 % at N = 8192, -1.6 % at N = 4096 (profiles/r03_exp_stagger.log).  NOT shipped: the same one-line branch in the
-      // single-transform path made hipcc demote that kernel's register arrays to scratch (170 -> 2 716 ms per launch, same log) -- a
-      // third of a per cent is not worth standing that close to the cliff.
-      if constexpr (W > 64 && DCTFHE_PAIR_STAGGER > 0) { if (threadIdx.x & 256) __builtin_amdgcn_s_sleep(DCTFHE_PAIR_STAGGER); }
-#endif
       static_for<0, NP>([&](auto U) {
         constexpr int u = decltype(U)::value;
         const cplx* ex = exch + u * G::EXCH_ELEMS;
-#if !defined(DCTFHE_ABLATE_EXCH)
         static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i + 1>(pass_addr<LOGM, P, i + 1>(t, j))]; });
-#endif
       });
-      DCTFHE_FFT_SCHED_BARRIER();
     } else {
       static_for<0, NP>([&](auto U) {
         constexpr int u = decltype(U)::value;
@@ -493,7 +400,6 @@ HD void fft_forward_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
           static_for<0, P / R>([&](auto Gp) { constexpr int g = decltype(Gp)::value; small_dft<R, 1, -1>::run(v[u] + g * R, y + g * R); });
         }
         static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = y[j]; });
-        DCTFHE_FFT_SCHED_BARRIER();
       });
     }
   });
@@ -502,51 +408,21 @@ HD void fft_forward_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
 
 template <int LOGM, int P, int NP, class Sync, class WSync, class Tick = no_tick>
 HD void fft_inverse_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist, cplx* exch, Sync&& sync, WSync&& wsync, Tick&& tick = Tick{}) {
-#if defined(DCTFHE_ABLATE_FFT)
-  return;
-#endif
   using G = fft_geom<LOGM, P>;
   constexpr int S = G::S;
-  [[maybe_unused]] cplx bpre = cmk(1.0, 0.0);      // DCTFHE_PIPE_LOCAL: the next pass's twiddle base, read a pass ahead (see fft_forward_n)
   static_for<0, S>([&](auto Irev) {
     constexpr int i = S - 1 - decltype(Irev)::value;
     constexpr int R = G::radix(i);
     constexpr int W = G::weight(i);
     if constexpr (i > 0 && G::weight(i > 0 ? i - 1 : 0) > 64) tick.template at<6>();             // phase 6: the passes that end in wave-local exchanges
-    constexpr bool PIPE = DCTFHE_PIPE_LOCAL && i > 0 && G::weight(i > 0 ? i - 1 : 0) <= 64;   // this pass ends in a wave-local exchange
-    constexpr bool PREV_PIPE = DCTFHE_PIPE_LOCAL && i < S - 1 && W <= 64;                      // ... and so did the one before it
     cplx b = cmk(1.0, 0.0), run0 = cmk(1.0, 0.0);
     if constexpr (i < S - 1) {
-      if constexpr (PREV_PIPE) b = bpre; else b = tw[G::tw_offset(i) + (t % W)];
+      b = tw[G::tw_offset(i) + (t % W)];
       if constexpr (i == 0) run0 = twist;
     }
-    if constexpr (PIPE) {
-      static_for<0, NP>([&](auto U) {
-        constexpr int u = decltype(U)::value;
-        if constexpr (i < S - 1) {
-          cplx run = run0;
-          static_for<1, R>([&](auto K) { constexpr int k = decltype(K)::value; run = cmul(run, b); v[u][k] = cmulc(v[u][k], run); });
-        }
-        cplx y[P];
-        if constexpr (R == P) {
-          small_dft<P, 1, +1>::run(v[u], y);
-        } else {
-          static_for<0, P / R>([&](auto Gp) { constexpr int g = decltype(Gp)::value; small_dft<R, 1, +1>::run(v[u] + g * R, y + g * R); });
-        }
-        cplx* ex = exch + u * G::EXCH_ELEMS;
-        if constexpr (u == 0) bpre = tw[G::tw_offset(i - 1) + (t % G::weight(i - 1))];
-        wsync();
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i - 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
-        wsync();
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i - 1>(pass_addr<LOGM, P, i - 1>(t, j))]; });
-        DCTFHE_PIPE_SCHED_BARRIER();
-      });
-      return;
-    }
-    constexpr bool FUSED = DCTFHE_FUSED_INV && i > 0 && i < S - 1 && R == P && P == 8;
+    constexpr bool FUSED = i > 0 && i < S - 1 && R == P && P == 8;
     [[maybe_unused]] cplx pw[3], cw8;
     if constexpr (FUSED) fused_idft_factors(b, pw, cw8);
-#if DCTFHE_SHARED_TWIDDLES
     if constexpr (i < S - 1 && !FUSED) {
       cplx run = run0;
       if constexpr (i == 0) static_for<0, NP>([&](auto U) { constexpr int u = decltype(U)::value; v[u][0] = cmulc(v[u][0], run); });
@@ -556,16 +432,8 @@ HD void fft_inverse_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
         static_for<0, NP>([&](auto U) { constexpr int u = decltype(U)::value; v[u][k] = cmulc(v[u][k], run); });
       });
     }
-#endif
     static_for<0, NP>([&](auto U) {
       constexpr int u = decltype(U)::value;
-#if !DCTFHE_SHARED_TWIDDLES
-      if constexpr (i < S - 1 && !FUSED) {
-        cplx run = run0;
-        if constexpr (i == 0) v[u][0] = cmulc(v[u][0], run);
-        static_for<1, R>([&](auto K) { constexpr int k = decltype(K)::value; run = cmul(run, b); v[u][k] = cmulc(v[u][k], run); });
-      }
-#endif
       cplx y[P];
       if constexpr (FUSED) {
         fused_idft<P, 1, 0>::run(v[u], y, pw, cw8);
@@ -576,15 +444,10 @@ HD void fft_inverse_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       }
       if constexpr (i > 0) {
         cplx* ex = exch + u * G::EXCH_ELEMS;
-#if defined(DCTFHE_ABLATE_EXCH)
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = y[(j + 1) % P]; });
-#else
         static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i - 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
-#endif
       } else {
         static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = mul_root64<j*(64 / (4 * P)), -1>(y[j]); });
       }
-      DCTFHE_FFT_SCHED_BARRIER();
     });
     if constexpr (i > 0) {
       constexpr int Wp = G::weight(i - 1);
@@ -594,14 +457,11 @@ HD void fft_inverse_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       static_for<0, NP>([&](auto U) {
         constexpr int u = decltype(U)::value;
         const cplx* ex = exch + u * G::EXCH_ELEMS;
-#if !defined(DCTFHE_ABLATE_EXCH)
         static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i - 1>(pass_addr<LOGM, P, i - 1>(t, j))]; });
-#endif
       });
       if constexpr (Wp > 64) tick.template at<9>();       // phase 9: the cross-wave gather
       if constexpr (Wp <= 64) wsync(); else sync();
       if constexpr (Wp > 64) tick.template at<10>();      // phase 10: waiting at the trailing barrier
-      DCTFHE_FFT_SCHED_BARRIER();
     }
   });
 }

@@ -557,18 +557,17 @@ struct pbs_launch {
   int accumulate;
   uint64_t body_add;
   uint64_t* dummy;            // D_out+1 words: sink for the padded groups of the last workgroup
-  int bsk_wrap;               // cache experiments only (0 in the library)
+  int bsk_wrap;               // cache experiments only (0 in the library; kept for the register allocation: pbs_args)
   int pf_parts;               // 0: no L2 warm-up; else each workgroup touches 1/pf_parts of the next key rows
 };
 
-// KLDS > 0: the GROUPS waves of a workgroup share each key tile through a ring of KLDS tiles in LDS (pbs_core.h, pbs_thread)
-template <int LOGN, int K, int L, int P, int MB, int KLDS>
+template <int LOGN, int K, int L, int P, int MB>
 constexpr size_t pbs_lds_bytes(int groups) {
   using G = pbs_geom<LOGN, K, L, P, MB>;
-  return (size_t)G::TW_BYTES + (size_t)groups * G::GROUP_BYTES + (size_t)KLDS * 3 * (K + 1) * G::T * 16;
+  return (size_t)G::TW_BYTES + (size_t)groups * G::GROUP_BYTES;
 }
 
-template <int LOGN, int K, int L, int P, int GROUPS, int MB = 0, int KLDS = 0>
+template <int LOGN, int K, int L, int P, int GROUPS, int MB = 0>
 __global__ void __launch_bounds__((pbs_geom<LOGN, K, L, P, MB>::T * GROUPS), ((P >= 16 || (pbs_geom<LOGN, K, L, P, MB>::T * GROUPS) >= 512) ? 1 : 2))
 pbs_kernel(pbs_launch a) {
   using G = pbs_geom<LOGN, K, L, P, MB>;
@@ -582,12 +581,6 @@ pbs_kernel(pbs_launch a) {
     for (int x = threadIdx.x; x < G::ZLUT_ELEMS; x += blockDim.x) zl[x] = x < (1 << G::ZLO) ? a.wtab[x] : a.wtab[(size_t)(x - (1 << G::ZLO)) << G::ZLO];
   }
   __syncthreads();
-#if defined(DCTFHE_WAVE_STAGGER)   // experiment: the free-running waves of a workgroup (one ciphertext each) start DCTFHE_WAVE_STAGGER x ~4 100 clocks apart
-  if constexpr (T <= 64) { const int w0 = (threadIdx.x >> 6) + ((blockIdx.x >> 8) & 1) * GROUPS; for (int z = 0; z < w0 * DCTFHE_WAVE_STAGGER; z++) __builtin_amdgcn_s_sleep(64); }
-#endif
-#if defined(DCTFHE_STAGGER)   // experiment: desynchronise co-resident workgroups by half a transform
-  if ((blockIdx.x >> 8) & 1) for (int z = 0; z < DCTFHE_STAGGER; z++) __builtin_amdgcn_s_sleep(64);
-#endif
   const int g = threadIdx.x / T, t = threadIdx.x % T;
   size_t e = (size_t)blockIdx.x * GROUPS + g;
   const bool live = e < a.count;
@@ -614,19 +607,11 @@ pbs_kernel(pbs_launch a) {
   A.zlut = MB ? tw + G::TW_LDS_ELEMS : nullptr;
   if constexpr (G::TWIST_LDS) A.twist = tw + G::F::TW_TOTAL; else A.twist = a.tw + G::F::TW_TOTAL;
   A.pf_rank = (int)((blockIdx.x / 8) % (unsigned)(a.pf_parts > 0 ? a.pf_parts : 1));   // blocks b and b+8 share an XCD (round-robin dispatch; speed only)
-  A.kring = reinterpret_cast<const cplx*>(per_group + (size_t)GROUPS * G::GROUP_BYTES);
-  A.kring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(per_group + (size_t)GROUPS * G::GROUP_BYTES);
-  A.kwave = g;
-#if defined(DCTFHE_ABLATE_BARRIER)   // timing experiments only (tools/exp_pbs.hip): no workgroup barriers, wrong results
-  if constexpr (true) {
-#else
   if constexpr (T <= 64) {
-#endif
     // one ciphertext per wave (or less): every exchange and the rotation stage stay inside the wave, whose LDS
     // queue is in order -- no workgroup barrier anywhere in the loop, the waves of a workgroup run decoupled
-    pbs_thread<LOGN, K, L, P, MB, KLDS, GROUPS>(A, t, tw, stage, exch, accl, pf_dump, [] { __builtin_amdgcn_wave_barrier(); }, [] { __builtin_amdgcn_wave_barrier(); });
+    pbs_thread<LOGN, K, L, P, MB>(A, t, tw, stage, exch, accl, pf_dump, [] { __builtin_amdgcn_wave_barrier(); }, [] { __builtin_amdgcn_wave_barrier(); });
   } else {
-    static_assert(KLDS == 0 || T <= 64, "key tiles through LDS: one wave per ciphertext");
     pbs_thread<LOGN, K, L, P, MB>(A, t, tw, stage, exch, accl, pf_dump, [] { __syncthreads(); }, [] { __builtin_amdgcn_wave_barrier(); });
   }
 }

@@ -28,39 +28,9 @@ namespace dctfhe {
 
 // key loads in flight per thread between two waits: 8 spilled more than it hid, 2 exposed the latency
 // (measured on T5 / B / T4: 4 is +10..20% over 8)
-// accumulator polynomials kept in LDS rather than registers: -1 = per-kernel rule (pbs_geom::NL_AUTO), 0/1 force
-#ifndef PBS_LDS_POLYS
-#define PBS_LDS_POLYS (-1)
-#endif
-
-#ifndef PBS_KEY_BATCH
-#define PBS_KEY_BATCH 4
-#endif
-
-#ifndef PBS_PAIR
-#define PBS_PAIR 1
-#endif
-#ifndef PBS_MB_BAR_A
-#define PBS_MB_BAR_A() DCTFHE_SCHED_BARRIER()
-#endif
-#ifndef PBS_MB_BAR_B
-#define PBS_MB_BAR_B() ((void)0)     // no barrier after the fold: hipcc may hoist the next batch's loads over it (+3 %)
-#endif
-#ifndef PBS_MBG_BAR_B
-#define PBS_MBG_BAR_B() DCTFHE_SCHED_BARRIER()
-#endif
-#ifndef PBS_STD_BAR_B
-#define PBS_STD_BAR_B() DCTFHE_SCHED_BARRIER()
-#endif
-
-// one-level tiers keep the accumulator as 32-bit torus values (see pbs_geom::ACC32)
-#ifndef PBS_ACC32
-#define PBS_ACC32 1
-#endif
-
-#ifndef PBS_PF_DIST
-#define PBS_PF_DIST 2
-#endif
+constexpr int PBS_KEY_BATCH = 4;
+// the L2 warm-up touches the key this many iterations ahead (pbs_thread)
+constexpr int PBS_PF_DIST = 2;
 
 // MB = 1: two-bit blind rotation (see pbs_thread).
 template <int LOGN, int K, int L, int P, int MB = 0>
@@ -80,7 +50,7 @@ struct pbs_geom {
   // PAIR: the K+1 = 2 forward transforms of a one-level k = 1 bootstrap run interleaved (fft_forward_n), and so do
   // the two inverse ones: LDS scatter/gather of one polynomial overlaps the butterflies of the other, and the
   // barrier count per CMUX drops from 11 to 6.  Costs a second exchange buffer; the rotation stages alias the two.
-  static constexpr bool PAIR = (PBS_PAIR || MB) && K == 1 && L == 1;
+  static constexpr bool PAIR = K == 1 && L == 1;
 #if defined(__HIP_DEVICE_COMPILE__)
   static_assert(!MB || F::T >= 64, "two-bit kernels assume one ciphertext per wave");
 #endif
@@ -89,13 +59,12 @@ struct pbs_geom {
   static constexpr int NG = P / RL;                    // small transforms per thread in the last pass
   // k = 2 with two levels: both mask polynomials in LDS -- with one the kernel spilled 71 VGPRs (216 B/lane of scratch, 78 GB
   // written per launch of 12 288 ciphertexts: profiles/r02_pmc_tiers.txt)
-  static constexpr int NL_AUTO = (K >= 2 && L >= 2) ? 2 : (K >= 2 || L >= 3) ? 1 : 0;
-  static constexpr int NL = PBS_LDS_POLYS < 0 ? NL_AUTO : (PBS_LDS_POLYS < K ? PBS_LDS_POLYS : K);
+  static constexpr int NL = (K >= 2 && L >= 2) ? 2 : (K >= 2 || L >= 3) ? 1 : 0;
   // ACC32: a one-level gadget rounds every accumulator coefficient to 2^-(beta+1) >= 2^-29 of the torus at each step anyway
   // (beta <= 28 enforced by the library for such tiers), so the accumulator of a one-level tier is kept as the top 32 bits:
   // the rounding of each update (2^-33) is far below that, the registers and the LDS traffic of the rotation halve, and
   // the f64 -> torus conversion drops from 8+3 to 5+1 instructions.  Multi-level tiers (convolution-grade outputs) keep 64.
-  static constexpr bool ACC32 = PBS_ACC32 && L == 1;
+  static constexpr bool ACC32 = L == 1;
   using acc_t = std::conditional_t<ACC32, uint32_t, uint64_t>;
   static constexpr int ACC_BYTES = (int)sizeof(acc_t);
   static constexpr int STAGE_BYTES = N * ACC_BYTES;
@@ -208,14 +177,13 @@ struct pbs_args {
   int D_out;
   int accumulate;             // 0: out = extract(ACC) (mask beyond K*N zeroed); 1: out += extract(ACC)
   uint64_t body_add;          // added to the body word (accumulate mode: the "- v" of a bit step)
-  int bsk_wrap;               // 0 = off; >0: key bit i reads BSK[i % bsk_wrap] (cache experiments only)
+  int bsk_wrap;               // 0 = off; >0: key bit i reads BSK[i % bsk_wrap] (cache experiments only; the library passes 0)
+                              // -- kept because deleting it and its two selects moved hipcc's register allocation: 16-124 B/lane of new
+                              //    scratch on ten one-bit kernels (<10,2,2,8,2> 0 -> 96, <11,1,2,8,2> 40 -> 124, <8,2,2,8,8> 0 -> 92)
   const cplx* wtab;           // MB: e^{i pi m / N}, m < 2N (monomials in the Fourier domain), then e^{2 pi i k / 8}, k < 8
   const cplx* zlut;           // MB, device: the same roots as two LDS tables, lo[2^ZLO] then hi[2^ZHI] (nullptr: gather from wtab)
   const cplx* twist;          // the T twist bases e^{i pi t/N} (entries TW_TOTAL.. of the twiddle table; LDS or global)
   int pf_rank, pf_parts;      // L2 warm-up: this workgroup touches part pf_rank of pf_parts of BSK[i + PF_DIST]
-  const cplx* kring;          // KLDS: ring of key tiles in LDS shared by the KW waves of the workgroup (generic pointer for the reads)
-  uint32_t kring_lds;         // ... its LDS byte address (what the LDS-DMA instruction takes in M0)
-  int kwave;                  // ... this wave's index among the KW
 };
 
 // The whole bootstrap for one ciphertext, executed by thread t of its group.
@@ -227,15 +195,7 @@ struct pbs_args {
 // PAIR of key bits, no rotation through LDS -- and the monomials act in the Fourier domain, where X^e is the pointwise
 // factor zeta^e, zeta = e^{i pi (1-4k)/N} the evaluation point (spectrum_freq).  Price: three key blocks per pair
 // instead of two, and the key/FFT noise of three products scaled by |X^e - 1|^2 = 2 (dctfhe/params.py prices it).
-// KLDS > 0 (device, general two-bit form, one wave per ciphertext): the KW waves of a workgroup -- KW ciphertexts -- walk the key in
-// lock-step and share every key tile through LDS: each (gadget row, point j) step of 3 (K+1) key vectors is fetched ONCE per workgroup
-// by LDS-DMA (global_load_lds_dwordx4: every wave brings 1/KW of it, no registers), KLDS - 1 steps ahead into a ring of KLDS tiles,
-// and read by all KW waves with ds_read_b128.  Without it every wave pulls its own copy of the same lines through the CU's vector L1
-// (64 B/clk): 8 waves x 221 KB per iteration on the k = 2 one-level tier, the path that kernel saturated (profiles/r02_exp_ablations.log).
-// Protocol per step s: wait until this wave's DMAs of step s have landed (counted vmcnt: the younger ones stay in flight), workgroup
-// barrier (=> everybody's part of step s is there, and everybody is done reading step s - 1), issue the DMAs of step s + KLDS - 1 into
-// the tile step s - 1 used, read step s.
-template <int LOGN, int K, int L, int P, int MB = 0, int KLDS = 0, int KW = 1, class Sync, class WSync>
+template <int LOGN, int K, int L, int P, int MB = 0, class Sync, class WSync>
 HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw, cplx* exch, uint64_t* accl_raw, uint32_t* pf_dump, Sync&& sync, WSync&& wsync) {
   using G = pbs_geom<LOGN, K, L, P, MB>;
   constexpr int N = G::N, M = G::M, T = G::T, NL = G::NL;
@@ -293,53 +253,10 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
   constexpr uint32_t USTEP = 4u * (uint32_t)(M / (P * G::RL));
   if constexpr (MB) ulow0 = (uint32_t)(1 - 4 * spectrum_freq<G::LOGM, P>(P * t)) & (2 * N - 1);
 
-#if defined(DCTFHE_DEVICE)
-  constexpr bool KL = KLDS > 0;
-#else
-  constexpr bool KL = false;       // the host emulator reads the key where it lies
-#endif
-  constexpr int K_SPI = G::ROWS * P;                       // steps (gadget row, point j) per iteration
-  constexpr int K_STEP = 3 * (K + 1) * T;                  // complex values per step: blocks w x output polynomials q x T lanes
-  constexpr int K_LPW = KL ? 3 * (K + 1) * 64 / KW : 64;   // 16-byte lanes per wave and step
-  constexpr int K_CH = (K_LPW + 63) / 64, K_CHL = K_LPW / K_CH;       // DMA instructions per wave and step, active lanes in each
-  static_assert(!KL || (MB && !G::PAIR && L == 1 && T == 64 && KLDS >= 2 && (3 * (K + 1) * 64) % KW == 0 && K_LPW % K_CH == 0 && K_SPI % KLDS == 0),
-                "key tiles through LDS: general two-bit form, one wave per ciphertext, tile count divides the steps per iteration");
-  uint32_t koff[K_CH];       // byte offset of this lane's 16 bytes of chunk i inside a pair's key, without the step's (row, j) part
-#if defined(DCTFHE_DEVICE)
-  [[maybe_unused]] const uint32_t kwave = KL ? DCTFHE_UNIFORM(A.kwave) : 0;
-  [[maybe_unused]] auto kissue = [&](const cplx* key_pair /* wave-uniform */, auto RowJ, auto Buf) {
-    constexpr int s = decltype(RowJ)::value, row = s / P, j = s % P, buf = decltype(Buf)::value;
-    const uint64_t base = (uint64_t)(key_pair + ((size_t)row * (K + 1) * M + (size_t)j * T));
-    static_for<0, K_CH>([&](auto I) {
-      constexpr int i = decltype(I)::value;
-      const uint32_t dst = A.kring_lds + (uint32_t)((buf * K_STEP + (int)(kwave * K_CH + i) * K_CHL) * 16);
-      const uint64_t mask = K_CHL >= 64 ? ~0ull : ((1ull << K_CHL) - 1);
-      uint32_t keep_m0; uint64_t keep_exec;
-      const uint32_t vo = koff[i];
-      const uint64_t sb = base;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %4\n\ts_mov_b64 exec, %5\n\ts_nop 0\n\t"
-                   "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep_m0), "=&s"(keep_exec) : "v"(vo), "s"(sb), "s"(dst), "s"(mask) : "memory");
-    });
-  };
-  if constexpr (KL) {
-    static_for<0, K_CH>([&](auto I) {
-      constexpr int i = decltype(I)::value;
-      const uint32_t pos = (kwave * K_CH + i) * K_CHL + (uint32_t)t;          // 16-byte slot of this lane in the step's tile (t < K_CHL)
-      const uint32_t vi = pos / 64, tt = pos % 64, w = vi / (K + 1), q = vi % (K + 1);
-      koff[i] = ((w * G::ROWS * (K + 1) + q) * M + tt) * 16;
-    });
-    // steps 0 .. KLDS-2 of the first iteration
-    static_for<0, KLDS - 1>([&](auto S) { kissue(make_uniform(A.bsk), S, S); });
-  }
-#endif
-
   // zeta^m: on the device the product of the two LDS tables, on the host emulator (zlut == nullptr) the full table
   auto zeta = [&](uint32_t m) -> cplx {
-#if defined(DCTFHE_DEVICE) && !defined(DCTFHE_NO_ZLUT)      // (DCTFHE_NO_ZLUT: timing experiments, tools/exp_pbs.hip)
+#if defined(DCTFHE_DEVICE)
     return cmul(A.zlut[(1 << G::ZLO) + (m >> G::ZLO)], A.zlut[m & ((1u << G::ZLO) - 1)]);
-#elif defined(DCTFHE_DEVICE)
-    return A.wtab[m];
 #else
     return A.zlut ? cmul(A.zlut[(1 << G::ZLO) + (m >> G::ZLO)], A.zlut[m & ((1u << G::ZLO) - 1)]) : A.wtab[m];
 #endif
@@ -404,36 +321,13 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
               z2 = cmul(z2, root8((0u - a2u * (uint32_t)jp) * (8 / G::RL)));
             }
             cplx kk[3][K + 1];
-#if defined(DCTFHE_DEVICE)
-            if constexpr (KL) {
-              constexpr int s = row * P + j, ahead = s + KLDS - 1;
-              // this wave's DMAs of step s have landed when at most those of the KLDS - 2 younger steps are outstanding; its own
-              // reads of step s - 1 are over (lgkmcnt) before anybody may overwrite that tile
-              asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((KLDS - 2) * K_CH) : "memory");
-              __builtin_amdgcn_s_barrier();
-              asm volatile("" ::: "memory");
-              kissue(make_uniform(key + (ahead >= K_SPI ? (size_t)3 * G::BSK_ELEMS_PER_KEYBIT : 0)), std::integral_constant<int, ahead % K_SPI>{},
-                     std::integral_constant<int, ahead % KLDS>{});
-              const cplx* tile = A.kring + (s % KLDS) * K_STEP;
-              static_for<0, 3>([&](auto Ww) {
-                constexpr int w = decltype(Ww)::value;
-                static_for<0, K + 1>([&](auto Q) { constexpr int q = decltype(Q)::value; kk[w][q] = tile[(w * (K + 1) + q) * 64 + t]; });
-              });
-            } else
-#endif
-            {
             static_for<0, 3>([&](auto Ww) {
               constexpr int w = decltype(Ww)::value;
               static_for<0, K + 1>([&](auto Q) {
                 constexpr int q = decltype(Q)::value;
-#if defined(DCTFHE_ABLATE_BSK)
-                kk[w][q] = cmk(1.0 + w, 0.5 * q + row);
-#else
                 kk[w][q] = load_uniform_base(key + (((size_t)w * G::ROWS * (K + 1) + (size_t)row * (K + 1) + q) * M + j * T), (unsigned)t);    // uniform base + lane index
-#endif
               });
             });
-            }
             DCTFHE_SCHED_BARRIER();
             const cplx m1 = cmk(z1.re - 1.0, z1.im), m2 = cmk(z2.re - 1.0, z2.im);
             cplx m12 = cmul(z1, z2); m12.re -= 1.0;
@@ -442,7 +336,7 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
               const cplx bundle = cfma(m12, kk[2][q], cfma(m2, kk[1][q], cmul(m1, kk[0][q])));
               if constexpr (row == 0) out[q][j] = cmul(v[j], bundle); else out[q][j] = cfma(v[j], bundle, out[q][j]);
             });
-            PBS_MBG_BAR_B();
+            DCTFHE_SCHED_BARRIER();
           });
           tick.template at<5>();                          // phase 5: the products with the key of one gadget row
         });
@@ -487,14 +381,10 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
             constexpr int w = decltype(Ww)::value;
             static_for<0, 2>([&](auto Rr) {
               constexpr int r = decltype(Rr)::value;
-#if defined(DCTFHE_ABLATE_BSK)
-              kk[w][r] = cmk(1.0 + w, 0.5 * q + r);
-#else
               kk[w][r] = load_uniform_base(key + ((size_t)((w * 2 + r) * 2 + q) * M + j * T), (unsigned)t);      // uniform base + zero-extended lane index: scalar address math
-#endif
             });
           });
-          PBS_MB_BAR_A();
+          DCTFHE_SCHED_BARRIER();
           const cplx m1 = cmk(z1.re - 1.0, z1.im), m2 = cmk(z2.re - 1.0, z2.im);
           cplx m12 = cmul(z1, z2); m12.re -= 1.0;
           static_for<0, 2>([&](auto Rr) {
@@ -502,7 +392,7 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
             const cplx bundle = cfma(m12, kk[2][r], cfma(m2, kk[1][r], cmul(m1, kk[0][r])));
             if constexpr (r == 0) out[q][j] = cmul(v[0][j], bundle); else out[q][j] = cfma(v[1][j], bundle, out[q][j]);
           });
-          PBS_MB_BAR_B();
+          // (no barrier after the fold: hipcc may hoist the next batch's loads over it, +3 %)
         });
       });
     } else if constexpr (G::PAIR) {
@@ -537,12 +427,8 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
           cplx k0[KB], k1[KB];
           static_for<0, KB>([&](auto J) {
             constexpr int j = decltype(J)::value;
-#if defined(DCTFHE_ABLATE_BSK)
-            k0[j] = cmk(1.0 + j, 0.5 * q); k1[j] = cmk(0.5 * q, 1.0 + j);
-#else
             k0[j] = load_uniform_base(bsk_i + ((size_t)(0 * 2 + q) * M + (j0 + j) * T), (unsigned)t);
             k1[j] = load_uniform_base(bsk_i + ((size_t)(1 * 2 + q) * M + (j0 + j) * T), (unsigned)t);
-#endif
           });
           DCTFHE_SCHED_BARRIER();
           static_for<0, KB>([&](auto J) {
@@ -613,15 +499,11 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
             cplx kb[KB];
             static_for<0, KB>([&](auto J) {
               constexpr int j = decltype(J)::value;
-#if defined(DCTFHE_ABLATE_BSK)   // timing experiments only (tools/exp_pbs.hip): no key traffic
-              kb[j] = cmk(1.0 + j, 0.5 * q);
-#else
               kb[j] = load_uniform_base(row + ((size_t)q * M + (j0 + j) * T), (unsigned)t);
-#endif
             });
             DCTFHE_SCHED_BARRIER();
             static_for<0, KB>([&](auto J) { constexpr int j = decltype(J)::value; out[q][j0 + j] = cfma(v[j0 + j], kb[j], out[q][j0 + j]); });
-            PBS_STD_BAR_B();
+            DCTFHE_SCHED_BARRIER();
           });
         });
       });
@@ -672,9 +554,6 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
   tick.template at<0>();
   if (blockIdx.x == DCTFHE_PHASE_TIMERS && (threadIdx.x & 63) == 0)          // every wave of one workgroup reports: [wave][phase]
     for (int k = 0; k < 12; k++) dctfhe_phase_ticks[(threadIdx.x >> 6) * 12 + k] = tick.acc[k];
-#endif
-#if defined(DCTFHE_DEVICE)
-  if constexpr (KL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the tiles fetched ahead of the last step (key padding) land before the wave ends
 #endif
   // sample extract (coefficient 0) straight into the output LWE ciphertext
   uint64_t* o = A.out;

@@ -44,8 +44,7 @@ typedef struct {
   int32_t lk, betak;    /* key-switch gadget: levels, base log */
   int32_t ksk_share;    /* >= 0: reuse the key-switch key of that (earlier) tier; -1: own key */
   int32_t unroll;       /* key bits per blind-rotate iteration: 1, or 2 (k = 1, l = 1, n even; key of 3n/2 blocks) */
-  int32_t key_lds;      /* 1: the waves of a workgroup share each bootstrap-key tile through LDS (LDS-DMA ring) instead of each pulling its own
-                           copy through L1 -- (k, l, N, unroll) = (2, 1, 1024, 2) only; same results, measured no faster */
+  int32_t reserved;     /* must be 0 (formerly key_lds; kept so that the evaluation-key blob layout does not change) */
   double lwe_sigma;     /* noise std of key-switch-key rows (fraction of the torus) */
   double glwe_sigma;    /* noise std of bootstrap-key rows */
 } dctfhe_tier;

@@ -75,11 +75,13 @@ def test_seed_bytes():
 
 
 # ------------------------------------------------------------------------------------------ parameters
-def _params(**over):
+def _params(reserved=0, **over):
     from dctfhe.engine import make_params
     t = dict(n=40, k=1, logN=10, l=2, beta=10, lk=4, betak=4, lwe_sigma=2.0 ** -30, glwe_sigma=2.0 ** -40)
     t.update(over)
-    return make_params(1024, 40, [t], 2.0 ** -50)
+    p = make_params(1024, 40, [t], 2.0 ** -50)
+    p.tiers[0].reserved = reserved
+    return p
 
 
 def _err(L):
@@ -101,7 +103,7 @@ def test_params_check_accepts_the_catalogues(L):
     (dict(betak=-3), "bad key-switch gadget"), (dict(betak=0), "bad key-switch gadget"), (dict(lk=-1), "bad key-switch gadget"),
     (dict(lk=64, betak=1), "bad key-switch gadget"), (dict(k=0), "k or logN out of range"), (dict(k=3), "k or logN out of range"),
     (dict(logN=14), "k or logN out of range"), (dict(lwe_sigma=-1.0), "noise parameter"), (dict(glwe_sigma=float("nan")), "noise parameter"),
-    (dict(key_lds=1), "key_lds"), (dict(key_lds=2, k=2, logN=10, l=1, beta=20, unroll=2), "k*N exceeds D")])
+    (dict(reserved=1), "reserved must be 0"), (dict(k=2, logN=10, l=1, beta=20, unroll=2), "k*N exceeds D")])
 def test_params_check_rejects(L, over, needle):
     assert L.dctfhe_params_check(C.byref(_params(**over))) != 0
     assert needle in _err(L), _err(L)

@@ -120,7 +120,7 @@ struct dctfhe_eval_keys {
 };
 using dctfhe_keys = dctfhe_eval_keys;   // the server-side code below says K for the evaluation keys
 
-enum { OP_CONV = 1, OP_ADD = 2, OP_SUMPOOL = 3, OP_LUT = 4 };
+enum { OP_CONV = 1, OP_ADD = 2, OP_SUMPOOL = 3, OP_LUT = 4, OP_MAXPOOL = 5 };
 struct Op {
   int32_t type, src0, src1, dst;
   int32_t ip[12];
@@ -196,6 +196,114 @@ struct dctfhe_circuit {
   }
 };
 
+// ---- max pool (OP_MAXPOOL): separable passes, rows then columns; each pass a log-depth tree of pairwise maxima
+// max(a, b) = b + relu(a - b) over the window's in-range taps.  Late pairing: a pass of L = ceil(log2 max taps) levels; at level l an
+// output with m candidates combines its first 2 * max(0, m - 2^(L-l-1)) candidates pairwise (a = the even one, b = the odd one) and
+// carries the rest, so every output reaches one candidate at the last level (dctfhe/compile.py pool_level_pairs is the same rule).  A
+// level writes its output rows as [pair results in output order][carried candidates in output order]: the gather copies each pair's b
+// (and each carried row) there, and the difference bootstraps accumulate into the first `pairs` rows -- one contiguous batch.
+struct PoolLevel {
+  int src, dst;            // 0: the op's input, 1 / 2: level buffers A / B, 3: the op's output
+  size_t n_dst, pairs;     // rows written; the first `pairs` of them take a bootstrap
+  size_t g_off, a_off, b_off;   // int32 offsets into PoolPlan::maps: gather map [n_dst], ia / ib [pairs] (rows of the source)
+};
+struct PoolPlan {
+  std::vector<PoolLevel> lv;
+  size_t rows_buf[2] = {0, 0};  // rows of level buffers A and B
+  size_t pairs_per_batch = 0;
+  DevBuf maps;
+};
+static int pool_out_size(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
+// pairwise maxima of one image: every output of a pass costs its in-range taps minus one
+static int64_t pool_pairs(int C, int H, int W, int k, int s, int p) {
+  auto pass = [&](int n) {
+    int64_t t = 0;
+    for (int o = 0; o < pool_out_size(n, k, s, p); o++)
+      for (int j = 0; j < k; j++) t += (o * s - p + j >= 0 && o * s - p + j < n) ? 1 : 0;
+    return t - pool_out_size(n, k, s, p);
+  };
+  return (int64_t)C * H * pass(W) + (int64_t)C * pool_out_size(W, k, s, p) * pass(H);
+}
+static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, PoolPlan* P) {
+  const int Ho = pool_out_size(H, k, s, p), Wo = pool_out_size(W, k, s, p);
+  if ((double)batch * C * H * W >= 2147483647.0) return fail("max pool: %d x %d x %d x %d rows exceed the int32 index maps", batch, C, H, W);
+  std::vector<int32_t> maps;
+  std::vector<std::vector<int32_t>> cand;      // per output of the current pass: its candidates' rows in the current source buffer
+  int cur = 0;                                 // buffer the candidates live in
+  int next_buf = 1;
+  auto run_pass = [&](size_t outer, int n_in, int inner, int n_out, const std::vector<int32_t>& row_of) {
+    // row_of[(ou * n_in + x) * inner + i]: row of input element (ou, x, i) in buffer `cur`
+    const size_t nout = outer * (size_t)n_out * inner;
+    cand.assign(nout, {});
+    int mmax = 1;
+    for (size_t e = 0; e < nout; e++) {
+      const int i = (int)(e % inner), o = (int)((e / inner) % n_out);
+      const size_t ou = e / ((size_t)inner * n_out);
+      for (int j = 0; j < k; j++) {
+        const int x = o * s - p + j;
+        if (x >= 0 && x < n_in) cand[e].push_back(row_of[(ou * n_in + x) * inner + i]);
+      }
+      mmax = std::max(mmax, (int)cand[e].size());
+    }
+    int L = 0;
+    while ((1 << L) < mmax) L++;
+    for (int lev = 0; lev < L; lev++) {
+      const int cap = 1 << (L - lev - 1);
+      PoolLevel pl{cur, next_buf, 0, 0, maps.size(), 0, 0};
+      std::vector<int32_t> g, ia, ib, carried_src;
+      std::vector<std::pair<size_t, int>> carried;     // (output, index into its candidates)
+      std::vector<std::vector<int32_t>> nc(nout);
+      for (size_t e = 0; e < nout; e++) {
+        const int m = (int)cand[e].size(), pr = m > cap ? m - cap : 0;
+        for (int q = 0; q < pr; q++) {
+          nc[e].push_back((int32_t)g.size());
+          g.push_back(cand[e][2 * q + 1]);
+          ia.push_back(cand[e][2 * q]);
+          ib.push_back(cand[e][2 * q + 1]);
+        }
+        for (int q = 2 * pr; q < m; q++) carried.push_back({e, cand[e][q]});
+      }
+      pl.pairs = g.size();
+      for (auto& c : carried) { nc[c.first].push_back((int32_t)g.size()); g.push_back(c.second); }
+      pl.n_dst = g.size();
+      maps.insert(maps.end(), g.begin(), g.end());
+      pl.a_off = maps.size(); maps.insert(maps.end(), ia.begin(), ia.end());
+      pl.b_off = maps.size(); maps.insert(maps.end(), ib.begin(), ib.end());
+      P->rows_buf[next_buf - 1] = std::max(P->rows_buf[next_buf - 1], pl.n_dst);
+      P->lv.push_back(pl);
+      cand.swap(nc);
+      cur = next_buf;
+      next_buf = 3 - next_buf;
+    }
+  };
+  // row pass: [B*C*H][W] -> [B*C*H][Wo]
+  std::vector<int32_t> rows((size_t)batch * C * H * W);
+  for (size_t r = 0; r < rows.size(); r++) rows[r] = (int32_t)r;
+  run_pass((size_t)batch * C * H, W, 1, Wo, rows);
+  std::vector<int32_t> mid(cand.size());
+  for (size_t e = 0; e < cand.size(); e++) mid[e] = cand[e][0];
+  // column pass on the row pass's output: [B*C][H][Wo] -> [B*C][Ho][Wo]
+  run_pass((size_t)batch * C, H, Wo, Ho, mid);
+  // the op's output is in output order: the last level already wrote it so when every output ended on row e; else one more gather
+  bool identity = !P->lv.empty();
+  for (size_t e = 0; e < cand.size() && identity; e++) identity = cand[e][0] == (int32_t)e;
+  if (identity) {
+    P->lv.back().dst = 3;
+  } else {
+    PoolLevel pl{cur, 3, cand.size(), 0, maps.size(), 0, 0};
+    for (size_t e = 0; e < cand.size(); e++) maps.push_back(cand[e][0]);
+    pl.a_off = pl.b_off = maps.size();
+    P->lv.push_back(pl);
+  }
+  P->rows_buf[0] = P->rows_buf[1] = 0;
+  for (const PoolLevel& l : P->lv)
+    if (l.dst == 1 || l.dst == 2) P->rows_buf[l.dst - 1] = std::max(P->rows_buf[l.dst - 1], l.n_dst);
+  for (const PoolLevel& l : P->lv) P->pairs_per_batch += l.pairs;
+  HIPCHK(P->maps.alloc(maps.size() * 4));
+  if (!maps.empty()) HIPCHK(hipMemcpy(P->maps.p, maps.data(), maps.size() * 4, hipMemcpyHostToDevice));
+  return 0;
+}
+
 struct dctfhe_session {
   dctfhe_ctx* ctx = nullptr;
   dctfhe_circuit* circ = nullptr;
@@ -221,6 +329,9 @@ struct dctfhe_session {
   // timing: events are created once and reused by every run; bootstraps per tier and image are fixed by the circuit
   std::vector<hipEvent_t> ev_pool;
   int64_t pbs_per_image[DCTFHE_MAX_TIERS] = {};
+  // per op: the tree of a max pool (index maps in device memory) and its two level buffers (planner-owned, reused after the op)
+  std::vector<std::unique_ptr<PoolPlan>> pool;
+  std::vector<std::array<uint64_t*, 2>> pool_buf;
   ~dctfhe_session() {
     if (ctx) hipSetDevice(ctx->device);
     for (auto& o : owned) hipFree(o.second);
@@ -1048,7 +1159,8 @@ enum { CAT_LINEAR = 100, CAT_KS = 101 };  // 0..7: bootstrap of tier i
 // deff: mask words beyond it are known to be zero in every input (0 or >= D: no such knowledge).  The key switch then
 // runs on the first deff rows of the key only -- the same result bit for bit, deff/D of the work.
 static int dev_keyswitch(dctfhe_keys* K, int tier, const uint64_t* d_cts, size_t count, int shift, uint8_t* d_digits, uint64_t* d_bodies,
-                         uint64_t* d_small, Timers* tm, int deff = 0, size_t L = 0, uint64_t body_add = 0) {
+                         uint64_t* d_small, Timers* tm, int deff = 0, size_t L = 0, uint64_t body_add = 0, const int32_t* d_ia = nullptr,
+                         const int32_t* d_ib = nullptr) {
   const dctfhe_tier& t = K->p.tiers[tier];
   TierKeys& tk = K->tiers[tier];
   const int D = K->p.D;
@@ -1073,7 +1185,10 @@ static int dev_keyswitch(dctfhe_keys* K, int tier, const uint64_t* d_cts, size_t
   const int h = tm ? tm->begin(CAT_KS) : -1;
   const size_t total = count * (size_t)De;
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
-  hipLaunchKernelGGL(k_ks_decompose, dim3(grid), dim3(256), 0, st, d_cts, count, L, De, shift, body_add, t.lk, t.betak, d_digits, d_bodies);
+  if (d_ia)    // ciphertext c is row ia[c] - row ib[c] of d_cts (the pairwise maxima of a max pool)
+    hipLaunchKernelGGL(k_ks_decompose_diff, dim3(grid), dim3(256), 0, st, d_cts, L, d_ia, d_ib, count, De, shift, body_add, t.lk, t.betak, d_digits, d_bodies);
+  else
+    hipLaunchKernelGGL(k_ks_decompose, dim3(grid), dim3(256), 0, st, d_cts, count, L, De, shift, body_add, t.lk, t.betak, d_digits, d_bodies);
   if (tk.d_kskT) {   // matrix-core path: i8 digits x signed byte limbs of the key
     const unsigned ncb = (unsigned)(tk.ncol_pad / 128), nrb = (unsigned)((count + 127) / 128), cpx = (ncb + 7) / 8;
 #define KS_LAUNCH(LB)                                                                                                                      \
@@ -1218,6 +1333,47 @@ static void free_lut_scratch(LutScratch* sc) {
   sc->digits = nullptr; sc->bodies = nullptr; sc->small = nullptr; sc->bit_tables = nullptr;
 }
 struct LutScratchOwner { LutScratch s{}; ~LutScratchOwner() { free_lut_scratch(&s); } };
+
+// the levels of a max-pool plan on device rows.  Input rows of stride Ls (first ds mask words meaningful); level buffers and output rows of
+// stride Lo, of which the first `dout` = max(ds, ring of the tier) mask words may be non-zero.  Each level: the gather, then per chunk the
+// key switch of the differences (k_ks_decompose_diff), the centred mod switch and the relu bootstrap accumulated into the gathered b rows.
+static int dev_max_pool(dctfhe_keys* K, int tier, const PoolPlan& P, const uint64_t* d_in, size_t Ls, size_t ds, uint64_t* const bufs[2],
+                        uint64_t* d_out, size_t Lo, size_t dout, int shift, uint64_t body_add, const int64_t* d_table, int p_d,
+                        const LutScratch& sc, Timers* tm) {
+  hipStream_t st = K->ctx->stream;
+  const int32_t* maps = P.maps.as<int32_t>();
+  for (const PoolLevel& l : P.lv) {
+    const uint64_t* src = l.src == 0 ? d_in : bufs[l.src - 1];
+    const size_t L_src = l.src == 0 ? Ls : Lo, d_src = l.src == 0 ? ds : dout;
+    uint64_t* dst = l.dst == 3 ? d_out : bufs[l.dst - 1];
+    const int h = tm ? tm->begin(CAT_LINEAR) : -1;
+    hipLaunchKernelGGL(k_pool_gather, dim3(ew_grid(l.n_dst * Lo)), dim3(256), 0, st, src, L_src, d_src, maps + l.g_off, dst, Lo, l.n_dst);
+    HIPCHK(hipGetLastError());
+    if (tm) tm->end(h);
+    for (size_t c0 = 0; c0 < l.pairs; c0 += sc.chunk) {
+      const size_t cn = std::min(sc.chunk, l.pairs - c0);
+      CHK(dev_keyswitch(K, tier, src, cn, shift, sc.digits, sc.bodies, sc.small, tm, (int)d_src, L_src, body_add, maps + l.a_off + c0,
+                        maps + l.b_off + c0));
+      CHK(dev_ms_center(K, tier, sc.small, cn, tm));
+      CHK(dev_pbs(K, tier, sc.small, cn, d_table, p_d, nullptr, 1, 1, 0, dst + c0 * Lo, 1, 0, tm, Lo));
+    }
+  }
+  return 0;
+}
+// clear mode: row pass into `mid` ([B*C*H][Wo] words), column pass into out
+static int clear_max_pool(hipStream_t st, const uint64_t* in, uint64_t* mid, uint64_t* out, int batch, int C, int H, int W, int k, int s, int p,
+                          int shift, uint64_t body_add, int p_d, const int64_t* d_table, double sigma, uint64_t seed, uint64_t stream) {
+  const int Ho = pool_out_size(H, k, s, p), Wo = pool_out_size(W, k, s, p);
+  const rng_key key{{(uint32_t)seed, (uint32_t)(seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}};
+  const size_t n1 = (size_t)batch * C * H * Wo, n2 = (size_t)batch * C * Ho * Wo;
+  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(n1)), dim3(256), 0, st, in, mid, (size_t)batch * C * H, W, 1, Wo, k, s, p, shift, body_add, p_d,
+                     d_table, sigma, key, stream);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(n2)), dim3(256), 0, st, mid, out, (size_t)batch * C, H, Wo, Ho, k, s, p, shift, body_add, p_d,
+                     d_table, sigma, key, stream + 1);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 // ------------------------------------------------------------------------------------------ primitives on host buffers
 extern "C" int dctfhe_keyswitch_prefix(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, int shift, int deff,
@@ -1421,6 +1577,89 @@ extern "C" int dctfhe_sum_pool_rows(dctfhe_ctx* ctx, const uint64_t* in, int dim
   return 0;
 }
 
+// key switch of the differences cts[ia[c]] - cts[ib[c]] (c < count; rows of D + 1 words, of which the first deff mask words may be
+// non-zero), each shifted left by `shift` with body_add on the body: what a max pool's pairwise maxima feed their relu bootstrap
+extern "C" int dctfhe_keyswitch_diff(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, const int32_t* ia,
+                                     const int32_t* ib, int shift, uint64_t body_add, int deff, uint64_t* cts_small) {
+  if (!ctx || !K || (count && (!cts || !ia || !ib || !cts_small))) return fail("dctfhe_keyswitch_diff: null argument");
+  if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  if (deff < 0 || deff > K->p.D) return fail("deff out of range");
+  if (shift < 0 || shift > 63) return fail("shift out of range");
+  for (size_t c = 0; c < count; c++)
+    if (ia[c] < 0 || (size_t)ia[c] >= count || ib[c] < 0 || (size_t)ib[c] >= count)
+      return fail("dctfhe_keyswitch_diff: index %zu (%d, %d) out of range (%zu rows)", c, ia[c], ib[c], count);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const dctfhe_tier& t = K->p.tiers[tier];
+  const size_t L = (size_t)K->p.D + 1;
+  DevBuf d_in, d_small, d_bodies, d_dig, d_idx;
+  HIPCHK(d_in.alloc(count * L * 8));
+  HIPCHK(d_small.alloc(count * (size_t)(t.n + 1) * 8));
+  HIPCHK(d_bodies.alloc(count * 8));
+  HIPCHK(d_dig.alloc(count * (size_t)K->p.D * t.lk));
+  HIPCHK(d_idx.alloc(count * 8));
+  HIPCHK(hipMemcpy(d_in.p, cts, count * L * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_idx.p, ia, count * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_idx.as<int32_t>() + count, ib, count * 4, hipMemcpyHostToDevice));
+  CHK(dev_keyswitch(K, tier, d_in.as<uint64_t>(), count, shift, d_dig.as<uint8_t>(), d_bodies.as<uint64_t>(), d_small.as<uint64_t>(), nullptr, deff, L,
+                    body_add, d_idx.as<int32_t>(), d_idx.as<int32_t>() + count));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  HIPCHK(hipMemcpy(cts_small, d_small.p, count * (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// MaxPool2d(k, s, p) on [batch][C][H][W] rows -> [batch][C][Ho][Wo] rows of dim_o + 1 words, with the session's tree (dev_max_pool).
+// Inputs hold value * 2^(63 - p_d) (shift 0, signed body offset 2^62 on the differences); table: the 2^p_d entries of relu on the signed
+// differences, at the same encoding.  keys == NULL: the clear form on one word per element (dim_in, deff_in, dim_o ignored; table unused).
+extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* in, int dim_in, int deff_in, int batch, int C,
+                                    int H, int W, int k, int s, int p, int p_d, const int64_t* table, int dim_o, uint64_t* out) {
+  if (!ctx || !in || !out) return fail("dctfhe_max_pool_rows: null argument");
+  if (batch < 1 || C < 1 || H < 1 || W < 1 || k < 1 || k > 32 || s < 1 || p < 0 || 2 * p > k || H + 2 * p < k || W + 2 * p < k)
+    return fail("dctfhe_max_pool_rows: bad geometry (1 <= k <= 32, s >= 1, 0 <= p <= k/2, window inside the padded input)");
+  if (p_d < 2 || p_d > 16) return fail("dctfhe_max_pool_rows: p_d %d out of range", p_d);
+  const int Ho = pool_out_size(H, k, s, p), Wo = pool_out_size(W, k, s, p);
+  const size_t nin = (size_t)batch * C * H * W, nout = (size_t)batch * C * Ho * Wo;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (!K) {
+    DevBuf di, dm, d_o;
+    HIPCHK(di.alloc(nin * 8)); HIPCHK(dm.alloc((size_t)batch * C * H * Wo * 8)); HIPCHK(d_o.alloc(nout * 8));
+    HIPCHK(hipMemcpy(di.p, in, nin * 8, hipMemcpyHostToDevice));
+    CHK(clear_max_pool(st, di.as<uint64_t>(), dm.as<uint64_t>(), d_o.as<uint64_t>(), batch, C, H, W, k, s, p, 0, 1ULL << 62, p_d, nullptr, 0.0, 0, 0));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(out, d_o.p, nout * 8, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if (!table) return fail("dctfhe_max_pool_rows: null table");
+  if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  const dctfhe_tier& t = K->p.tiers[tier];
+  if (p_d > t.logN - 1) return fail("dctfhe_max_pool_rows: table of 2^%d entries does not fit tier %d", p_d, tier);
+  CHK(rows_ok("dctfhe_max_pool_rows", dim_in, deff_in));
+  if (dim_in > K->p.D) return fail("dctfhe_max_pool_rows: rows of %d mask words, the key has %d", dim_in, K->p.D);
+  const int ring = t.k << t.logN, dout = std::max(deff_in, ring);
+  if (dim_o < dout || dim_o > K->p.D) return fail("dctfhe_max_pool_rows: output rows of %d mask words cannot hold the maxima (%d needed, at most D)", dim_o, dout);
+  if (!ks_narrows(K, tier, deff_in) || !ks_narrows(K, tier, dout)) {
+    if (dim_in != K->p.D || dim_o != K->p.D) return fail("dctfhe_max_pool_rows: this tier's key switch needs full-width rows (dim_in = dim_o = D)");
+  }
+  const size_t Li = (size_t)dim_in + 1, Lo = (size_t)dim_o + 1;
+  PoolPlan P;
+  CHK(pool_plan(batch, C, H, W, k, s, p, &P));
+  DevBuf di, d_o, ba, bb, d_tab;
+  HIPCHK(di.alloc(nin * Li * 8)); HIPCHK(d_o.alloc(nout * Lo * 8));
+  HIPCHK(ba.alloc(P.rows_buf[0] * Lo * 8)); HIPCHK(bb.alloc(P.rows_buf[1] * Lo * 8));
+  HIPCHK(d_tab.alloc(((size_t)1 << p_d) * 8));
+  HIPCHK(hipMemcpy(di.p, in, nin * Li * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_tab.p, table, ((size_t)1 << p_d) * 8, hipMemcpyHostToDevice));
+  LutScratchOwner sc;
+  CHK(alloc_lut_scratch(K, std::min<size_t>(std::max<size_t>(P.pairs_per_batch, 1), 4096), &sc.s));
+  uint64_t* const bufs[2] = {ba.as<uint64_t>(), bb.as<uint64_t>()};
+  CHK(dev_max_pool(K, tier, P, di.as<uint64_t>(), Li, (size_t)deff_in, bufs, d_o.as<uint64_t>(), Lo, (size_t)dout, 0, 1ULL << 62, d_tab.as<int64_t>(), p_d,
+                   sc.s, nullptr));
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(out, d_o.p, nout * Lo * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------ K10 front-end
 extern "C" int dctfhe_dct_frontend(dctfhe_ctx* ctx, const uint8_t* y, const uint8_t* c1, const uint8_t* c2, int batch, int S, int Sc, int fs,
                                    const int32_t* idx_y, int ny, const int32_t* idx_c1, int n1, const int32_t* idx_c2, int n2,
@@ -1488,7 +1727,7 @@ static int parse_circuit(const void* blob, size_t size, dctfhe_circuit* c) {
     if (t.C < 1 || t.H < 1 || t.W < 1) return fail("circuit blob: empty tensor shape");
   for (int i = 0; i < h.n_ops; i++) {
     const Op& o = c->ops[i];
-    if (o.type < OP_CONV || o.type > OP_LUT) return fail("op %d: unknown type %d", i, o.type);
+    if (o.type < OP_CONV || o.type > OP_MAXPOOL) return fail("op %d: unknown type %d", i, o.type);
     if (bad_t(o.src0) || bad_t(o.dst) || (o.type == OP_ADD && bad_t(o.src1))) return fail("op %d: tensor id out of range", i);
     if (o.payload_len < 0 || (o.payload_len > 0 && (o.payload_off < (int64_t)need || (size_t)o.payload_off + (size_t)o.payload_len > size)))
       return fail("op %d: payload out of range", i);
@@ -1518,6 +1757,17 @@ static int parse_circuit(const void* blob, size_t size, dctfhe_circuit* c) {
         if (ntab != 1 && ntab != a.C) return fail("op %d: %d tables for %d channels", i, ntab, a.C);
         if (o.payload_len != ((int64_t)ntab << w) * 8) return fail("op %d: table payload of %lld bytes, expected %lld", i, (long long)o.payload_len, (long long)(((int64_t)ntab << w) * 8));
         if (a.C != d.C || a.H != d.H || a.W != d.W) return fail("op %d: look-up changes the shape", i);
+        break;
+      }
+      case OP_MAXPOOL: {
+        const int k = o.ip[0], st = o.ip[1], pad = o.ip[2], shift = o.ip[3], tier = o.ip[4], pd = o.ip[5];
+        if (k < 1 || k > 32 || st < 1 || pad < 0 || 2 * pad > k || a.H + 2 * pad < k || a.W + 2 * pad < k)
+          return fail("op %d: bad max-pool geometry (k=%d s=%d p=%d: need 1 <= k <= 32, s >= 1, 0 <= p <= k/2, window inside the padded input)", i, k, st, pad);
+        if (d.C != a.C) return fail("op %d: max pool changes the channel count (%d -> %d)", i, a.C, d.C);
+        if (d.H != pool_out_size(a.H, k, st, pad) || d.W != pool_out_size(a.W, k, st, pad)) return fail("op %d: max-pool output shape mismatch", i);
+        if (pd < 2 || pd > 16 || shift < 0 || pd + shift > 63) return fail("op %d: bad max-pool difference precision (p_d=%d shift=%d)", i, pd, shift);
+        if (tier < 0 || tier >= DCTFHE_MAX_TIERS) return fail("op %d: max-pool tier %d out of range", i, tier);
+        if (o.payload_len != ((int64_t)1 << pd) * 8) return fail("op %d: max-pool table payload of %lld bytes, expected %lld", i, (long long)o.payload_len, (long long)(((int64_t)1 << pd) * 8));
         break;
       }
     }
@@ -1617,6 +1867,18 @@ extern "C" int dctfhe_circuit_stats(dctfhe_circuit* c, const dctfhe_params* P, d
         }
         break;
       }
+      case OP_MAXPOOL: {
+        const TensorShape& a = c->tensors[o.src0];
+        const double n = (double)pool_pairs(a.C, a.H, a.W, o.ip[0], o.ip[1], o.ip[2]);
+        const int tt = o.ip[4];
+        s->bytes_algorithmic += (ein + 3 * n) * Lb;     // gathers, and two rows read per difference
+        if (tt >= 0 && tt < P->n_tiers) {
+          s->pbs_count[tt] += (int64_t)n; s->ks_count[tt] += (int64_t)n;
+          s->flops_f64 += n * tier_flops(P->tiers[tt]);
+          s->key_bytes_per_pass += key_bytes(P->tiers[tt]);
+        }
+        break;
+      }
       default: break;
     }
   }
@@ -1634,6 +1896,11 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   if (keys)
     for (size_t i = 0; i < circ->ops.size(); i++) {
       const Op& o = circ->ops[i];
+      if (o.type == OP_MAXPOOL) {
+        if (o.ip[4] >= keys->p.n_tiers) return fail("op %zu names a tier the keys lack", i);
+        if (o.ip[5] > keys->p.tiers[o.ip[4]].logN - 1) return fail("op %zu: max-pool table of 2^%d entries does not fit tier %d", i, o.ip[5], o.ip[4]);
+        continue;
+      }
       if (o.type != OP_LUT) continue;
       const int tt = o.ip[4], bt = o.ip[5], r = o.ip[9] ? 0 : o.ip[1], w = o.ip[2];
       if (tt < 0 || tt >= keys->p.n_tiers || (r > 0 && (bt < 0 || bt >= keys->p.n_tiers))) return fail("op %zu names a tier the keys lack", i);
@@ -1676,6 +1943,7 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
     // circuit that uses such a tier keeps every tensor at full width
     bool all_mfma = true;
     for (const Op& o : circ->ops) {
+      if (o.type == OP_MAXPOOL) all_mfma = all_mfma && keys->tiers[o.ip[4]].d_kskT != nullptr;
       if (o.type != OP_LUT) continue;
       all_mfma = all_mfma && keys->tiers[o.ip[4]].d_kskT != nullptr;
       const int r = o.ip[9] ? 0 : o.ip[1];
@@ -1697,6 +1965,9 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
         if (clampd(o.ip[10]) < s->t_deff[o.src0]) return fail("op %zu: look-up compiled for effective dimension %d, its input has %zu", i, o.ip[10], s->t_deff[o.src0]);
         const size_t chain = r > 0 ? (size_t)round_chain_deff(keys, (int)clampd(o.ip[10]), step_tiers_of(o), r) : 0;
         set(o.dst, ring, chain);
+      } else if (o.type == OP_MAXPOOL) {      // the relu bootstraps accumulate into the first kN words of copies of the input
+        const size_t ring = (size_t)keys->p.tiers[o.ip[4]].k << keys->p.tiers[o.ip[4]].logN;
+        set(o.dst, std::max(s->t_deff[o.src0], ring), 0);
       } else if (o.type == OP_ADD) {
         set(o.dst, std::max(s->t_deff[o.src0], s->t_deff[o.src1]), 0);
       } else {
@@ -1728,9 +1999,37 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
     return 0;
   };
   CHK(alloc_t(circ->input_tensor));
+  s->pool.resize(circ->ops.size());
+  s->pool_buf.assign(circ->ops.size(), {nullptr, nullptr});
   for (int i = 0; i < (int)circ->ops.size(); i++) {
     const Op& o = circ->ops[i];
     CHK(alloc_t(o.dst));
+    if (o.type == OP_MAXPOOL) {
+      // the tree's level buffers (encrypted) or the row pass's output (clear), held for this op only: back to the free list after it
+      const TensorShape& a = circ->tensors[o.src0];
+      size_t words[2] = {0, 0};
+      if (keys) {
+        s->pool[i].reset(new PoolPlan);
+        CHK(pool_plan(batch, a.C, a.H, a.W, o.ip[0], o.ip[1], o.ip[2], s->pool[i].get()));
+        for (int b = 0; b < 2; b++) words[b] = s->pool[i]->rows_buf[b] * s->t_L[o.dst];
+      } else {
+        words[0] = (size_t)batch * a.C * a.H * pool_out_size(a.W, o.ip[0], o.ip[1], o.ip[2]);
+      }
+      for (int b = 0; b < 2; b++) {
+        if (!words[b]) continue;
+        size_t fr = 0, tot = 0;
+        hipMemGetInfo(&fr, &tot);
+        bool reuse = false;
+        for (auto& f : freelist) reuse = reuse || f.first >= words[b];
+        if (!reuse && words[b] * 8 > fr)
+          return fail("op %d: the max pool's level buffer needs %.1f GB, %.1f GB of device memory are free (batch %d too large for one device)", i,
+                      words[b] * 8e-9, fr * 1e-9, batch);
+        CHK(get(words[b], &s->pool_buf[i][b]));
+        if (!cap.count(s->pool_buf[i][b])) cap[s->pool_buf[i][b]] = words[b];
+      }
+      for (int b = 0; b < 2; b++)
+        if (s->pool_buf[i][b]) freelist.push_back({cap[s->pool_buf[i][b]], s->pool_buf[i][b]});
+    }
     auto release = [&](int t) {
       if (last_use[t] == i && t != o.dst && s->d_tensor[t]) freelist.push_back({cap[s->d_tensor[t]], s->d_tensor[t]});
     };
@@ -1739,8 +2038,11 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   }
   if (keys) {
     size_t maxe = 1;
-    for (const Op& o : circ->ops)
+    for (size_t i = 0; i < circ->ops.size(); i++) {
+      const Op& o = circ->ops[i];
       if (o.type == OP_LUT) { const TensorShape& x = circ->tensors[o.src0]; maxe = std::max(maxe, (size_t)batch * x.C * x.H * x.W); }
+      if (o.type == OP_MAXPOOL) for (const PoolLevel& l : s->pool[i]->lv) maxe = std::max(maxe, l.pairs);
+    }
     LutScratchOwner sc;
     CHK(alloc_lut_scratch(keys, std::min<size_t>(maxe, 16384), &sc.s));
     s->chunk = sc.s.chunk; s->d_digits = sc.s.digits; s->d_bodies = sc.s.bodies; s->d_small = sc.s.small; s->d_bit_tables = sc.s.bit_tables;
@@ -1936,6 +2238,21 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
             tm.end(h);
           }
           CHK(dev_round_lut(K, step_tiers_of(o), tt, src, Ls, shift, add, dst, Ld, E, p, steps, (const int64_t*)c->d_payload[i], w, nullptr, hw, nchan, sc, &tm, deff));
+        }
+        break;
+      }
+      case OP_MAXPOOL: {
+        const int k = o.ip[0], sp = o.ip[1], pad = o.ip[2], shift = o.ip[3], tt = o.ip[4], pd = o.ip[5];
+        const uint64_t body_add = (uint64_t)o.lp[0];
+        if (!K) {
+          const double sg = i < s->sim_sigma.size() ? s->sim_sigma[i] : 0.0;
+          const int h = tm.begin(CAT_LINEAR);
+          CHK(clear_max_pool(st, src, s->pool_buf[i][0], dst, B, a.C, a.H, a.W, k, sp, pad, shift, body_add, pd, (const int64_t*)c->d_payload[i], sg,
+                             s->sim_seed, (1ULL << 40) | ((uint64_t)(0x51D0000 + (s->sim_run << 12) + i) << 1)));
+          tm.end(h);
+        } else {
+          uint64_t* const bufs[2] = {s->pool_buf[i][0], s->pool_buf[i][1]};
+          CHK(dev_max_pool(K, tt, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], shift, body_add, (const int64_t*)c->d_payload[i], pd, sc, &tm));
         }
         break;
       }

@@ -342,6 +342,36 @@ __global__ void k_ks_decompose(const uint64_t* __restrict__ cts, size_t count, s
   }
 }
 
+// Step 1 on the difference of two rows, for the pairwise maxima of a max pool: ciphertext c is rows[ia[c]] - rows[ib[c]] (rows of
+// stride L, the first Deff mask words meaningful), shifted and body-offset on the fly -- no difference tensor is ever written.  The digit
+// split is k_ks_decompose's.
+__global__ void k_ks_decompose_diff(const uint64_t* __restrict__ rows, size_t L, const int32_t* __restrict__ ia, const int32_t* __restrict__ ib,
+                                    size_t count, int Deff, int shift, uint64_t body_add, int lk, int betak, uint8_t* __restrict__ digits,
+                                    uint64_t* __restrict__ bodies) {
+  const size_t total = count * (size_t)Deff;
+  const int half = 1 << (betak - 1);
+  for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = x / Deff;
+    const int i = (int)(x % Deff);
+    const uint64_t* ra = rows + (size_t)ia[c] * L;
+    const uint64_t* rb = rows + (size_t)ib[c] * L;
+    const uint64_t v = (ra[i] - rb[i]) << shift;
+    const int tot = lk * betak;
+    uint64_t xx = (v + (1ULL << (63 - tot))) >> (64 - tot);
+    const uint64_t B = 1ULL << betak, mask = B - 1;
+    uint64_t carry = 0;
+    uint8_t* dst = digits + (c * (size_t)Deff + i) * lk;
+    for (int lev = lk - 1; lev >= 0; lev--) {
+      uint64_t d = (xx & mask) + carry;
+      xx >>= betak;
+      int dv;
+      if (d >= (uint64_t)half) { dv = (int)d - (int)B; carry = 1; } else { dv = (int)d; carry = 0; }
+      dst[lev] = (uint8_t)(dv + half);
+    }
+    if (i == 0) bodies[c] = ((ra[L - 1] - rb[L - 1]) << shift) + body_add;
+  }
+}
+
 // Step 2: out[c][j] = body_c*[j==n] - sum_r (dig'[c][r] - B/2) * ksk[r][j]
 //       = body_c*[j==n] + (B/2) * colsum[j] - sum_r dig'[c][r] * ksk[r][j],   colsum[j] = sum_r ksk[r][j].
 // Block: CT ciphertexts x 256 columns; digits are wave-uniform (scalar loads), the key is read
@@ -816,6 +846,30 @@ __global__ void k_sum_pool(const uint64_t* __restrict__ in, int C, int H, int W,
   }
 }
 
+// one tree level of a max pool: row r of the level's output is a copy of source row map[r] (the `b` of a pairwise maximum, which the
+// difference bootstrap then accumulates into, or a candidate carried to the next level), at the output's row stride; mask words beyond
+// the source's effective dimension are written as zeros
+__global__ void k_pool_gather(const uint64_t* __restrict__ src, size_t Ls, size_t ds, const int32_t* __restrict__ map, uint64_t* __restrict__ dst,
+                              size_t Ld, size_t count) {
+  const size_t total = count * Ld;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t r = i / Ld, w = i % Ld;
+    dst[i] = row_word(src + (size_t)map[r] * Ls, Ls, ds, w, w == Ld - 1);
+  }
+}
+
+// simulate: Gaussian noise of std sigma on a phase sitting at `centre`, then the bootstrap's half-box rotation and negacyclic wrap, the
+// entry of `table` it lands on (the look-up of k_lut_clear and k_maxpool_clear)
+__device__ __forceinline__ uint64_t noisy_lookup(uint64_t centre, int w, const int64_t* __restrict__ table, const rng_key& seed, uint64_t stream,
+                                                 uint64_t idx, double sigma) {
+  const uint64_t half_box = 1ULL << (62 - w);
+  const uint64_t noisy = centre + (uint64_t)gauss_torus(seed, stream, idx, sigma);
+  // negacyclic wrap: a value pushed across the padding bit comes back negated -- reproduce the bootstrap's behaviour
+  const uint64_t pos = noisy + half_box;
+  const uint64_t t = (uint64_t)table[(pos >> (63 - w)) & ((1ULL << w) - 1)];
+  return (pos >> 63) ? (uint64_t)0 - t : t;
+}
+
 // clear-mode table look-up on 1-word "ciphertexts" (D = 0): same arithmetic as round_lut without noise.
 // sigma > 0 (`simulate` with the noise model): Gaussian noise of that standard deviation (fraction of the torus: what the
 // compiler predicts at the input of this site's table bootstrap) is added where the encrypted run has it -- after the exact
@@ -830,20 +884,47 @@ __global__ void k_lut_clear(const uint64_t* __restrict__ in, uint64_t* __restric
     if (v >> 63) atomicOr(overflow, 1);  // message left the padded range: an FHE run would wrap
     uint64_t idx = (v >> (63 - w)) & ((1ULL << w) - 1);
     if (sigma > 0) {
-      const uint64_t half_box = 1ULL << (62 - w);
       // exact rounding: the value sits at the centre of its box; approximate: where its low bits put it (+ half an input unit)
       const uint64_t centre = approx && r > 0 ? v + (1ULL << (62 - p)) : (idx << (63 - w));
-      const uint64_t noisy = centre + (uint64_t)gauss_torus(seed, stream, e, sigma);
-      // negacyclic wrap: a value pushed across the padding bit comes back negated -- reproduce the bootstrap's behaviour
-      const uint64_t pos = noisy + half_box;
-      idx = (pos >> (63 - w)) & ((1ULL << w) - 1);
       const size_t ti = nchan > 1 ? (e / (size_t)hw) % (size_t)nchan : 0;
-      const uint64_t t = (uint64_t)tables[(ti << w) + idx];
-      out[e] = (pos >> 63) ? (uint64_t)0 - t : t;
+      out[e] = noisy_lookup(centre, w, tables + (ti << w), seed, stream, e, sigma);
       continue;
     }
     const size_t ti = nchan > 1 ? (e / (size_t)hw) % (size_t)nchan : 0;
     out[e] = (uint64_t)tables[(ti << w) + idx];
+  }
+}
+
+// clear-mode max pool, one 1-D pass: in [outer][n_in][inner] -> out [outer][n_out][inner], one thread per output, over the window's
+// in-range taps.  sigma == 0: the maximum of the words read as signed int64.  sigma > 0 (`simulate`): the taps are folded as
+// m = m + relu(x - m) with the noise sampled on every difference before the relu table (`table`: 2^p_d entries, index
+// ((x - m) << shift) + body_add) -- one noisy look-up per pairwise maximum, as many as the encrypted tree runs.
+__global__ void k_maxpool_clear(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, size_t outer, int n_in, int inner, int n_out, int k,
+                                int s, int p, int shift, uint64_t body_add, int p_d, const int64_t* __restrict__ table, double sigma,
+                                rng_key seed, uint64_t stream) {
+  const size_t total = outer * (size_t)n_out * inner;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e % inner);
+    const int o = (int)((e / inner) % n_out);
+    const size_t ou = e / ((size_t)inner * n_out);
+    uint64_t m = 0;
+    int taken = 0;
+    for (int j = 0; j < k; j++) {
+      const int x = o * s - p + j;
+      if (x < 0 || x >= n_in) continue;
+      const uint64_t v = in[(ou * n_in + x) * inner + i];
+      if (taken == 0) {
+        m = v;
+      } else if (sigma > 0) {
+        const uint64_t d = ((v - m) << shift) + body_add;
+        const uint64_t centre = ((d >> (63 - p_d)) & ((1ULL << p_d) - 1)) << (63 - p_d);
+        m += noisy_lookup(centre, p_d, table, seed, stream, e * 64 + (uint64_t)taken, sigma);
+      } else {
+        m = (int64_t)v > (int64_t)m ? v : m;
+      }
+      taken++;
+    }
+    out[e] = m;
   }
 }
 

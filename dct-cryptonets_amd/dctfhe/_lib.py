@@ -47,7 +47,7 @@ EXPORTS = [
     "dctfhe_circuit_stats", "dctfhe_circuit_io", "dctfhe_session_create", "dctfhe_session_destroy",
     "dctfhe_session_upload", "dctfhe_session_run", "dctfhe_session_download", "dctfhe_session_upload_rows", "dctfhe_session_download_rows", "dctfhe_session_dims", "dctfhe_fp64_peak", "dctfhe_bench_pbs",
     "dctfhe_encrypt_seeded", "dctfhe_expand_seeded", "dctfhe_session_upload_seeded", "dctfhe_eval_keys_export_compressed",
-    "dctfhe_eval_keys_decompress_bsk",
+    "dctfhe_eval_keys_decompress_bsk", "dctfhe_keyswitch_diff", "dctfhe_max_pool_rows",
 ]
 
 _lib = None
@@ -122,6 +122,8 @@ def load():
     L.dctfhe_session_upload_seeded.argtypes = [vp, C.c_char_p, u64, i32, vp, sz]
     L.dctfhe_eval_keys_export_compressed.argtypes = [vp, vp, sz, C.POINTER(sz)]
     L.dctfhe_eval_keys_decompress_bsk.argtypes = [vp, vp, sz, i32, vp]
+    L.dctfhe_keyswitch_diff.argtypes = [vp, vp, i32, vp, sz, vp, vp, i32, u64, i32, vp]
+    L.dctfhe_max_pool_rows.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]
     _lib = L
     return L
 

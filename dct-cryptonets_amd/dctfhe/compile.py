@@ -12,6 +12,8 @@ produces is the specification the engine and the oracle are both held to.
 Circuit semantics (all integers):
   CONV / ADD / SUMPOOL   exact integer arithmetic on message values
   LUT(p, r, w, signed)   idx = m + (2^(p-1) if signed else 0);  t = (idx + 2^(r-1) * [r>0]) >> r;  y = table[channel][t]
+  MAXPOOL(k, s, p)       max over the window's in-range taps (torch's -inf padding, floor mode), evaluated as separable
+                         row / column passes of pairwise max(a, b) = b + relu(a - b): one signed p_d-bit table per pair
 Encodings: a tensor with exponent e holds  phase = value * 2^e  (mod 2^64); a LUT shifts its input up to
 e = 63 - p first, so that t sits in the top w+1 bits with the padding bit clear.
 """
@@ -26,6 +28,7 @@ import torch.nn.functional as F
 from . import params as P
 
 OP_CONV, OP_ADD, OP_SUMPOOL, OP_LUT = 1, 2, 3, 4
+OP_MAXPOOL = 5            # not 9: the ABI tests use 9 as the unknown type
 MAGIC = 0x46544344
 
 
@@ -49,6 +52,47 @@ def act_scale(x, signed, bits):
 def act_quant(x, s, signed, bits):
     lo, hi = (-(2 ** (bits - 1)), 2 ** (bits - 1) - 1) if signed else (0, 2 ** bits - 1)
     return np.clip(np.rint(x / s), lo, hi).astype(np.int64)
+
+
+def max_pool_int(q, k, s, p):
+    """integer max over the in-range taps of every k x k window (stride s, padding p, floor mode)"""
+    B, C, H, W = q.shape
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    lo = np.iinfo(np.int64).min
+    qp = np.full((B, C, H + 2 * p, W + 2 * p), lo, np.int64)
+    qp[:, :, p:p + H, p:p + W] = q
+    out = np.full((B, C, Ho, Wo), lo, np.int64)
+    for i in range(k):
+        for j in range(k):
+            out = np.maximum(out, qp[:, :, i:i + (Ho - 1) * s + 1:s, j:j + (Wo - 1) * s + 1:s])
+    return out
+
+
+def pool_taps(n_in, k, s, p):
+    """in-range taps of every output of a 1-D pass"""
+    n_out = (n_in + 2 * p - k) // s + 1
+    return [sum(1 for j in range(k) if 0 <= o * s - p + j < n_in) for o in range(n_out)]
+
+
+def pool_level_pairs(taps):
+    """pairwise maxima per tree level of one 1-D pass.  Late pairing: at level l of L = ceil(log2 max taps), an output with m
+    candidates combines max(0, m - 2^(L-l-1)) pairs and carries the rest, so every output reaches one candidate at the last level
+    and an output with two taps pairs there (csrc/dctfhe.hip pool_schedule is the same rule)."""
+    nmax = max(taps)
+    L = (nmax - 1).bit_length()
+    m, out = list(taps), []
+    for lev in range(L):
+        cap = 1 << (L - lev - 1)
+        pr = [max(0, x - cap) for x in m]
+        out.append(sum(pr))
+        m = [x - y for x, y in zip(m, pr)]
+    return out
+
+
+def pool_geometry(C, H, W, k, s, p):
+    """[(multiplicity, pairs per level)] of the row pass then the column pass: pairs per image"""
+    Wo = (W + 2 * p - k) // s + 1
+    return [(C * H, pool_level_pairs(pool_taps(W, k, s, p))), (C * Wo, pool_level_pairs(pool_taps(H, k, s, p)))]
 
 
 def conv_int(q, w, stride, pad):
@@ -102,6 +146,10 @@ class OpInfo:
     coarse_from: int = -1             # rounding steps i >= coarse_from run on the one-level bit tier
     coarse2_from: int = -1            # ... and steps i >= coarse2_from on the two-bit-rotation bit tier (ip[11] = tier << 8 | from)
     sim_sigma: float = 0.0            # modelled noise std at the input of the site's table bootstrap (fraction of the torus)
+    # MAXPOOL metadata: [(multiplicity, pairs per level)] per pass (pool_geometry), pairwise maxima per image, tree levels
+    pool_geom: list = None
+    n_max: int = 0
+    levels: int = 0
 
 
 @dataclass
@@ -141,18 +189,22 @@ class CompiledCircuit:
 
     @property
     def worst_site_failure(self):
-        """largest modelled failure probability per element over the look-up sites"""
-        return max((o.pfail for o in self.ops if o.type == OP_LUT), default=0.0)
+        """largest modelled failure probability per element over the look-up sites (a max pool: per pairwise maximum)"""
+        return max((o.pfail for o in self.ops if o.type in (OP_LUT, OP_MAXPOOL)), default=0.0)
 
     def simulation_sigmas(self):
         """per op, the noise std `simulate` injects at the look-up (0 for the levelled ops)"""
-        return [o.sim_sigma if o.type == OP_LUT else 0.0 for o in self.ops]
+        return [o.sim_sigma if o.type in (OP_LUT, OP_MAXPOOL) else 0.0 for o in self.ops]
 
     def pbs_counts(self):
         """{tier name: programmable bootstraps per image} -- table lookups on the site's table tier, rounding steps
         on the bit tier (steps below coarse_from) or the one-level bit tier (steps from coarse_from on)."""
         ps, out = self.param_set, {}
         for o in self.ops:
+            if o.type == OP_MAXPOOL:
+                nm = ps.tiers[o.ip[4]].name
+                out[nm] = out.get(nm, 0) + o.n_max
+                continue
             if o.type != OP_LUT:
                 continue
             s = self.tensors[o.src0]
@@ -166,7 +218,7 @@ class CompiledCircuit:
 
     def report(self):
         """Text dump standing in for `fhe_circuit.mlir` (reference homomorphic_eval.py:309-311)."""
-        names = {OP_CONV: "conv2d", OP_ADD: "add", OP_SUMPOOL: "sum_pool", OP_LUT: "round_lut"}
+        names = {OP_CONV: "conv2d", OP_ADD: "add", OP_SUMPOOL: "sum_pool", OP_LUT: "round_lut", OP_MAXPOOL: "max_pool2d"}
         ps = self.param_set
         lines = [f"// dctfhe circuit: {len(self.ops)} ops, max accumulator bit-width {self.max_bit_width}, D={ps.D}"]
         for i, t in enumerate(ps.tiers):
@@ -179,6 +231,9 @@ class CompiledCircuit:
                 head += f" {{cout={o.ip[0]}, k={o.ip[1]}x{o.ip[2]}, stride={o.ip[3]}, pad={o.ip[4]}, nu2={o.nu2:.0f}}}"
             elif o.type == OP_SUMPOOL:
                 head += f" {{k={o.ip[0]}}}"
+            elif o.type == OP_MAXPOOL:
+                head = (f"%{o.dst} = max_pool2d(%{o.src0}, {o.ip[0]}, {o.ip[1]}, {o.ip[2]}) {{p_d={o.ip[5]}, shift={o.ip[3]}, "
+                        f"tier={ps.tiers[o.ip[4]].name}, levels={o.levels}, pairwise_max={o.n_max}, p_fail/max={o.pfail:.1e}}}  // {o.note}")
             elif o.type == OP_LUT:
                 head += (f" {{p={o.p}, lsbs_removed={o.r}, table_bits={o.w}, signed={int(o.signed)}, shift={o.ip[3]}, "
                          f"tier={ps.tiers[o.ip[4]].name}" + (", rounding=approximate" if o.ip[9] else "") +
@@ -277,6 +332,24 @@ class _Builder:
         self.ops.append(op)
         return _Act(q, a.scale, tid, a.lo * K * K, a.hi * K * K)
 
+    def max_pool(self, a, k, s, p, note):
+        """stem MaxPool2d(k, s, p) on the integers of a table's output (guaranteed range [lo, hi])"""
+        q = max_pool_int(a.q, k, s, p)
+        _, C, H, W = a.q.shape
+        tid = self.tensor(C, q.shape[2], q.shape[3], a.lo, a.hi)
+        p_d = max(1, (a.hi - a.lo).bit_length()) + 1               # the signed difference of two operands
+        op = OpInfo(OP_MAXPOOL, a.tid, -1, tid, p=p_d, w=p_d, signed=True, note=note)
+        op.ip[:3] = [k, s, p]
+        op.ip[5] = p_d
+        op.ip[6] = 1
+        centres = lut_centers(p_d, 0, p_d, True)
+        op.table_values = np.maximum(centres, 0).reshape(1, -1)     # relu(d): max(a, b) = b + relu(a - b)
+        op.pool_geom = pool_geometry(C, H, W, k, s, p)
+        op.n_max = sum(m * sum(pl) for m, pl in op.pool_geom)
+        op.levels = sum(len(pl) for _, pl in op.pool_geom)
+        self.ops.append(op)
+        return _Act(q, a.scale, tid, a.lo, a.hi)
+
     def lut_to_conv(self, a, fn, per_channel, rounding, out_scale, note):
         """table site whose output feeds a convolution; wide sites are split into a cheap noisy look-up followed by an
         identity 'refresh' bootstrap on a small ring (ParamSet.refresh_min_w)"""
@@ -355,11 +428,16 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
     real = acc.q * acc.scale
     _bn_calibrate(model.bn1, real)
     h = _bn_apply(model.bn1, real)
+    pool1 = getattr(model, "pool1", None)
+    if pool1 and not model.relu1:
+        raise ValueError("the stem MaxPool2d follows the stem QuantReLU (reference backbone.py:248-259)")
     if model.relu1:
         s_r = scale_of("stem_relu", np.maximum(h, 0), False)
         hq = act_quant(np.maximum(h, 0), s_r, False, bits) * s_r
     else:
         s_r, hq = None, h
+    if pool1:
+        hq = max_pool_int(np.rint(hq / s_r).astype(np.int64), *pool1) * s_r
     s_q0 = scale_of("stem_quant_out", hq, True)
 
     def chan_fn(bn, s_acc, post):
@@ -373,7 +451,15 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
             x = act_quant(np.maximum(x, 0), s_r, False, bits) * s_r
         return act_quant(x, s_q0, True, bits)
 
-    a = bld.lut_to_conv(acc, chan_fn(model.bn1, acc.scale, stem_post), True, True, s_q0, "stem: bn1+relu+quant_out")
+    if pool1:
+        # three sites: bn1 + QuantReLU (u-bit on s_r), the max pool on those integers, quant_out.  The first runs split + refreshed
+        # (lut_to_conv) so that the 3x-larger-than-the-pool-output stem tensor is stored at the refresh ring
+        r0 = bld.lut_to_conv(acc, chan_fn(model.bn1, acc.scale, lambda x: act_quant(np.maximum(x, 0), s_r, False, bits)), True, True, s_r,
+                             "stem: bn1+relu")
+        mp = bld.max_pool(r0, *pool1, "stem: pool1")
+        a = bld.lut_to_conv(mp, lambda vals: act_quant(vals * s_r, s_q0, True, bits), False, False, s_q0, "stem: pool1 -> quant_out")
+    else:
+        a = bld.lut_to_conv(acc, chan_fn(model.bn1, acc.scale, stem_post), True, True, s_q0, "stem: bn1+relu+quant_out")
 
     for bi, blk in enumerate(model.blocks):
         # C1 -> BN1 -> relu1 (u4)                                            backbone.py:94-96
@@ -453,6 +539,8 @@ def _assign_encodings(circ):
     for o in reversed(ops):
         if o.type == OP_LUT:
             need = 63 - o.p
+        elif o.type == OP_MAXPOOL:               # the output shares the input's encoding; the difference needs p_d bits
+            need = 63 - o.p if req[o.dst] is None else min(req[o.dst], 63 - o.p)
         else:
             need = req[o.dst]
         for s in ([o.src0, o.src1] if o.type == OP_ADD else [o.src0]):
@@ -462,7 +550,7 @@ def _assign_encodings(circ):
     # a table whose output is only ever added (or decrypted) tolerates a noisier, cheaper tier
     amplified = [False] * len(T)
     for o in ops:
-        if o.type in (OP_CONV, OP_SUMPOOL):
+        if o.type in (OP_CONV, OP_SUMPOOL, OP_MAXPOOL):     # a max pool subtracts two inputs and adds bootstrap outputs to one
             amplified[o.src0] = True
     for o in reversed(ops):          # an add passes the requirement of its result on to its operands
         if o.type == OP_ADD and amplified[o.dst]:
@@ -483,6 +571,21 @@ def _assign_encodings(circ):
             o.ip[10] = T[o.src0].deff
             T[o.dst].deff = ps.tiers[tier].k << ps.tiers[tier].logN
             o.lp[0] = (1 << 62) if o.signed else 0
+            enc = (o.table_values.astype(object) * (1 << T[o.dst].e)) % (1 << 64)
+            o.payload = np.array(enc, dtype=np.uint64).view(np.int64)
+        elif o.type == OP_MAXPOOL:
+            ps = circ.param_set
+            T[o.dst].e = T[o.src0].e
+            shift = (63 - o.p) - T[o.src0].e
+            assert shift >= 0
+            tier = ps.tier_for_width(o.p, coarse=not amplified[o.dst])
+            if o.p > ps.tiers[tier].logN - 1:
+                raise ValueError("max-pool difference table wider than the ring")
+            o.ip[3], o.ip[4] = shift, tier
+            o.ip[10] = T[o.src0].deff
+            # the pairwise maxima accumulate a bootstrap output into the first kN words of a copy of `b`
+            T[o.dst].deff = max(T[o.src0].deff, ps.tiers[tier].k << ps.tiers[tier].logN)
+            o.lp[0] = 1 << 62                        # signed body offset: index = d + 2^(p_d - 1)
             enc = (o.table_values.astype(object) * (1 << T[o.dst].e)) % (1 << 64)
             o.payload = np.array(enc, dtype=np.uint64).view(np.int64)
         else:
@@ -507,6 +610,24 @@ def _estimate_noise(circ):
             T[o.dst].var = s.var + T[o.src1].var
         elif o.type == OP_SUMPOOL:
             T[o.dst].var = o.ip[0] ** 2 * s.var
+        elif o.type == OP_MAXPOOL:
+            # every tree level: the difference of two candidates (variance var(a) + var(b), bounded by twice the level's worst),
+            # key-switched over the level's effective dimension, mod-switched, one signed p_d-bit table; b + relu(a - b) adds one
+            # bootstrap output to b.  The column pass starts from the row pass's output.
+            tt = ps.tiers[o.ip[4]]
+            ring = tt.k << tt.logN
+            v, d_in, worst, v_tab = s.var, s.deff or ps.D, 0.0, 0.0
+            for mult, pairs in o.pool_geom:
+                for npair in pairs:
+                    v_tab = 2.0 * v * 4.0 ** o.ip[3] + P.var_keyswitch(d_in, tt) + P.var_modswitch(tt)
+                    pf = P.p_fail(2.0 ** -(o.p + 2), v_tab)
+                    worst = max(worst, pf)
+                    total += pf * mult * npair
+                    v += P.var_pbs_out(tt, ps.fft_noise_c)
+                    d_in = max(d_in, ring)
+            o.pfail = worst
+            o.sim_sigma = math.sqrt(v_tab)
+            T[o.dst].var = v
         else:
             tt = ps.tiers[o.ip[4]]
             v_in0 = s.var * 4.0 ** o.ip[3]

@@ -71,6 +71,20 @@ class Context:
         check(self.L.dctfhe_sum_pool_rows(self.h, ptr(x), L - 1, deff, B, Cc, H, W, K, dim_o, ptr(out)))
         return out
 
+    def max_pool_rows(self, x, deff, k, s, p, p_d, table=None, dim_o=0, keys=None, tier=0):
+        """MaxPool2d(k, s, p) as the session's tree (include/dctfhe.h dctfhe_max_pool_rows).  keys given: x [batch, C, H, W, dim + 1]
+        encrypted rows -> [batch, C, Ho, Wo, dim_o + 1]; keys None: the clear form, x [batch, C, H, W] words -> [batch, C, Ho, Wo]"""
+        keys = getattr(keys, "eval", keys)
+        x = np.ascontiguousarray(x, np.uint64)
+        B, Cc, H, W = x.shape[:4]
+        Ho, Wo = (max(H + 2 * p - k, 0) // max(s, 1) + 1, max(W + 2 * p - k, 0) // max(s, 1) + 1)   # the library checks the geometry
+        dim_in = x.shape[4] - 1 if keys is not None else 0
+        out = np.empty((B, Cc, Ho, Wo) + ((dim_o + 1,) if keys is not None else ()), np.uint64)
+        tab = None if table is None else np.ascontiguousarray(table, np.int64)
+        check(self.L.dctfhe_max_pool_rows(self.h, None if keys is None else keys.h, tier, ptr(x), dim_in, deff, B, Cc, H, W, k, s, p, p_d,
+                                          None if tab is None else ptr(tab), dim_o, ptr(out)))
+        return out
+
     def conv2d(self, D, cts, batch, Cin, H, W, weight, stride, pad):
         weight = np.ascontiguousarray(weight, np.int8)
         Cout, _, KH, KW = weight.shape
@@ -300,6 +314,17 @@ class EvalKeys:
         check(self.L.dctfhe_keyswitch_prefix(self.ctx.h, self.h, tier, ptr(cts), cts.shape[0], shift, deff, ptr(out)))
         return out
 
+    def keyswitch_diff(self, tier, cts, ia, ib, shift=0, body_add=0, deff=0):
+        """key switch of cts[ia[c]] - cts[ib[c]] (dctfhe_keyswitch_diff): small ciphertexts [len(ia), n + 1]"""
+        cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, self.D + 1)
+        ia, ib = np.ascontiguousarray(ia, np.int32), np.ascontiguousarray(ib, np.int32)
+        if ia.size != cts.shape[0] or ib.size != cts.shape[0]:
+            raise ValueError("keyswitch_diff takes one index pair per row")
+        out = np.empty((cts.shape[0], self.tier(tier).n + 1), np.uint64)
+        check(self.L.dctfhe_keyswitch_diff(self.ctx.h, self.h, tier, ptr(cts), cts.shape[0], ptr(ia), ptr(ib), shift, C.c_uint64(body_add), deff,
+                                           ptr(out)))
+        return out
+
     def modswitch_center(self, tier, cts_small):
         """centred mod switch (dctfhe_modswitch_center): the adjusted copy of small ciphertexts [count, n + 1]"""
         out = np.ascontiguousarray(cts_small, np.uint64).copy()
@@ -355,7 +380,7 @@ class Keys:
         if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter",
                     "encrypt_seeded", "export_eval_keys_compressed"):
             return getattr(self.client, name)
-        if name in ("export_ksk", "keyswitch", "modswitch_center", "pbs", "round_lut", "bench_pbs", "to_blob"):
+        if name in ("export_ksk", "keyswitch", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
         raise AttributeError(name)
 

@@ -18,7 +18,21 @@ NET_PERTURBATIONS = {
     "48_24_8": dict(conv1_kernel=1, conv1_stride=1, conv1_padding=0, relu1=True, avgpool_kernel=3),
     "64_3_32": dict(conv1_kernel=3, conv1_stride=1, conv1_padding=1, relu1=True, avgpool_kernel=3),
     "64_48_112": dict(conv1_kernel=1, conv1_stride=1, conv1_padding=0, relu1=False, avgpool_kernel=14),
+    # RGB ResNet-18 trunks with the stem MaxPool2d(pool1_kernel, pool1_stride, padding=1) (backbone.py:252-259, 447-481)
+    "64_3_128": dict(conv1_kernel=7, conv1_stride=2, conv1_padding=3, relu1=True, pool1_kernel=3, pool1_stride=2, avgpool_kernel=3),
+    "64_3_224": dict(conv1_kernel=7, conv1_stride=2, conv1_padding=3, relu1=True, pool1_kernel=3, pool1_stride=2, avgpool_kernel=7),
+    "64_3_448": dict(conv1_kernel=7, conv1_stride=2, conv1_padding=3, relu1=True, pool1_kernel=3, pool1_stride=2, avgpool_kernel=14),
+    "64_3_1024": dict(conv1_kernel=7, conv1_stride=2, conv1_padding=3, relu1=True, pool1_kernel=7, pool1_stride=4, avgpool_kernel=11),
 }
+POOL1_PADDING = 1       # fixed in the reference (backbone.py:256)
+
+
+def pool_out(s, pool):
+    """spatial size after MaxPool2d(k, stride, padding) with floor mode; pool = (k, stride, padding) or None"""
+    if pool is None:
+        return s
+    k, st, p = pool
+    return (s + 2 * p - k) // st + 1
 
 
 @dataclass
@@ -65,6 +79,8 @@ class ResNetQ:                    # reference ResNetQDCT, backbone.py:187-288
     # dctfhe.checkpoint; keys: "quant_inp", "stem_relu", "stem_quant_out", ("block", i, "relu1" | "quant_out" |
     # "BNquant_out" | "relu2"), "final".  A missing key falls back to calibration (dctfhe.compile.act_scale).
     act_scales: dict = field(default_factory=dict)
+    # stem nn.MaxPool2d after the stem QuantReLU as (kernel, stride, padding); None: no pool (every non-RGB-224 configuration)
+    pool1: tuple = None
 
 
 def _init_conv(rng, cout, cin, k):
@@ -101,7 +117,9 @@ def build_resnet_q(list_num_layers, list_out_dims, in_channels, img_size, bit_wi
             indim = outdim
     # spatial size after the trunk decides the flattened feature count (the reference hard-codes indim,
     # backbone.py:280 -- wrong for '48_3_32'; we report the real size)
+    pool1 = (pert["pool1_kernel"], pert["pool1_stride"], POOL1_PADDING) if pert.get("pool1_kernel") else None
     s = (img_size + 2 * pert["conv1_padding"] - pert["conv1_kernel"]) // pert["conv1_stride"] + 1
+    s = pool_out(s, pool1)
     for b in blocks:
         s = (s + 2 - 3) // b.C1.stride + 1
     s_out = s // pert["avgpool_kernel"]
@@ -109,7 +127,7 @@ def build_resnet_q(list_num_layers, list_out_dims, in_channels, img_size, bit_wi
     cw = rng.normal(0.0, 1.0 / math.sqrt(feat), size=(num_classes, feat))
     return ResNetQ(name=name, in_channels=in_channels, img_size=img_size, bit_width=bit_width, conv1=conv1, bn1=_init_bn(list_out_dims[0]),
                    relu1=pert.get("relu1", True), blocks=blocks, avgpool_kernel=pert["avgpool_kernel"], final_feat_dim=feat,
-                   classifier_w=cw, classifier_b=np.zeros(num_classes))
+                   classifier_w=cw, classifier_b=np.zeros(num_classes), pool1=pool1)
 
 
 def ResNet20QAT(bit_width=4, in_channels=3, img_size=224, seed=0, num_classes=10):
@@ -122,9 +140,10 @@ def ResNet18QAT(bit_width=4, in_channels=3, img_size=224, seed=0, num_classes=10
     return build_resnet_q([2, 2, 2, 2], [64, 128, 256, 512], in_channels, img_size, bit_width, False, num_classes, seed, "ResNet18qat")
 
 
-def tiny_resnet_q(in_channels=4, img_size=6, width=(6, 8), seed=0, bit_width=4):
+def tiny_resnet_q(in_channels=4, img_size=6, width=(6, 8), seed=0, bit_width=4, pool1=None):
     """Two-block miniature with the same block structure (identity and 1x1 shortcuts, a stride-2
-    stage, floor-mode pooling): small enough for the CPU oracle's encrypted twin."""
+    stage, floor-mode pooling): small enough for the CPU oracle's encrypted twin.  pool1 = (k, stride, padding): a stem
+    max pool as in the RGB ResNet-18 trunks (None, the default, keeps the model and its circuit as they were)."""
     rng = np.random.default_rng(seed)
     conv1 = ConvLayer(_init_conv(rng, width[0], in_channels, 1), 1, 0)
     blocks = []
@@ -138,14 +157,15 @@ def tiny_resnet_q(in_channels=4, img_size=6, width=(6, 8), seed=0, bit_width=4):
             b.BNshortcut = _init_bn(outdim)
         blocks.append(b)
         indim = outdim
-    s = img_size
+    s = pool_out(img_size, None if pool1 is None else tuple(pool1))
     for b in blocks:
         s = (s + 2 - 3) // b.C1.stride + 1
     k = s if s < 3 else s - 1                 # floor-mode pooling drops a border when s > k
     feat = indim * (s // k) ** 2
     return ResNetQ(name="tiny", in_channels=in_channels, img_size=img_size, bit_width=bit_width, conv1=conv1, bn1=_init_bn(width[0]), relu1=True,
                    blocks=blocks, avgpool_kernel=k, final_feat_dim=feat,
-                   classifier_w=rng.normal(0, 1.0 / math.sqrt(feat), size=(10, feat)), classifier_b=np.zeros(10))
+                   classifier_w=rng.normal(0, 1.0 / math.sqrt(feat), size=(10, feat)), classifier_b=np.zeros(10),
+                   pool1=None if pool1 is None else tuple(pool1))
 
 
 def float_forward(model, x):
@@ -164,6 +184,9 @@ def float_forward(model, x):
     h = bn(model.bn1, conv(model.conv1, t(x)))
     if model.relu1:
         h = F.relu(h)
+    if getattr(model, "pool1", None):
+        k, st, p = model.pool1
+        h = F.max_pool2d(h, k, st, p)
     for b in model.blocks:
         o = bn(b.BN2, conv(b.C2, F.relu(bn(b.BN1, conv(b.C1, h)))))
         sc = h if b.shortcut is None else bn(b.BNshortcut, conv(b.shortcut, h))

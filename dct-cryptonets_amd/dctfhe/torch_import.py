@@ -40,6 +40,18 @@ def _bn(m):
     return models.BatchNorm(gamma=g, beta=b, mean=_np(m.running_mean), var=_np(m.running_var), eps=float(m.eps))
 
 
+def _maxpool(m):
+    """(kernel, stride, padding) of a square nn.MaxPool2d with dilation 1, floor mode and no indices"""
+    two = lambda v: (v, v) if isinstance(v, int) else tuple(v)
+    k, st, p, d = two(m.kernel_size), two(m.stride if m.stride is not None else m.kernel_size), two(m.padding), two(getattr(m, "dilation", 1))
+    if k[0] != k[1] or st[0] != st[1] or p[0] != p[1] or d != (1, 1) or getattr(m, "ceil_mode", False) or getattr(m, "return_indices", False):
+        raise ValueError(f"unsupported MaxPool2d geometry: kernel {k} stride {st} padding {p} dilation {d} "
+                         f"(square, dilation 1, ceil_mode=False, no indices)")
+    if not (k[0] >= 1 and st[0] >= 1 and 0 <= p[0] <= k[0] // 2):
+        raise ValueError(f"unsupported MaxPool2d geometry: kernel {k[0]} stride {st[0]} padding {p[0]}")
+    return int(k[0]), int(st[0]), int(p[0])
+
+
 def _is_block(m):
     return all(hasattr(m, a) for a in ("C1", "BN1", "C2", "BN2"))
 
@@ -72,7 +84,8 @@ def from_torch_module(module, bit_width=4, in_channels=None, img_size=None, name
     layers = list(seq.children())
     conv1 = bn1 = None
     relu1 = False
-    blocks, avgpool = [], None
+    blocks, avgpool, pool1 = [], None, None
+    prev = None                                          # class name of the previous non-quantiser layer
     for m in layers:
         c = _cls(m)
         if _is_block(m):
@@ -96,11 +109,16 @@ def from_torch_module(module, bit_width=4, in_channels=None, img_size=None, name
                 raise ValueError("AvgPool2d must be non-overlapping and unpadded (reference backbone.py:276)")
             avgpool = int(k)
         elif "MaxPool" in c:
-            raise ValueError("MaxPool2d in the trunk (pool1_kernel perturbations, reference backbone.py:252-258) has no encrypted operator here")
+            # only the stem pool of the RGB ResNet-18 trunks: directly after the stem ReLU, before any block (backbone.py:252-259)
+            if blocks or pool1 is not None or prev is None or "ReLU" not in prev or conv1 is None or bn1 is None:
+                raise ValueError("MaxPool2d is supported only directly after the stem ReLU, before the residual blocks "
+                                 "(reference backbone.py:252-259)")
+            pool1 = _maxpool(m)
         elif "QuantIdentity" in c or "Flatten" in c or "Identity" in c or "Dropout" in c:
             continue            # quantisers are re-stated by the compiler; Flatten is a view
         else:
             raise ValueError(f"unsupported layer in the trunk: {c}")
+        prev = c
     if conv1 is None or bn1 is None or avgpool is None:
         raise ValueError("trunk must contain the stem Conv2d + BatchNorm2d and a final AvgPool2d")
     cin = conv1.weight.shape[1]
@@ -109,6 +127,7 @@ def from_torch_module(module, bit_width=4, in_channels=None, img_size=None, name
     feat = (blocks[-1].C2.weight.shape[0] if blocks else conv1.weight.shape[0])
     if img_size is not None:
         s = (img_size + 2 * conv1.pad - conv1.weight.shape[2]) // conv1.stride + 1
+        s = models.pool_out(s, pool1)
         for b in blocks:
             s = (s + 2 - 3) // b.C1.stride + 1
         feat *= (s // avgpool) ** 2
@@ -117,7 +136,8 @@ def from_torch_module(module, bit_width=4, in_channels=None, img_size=None, name
         cw = _np(classifier.weight)
         cb = _np(classifier.bias) if classifier.bias is not None else np.zeros(cw.shape[0])
     return models.ResNetQ(name=name or _cls(module), in_channels=cin, img_size=img_size or 0, bit_width=bit_width, conv1=conv1, bn1=bn1,
-                          relu1=relu1, blocks=blocks, avgpool_kernel=avgpool, final_feat_dim=feat, classifier_w=cw, classifier_b=cb)
+                          relu1=relu1, blocks=blocks, avgpool_kernel=avgpool, final_feat_dim=feat, classifier_w=cw, classifier_b=cb,
+                          pool1=pool1)
 
 
 def seed_parameters(module, seed):

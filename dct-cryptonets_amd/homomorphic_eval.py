@@ -45,7 +45,8 @@ def parse_args():
     h.add_argument("--calib_batch_size", default=64, type=int, help="Batch size used for post-training quantization calibration")
     h.add_argument("--test_batch_size", default=1, type=int, help="Inference batch size")
     h.add_argument("--test_subset", default=1, type=int, help="Number of images to perform inference on")
-    h.add_argument("--fhe_mode", default="simulate", type=str, choices=["simulate", "execute"], help="simulate (accuracy) or execute (latency)")
+    h.add_argument("--fhe_mode", default="simulate", type=str, choices=["simulate", "execute", "disable"],
+                   help="simulate (accuracy), execute (latency) or disable (the clear integer circuit)")
     h.add_argument("--rounding_threshold_bits", default=6, type=int, help="Scaling factor to remove least significant bits")
     h.add_argument("--n_bits", default=5, type=int, help="Bit-width of homomorphic circuit")
     h.add_argument("--p_error", default=0.01, type=float, help="PBS error probability")

@@ -204,6 +204,20 @@ int dctfhe_affine_rows(dctfhe_ctx* ctx, const uint64_t* a, int dim_a, int deff_a
 int dctfhe_sum_pool_rows(dctfhe_ctx* ctx, const uint64_t* in /* [batch][C][H][W] rows */, int dim_in, int deff_in, int batch, int C, int H,
                          int W, int K, int dim_o, uint64_t* out /* [batch][C][H/K][W/K] rows */);
 
+/* max pool (circuit op 5), one piece at a time on host buffers.
+ * keyswitch_diff: key switch of cts[ia[c]] - cts[ib[c]] (count rows of D + 1 words and count index pairs, indices < count), shifted
+ * left by `shift`, body_add on the body; deff as dctfhe_keyswitch_prefix.  Output: count small ciphertexts of `tier`.
+ * max_pool_rows: MaxPool2d(k, s, p) (1 <= k <= 32, 0 <= p <= k/2, floor mode, out-of-range taps ignored) as the session runs it:
+ * row pass then column pass, each a tree of pairwise maxima b + relu(a - b) with one bootstrap of the signed p_d-bit `table` (2^p_d
+ * entries, relu of the centred differences) on `tier`.  Inputs carry value * 2^(63 - p_d); outputs rows of dim_o + 1 words,
+ * dim_o >= max(deff_in, ring of the tier).  keys == NULL: the clear form, one word per element, the maximum of the words read as
+ * signed int64 (dim_in, deff_in, dim_o, tier and table unused). */
+int dctfhe_keyswitch_diff(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, const uint64_t* cts, size_t count, const int32_t* ia,
+                          const int32_t* ib, int shift, uint64_t body_add, int deff, uint64_t* out_small);
+int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, const uint64_t* in /* [batch][C][H][W] rows */, int dim_in,
+                         int deff_in, int batch, int C, int H, int W, int k, int s, int p, int p_d, const int64_t* table, int dim_o,
+                         uint64_t* out /* [batch][C][Ho][Wo] rows */);
+
 /* K10, client side, plaintext: the DCT front-end of reference data/cvfunctional.py:37-74 + data/cvtransforms.py:56-64,117-208 on
  * uint8 planes (luma [batch][fs*S][fs*S]; two chroma slots [batch][fs*Sc][fs*Sc], Sc = S/2 for the 4:2:0 paths or S):
  * blockwise orthonormal DCT-II of (pixel - 128), only the kept coefficients idx_* (row-major u*fs+v), chroma grids
@@ -215,6 +229,10 @@ int dctfhe_dct_frontend(dctfhe_ctx* ctx, const uint8_t* y, const uint8_t* c1, co
 
 /* host-only validators (no GPU): parameter set / circuit blob well-formed?  0 or -1 with dctfhe_last_error() */
 int dctfhe_params_check(const dctfhe_params* params);
+/* Circuit op types: 1 conv2d, 2 add, 3 sum_pool, 4 look-up, 5 max pool.  Max-pool record: ip[0..2] = k, stride, padding; ip[3] = shift
+ * of the differences to 63 - p_d; ip[4] = tier of the relu table; ip[5] = p_d (signed difference bits); ip[6] = 1 table; ip[10] =
+ * effective dimension of the input; lp[0] = body offset of the differences (2^62); payload: 2^p_d int64 entries relu(d) * 2^e.
+ * The output keeps the input's encoding e. */
 int dctfhe_circuit_validate(const void* blob, size_t size);
 
 /* R1: load a compiled circuit description (built by dctfhe.compile, format in DESIGN.md section 4). */

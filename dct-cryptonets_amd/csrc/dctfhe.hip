@@ -347,7 +347,7 @@ struct dctfhe_session {
 #define PBS_CASES(X)                                                                                 \
   X(8, 2, 2, 8) X(9, 1, 2, 16) X(9, 1, 3, 8) X(10, 1, 1, 8) X(10, 1, 2, 8) X(10, 2, 1, 8) X(10, 2, 2, 8)  \
   X(11, 1, 1, 8) X(11, 1, 2, 8) X(11, 1, 3, 8) X(12, 1, 1, 8) X(12, 1, 2, 8) X(12, 1, 3, 8)           \
-  X(13, 1, 1, 8) X(13, 1, 2, 8) X(13, 1, 3, 8)
+  X(13, 1, 1, 8) X(13, 1, 2, 8) X(13, 1, 3, 8) X(11, 1, 4, 8)
 
 // two-bit blind rotation (tier.unroll == 2): k = 1, one level
 #define PBS_MB_CASES(X) X(11) X(12) X(13)
@@ -495,8 +495,12 @@ static int check_params(const dctfhe_params* p) {
     if (t.n < 1 || t.n > p->n_max) return fail("tier %d: n out of range", i);
     if (t.k < 1 || t.k > 2 || t.logN < 8 || t.logN > 13) return fail("tier %d: k or logN out of range", i);
     if ((t.k << t.logN) > p->D) return fail("tier %d: k*N exceeds D", i);
-    if (t.l * t.beta > 63 || t.l < 1 || t.l > 3 || t.beta < 1 || (t.l >= 2 && t.beta > 16) || (t.l == 1 && t.beta > 28))
-      return fail("tier %d: bad bootstrap gadget (l <= 3; beta <= 16 when l >= 2, <= 28 when l == 1: 32-bit accumulators)", i);
+    if (t.l * t.beta > 63 || t.l < 1 || t.l > 4 || t.beta < 1 || (t.l >= 2 && t.beta > 16) || (t.l == 1 && t.beta > 28))
+      return fail("tier %d: bad bootstrap gadget (l <= 4; beta <= 16 when l >= 2, <= 28 when l == 1: 32-bit accumulators)", i);
+    // four levels: one kernel shape (tier T5r); its deferred digits of levels 1..3 share one 32-bit word in 10-bit fields
+    // (pbs_core.h pack_digits)
+    if (t.l == 4 && !(t.k == 1 && t.logN == 11 && t.beta <= 10))
+      return fail("tier %d: bad bootstrap gadget (four levels only with k = 1, N = 2048, beta <= 10)", i);
     if (t.unroll != 1 && t.unroll != 2) return fail("tier %d: unroll must be 1 or 2", i);
     if (t.unroll == 2) {
       const bool paired = t.k == 1 && t.l == 1 && t.logN >= 11;                                        // pair-interleaved kernels

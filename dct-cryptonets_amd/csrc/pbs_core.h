@@ -117,6 +117,38 @@ HD void decompose(uint32_t v, int beta, int32_t* digs) {
   static_assert(L == 1, "32-bit accumulators are for one-level tiers");
   digs[0] = (int32_t)(v + (1u << (31 - beta))) >> (32 - beta);
 }
+
+// The digits of levels 1 .. L-1 wait packed in one 32-bit word per coefficient while level 0 goes through its transform:
+// 16-bit fields up to three levels (beta <= 16), 32 / (L - 1)-bit fields beyond (four levels: 10-bit fields, beta <= 10;
+// the library refuses wider digits, csrc/dctfhe.hip check_params).  Digits are balanced, in [-B/2, B/2), so a field of
+// beta bits holds one as two's complement.
+template <int L>
+constexpr int packed_digit_bits() { return L <= 3 ? 16 : 32 / (L - 1); }
+
+template <int L>
+HD uint32_t pack_digits(const int32_t* dg) {
+  constexpr int FB = packed_digit_bits<L>();
+  static_assert((L - 1) * FB <= 32, "the deferred digits share one 32-bit word");
+  uint32_t pk = 0;
+  if constexpr (L <= 3) {
+    if constexpr (L > 1) pk = (uint32_t)(uint16_t)(int16_t)dg[1];
+    if constexpr (L > 2) pk |= (uint32_t)(uint16_t)(int16_t)dg[2] << 16;
+  } else {
+    static_for<1, L>([&](auto Lv) {
+      constexpr int lev = decltype(Lv)::value;
+      pk |= ((uint32_t)dg[lev] & ((1u << FB) - 1)) << (FB * (lev - 1));
+    });
+  }
+  return pk;
+}
+
+// digit of level LEV >= 1 out of a packed word, sign-extended
+template <int L, int LEV>
+HD double unpack_digit(uint32_t pk) {
+  constexpr int FB = packed_digit_bits<L>();
+  if constexpr (L <= 3) return (double)(int16_t)(pk >> (16 * (LEV - 1)));
+  else return (double)((int32_t)(pk << (32 - FB * LEV)) >> (32 - FB));
+}
 HD void acc_add(uint64_t& a, double d) { a += f64_to_torus(d); }
 HD void acc_add(uint32_t& a, double d) { a += f64_to_torus32(d); }
 HD uint64_t acc_wide(uint64_t a) { return a; }
@@ -281,7 +313,6 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
       const cplx* key = A.bsk + (size_t)(3 * (i >> 1)) * G::BSK_ELEMS_PER_KEYBIT;
       static_for<0, K + 1>([&](auto Pp) {
         constexpr int p = decltype(Pp)::value;
-        static_assert(L <= 3, "packing holds two deferred digits");
         uint32_t packed[2 * P];
         double first[2 * P];
         static_for<0, 2 * P>([&](auto R) {
@@ -291,10 +322,7 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
           int32_t dg[L];
           decompose<L>(own, A.beta, dg);
           first[r] = (double)dg[0];
-          uint32_t pk = 0;
-          if constexpr (L > 1) pk = (uint32_t)(uint16_t)(int16_t)dg[1];
-          if constexpr (L > 2) pk |= (uint32_t)(uint16_t)(int16_t)dg[2] << 16;
-          packed[r] = pk;
+          packed[r] = pack_digits<L>(dg);
         });
         static_for<0, L>([&](auto Lv) {
           constexpr int lev = decltype(Lv)::value;
@@ -303,7 +331,7 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
           static_for<0, P>([&](auto J) {
             constexpr int j = decltype(J)::value;
             if constexpr (lev == 0) v[j] = cmk(first[j], first[P + j]);
-            else v[j] = cmk((double)(int16_t)(packed[j] >> (16 * (lev - 1))), (double)(int16_t)(packed[P + j] >> (16 * (lev - 1))));
+            else v[j] = cmk(unpack_digit<L, lev>(packed[j]), unpack_digit<L, lev>(packed[P + j]));
           });
           fft_forward<G::LOGM, P>(v, t, tw, twist, exch, sync, wsync);
           tick.template at<4>();                          // (general form) phase 4: decomposition + one forward transform
@@ -445,8 +473,8 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
     static_for<0, K + 1>([&](auto Pp) {
       constexpr int p = decltype(Pp)::value;
       // rotate polynomial p through LDS: every coefficient is read (rotated) and decomposed once; level 0 goes
-      // straight to the transform, the other digits (<= 16 bits each: beta <= 16 whenever l >= 2) wait packed in
-      // one register per coefficient.  (Re-reading + re-decomposing per level cost 15% more: integer VALU.)
+      // straight to the transform, the other digits wait packed in one register per coefficient (pack_digits).
+      // (Re-reading + re-decomposing per level cost 15% more: integer VALU.)
       // LDS-resident polynomials are rotated straight out of their home array; the others go through the stage,
       // which shares memory with the exchange buffer: barrier before the (cross-wave) stage write so that nobody
       // is still gathering there, barrier after it; the next transform's leading barrier covers the reads.
@@ -456,7 +484,6 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
         sync();
       }
       // one rotated read + one full decomposition per coefficient; the digits of levels >= 1 wait packed in a register
-      static_assert(L <= 3, "packing holds two deferred digits");
       uint32_t packed[2 * P];
       double first[2 * P];
       static_for<0, 2 * P>([&](auto R) {
@@ -469,10 +496,7 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
         int32_t dg[L];
         decompose<L>((acc_t)(x - own), A.beta, dg);
         first[r] = (double)dg[0];
-        uint32_t pk = 0;
-        if constexpr (L > 1) pk = (uint32_t)(uint16_t)(int16_t)dg[1];
-        if constexpr (L > 2) pk |= (uint32_t)(uint16_t)(int16_t)dg[2] << 16;
-        packed[r] = pk;
+        packed[r] = pack_digits<L>(dg);
       });
       static_for<0, L>([&](auto Lv) {
         constexpr int lev = decltype(Lv)::value;
@@ -480,7 +504,7 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
         static_for<0, P>([&](auto J) {
           constexpr int j = decltype(J)::value;
           if constexpr (lev == 0) v[j] = cmk(first[j], first[P + j]);
-          else v[j] = cmk((double)(int16_t)(packed[j] >> (16 * (lev - 1))), (double)(int16_t)(packed[P + j] >> (16 * (lev - 1))));
+          else v[j] = cmk(unpack_digit<L, lev>(packed[j]), unpack_digit<L, lev>(packed[P + j]));
         });
         fft_forward<G::LOGM, P>(v, t, tw, twist, exch, sync, wsync);
         const cplx* row = bsk_i + (size_t)(p * L + lev) * (K + 1) * M;

@@ -390,7 +390,8 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
                   rounding_method="exact", tier_policy="exact"):
     """-> CompiledCircuit.  calib: float [B, C, H, W] calibration inputs (reference: first training batch,
     homomorphic_eval.py:258-261).
-    tier_policy "exact" (default): the exact-evaluation catalogue of dctfhe/params.py whatever p_error says (the
+    tier_policy "exact" (default): the exact-evaluation catalogue of dctfhe/params.py for the model's bit width
+    (params_for_bit_width: its own for 5-bit trunks, default_params() otherwise) whatever p_error says (the
     reference hands p_error = 0.01 to Concrete's optimiser, homomorphic_eval.py:282; here outputs then equal the integer
     circuit and the modelled failure estimate is reported).  tier_policy "p_error": the cheaper catalogue whose look-ups
     fail with probability <= p_error each -- stochastic outputs, like the reference's.
@@ -403,7 +404,8 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
         raise ValueError(f"tier_policy {tier_policy!r}")
     own_catalogue = param_set is None
     if param_set is None:
-        param_set = P.params_for_p_error(p_error if p_error is not None else 0.01) if tier_policy == "p_error" else P.default_params()
+        param_set = (P.params_for_p_error(p_error if p_error is not None else 0.01) if tier_policy == "p_error"
+                     else P.params_for_bit_width(model.bit_width))
     ps = param_set
     calib = np.asarray(calib, dtype=np.float64)
     bits = model.bit_width

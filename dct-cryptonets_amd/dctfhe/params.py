@@ -181,6 +181,40 @@ def default_params():
                     input_dim=2048)
 
 
+def params_for_bit_width(bit_width):
+    """Exact-evaluation catalogue for circuits of `bit_width`-bit weights and activations: the 5-bit one below for 5, default_params()
+    for every other width (that catalogue, its blob and its evaluation keys are what every 4-bit circuit depends on)."""
+    return default_params_5bit() if bit_width == 5 else default_params()
+
+
+def default_params_5bit():
+    """Exact-evaluation set for 5-bit trunks: default_params() plus a 5-bit refresh tier and a longer key for the first rounding steps.
+
+    Two things break the exact budget when default_params() prices a 5-bit circuit (tools/param_search.py --bit-width 5 ->
+    profiles/bw5_param_search.log):
+      * the 5-bit activations that feed a convolution would be refreshed on T6 (N = 8192), so every tensor downstream would have
+        effective dimension 8192 instead of 2048 and every key switch four times the noise.  T5r refreshes them on N = 2048.  It has
+        four levels of 10 bits: the f64 FFT error grows as N^2 B^2 per level, and 4 x 10 bits of gadget at B = 2^10 leave a
+        quarter of the variance of 3 x 12 at B = 2^12 -- what a 3x3x512 convolution of its outputs into a 14-bit accumulator needs
+        (ResNet-18: the convolution of refresh outputs and the key switch of the first rounding step each sat at 2^-5.3 of a 1/4
+        margin).
+      * the rounding steps before the one-level twins take over (B) key-switch to a longer small key: its own key-switch noise was
+        the other half of that first-step failure.  Ba / Ba2 keep n = 560 and therefore a key-switch key of their own (ksk_share
+        needs the same shape).
+    Every 4-bit tier of default_params() stays as it is (same indices), so a 5-bit blob runs on the same engine code paths."""
+    ps = default_params()
+    t = ps.tiers
+    # B: the bit tier of the first rounding steps, longer small key
+    t[3] = TierSpec("B", n=576, k=2, logN=10, l=2, beta=14, lk=5, betak=2)
+    # Ba / Ba2: the one-level bit tiers keep n = 560 -- Ba owns the key-switch key Ba2 shares
+    t[5] = TierSpec("Ba", n=560, k=2, logN=10, l=1, beta=23, lk=5, betak=2)
+    t[8] = TierSpec("Ba2", n=560, k=2, logN=10, l=1, beta=23, lk=5, betak=2, ksk_share=5, unroll=2)
+    # T5r: refresh of 5-bit tables that feed a convolution, four levels (csrc/pbs_core.h pack_digits: beta <= 10)
+    t.append(TierSpec("T5r", n=856, k=1, logN=11, l=4, beta=10, lk=9, betak=2))
+    ps.table_tier_for_w = {4: 6, 5: 9, 6: 0}
+    return ps
+
+
 def params_for_p_error(p_error=0.01):
     """Catalogue for tier_policy "p_error" (SURVEY 8f-4): every look-up may fail with probability ~p_error, the regime the
     reference runs in (run_homomorphic_eval.sh:26).  z = 2.6 sigma inside the half-box instead of 7, so a 6-bit table fits

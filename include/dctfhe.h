@@ -40,7 +40,7 @@ typedef struct dctfhe_session dctfhe_session;
 typedef struct {
   int32_t n;            /* small LWE dimension (prefix of the small secret key) */
   int32_t k, logN;      /* GLWE dimension, log2 polynomial size; k*N <= D (prefix of the big key) */
-  int32_t l, beta;      /* bootstrap gadget: levels, base log */
+  int32_t l, beta;      /* bootstrap gadget: levels 1..4, base log; l*beta <= 63, beta <= 28 (l = 1), 16 (l = 2, 3), 10 (l = 4: k = 1, N = 2048 only) */
   int32_t lk, betak;    /* key-switch gadget: levels, base log */
   int32_t ksk_share;    /* >= 0: reuse the key-switch key of that (earlier) tier; -1: own key */
   int32_t unroll;       /* key bits per blind-rotate iteration: 1, or 2 (k = 1, l = 1, n even; key of 3n/2 blocks) */

@@ -2,7 +2,9 @@
 tiers that share a key-switch key, the smallest n (steps of 8) that keeps the worst look-up site of the benchmark circuits at the
 budget.  The circuits are compiled once (calibration is the slow part); each candidate only re-runs the encoding / tier assignment
 and the noise pricing (dctfhe/compile.py::_assign_encodings, _estimate_noise).  CPU only.
-usage: python tools/param_search.py [--configs r20_24_16,r20_3_32,r18_3_32]   -> the table profiles/r03_param_search.log holds"""
+usage: python tools/param_search.py [--configs r20_24_16,r20_3_32,r18_3_32]   -> the table profiles/r03_param_search.log holds
+       python tools/param_search.py --bit-width 5 --configs r20_24_16,r20_3_32,r18_3_32,r18_48_112
+           -> the 5-bit catalogue (params.default_params_5bit: its new tiers only), profiles/bw5_param_search.log"""
 import argparse
 import copy
 import dataclasses
@@ -18,26 +20,29 @@ import numpy as np  # noqa: E402
 from dctfhe import compile as cc, models, params as P  # noqa: E402
 
 GROUPS = {"table808": ["T6", "T6a", "T5a"], "refresh": ["T4r", "T4r2"], "rescale": ["T4"], "bit": ["B", "Ba", "Ba2"]}
+# the 5-bit catalogue keeps the 4-bit tiers as they are; searched: the bit tier of the first rounding steps and the 5-bit refresh
+GROUPS_BY_WIDTH = {4: GROUPS, 5: {"bit": ["B"], "refresh5": ["T5r"]}}
 
 
-def circuits(names):
+def circuits(names, bit_width=4):
     import bench
     out = {}
     for name in names:
         factory, in_ch, img, make_batch, _ = bench.CONFIGS[name]
         t0 = time.time()
         calib = make_batch(16 if name == "r18_48_112" else 100, 7)
-        model = getattr(models, factory)(bit_width=4, in_channels=in_ch, img_size=img, seed=0)
-        out[name] = cc.compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, p_error=0.01)
+        model = getattr(models, factory)(bit_width=bit_width, in_channels=in_ch, img_size=img, seed=0)
+        out[name] = cc.compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, p_error=0.01, param_set=P.params_for_bit_width(bit_width))
         print(f"# compiled {name} in {time.time() - t0:.0f} s: worst site {out[name].worst_site_failure:.2e}, expected failures / image "
               f"{out[name].expected_failures_per_image:.2e}", flush=True)
     return out
 
 
-def with_n(ps, changes):
+def with_n(ps, changes, bit_width=4):
     tiers = [dataclasses.replace(t, n=changes.get(t.name, t.n), lwe_sigma=0.0) if t.name in changes else t for t in ps.tiers]
-    return dataclasses.replace(ps, tiers=tiers, table_tier_for_w=dict(P.default_params().table_tier_for_w),
-                               table_tier_fallback_for_w=dict(P.default_params().table_tier_fallback_for_w))
+    ref = P.params_for_bit_width(bit_width)
+    return dataclasses.replace(ps, tiers=tiers, table_tier_for_w=dict(ref.table_tier_for_w),
+                               table_tier_fallback_for_w=dict(ref.table_tier_fallback_for_w))
 
 
 def price(circs, ps):
@@ -66,18 +71,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="r20_24_16,r20_3_32,r18_3_32")
     ap.add_argument("--budget", type=float, default=1e-12)
+    ap.add_argument("--bit-width", type=int, default=4, choices=sorted(GROUPS_BY_WIDTH))
     args = ap.parse_args()
-    circs = circuits(args.configs.split(","))
-    base = P.default_params()
+    bw = args.bit_width
+    circs = circuits(args.configs.split(","), bw)
+    base = P.params_for_bit_width(bw)
     w0, f0, c0 = price(circs, base)
     print(f"# catalogue as shipped: worst site {w0:.2e}; tiers " + ", ".join(f"{t.name} n={t.n}" for t in base.tiers))
     print("# pbs per image:", {k: v for k, v in c0.items()})
     best = {}
-    for gname, names in GROUPS.items():
+    groups = GROUPS_BY_WIDTH[bw]
+    for gname, names in groups.items():
         n0 = next(t.n for t in base.tiers if t.name == names[0])
         row = []
-        for n in range(n0 + 16, n0 - 49, -8):
-            w, f, c = price(circs, with_n(base, {nm: n for nm in names}))
+        for n in range(n0 + 16, n0 - (49 if bw == 4 else 97), -8):
+            w, f, c = price(circs, with_n(base, {nm: n for nm in names}, bw))
             moved = {k: {t: v.get(t, 0) for t in ("B", "Ba", "Ba2", "T4r", "T4r2")} for k, v in c.items()}
             row.append((n, w))
             print(f"{gname:9s} n={n:4d}: worst site {w:.2e}" + ("" if moved == {k: {t: v.get(t, 0) for t in ('B', 'Ba', 'Ba2', 'T4r', 'T4r2')} for k, v in c0.items()} else
@@ -85,8 +93,8 @@ def main():
         ok = [n for n, w in row if w <= args.budget]
         best[gname] = min(ok) if ok else n0
     print("# smallest n within the budget, one group at a time:", best)
-    allc = {nm: best[g] for g, names in GROUPS.items() for nm in names}
-    w, f, c = price(circs, with_n(base, allc))
+    allc = {nm: best[g] for g, names in groups.items() for nm in names}
+    w, f, c = price(circs, with_n(base, allc, bw))
     print(f"# all groups at once: worst site {w:.2e}, expected failures per image {f}, pbs per image {c}")
 
 

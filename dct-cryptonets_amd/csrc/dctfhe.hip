@@ -185,6 +185,7 @@ struct dctfhe_circuit {
   std::vector<TensorShape> tensors;
   std::vector<Op> ops;
   std::vector<void*> d_payload;  // per op, device copy of its payload (weights / tables)
+  std::vector<int64_t*> d_split; // per op: the half tables [S | Dt] of a parity-split look-up, each [ntab][2^(w-1)] (nullptr for other ops)
   std::vector<ConvPack> conv;    // per op: the matrix-core form of a convolution's weights (empty for other ops)
   ConvSlab conv_slab;            // ... all of them in one allocation, made when the first encrypted session is created
   std::vector<std::vector<int8_t>> conv_w;          // host copies of the convolution weights until then
@@ -193,8 +194,30 @@ struct dctfhe_circuit {
   ~dctfhe_circuit() {
     if (ctx) hipSetDevice(ctx->device);
     for (void* p : d_payload) if (p) hipFree(p);
+    for (int64_t* p : d_split) if (p) hipFree(p);
   }
 };
+
+// ---- look-up modes (ip[9] of an OP_LUT record; dctfhe/compile.py LUT_*)
+enum { LUT_EXACT = 0, LUT_APPROX = 1, LUT_SPLIT = 2, LUT_SPLIT_QUIET = 3 };
+static bool lut_is_split(const Op& o) { return o.ip[9] == LUT_SPLIT || o.ip[9] == LUT_SPLIT_QUIET; }
+// one-bit steps of a look-up op: none with approximate rounding; the r rounding steps, and for a parity split the step that takes the
+// table index's low bit off the working ciphertext
+static int lut_steps(const Op& o) { return o.ip[9] == LUT_APPROX ? 0 : o.ip[1] + (lut_is_split(o) ? 1 : 0); }
+// Parity split of tables [ntab][2^w] (t = 2 t' + b0): S[j] = ((T[2j] + T[2j+1]) mod 2^64) >> 1, Dt[j] = T[2j] - S[j], so that
+// S + Dt = T[2j] and S - Dt = T[2j+1] (mod 2^64) whatever the top bit of S.  out = [S: ntab << (w-1)][Dt: the same].  An odd sum has no
+// half: -1 (the compiler keeps the output exponent of a split site >= 1).
+static int split_tables_host(const int64_t* T, size_t ntab, int w, std::vector<int64_t>* out) {
+  const size_t half = (size_t)1 << (w - 1), n = ntab * half;
+  out->resize(2 * n);
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t a = (uint64_t)T[2 * i], b = (uint64_t)T[2 * i + 1], sum = a + b;
+    if (sum & 1) return -1;
+    (*out)[i] = (int64_t)(sum >> 1);
+    (*out)[n + i] = (int64_t)(a - (sum >> 1));
+  }
+  return 0;
+}
 
 // ---- max pool (OP_MAXPOOL): separable passes, rows then columns; each pass a log-depth tree of pairwise maxima
 // max(a, b) = b + relu(a - b) over the window's in-range taps.  Late pairing: a pass of L = ceil(log2 max taps) levels; at level l an
@@ -325,6 +348,7 @@ struct dctfhe_session {
   int* d_overflow = nullptr;
   // `simulate`: per-op noise (fraction of the torus) injected by the clear look-up kernel; empty = noise-free
   std::vector<double> sim_sigma;
+  std::vector<double> sim_sigma2;   // parity-split sites: the second look-up's (0 or absent: the first one's)
   uint64_t sim_seed = 0, sim_run = 0;
   // timing: events are created once and reused by every run; bootstraps per tier and image are fixed by the circuit
   std::vector<hipEvent_t> ev_pool;
@@ -1164,7 +1188,7 @@ enum { CAT_LINEAR = 100, CAT_KS = 101 };  // 0..7: bootstrap of tier i
 // runs on the first deff rows of the key only -- the same result bit for bit, deff/D of the work.
 static int dev_keyswitch(dctfhe_keys* K, int tier, const uint64_t* d_cts, size_t count, int shift, uint8_t* d_digits, uint64_t* d_bodies,
                          uint64_t* d_small, Timers* tm, int deff = 0, size_t L = 0, uint64_t body_add = 0, const int32_t* d_ia = nullptr,
-                         const int32_t* d_ib = nullptr) {
+                         const int32_t* d_ib = nullptr, const uint64_t* d_sum = nullptr, size_t L_sum = 0) {
   const dctfhe_tier& t = K->p.tiers[tier];
   TierKeys& tk = K->tiers[tier];
   const int D = K->p.D;
@@ -1191,6 +1215,9 @@ static int dev_keyswitch(dctfhe_keys* K, int tier, const uint64_t* d_cts, size_t
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
   if (d_ia)    // ciphertext c is row ia[c] - row ib[c] of d_cts (the pairwise maxima of a max pool)
     hipLaunchKernelGGL(k_ks_decompose_diff, dim3(grid), dim3(256), 0, st, d_cts, L, d_ia, d_ib, count, De, shift, body_add, t.lk, t.betak, d_digits, d_bodies);
+  else if (d_sum)   // ciphertext c is row c of d_cts + row c of d_sum (rows of L_sum words): the second look-up of a parity-split site
+    hipLaunchKernelGGL(k_ks_decompose_sum, dim3(grid), dim3(256), 0, st, d_cts, L, d_sum, L_sum, L_sum - 1, count, De, shift, body_add, t.lk, t.betak, d_digits,
+                       d_bodies);
   else
     hipLaunchKernelGGL(k_ks_decompose, dim3(grid), dim3(256), 0, st, d_cts, count, L, De, shift, body_add, t.lk, t.betak, d_digits, d_bodies);
   if (tk.d_kskT) {   // matrix-core path: i8 digits x signed byte limbs of the key
@@ -1280,15 +1307,52 @@ static StepTiers step_tiers_of(const Op& o) {
   if (o.ip[11] >= 0) { s.coarse2 = o.ip[11] >> 8; s.coarse2_from = o.ip[11] & 255; }
   return s;
 }
+// Parity split of a w-bit table (7 on the shipped catalogues) into two (w-1)-bit look-ups: tier2 < 0 = no split.  par: rows of Lp words for
+// the parity bootstrap's output and then the second look-up's (Lp - 1 >= the rings of both); tab_s / tab_d: the half tables.
+struct LutSplit { int tier2 = -1; uint64_t* par = nullptr; size_t Lp = 0; const int64_t* tab_s = nullptr; const int64_t* tab_d = nullptr; };
 // r > 0: in place on d_work (rows of Lw words, already shifted / offset; the first `deff` mask words may be non-zero).
 // r == 0: nothing modifies the input, so the key switch reads d_src (rows of Ls words) directly with the site's shift and
 // body offset applied on the fly, and the table bootstrap writes d_work -- no copy of the tensor at all.
 static int dev_round_lut(dctfhe_keys* K, const StepTiers& stp, int tab_tier, const uint64_t* d_src, size_t Ls, int shift,
                          uint64_t body_add, uint64_t* d_work, size_t Lw, size_t count, int p, int r, const int64_t* d_tables, int w, const int32_t* d_idx,
-                         int hw, int nchan, const LutScratch& sc, Timers* tm, int deff = 0) {
+                         int hw, int nchan, const LutScratch& sc, Timers* tm, int deff = 0, const LutSplit* sp = nullptr) {
+  const bool split = sp && sp->tier2 >= 0;
+  if (split) {
+    const size_t ring2 = (size_t)K->p.tiers[sp->tier2].k << K->p.tiers[sp->tier2].logN;
+    if (w < 2 || !sp->par || !sp->tab_s || !sp->tab_d) return fail("parity split: needs a table of at least 2 input bits, a parity buffer and the half tables");
+    if (Lw < ring2 + 1 || sp->Lp < ring2 + 1) return fail("parity split: rows of %zu / %zu words cannot hold the second look-up's ring of %zu", Lw, sp->Lp, ring2);
+  }
   for (size_t c0 = 0; c0 < count; c0 += sc.chunk) {
     const size_t cn = std::min(sc.chunk, count - c0);
     uint64_t* w0 = d_work + c0 * Lw;
+    if (split) {
+      // t = 2 t' + b0 sits under the padding bit once the r rounding steps are done.  Step r is one more of them, on b0: it leaves t' as
+      // a (w-1)-bit message in w0.  The same small ciphertext, bootstrapped with 2^62 and body offset -2^62, gives b0 * 2^63 (par).
+      // Second look-up first, while w0 still holds t': key switch of w0 + par (b0 in the padding bit, never materialised), table Dt
+      // -> (-1)^b0 Dt[t'] into par; then the first look-up S[t'] into w0 as for any site, and the sum.
+      hipStream_t st = K->ctx->stream;
+      for (int i = 0; i <= r; i++) {
+        const int bt = stp.at(i);
+        CHK(dev_keyswitch(K, bt, w0, cn, p - i, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
+        CHK(dev_ms_center(K, bt, sc.small, cn, tm));
+        const int vlog = 62 - p + i;
+        CHK(dev_pbs(K, bt, sc.small, cn, sc.bit_tables + vlog, 0, nullptr, 1, 1, 0, w0, 1, (uint64_t)0 - (1ULL << vlog), tm, Lw));
+        if (i == r) CHK(dev_pbs(K, bt, sc.small, cn, sc.bit_tables + 62, 0, nullptr, 1, 1, 0, sp->par, 0, (uint64_t)0 - (1ULL << 62), tm, sp->Lp));
+      }
+      const int* idx = d_idx ? d_idx + c0 : nullptr;
+      CHK(dev_keyswitch(K, sp->tier2, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw, 0, nullptr, nullptr, sp->par, sp->Lp));
+      CHK(dev_ms_center(K, sp->tier2, sc.small, cn, tm));
+      CHK(dev_pbs(K, sp->tier2, sc.small, cn, sp->tab_d, w - 1, idx, hw, nchan, c0, sp->par, 0, 0, tm, sp->Lp));
+      CHK(dev_keyswitch(K, tab_tier, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
+      CHK(dev_ms_center(K, tab_tier, sc.small, cn, tm));
+      CHK(dev_pbs(K, tab_tier, sc.small, cn, sp->tab_s, w - 1, idx, hw, nchan, c0, w0, 0, 0, tm, Lw));
+      const size_t ring2 = (size_t)K->p.tiers[sp->tier2].k << K->p.tiers[sp->tier2].logN;
+      const int h = tm ? tm->begin(CAT_LINEAR) : -1;
+      hipLaunchKernelGGL(k_acc_rows, dim3(ew_grid(cn * (ring2 + 1))), dim3(256), 0, st, w0, Lw, sp->par, sp->Lp, cn, ring2);
+      HIPCHK(hipGetLastError());
+      if (tm) tm->end(h);
+      continue;
+    }
     for (int i = 0; i < r; i++) {
       const int bt = stp.at(i);
       CHK(dev_keyswitch(K, bt, w0, cn, p - i, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
@@ -1450,31 +1514,47 @@ extern "C" int dctfhe_pbs(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const 
   return 0;
 }
 
-extern "C" int dctfhe_round_lut(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int bit_tier, int tab_tier, const uint64_t* cts, size_t count, int p, int r,
-                                const int64_t* tables, int ntab, int w, const int32_t* table_idx, uint64_t* cts_out) {
+// tab_tier2 >= 0: parity split (dev_round_lut) -- the table's low bit goes through one more one-bit step on bit_tier, the two half-table
+// look-ups run on tab_tier and tab_tier2
+extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int bit_tier, int tab_tier, int tab_tier2, const uint64_t* cts, size_t count,
+                                      int p, int r, const int64_t* tables, int ntab, int w, const int32_t* table_idx, uint64_t* cts_out) {
   if (!ctx || !K) return fail("dctfhe_round_lut: null handle");
-  if (tab_tier < 0 || tab_tier >= K->p.n_tiers || (r > 0 && (bit_tier < 0 || bit_tier >= K->p.n_tiers))) return fail("tier out of range");
+  const bool split = tab_tier2 >= 0;
+  if (tab_tier < 0 || tab_tier >= K->p.n_tiers || tab_tier2 >= K->p.n_tiers || ((r > 0 || split) && (bit_tier < 0 || bit_tier >= K->p.n_tiers)))
+    return fail("tier out of range");
   if (p < 1 || p > 62 || r < 0 || r >= p) return fail("need 1 <= p <= 62 and 0 <= r < p");
   if (w != p - r) return fail("w must equal p - r");
-  if (w > K->p.tiers[tab_tier].logN - 1) return fail("table of 2^%d entries does not fit tier %d", w, tab_tier);
+  if (split && w < 2) return fail("a parity split needs a table of at least 2 input bits");
+  const int wl = split ? w - 1 : w;      // input bits of the look-ups that run
+  if (wl > K->p.tiers[tab_tier].logN - 1) return fail("table of 2^%d entries does not fit tier %d", wl, tab_tier);
+  if (split && wl > K->p.tiers[tab_tier2].logN - 1) return fail("table of 2^%d entries does not fit tier %d", wl, tab_tier2);
   if (ntab < 1) return fail("need at least one table");
+  if (!tables) return fail("dctfhe_round_lut: null tables");
+  std::vector<int64_t> halves;
+  if (split && split_tables_host(tables, (size_t)ntab, w, &halves)) return fail("parity split of a table whose entry pairs have an odd sum");
   if (count == 0) return 0;
   if (table_idx)
     for (size_t i = 0; i < count; i++)
       if (table_idx[i] < 0 || table_idx[i] >= ntab) return fail("table_idx[%zu] = %d out of range (%d tables)", i, table_idx[i], ntab);
   HIPCHK(hipSetDevice(ctx->device));
   const size_t L = (size_t)K->p.D + 1;
-  DevBuf d_work, d_tab, d_idx;
+  DevBuf d_work, d_tab, d_idx, d_par;
   HIPCHK(d_work.alloc(count * L * 8));
   HIPCHK(d_tab.alloc(((size_t)ntab << w) * 8));
   HIPCHK(hipMemcpy(d_work.p, cts, count * L * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_tab.p, tables, ((size_t)ntab << w) * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_tab.p, split ? halves.data() : tables, ((size_t)ntab << w) * 8, hipMemcpyHostToDevice));
   if (table_idx) {
     HIPCHK(d_idx.alloc(count * 4));
     HIPCHK(hipMemcpy(d_idx.p, table_idx, count * 4, hipMemcpyHostToDevice));
   }
   LutScratchOwner sc;
   CHK(alloc_lut_scratch(K, std::min<size_t>(count, 4096), &sc.s));
+  LutSplit sp;
+  if (split) {
+    HIPCHK(d_par.alloc(sc.s.chunk * L * 8));
+    sp.tier2 = tab_tier2; sp.par = d_par.as<uint64_t>(); sp.Lp = L;
+    sp.tab_s = d_tab.as<int64_t>(); sp.tab_d = d_tab.as<int64_t>() + ((size_t)ntab << (w - 1));
+  }
   if (r > 0) {
     hipLaunchKernelGGL(k_affine, dim3(ew_grid(count * L)), dim3(256), 0, ctx->stream, d_work.as<uint64_t>(), L, L - 1, d_work.as<uint64_t>(), L, count, L - 1, 0,
                        1ULL << (63 - p + r - 1));
@@ -1483,10 +1563,15 @@ extern "C" int dctfhe_round_lut(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int bit_ti
   StepTiers stp;
   stp.bit = bit_tier;
   CHK(dev_round_lut(K, stp, tab_tier, d_work.as<uint64_t>(), L, 0, 0, d_work.as<uint64_t>(), L, count, p, r, d_tab.as<int64_t>(), w,
-                    d_idx.as<int32_t>(), 1, 1, sc.s, nullptr));
+                    d_idx.as<int32_t>(), 1, 1, sc.s, nullptr, 0, &sp));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipMemcpy(cts_out, d_work.p, count * L * 8, hipMemcpyDeviceToHost));
   return 0;
+}
+// A table of 7 input bits is split inside (both look-ups on tab_tier): at the half-box of a 6-bit table instead of half of it
+extern "C" int dctfhe_round_lut(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int bit_tier, int tab_tier, const uint64_t* cts, size_t count, int p, int r,
+                                const int64_t* tables, int ntab, int w, const int32_t* table_idx, uint64_t* cts_out) {
+  return dctfhe_round_lut_split(ctx, K, bit_tier, tab_tier, w == 7 ? tab_tier : -1, cts, count, p, r, tables, ntab, w, table_idx, cts_out);
 }
 
 extern "C" int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int batch, int Cin, int H, int W, const int8_t* weight, int Cout,
@@ -1761,6 +1846,14 @@ static int parse_circuit(const void* blob, size_t size, dctfhe_circuit* c) {
         if (ntab != 1 && ntab != a.C) return fail("op %d: %d tables for %d channels", i, ntab, a.C);
         if (o.payload_len != ((int64_t)ntab << w) * 8) return fail("op %d: table payload of %lld bytes, expected %lld", i, (long long)o.payload_len, (long long)(((int64_t)ntab << w) * 8));
         if (a.C != d.C || a.H != d.H || a.W != d.W) return fail("op %d: look-up changes the shape", i);
+        if (o.ip[9] < LUT_EXACT || o.ip[9] > LUT_SPLIT_QUIET) return fail("op %d: unknown look-up mode %d (0 exact, 1 approximate, 2 / 3 parity split)", i, o.ip[9]);
+        if (lut_is_split(o)) {
+          if (w < 2 || w > 16) return fail("op %d: a parity split needs a table of 2 to 16 input bits, not %d", i, w);
+          if (o.ip[5] < 0) return fail("op %d: a parity split needs a bit tier", i);
+          std::vector<int64_t> tmp((size_t)ntab << w), halves;
+          memcpy(tmp.data(), (const char*)blob + o.payload_off, (size_t)o.payload_len);
+          if (split_tables_host(tmp.data(), (size_t)ntab, w, &halves)) return fail("op %d: parity split of a table whose entry pairs have an odd sum", i);
+        }
         break;
       }
       case OP_MAXPOOL: {
@@ -1791,6 +1884,7 @@ extern "C" int dctfhe_circuit_load(dctfhe_ctx* ctx, const void* blob, size_t siz
   HIPCHK(hipSetDevice(ctx->device));
   c->ctx = ctx;
   c->d_payload.assign(c->ops.size(), nullptr);
+  c->d_split.assign(c->ops.size(), nullptr);
   std::vector<const int8_t*> cw(c->ops.size(), nullptr);
   std::vector<std::array<int, 7>> cg(c->ops.size());
   for (size_t i = 0; i < c->ops.size(); i++) {
@@ -1798,6 +1892,13 @@ extern "C" int dctfhe_circuit_load(dctfhe_ctx* ctx, const void* blob, size_t siz
     if (o.payload_len > 0) {
       HIPCHK(hipMalloc(&c->d_payload[i], (size_t)o.payload_len));
       HIPCHK(hipMemcpy(c->d_payload[i], (const char*)blob + o.payload_off, (size_t)o.payload_len, hipMemcpyHostToDevice));
+    }
+    if (o.type == OP_LUT && lut_is_split(o)) {      // the half tables of a parity split, once per circuit
+      std::vector<int64_t> tmp((size_t)o.payload_len / 8), halves;
+      memcpy(tmp.data(), (const char*)blob + o.payload_off, (size_t)o.payload_len);
+      if (split_tables_host(tmp.data(), (size_t)o.ip[6], o.ip[2], &halves)) return fail("op %zu: parity split of a table whose entry pairs have an odd sum", i);
+      HIPCHK(hipMalloc(&c->d_split[i], halves.size() * 8));
+      HIPCHK(hipMemcpy(c->d_split[i], halves.data(), halves.size() * 8, hipMemcpyHostToDevice));
     }
     if (o.type == OP_CONV) {
       const TensorShape& a = c->tensors[o.src0];
@@ -1852,7 +1953,7 @@ extern "C" int dctfhe_circuit_stats(dctfhe_circuit* c, const dctfhe_params* P, d
       case OP_ADD: s->bytes_algorithmic += 3 * eout * Lb; break;
       case OP_SUMPOOL: s->bytes_algorithmic += (ein + eout) * Lb; break;
       case OP_LUT: {
-        const int r = o.ip[9] ? 0 : o.ip[1], tt = o.ip[4], bt = o.ip[5];     // approximate rounding: no one-bit steps
+        const int r = lut_steps(o), tt = o.ip[4];     // approximate rounding: no one-bit steps; parity split: one more
         s->lut_sites += (int64_t)ein;
         s->bit_steps += (int64_t)(ein * r);
         s->bytes_algorithmic += 2 * ein * Lb * (1 + r);
@@ -1868,6 +1969,17 @@ extern "C" int dctfhe_circuit_stats(dctfhe_circuit* c, const dctfhe_params* P, d
           s->pbs_count[b2] += (int64_t)ein; s->ks_count[b2] += (int64_t)ein;
           s->flops_f64 += ein * tier_flops(P->tiers[b2]);
           s->key_bytes_per_pass += key_bytes(P->tiers[b2]);
+        }
+        if (lut_is_split(o)) {
+          // the parity bootstrap (tier of the last step, its small ciphertext: no key switch) and the second look-up with its key switch
+          const int pt = stp.at(r - 1), t2 = (tt >= 0 && tt < P->n_tiers) ? (o.ip[9] == LUT_SPLIT_QUIET ? P->tiers[tt].ksk_share : tt) : -1;
+          if (pt >= 0 && pt < P->n_tiers) { s->pbs_count[pt] += (int64_t)ein; s->flops_f64 += ein * tier_flops(P->tiers[pt]); }
+          if (t2 >= 0 && t2 < P->n_tiers) {
+            s->pbs_count[t2] += (int64_t)ein; s->ks_count[t2] += (int64_t)ein;
+            s->flops_f64 += ein * tier_flops(P->tiers[t2]);
+            s->key_bytes_per_pass += key_bytes(P->tiers[t2]);
+          }
+          s->bytes_algorithmic += 4 * ein * Lb;
         }
         break;
       }
@@ -1906,9 +2018,14 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
         continue;
       }
       if (o.type != OP_LUT) continue;
-      const int tt = o.ip[4], bt = o.ip[5], r = o.ip[9] ? 0 : o.ip[1], w = o.ip[2];
+      const int tt = o.ip[4], bt = o.ip[5], r = lut_steps(o), w = o.ip[2] - (lut_is_split(o) ? 1 : 0);
       if (tt < 0 || tt >= keys->p.n_tiers || (r > 0 && (bt < 0 || bt >= keys->p.n_tiers))) return fail("op %zu names a tier the keys lack", i);
       if (w > keys->p.tiers[tt].logN - 1) return fail("op %zu: table of 2^%d entries does not fit tier %d", i, w, tt);
+      if (o.ip[9] == LUT_SPLIT_QUIET) {
+        const int t2 = keys->p.tiers[tt].ksk_share;
+        if (t2 < 0 || t2 >= keys->p.n_tiers) return fail("op %zu: parity split on the quiet twin, but tier %d shares no key-switch key", i, tt);
+        if (w > keys->p.tiers[t2].logN - 1) return fail("op %zu: table of 2^%d entries does not fit tier %d", i, w, t2);
+      }
       const StepTiers stp = step_tiers_of(o);
       for (int st = 0; st < r; st++)
         if (stp.at(st) < 0 || stp.at(st) >= keys->p.n_tiers) return fail("op %zu names a coarse bit tier the keys lack", i);
@@ -1950,7 +2067,8 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
       if (o.type == OP_MAXPOOL) all_mfma = all_mfma && keys->tiers[o.ip[4]].d_kskT != nullptr;
       if (o.type != OP_LUT) continue;
       all_mfma = all_mfma && keys->tiers[o.ip[4]].d_kskT != nullptr;
-      const int r = o.ip[9] ? 0 : o.ip[1];
+      const int r = lut_steps(o);
+      if (o.ip[9] == LUT_SPLIT_QUIET) all_mfma = all_mfma && keys->tiers[keys->p.tiers[o.ip[4]].ksk_share].d_kskT != nullptr;
       const StepTiers stp = step_tiers_of(o);
       for (int st_i = 0; st_i < r; st_i++) all_mfma = all_mfma && keys->tiers[stp.at(st_i)].d_kskT != nullptr;
     }
@@ -1964,8 +2082,12 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
       const Op& o = circ->ops[i];
       if (!known[o.src0] || (o.type == OP_ADD && !known[o.src1])) return fail("op %zu reads a tensor no earlier op wrote", i);
       if (o.type == OP_LUT) {
-        const int r = o.ip[9] ? 0 : o.ip[1], tt = o.ip[4];
-        const size_t ring = (size_t)keys->p.tiers[tt].k << keys->p.tiers[tt].logN;
+        const int r = lut_steps(o), tt = o.ip[4];
+        size_t ring = (size_t)keys->p.tiers[tt].k << keys->p.tiers[tt].logN;
+        if (o.ip[9] == LUT_SPLIT_QUIET) {      // the sum of both look-ups: as wide as the wider ring
+          const dctfhe_tier& q = keys->p.tiers[keys->p.tiers[tt].ksk_share];
+          ring = std::max(ring, (size_t)q.k << q.logN);
+        }
         if (clampd(o.ip[10]) < s->t_deff[o.src0]) return fail("op %zu: look-up compiled for effective dimension %d, its input has %zu", i, o.ip[10], s->t_deff[o.src0]);
         const size_t chain = r > 0 ? (size_t)round_chain_deff(keys, (int)clampd(o.ip[10]), step_tiers_of(o), r) : 0;
         set(o.dst, ring, chain);
@@ -2033,6 +2155,16 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
       }
       for (int b = 0; b < 2; b++)
         if (s->pool_buf[i][b]) freelist.push_back({cap[s->pool_buf[i][b]], s->pool_buf[i][b]});
+    }
+    if (o.type == OP_LUT && keys && lut_is_split(o)) {
+      // the second work buffer of a parity-split site, chunk-sized: the parity bootstrap's output, then the second look-up's.  Held for
+      // this op only, like the level buffers of a max pool
+      const TensorShape& a = circ->tensors[o.src0];
+      const size_t rows = std::min<size_t>((size_t)batch * a.C * a.H * a.W, 16384);      // the look-up scratch's chunk is at most that
+      const size_t words = rows * s->t_L[o.dst];
+      CHK(get(words, &s->pool_buf[i][0]));
+      if (!cap.count(s->pool_buf[i][0])) cap[s->pool_buf[i][0]] = words;
+      freelist.push_back({cap[s->pool_buf[i][0]], s->pool_buf[i][0]});
     }
     auto release = [&](int t) {
       if (last_use[t] == i && t != o.dst && s->d_tensor[t]) freelist.push_back({cap[s->d_tensor[t]], s->d_tensor[t]});
@@ -2138,6 +2270,14 @@ extern "C" int dctfhe_session_set_noise(dctfhe_session* s, uint64_t seed, const 
   return 0;
 }
 
+extern "C" int dctfhe_session_set_noise_split(dctfhe_session* s, const double* sigma2_per_op, int n_ops) {
+  if (!s) return fail("dctfhe_session_set_noise_split: null session");
+  if (s->keys) return fail("noise simulation is a clear-mode feature: create the session without keys");
+  if (n_ops != 0 && n_ops != (int)s->circ->ops.size()) return fail("expected one sigma per op (%zu), got %d", s->circ->ops.size(), n_ops);
+  s->sim_sigma2.assign(sigma2_per_op, sigma2_per_op + n_ops);
+  return 0;
+}
+
 extern "C" int dctfhe_session_download_rows(dctfhe_session* s, uint64_t* cts_out, int dim) {
   if (!s || !cts_out) return fail("dctfhe_session_download: null argument");
   HIPCHK(hipSetDevice(s->ctx->device));
@@ -2213,17 +2353,21 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
         const int hw = a.H * a.W;
         if (!K) {
           const double sg = i < s->sim_sigma.size() ? s->sim_sigma[i] : 0.0;
+          const double sg2 = (i < s->sim_sigma2.size() && s->sim_sigma2[i] > 0) ? s->sim_sigma2[i] : sg;
+          const int split = lut_is_split(o);
+          const int64_t* halves = c->d_split[i];
           hipLaunchKernelGGL(k_lut_clear, dim3(ew_grid(E)), dim3(256), 0, st, src, dst, E, shift, body_add, p, r, w, (const int64_t*)c->d_payload[i],
                              hw, nchan, s->d_overflow, sg, rng_key{{(uint32_t)s->sim_seed, (uint32_t)(s->sim_seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}},
-                             (uint64_t)(0x51D0000 + (s->sim_run << 12) + i), (int)(o.ip[9] != 0));
+                             (uint64_t)(0x51D0000 + (s->sim_run << 12) + i), (int)(o.ip[9] == LUT_APPROX), split, sg2, halves,
+                             halves ? halves + ((size_t)nchan << (w - 1)) : nullptr);
           HIPCHK(hipGetLastError());
         } else {
           // exact rounding: + half of what is removed, then r one-bit steps clear the low bits, in place on a shifted copy of the
           // input.  Approximate rounding (ip[9], the reference README's {"method": "approximate"}): no steps -- the low bits stay
           // and the half-box rotation of the test vector does the rounding; + half an input unit puts the two inputs next to a
           // rounding boundary at equal distance from it.  Without steps nothing is copied: the key switch reads the input tensor.
-          const bool approx = o.ip[9] != 0 && r > 0;
-          const int steps = approx ? 0 : r;
+          const bool approx = o.ip[9] == LUT_APPROX && r > 0;
+          const int steps = lut_steps(o);      // one-bit steps on the working copy: the r rounding steps, + 1 for a parity split
           const uint64_t add = body_add + (approx ? (1ULL << (62 - p)) : (r > 0 ? (1ULL << (63 - p + r - 1)) : 0));
           int deff = (int)ds;
           if (steps > 0) {
@@ -2235,13 +2379,21 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
             // buffer held)
             bool narrow = ks_narrows(K, tt, deff);
             for (int st_i = 0; st_i < steps; st_i++) narrow = narrow && ks_narrows(K, stp.at(st_i), deff);
+            if (o.ip[9] == LUT_SPLIT_QUIET) narrow = narrow && ks_narrows(K, K->p.tiers[tt].ksk_share, deff);
             const size_t fill = narrow ? (size_t)deff : Ld - 1;
             const int h = tm.begin(CAT_LINEAR);
             hipLaunchKernelGGL(k_affine, dim3(ew_grid(E * (fill + 1))), dim3(256), 0, st, src, Ls, ds, dst, Ld, E, fill, shift, add);
             HIPCHK(hipGetLastError());
             tm.end(h);
           }
-          CHK(dev_round_lut(K, step_tiers_of(o), tt, src, Ls, shift, add, dst, Ld, E, p, steps, (const int64_t*)c->d_payload[i], w, nullptr, hw, nchan, sc, &tm, deff));
+          LutSplit sp;
+          if (lut_is_split(o)) {
+            sp.tier2 = o.ip[9] == LUT_SPLIT_QUIET ? K->p.tiers[tt].ksk_share : tt;
+            sp.par = s->pool_buf[i][0]; sp.Lp = Ld;
+            sp.tab_s = c->d_split[i]; sp.tab_d = c->d_split[i] + ((size_t)nchan << (w - 1));
+          }
+          CHK(dev_round_lut(K, step_tiers_of(o), tt, src, Ls, shift, add, dst, Ld, E, p, approx ? 0 : r, (const int64_t*)c->d_payload[i], w, nullptr, hw, nchan, sc,
+                            &tm, deff, &sp));
         }
         break;
       }

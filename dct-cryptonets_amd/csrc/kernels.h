@@ -372,6 +372,37 @@ __global__ void k_ks_decompose_diff(const uint64_t* __restrict__ rows, size_t L,
   }
 }
 
+// Step 1 on the sum of two row sets, for the second look-up of a parity-split site (7-bit tables): ciphertext c is rows_a[c] + rows_b[c]
+// -- the working ciphertext (rows of stride La) plus the parity bootstrap's output (rows of stride Lb, whose db stored mask words hold a
+// ring and zeros; a word beyond them counts as zero) -- so the copy with the parity in its padding bit is never written.  Lanes run over
+// consecutive words of a row; the digit split is k_ks_decompose's.
+__global__ void k_ks_decompose_sum(const uint64_t* __restrict__ rows_a, size_t La, const uint64_t* __restrict__ rows_b, size_t Lb, size_t db,
+                                   size_t count, int Deff, int shift, uint64_t body_add, int lk, int betak, uint8_t* __restrict__ digits,
+                                   uint64_t* __restrict__ bodies) {
+  const size_t total = count * (size_t)Deff;
+  const int half = 1 << (betak - 1);
+  for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = x / Deff;
+    const int i = (int)(x % Deff);
+    const uint64_t* ra = rows_a + c * La;
+    const uint64_t* rb = rows_b + c * Lb;
+    const uint64_t v = (ra[i] + ((size_t)i < db ? rb[i] : 0)) << shift;
+    const int tot = lk * betak;
+    uint64_t xx = (v + (1ULL << (63 - tot))) >> (64 - tot);
+    const uint64_t B = 1ULL << betak, mask = B - 1;
+    uint64_t carry = 0;
+    uint8_t* dst = digits + (c * (size_t)Deff + i) * lk;
+    for (int lev = lk - 1; lev >= 0; lev--) {
+      uint64_t d = (xx & mask) + carry;
+      xx >>= betak;
+      int dv;
+      if (d >= (uint64_t)half) { dv = (int)d - (int)B; carry = 1; } else { dv = (int)d; carry = 0; }
+      dst[lev] = (uint8_t)(dv + half);
+    }
+    if (i == 0) bodies[c] = ((ra[La - 1] + rb[Lb - 1]) << shift) + body_add;
+  }
+}
+
 // Step 2: out[c][j] = body_c*[j==n] - sum_r (dig'[c][r] - B/2) * ksk[r][j]
 //       = body_c*[j==n] + (B/2) * colsum[j] - sum_r dig'[c][r] * ksk[r][j],   colsum[j] = sum_r ksk[r][j].
 // Block: CT ciphertexts x 256 columns; digits are wave-uniform (scalar loads), the key is read
@@ -821,6 +852,16 @@ __global__ void k_affine(const uint64_t* __restrict__ a, size_t La, size_t da, u
     o[c * Lo + (body ? Lo - 1 : w)] = v;
   }
 }
+// o += b on the first nwords mask words and the body of every row (rows of stride Lo / Lb): the sum of the two look-ups of a
+// parity-split site, over the ring the second one wrote
+__global__ void k_acc_rows(uint64_t* __restrict__ o, size_t Lo, const uint64_t* __restrict__ b, size_t Lb, size_t count, size_t nwords) {
+  const size_t per = nwords + 1, total = count * per;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t c = i / per, w = i % per;
+    const bool body = w == nwords;
+    o[c * Lo + (body ? Lo - 1 : w)] += b[c * Lb + (body ? Lb - 1 : w)];
+  }
+}
 // rows of stride Ls -> rows of stride Ld: the first nwords mask words and the body; the other words of the output row are zero
 // (session upload: host rows of D+1 words -> stored rows; download: the reverse)
 __global__ void k_restride(const uint64_t* __restrict__ src, size_t Ls, uint64_t* __restrict__ dst, size_t Ld, size_t count, size_t nwords) {
@@ -875,14 +916,26 @@ __device__ __forceinline__ uint64_t noisy_lookup(uint64_t centre, int w, const i
 // compiler predicts at the input of this site's table bootstrap) is added where the encrypted run has it -- after the exact
 // rounding steps have cleared the low bits, or, with approximate rounding, on the raw accumulator -- and the half-box
 // rotation of the test vector does the rest.
+// split != 0 (parity split of a 7-bit table, t = 2 t' + b0): with sigma > 0 the noise is sampled at BOTH look-ups the encrypted run makes
+// (RNG indices 2e and 2e + 1; sigma at the first, sigma2 at the second, whose input also carries the parity bootstrap's output) on the
+// half tables S / Dt [ntab][2^(w-1)], the second with b0 in the padding bit, so that the negacyclic wrap returns (-1)^b0 Dt[t'];
+// with sigma == 0 it is the plain 2^w-entry read.
 __global__ void k_lut_clear(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, size_t count, int shift, uint64_t body_add,
                             int p, int r, int w, const int64_t* __restrict__ tables, int hw, int nchan, int* __restrict__ overflow,
-                            double sigma, rng_key seed, uint64_t stream, int approx) {
+                            double sigma, rng_key seed, uint64_t stream, int approx, int split, double sigma2,
+                            const int64_t* __restrict__ tab_s, const int64_t* __restrict__ tab_d) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x) {
     uint64_t v = (in[e] << shift) + body_add;
     if (r > 0 && !(approx && sigma > 0)) v += 1ULL << (63 - p + r - 1);
     if (v >> 63) atomicOr(overflow, 1);  // message left the padded range: an FHE run would wrap
     uint64_t idx = (v >> (63 - w)) & ((1ULL << w) - 1);
+    if (sigma > 0 && split) {
+      const size_t ti = nchan > 1 ? (e / (size_t)hw) % (size_t)nchan : 0;
+      const uint64_t centre = (idx >> 1) << (64 - w);              // t' as a (w-1)-bit message under a clear padding bit
+      out[e] = noisy_lookup(centre, w - 1, tab_s + (ti << (w - 1)), seed, stream, 2 * e, sigma) +
+               noisy_lookup(centre + ((idx & 1) << 63), w - 1, tab_d + (ti << (w - 1)), seed, stream, 2 * e + 1, sigma2);
+      continue;
+    }
     if (sigma > 0) {
       // exact rounding: the value sits at the centre of its box; approximate: where its low bits put it (+ half an input unit)
       const uint64_t centre = approx && r > 0 ? v + (1ULL << (62 - p)) : (idx << (63 - w));

@@ -48,6 +48,7 @@ EXPORTS = [
     "dctfhe_session_upload", "dctfhe_session_run", "dctfhe_session_download", "dctfhe_session_upload_rows", "dctfhe_session_download_rows", "dctfhe_session_dims", "dctfhe_fp64_peak", "dctfhe_bench_pbs",
     "dctfhe_encrypt_seeded", "dctfhe_expand_seeded", "dctfhe_session_upload_seeded", "dctfhe_eval_keys_export_compressed",
     "dctfhe_eval_keys_decompress_bsk", "dctfhe_keyswitch_diff", "dctfhe_max_pool_rows",
+    "dctfhe_round_lut_split", "dctfhe_session_set_noise_split",
 ]
 
 _lib = None
@@ -96,6 +97,8 @@ def load():
     L.dctfhe_modswitch_center.argtypes = [vp, vp, i32, vp, sz]
     L.dctfhe_pbs.argtypes = [vp, vp, i32, vp, sz, vp, i32, i32, vp, vp]
     L.dctfhe_round_lut.argtypes = [vp, vp, i32, i32, vp, sz, i32, i32, vp, i32, i32, vp, vp]
+    L.dctfhe_round_lut_split.argtypes = [vp, vp, i32, i32, i32, vp, sz, i32, i32, vp, i32, i32, vp, vp]
+    L.dctfhe_session_set_noise_split.argtypes = [vp, vp, i32]
     L.dctfhe_conv2d.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp]
     L.dctfhe_add_rows.argtypes = [vp, vp, i32, i32, vp, i32, i32, sz, i32, vp]
     L.dctfhe_affine_rows.argtypes = [vp, vp, i32, i32, sz, i32, i32, u64, i32, vp]

@@ -16,6 +16,11 @@ Circuit semantics (all integers):
                          row / column passes of pairwise max(a, b) = b + relu(a - b): one signed p_d-bit table per pair
 Encodings: a tensor with exponent e holds  phase = value * 2^e  (mod 2^64); a LUT shifts its input up to
 e = 63 - p first, so that t sits in the top w+1 bits with the padding bit clear.
+
+A table of 7 input bits is evaluated by a PARITY SPLIT on the 6-bit tiers: one more one-bit step takes the
+low bit b0 of t = 2 t' + b0 off the working ciphertext, a second sign bootstrap of the same small ciphertext puts b0 into the
+padding bit of a copy, and two 6-bit look-ups give  S[t'] + (-1)^b0 Dt[t'] = T[t]  with  S = (T[2j] + T[2j+1]) / 2,
+Dt = T[2j] - S  (split_tables).  The blob keeps one LUT record with w = 7 and the 128-entry tables; ip[9] says how it runs.
 """
 import math
 import struct
@@ -30,6 +35,23 @@ from . import params as P
 OP_CONV, OP_ADD, OP_SUMPOOL, OP_LUT = 1, 2, 3, 4
 OP_MAXPOOL = 5            # not 9: the ABI tests use 9 as the unknown type
 MAGIC = 0x46544344
+# ip[9] of a LUT record: how the site is evaluated
+LUT_EXACT, LUT_APPROX = 0, 1
+LUT_SPLIT = 2             # parity split, both look-ups on the site's table tier ip[4]
+LUT_SPLIT_QUIET = 3       # parity split, the second look-up on the quiet twin: the tier whose key-switch key ip[4] shares (ksk_share)
+
+
+def split_tables(enc):
+    """encoded tables [ntab, 2^w] (uint64 / int64 words as the blob stores them) -> (S, Dt) [ntab, 2^(w-1)] uint64 with
+    S[j] + Dt[j] = T[2j] and S[j] - Dt[j] = T[2j+1] (mod 2^64): S = ((T[2j] + T[2j+1]) mod 2^64) >> 1, Dt = T[2j] - S.  The engine
+    derives the same pair at dctfhe_circuit_load.  An odd sum has no half: ValueError (the consumer's exponent must be >= 1)."""
+    t = np.ascontiguousarray(enc).view(np.uint64).reshape(-1, np.asarray(enc).shape[-1])
+    with np.errstate(over="ignore"):
+        sm = t[:, 0::2] + t[:, 1::2]
+        if (sm & np.uint64(1)).any():
+            raise ValueError("parity split: a pair of table entries has an odd sum (the table's output exponent must be >= 1)")
+        s_ = sm >> np.uint64(1)
+        return s_, t[:, 0::2] - s_
 
 
 # ------------------------------------------------------------------------------------------ quantisers
@@ -146,6 +168,7 @@ class OpInfo:
     coarse_from: int = -1             # rounding steps i >= coarse_from run on the one-level bit tier
     coarse2_from: int = -1            # ... and steps i >= coarse2_from on the two-bit-rotation bit tier (ip[11] = tier << 8 | from)
     sim_sigma: float = 0.0            # modelled noise std at the input of the site's table bootstrap (fraction of the torus)
+    sim_sigma2: float = 0.0           # parity-split sites: the same at the second look-up (one more bit-tier output on its input)
     # MAXPOOL metadata: [(multiplicity, pairs per level)] per pass (pool_geometry), pairwise maxima per image, tree levels
     pool_geom: list = None
     n_max: int = 0
@@ -170,6 +193,8 @@ class CompiledCircuit:
     expected_failures_per_image: float = 0.0
     rounding_method: str = "exact"
     expected_boundary_flips_per_image: float = 0.0    # approximate rounding only
+    tier_policy: str = "exact"
+    calib_out: np.ndarray = None                      # the compile-time integer forward: outputs [B, n_out] on the calibration batch
 
     @property
     def e_in(self):
@@ -196,6 +221,10 @@ class CompiledCircuit:
         """per op, the noise std `simulate` injects at the look-up (0 for the levelled ops)"""
         return [o.sim_sigma if o.type in (OP_LUT, OP_MAXPOOL) else 0.0 for o in self.ops]
 
+    def simulation_sigmas_split(self):
+        """per op, the noise std `simulate` injects at the SECOND look-up of a parity-split site (0 elsewhere)"""
+        return [o.sim_sigma2 if (o.type == OP_LUT and is_split(o)) else 0.0 for o in self.ops]
+
     def pbs_counts(self):
         """{tier name: programmable bootstraps per image} -- table lookups on the site's table tier, rounding steps
         on the bit tier (steps below coarse_from) or the one-level bit tier (steps from coarse_from on)."""
@@ -210,9 +239,12 @@ class CompiledCircuit:
             s = self.tensors[o.src0]
             n = s.C * s.H * s.W
             out[ps.tiers[o.ip[4]].name] = out.get(ps.tiers[o.ip[4]].name, 0) + n
-            if o.r and not o.ip[9]:
-                for st in range(o.r):
+            if o.ip[9] != LUT_APPROX:
+                for st in range(chain_steps(o)):
                     nm = ps.tiers[step_tier(o, st)].name
+                    out[nm] = out.get(nm, 0) + n
+            if is_split(o):      # the parity bootstrap (tier of step r, no key switch of its own) and the second look-up
+                for nm in (ps.tiers[step_tier(o, o.r)].name, ps.tiers[second_tier(ps, o)].name):
                     out[nm] = out.get(nm, 0) + n
         return out
 
@@ -235,11 +267,13 @@ class CompiledCircuit:
                 head = (f"%{o.dst} = max_pool2d(%{o.src0}, {o.ip[0]}, {o.ip[1]}, {o.ip[2]}) {{p_d={o.ip[5]}, shift={o.ip[3]}, "
                         f"tier={ps.tiers[o.ip[4]].name}, levels={o.levels}, pairwise_max={o.n_max}, p_fail/max={o.pfail:.1e}}}  // {o.note}")
             elif o.type == OP_LUT:
+                nst = 0 if o.ip[9] == LUT_APPROX else chain_steps(o)
                 head += (f" {{p={o.p}, lsbs_removed={o.r}, table_bits={o.w}, signed={int(o.signed)}, shift={o.ip[3]}, "
-                         f"tier={ps.tiers[o.ip[4]].name}" + (", rounding=approximate" if o.ip[9] else "") +
-                         (f", bit_tier={ps.tiers[o.ip[5]].name}" if (o.r and not o.ip[9]) else "") +
-                         (f", steps>={o.ip[8]}:{ps.tiers[o.ip[7]].name}" if (o.r and not o.ip[9] and o.ip[7] >= 0 and o.ip[8] < o.r) else "") +
-                         (f", steps>={o.ip[11] & 255}:{ps.tiers[o.ip[11] >> 8].name}" if (o.r and not o.ip[9] and o.ip[11] >= 0 and (o.ip[11] & 255) < o.r) else "") +
+                         f"tier={ps.tiers[o.ip[4]].name}" + (", rounding=approximate" if o.ip[9] == LUT_APPROX else "") +
+                         (f", parity_split={ps.tiers[o.ip[4]].name}+{ps.tiers[second_tier(ps, o)].name}, steps={o.r}+1" if is_split(o) else "") +
+                         (f", bit_tier={ps.tiers[o.ip[5]].name}" if nst else "") +
+                         (f", steps>={o.ip[8]}:{ps.tiers[o.ip[7]].name}" if (nst and o.ip[7] >= 0 and o.ip[8] < nst) else "") +
+                         (f", steps>={o.ip[11] & 255}:{ps.tiers[o.ip[11] >> 8].name}" if (nst and o.ip[11] >= 0 and (o.ip[11] & 255) < nst) else "") +
                          f", tables={o.ip[6]}, p_fail/elt={o.pfail:.1e}}}  // {o.note}")
             lines.append(f"{head} : [{s.C}x{s.H}x{s.W}] -> [{d.C}x{d.H}x{d.W}] e={d.e}")
         lines.append(f"// expected table failures per image (noise model): {self.expected_failures_per_image:.2e}")
@@ -256,6 +290,21 @@ def step_tier(o, i):
     if o.ip[11] >= 0 and i >= (o.ip[11] & 255):
         t = o.ip[11] >> 8
     return t
+
+
+def is_split(o):
+    """look-up op evaluated by the parity split (ip[9] = LUT_SPLIT / LUT_SPLIT_QUIET)"""
+    return o.ip[9] in (LUT_SPLIT, LUT_SPLIT_QUIET)
+
+
+def chain_steps(o):
+    """one-bit steps of an exact look-up op: the r rounding steps, plus the step that takes the parity bit off a split site"""
+    return o.r + (1 if is_split(o) else 0)
+
+
+def second_tier(ps, o):
+    """tier of the second look-up of a parity-split site"""
+    return ps.tiers[o.ip[4]].ksk_share if o.ip[9] == LUT_SPLIT_QUIET else o.ip[4]
 
 
 class _Act:
@@ -516,7 +565,8 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
 
     circ = CompiledCircuit(tensors=bld.tensors, ops=bld.ops, input_tensor=t_in, output_tensor=out.tid, in_scale=s_in, in_bits=bits,
                            out_scale=s_f, out_bits=bits, max_bit_width=bld.max_bits, param_set=ps,
-                           rounding_threshold_bits=rounding_threshold_bits, n_bits=n_bits, rounding_method=rounding_method)
+                           rounding_threshold_bits=rounding_threshold_bits, n_bits=n_bits, rounding_method=rounding_method,
+                           tier_policy=tier_policy, calib_out=out.q.reshape(out.q.shape[0], -1))
     _assign_encodings(circ)
     _estimate_noise(circ)
     if getattr(ps, "table_tier_fallback_for_w", None) and circ.worst_site_failure > ps.p_budget:
@@ -524,6 +574,18 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
         ps.table_tier_for_w = {**ps.table_tier_for_w, **ps.table_tier_fallback_for_w}
         ps.table_tier_fallback_for_w = None
         _assign_encodings(circ)
+        _estimate_noise(circ)
+    # parity-split sites: both look-ups on the site's (one-level) table tier where the budget holds; where the site's consumer -- the
+    # refresh that reads the sum of two bootstrap outputs -- leaves it, the second look-up moves to the quiet twin, site by site
+    budget = getattr(ps, "p_budget", 1e-12)
+    while True:
+        reader = {o.src0: o for o in circ.ops if o.type == OP_LUT}
+        move = [o for o in circ.ops if o.type == OP_LUT and o.ip[9] == LUT_SPLIT and ps.tiers[o.ip[4]].ksk_share >= 0
+                and max(o.pfail, reader[o.dst].pfail if o.dst in reader else 0.0) > budget]
+        if not move:
+            break
+        for o in move:
+            o.ip[9] = LUT_SPLIT_QUIET
         _estimate_noise(circ)
     if own_catalogue and tier_policy == "exact" and circ.worst_site_failure > 1e-10:
         import warnings
@@ -563,18 +625,43 @@ def _assign_encodings(circ):
             shift = (63 - o.p) - T[o.src0].e
             assert shift >= 0
             ps = circ.param_set
-            tier = ps.tier_for_width(o.w, coarse=not amplified[o.dst])
-            if o.w > ps.tiers[tier].logN - 1:
+            # a table one bit wider than the catalogue's widest (7 bits on the shipped ones) runs as a parity split: two look-ups of
+            # w - 1 bits on the tier a (w - 1)-bit site takes
+            coarse, split = not amplified[o.dst], False
+            try:
+                tier = ps.tier_for_width(o.w, coarse=coarse)
+            except ValueError:
+                try:
+                    tier = ps.tier_for_width(o.w - 1, coarse=coarse)
+                except ValueError:
+                    raise ValueError(f"{o.note}: no tier for a table of {o.w} input bits: the parity split reaches one bit beyond the catalogue's "
+                                     f"widest tables, more would need a larger ring (N = 16384 for 8 bits: DESIGN.md section 9)") from None
+                split = True
+                if circ.rounding_method == "approximate":
+                    raise ValueError(f"{o.note}: a table of {o.w} input bits needs the exact method: the parity split takes the table's low bit "
+                                     f"with a step of the one-bit rounding chain, which approximate rounding does not run")
+                if circ.tier_policy == "p_error":
+                    raise ValueError(f"{o.note}: a table of {o.w} input bits needs tier_policy='exact': the p_error catalogue has no tier with "
+                                     f"the 2^-{o.w + 1} half-box both look-ups of a parity split need")
+            if (o.w - 1 if split else o.w) > ps.tiers[tier].logN - 1:
                 raise ValueError("table wider than the ring")
-            o.ip[:7] = [o.p, o.r, o.w, shift, tier, ps.bit_tier if o.r > 0 else -1, o.table_values.shape[0]]
-            o.ip[7], o.ip[8] = (ps.bit_tier_coarse if ps.bit_tier_coarse is not None else -1), o.r      # refined by _estimate_noise
+            o.ip[:7] = [o.p, o.r, o.w, shift, tier, ps.bit_tier if (o.r > 0 or split) else -1, o.table_values.shape[0]]
+            o.ip[7], o.ip[8] = (ps.bit_tier_coarse if ps.bit_tier_coarse is not None else -1), o.r + int(split)      # refined by _estimate_noise
             o.ip[11] = -1
-            o.ip[9] = 1 if (circ.rounding_method == "approximate" and o.r > 0) else 0
+            if split:      # keeps a choice of the quiet second tier made by compile_model across a re-assignment
+                o.ip[9] = o.ip[9] if is_split(o) else LUT_SPLIT
+            else:
+                o.ip[9] = LUT_APPROX if (circ.rounding_method == "approximate" and o.r > 0) else LUT_EXACT
             o.ip[10] = T[o.src0].deff
             T[o.dst].deff = ps.tiers[tier].k << ps.tiers[tier].logN
+            if split and ps.tiers[tier].ksk_share >= 0:      # the second look-up may move to the quiet twin: room for its ring too
+                q = ps.tiers[ps.tiers[tier].ksk_share]
+                T[o.dst].deff = max(T[o.dst].deff, q.k << q.logN)
             o.lp[0] = (1 << 62) if o.signed else 0
             enc = (o.table_values.astype(object) * (1 << T[o.dst].e)) % (1 << 64)
             o.payload = np.array(enc, dtype=np.uint64).view(np.int64)
+            if split:
+                split_tables(o.payload)       # refuses a table whose pairs have no exact half (e = 0 with an odd sum)
         elif o.type == OP_MAXPOOL:
             ps = circ.param_set
             T[o.dst].e = T[o.src0].e
@@ -636,7 +723,13 @@ def _estimate_noise(circ):
             d_in = s.deff or ps.D                                     # the key switch only sums over the non-zero mask words
             v_tab_in = P.var_keyswitch(d_in, tt) + P.var_modswitch(tt)
 
-            approx = bool(o.ip[9])
+            approx = o.ip[9] == LUT_APPROX
+            # parity split: r + 1 one-bit steps, two look-ups of w - 1 bits; the second one's input carries the parity bootstrap's
+            # output (tier of the last step) on top of the chain's, its key switch and mod switch are its own tier's
+            split = is_split(o)
+            R_, W_ = chain_steps(o), o.w - (1 if split else 0)
+            t2 = ps.tiers[second_tier(ps, o)] if split else None
+            v_tab2_in = (P.var_keyswitch(d_in, t2) + P.var_modswitch(t2)) if split else 0.0
 
             c2 = getattr(ps, "bit_tier_coarse2", None)
 
@@ -647,8 +740,9 @@ def _estimate_noise(circ):
                     # next to a rounding boundary, 2 of 2^r, sit half an input unit from it and take the neighbouring
                     # entry far more often: the method's own inexactness, reported apart as boundary flips.)
                     return P.p_fail(2.0 ** -(o.w + 2), v_ + v_tab_in)
-                if o.r > 0:
-                    for i in range(o.r):
+                step = None
+                if R_ > 0:
+                    for i in range(R_):
                         step = ps.tiers[o.ip[5]]
                         if i >= coarse_from and o.ip[7] >= 0:
                             step = ps.tiers[o.ip[7]]
@@ -658,35 +752,36 @@ def _estimate_noise(circ):
                         v_bit_in = P.var_keyswitch(max(d_in, step.k << step.logN), step) + P.var_modswitch(step)
                         pf_ += P.p_fail(0.25, 4.0 ** (o.p - i) * v_ + v_bit_in)
                         v_ += P.var_pbs_out(step, ps.fft_noise_c)
-                return pf_ + P.p_fail(2.0 ** -(o.w + 2), v_ + v_tab_in)
+                second = P.p_fail(2.0 ** -(W_ + 2), v_ + P.var_pbs_out(step, ps.fft_noise_c) + v_tab2_in) if split else 0.0
+                return pf_ + P.p_fail(2.0 ** -(W_ + 2), v_ + v_tab_in) + second
 
-            pf = site_pfail(o.r)
-            if o.r > 0 and o.ip[7] >= 0 and not approx:
+            pf = site_pfail(R_)
+            if R_ > 0 and o.ip[7] >= 0 and not approx:
                 # earliest step from which the one-level bit tier keeps the site within 2x of its all-precise failure rate
                 budget = max(2.0 * pf, getattr(ps, "p_budget", 1e-12))
-                cf = o.r
+                cf = R_
                 while cf > 0 and site_pfail(cf - 1) <= budget:
                     cf -= 1
                 o.coarse_from = o.ip[8] = cf
                 pf = site_pfail(cf)
                 if c2 is not None:      # ... and, inside that budget, the earliest step from which the two-bit-rotation tier will do
-                    cf2 = o.r
+                    cf2 = R_
                     while cf2 > cf and site_pfail(cf, cf2 - 1) <= budget:
                         cf2 -= 1
                     o.coarse2_from = cf2
-                    o.ip[11] = (c2 << 8) | cf2 if cf2 < o.r else -1
-                    pf = site_pfail(cf, cf2 if cf2 < o.r else None)
+                    o.ip[11] = (c2 << 8) | cf2 if cf2 < R_ else -1
+                    pf = site_pfail(cf, cf2 if cf2 < R_ else None)
             o.pfail = pf
             v_sim = v_in0
-            if o.r > 0 and not approx:                      # what the rounding steps leave on the working ciphertext
-                bt = ps.tiers[o.ip[5]]
-                for i in range(o.r):
+            if R_ > 0 and not approx:                       # what the one-bit steps leave on the working ciphertext
+                for i in range(R_):
                     v_sim += P.var_pbs_out(ps.tiers[step_tier(o, i)], ps.fft_noise_c)
             o.sim_sigma = math.sqrt(v_sim + v_tab_in)
+            o.sim_sigma2 = math.sqrt(v_sim + P.var_pbs_out(ps.tiers[step_tier(o, o.r)], ps.fft_noise_c) + v_tab2_in) if split else 0.0
             if approx:
                 flips += (2.0 / 2 ** o.r) * P.p_fail(2.0 ** -(o.p + 2), v_in0 + v_tab_in) * n_elt
             total += pf * n_elt
-            T[o.dst].var = P.var_pbs_out(tt, ps.fft_noise_c)
+            T[o.dst].var = P.var_pbs_out(tt, ps.fft_noise_c) + (P.var_pbs_out(t2, ps.fft_noise_c) if split else 0.0)
     circ.expected_failures_per_image = total
     circ.expected_boundary_flips_per_image = flips
 

@@ -349,6 +349,16 @@ class EvalKeys:
                                       tables.shape[0], w, None if idx is None else ptr(idx), ptr(out)))
         return out
 
+    def round_lut_split(self, bit_tier, tab_tier, tab_tier2, cts, p, r, tables, w, table_idx=None):
+        """parity split of a w-bit table: the half-table look-ups run on tab_tier and tab_tier2 (dctfhe_round_lut_split)"""
+        cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, self.D + 1)
+        tables = np.ascontiguousarray(tables, np.int64).reshape(-1, 1 << w)
+        idx = None if table_idx is None else np.ascontiguousarray(table_idx, np.int32)
+        out = np.empty_like(cts)
+        check(self.L.dctfhe_round_lut_split(self.ctx.h, self.h, bit_tier, tab_tier, tab_tier2, ptr(cts), cts.shape[0], p, r, ptr(tables),
+                                            tables.shape[0], w, None if idx is None else ptr(idx), ptr(out)))
+        return out
+
     def bench_pbs(self, tier, count, reps=3):
         v = C.c_double()
         check(self.L.dctfhe_bench_pbs(self.ctx.h, self.h, tier, count, reps, C.byref(v)))
@@ -380,7 +390,7 @@ class Keys:
         if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter",
                     "encrypt_seeded", "export_eval_keys_compressed"):
             return getattr(self.client, name)
-        if name in ("export_ksk", "keyswitch", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "bench_pbs", "to_blob"):
+        if name in ("export_ksk", "keyswitch", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
         raise AttributeError(name)
 
@@ -450,6 +460,14 @@ class Session:
             return
         sg = np.ascontiguousarray(sigma_per_op, np.float64)
         check(self.L.dctfhe_session_set_noise(self.h, seed, ptr(sg), sg.size))
+
+    def set_noise_split(self, sigma2_per_op):
+        """the noise std at the SECOND look-up of parity-split sites (one per op, 0 elsewhere); None: the first look-up's"""
+        if sigma2_per_op is None:
+            check(self.L.dctfhe_session_set_noise_split(self.h, None, 0))
+            return
+        sg = np.ascontiguousarray(sigma2_per_op, np.float64)
+        check(self.L.dctfhe_session_set_noise_split(self.h, ptr(sg), sg.size))
 
     def run(self, timing=False):
         t = Timing() if timing else None

@@ -197,6 +197,7 @@ class QuantizedModule:
             # simulation, homomorphic_eval.py:333-347); "disable" = noise-free.  At the exact tiers the two coincide.
             if fhe == "simulate":
                 sess.set_noise(self.sim_seed, self.compiled.simulation_sigmas())
+                sess.set_noise_split(self.compiled.simulation_sigmas_split())
                 self.sim_seed += 1
             else:
                 sess.set_noise(0, None)

@@ -187,6 +187,14 @@ int dctfhe_pbs(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, const uint64_t
 int dctfhe_round_lut(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int bit_tier, int tab_tier, const uint64_t* cts,
                      size_t count, int p, int r, const int64_t* tables, int ntab, int w,
                      const int32_t* table_idx, uint64_t* cts_out);
+/* A table of w = 7 input bits is evaluated by a parity split: with t = 2 t' + b0 the index, one more one-bit step on
+ * bit_tier takes b0 off the ciphertext, a second sign bootstrap of the same small ciphertext puts b0 into the padding bit of a copy, and
+ * two 6-bit look-ups -- S[j] = (T[2j] + T[2j+1]) / 2 on tab_tier, Dt[j] = T[2j] - S[j] on tab_tier2, negated by the negacyclic rotation
+ * when b0 = 1 -- sum to T[t].  Every pair T[2j] + T[2j+1] must be even.  dctfhe_round_lut splits w = 7 with tab_tier2 = tab_tier;
+ * dctfhe_round_lut_split splits any w >= 2 when tab_tier2 >= 0 (and is dctfhe_round_lut without a split when tab_tier2 < 0). */
+int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int bit_tier, int tab_tier, int tab_tier2, const uint64_t* cts,
+                           size_t count, int p, int r, const int64_t* tables, int ntab, int w, const int32_t* table_idx,
+                           uint64_t* cts_out);
 int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int batch, int Cin, int H, int W,
                   const int8_t* weight /* [Cout][Cin][KH][KW] */, int Cout, int KH, int KW, int stride, int pad,
                   uint64_t* out);
@@ -232,7 +240,11 @@ int dctfhe_params_check(const dctfhe_params* params);
 /* Circuit op types: 1 conv2d, 2 add, 3 sum_pool, 4 look-up, 5 max pool.  Max-pool record: ip[0..2] = k, stride, padding; ip[3] = shift
  * of the differences to 63 - p_d; ip[4] = tier of the relu table; ip[5] = p_d (signed difference bits); ip[6] = 1 table; ip[10] =
  * effective dimension of the input; lp[0] = body offset of the differences (2^62); payload: 2^p_d int64 entries relu(d) * 2^e.
- * The output keeps the input's encoding e. */
+ * The output keeps the input's encoding e.
+ * Look-up record: ip[0..3] = p, r, w, shift; ip[4] = table tier; ip[5] = bit tier; ip[6] = tables; ip[7] / ip[8], ip[11] = hand-over of the
+ * one-bit steps to the cheaper bit tiers; ip[10] = effective dimension of the input; ip[9] = mode: 0 exact rounding, 1 approximate
+ * rounding, 2 parity split with both look-ups on ip[4], 3 parity split with the second look-up on the tier whose key-switch key ip[4]
+ * shares (its quiet twin).  A split record keeps the whole 2^w-entry tables; every other value of ip[9] is rejected. */
 int dctfhe_circuit_validate(const void* blob, size_t size);
 
 /* R1: load a compiled circuit description (built by dctfhe.compile, format in DESIGN.md section 4). */
@@ -260,6 +272,9 @@ int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing /* may be NULL *
 /* clear-mode sessions (keys == NULL) only: `simulate` with the noise model.  sigma_per_op[i] (fraction of the torus, 0 for
  * ops that are not look-ups) is added at the input of op i's table look-up, fresh draws every run; n_ops = 0 switches it off */
 int dctfhe_session_set_noise(dctfhe_session* s, uint64_t seed, const double* sigma_per_op, int n_ops);
+/* parity-split look-ups run two table bootstraps: sigma_per_op is sampled at the first, sigma2_per_op[i] (> 0) at the second, whose input
+ * also carries the parity bootstrap's output; without this call, or where the entry is 0, the second takes sigma_per_op[i] too */
+int dctfhe_session_set_noise_split(dctfhe_session* s, const double* sigma2_per_op, int n_ops);
 int dctfhe_session_download(dctfhe_session* s, uint64_t* cts_out /* batch x n_out x (D+1) */);
 
 /* f64 FMA peak micro-benchmark (TFLOP/s) used to price the blind-rotate kernel in bench.py. */

@@ -42,6 +42,8 @@ static int fail(const char* fmt, ...) {
     if (r_ != 0) return r_; \
   } while (0)
 
+#include "circuit.h"   // the blob's wire structs, parse_circuit and the decoded sites: host-only, needs `fail`
+
 extern "C" const char* dctfhe_last_error(void) { return g_err.c_str(); }
 extern "C" int dctfhe_version(void) { return 1; }
 
@@ -120,15 +122,6 @@ struct dctfhe_eval_keys {
 };
 using dctfhe_keys = dctfhe_eval_keys;   // the server-side code below says K for the evaluation keys
 
-enum { OP_CONV = 1, OP_ADD = 2, OP_SUMPOOL = 3, OP_LUT = 4, OP_MAXPOOL = 5 };
-struct Op {
-  int32_t type, src0, src1, dst;
-  int32_t ip[12];
-  int64_t lp[2];
-  int64_t payload_off, payload_len;
-};
-struct TensorShape { int32_t C, H, W, pad; };
-
 // a convolution's weights as the i8 MFMA kernel wants them: [Cout padded to 64][K padded to 32] K-contiguous, and per k the
 // input plane offset and the tap displacement (kernels.h k_conv2d_mfma)
 struct ConvPack {
@@ -157,22 +150,21 @@ struct ConvSlab {
   void* d = nullptr;
   ~ConvSlab() { hipFree(d); }
 };
-static int build_conv_packs(const std::vector<const int8_t*>& w, const std::vector<std::array<int, 7>>& g /* Cout,Cin,H,W,KH,KW,pad */, ConvSlab* slab,
-                            std::vector<ConvPack>* out) {
+static int build_conv_packs(const std::vector<const int8_t*>& w, const std::vector<ConvSite>& g, ConvSlab* slab, std::vector<ConvPack>* out) {
   size_t total = 0;
   std::vector<size_t> off_w(w.size()), off_t(w.size());
   out->assign(w.size(), ConvPack{});
   for (size_t i = 0; i < w.size(); i++) {
     if (!w[i]) continue;
     size_t wb, tb;
-    conv_pack_sizes(g[i][0], g[i][1], g[i][4], g[i][5], &wb, &tb, &(*out)[i].kpad);
+    conv_pack_sizes(g[i].Cout, g[i].Cin, g[i].KH, g[i].KW, &wb, &tb, &(*out)[i].kpad);
     off_w[i] = total; total += wb;
     off_t[i] = total; total += tb;
   }
   if (!total) return 0;
   std::vector<char> host(total, 0);
   for (size_t i = 0; i < w.size(); i++)
-    if (w[i]) pack_conv_host(w[i], g[i][0], g[i][1], g[i][2], g[i][3], g[i][4], g[i][5], g[i][6], (*out)[i].kpad, (int8_t*)&host[off_w[i]], (conv_tap*)&host[off_t[i]]);
+    if (w[i]) pack_conv_host(w[i], g[i].Cout, g[i].Cin, g[i].H, g[i].W, g[i].KH, g[i].KW, g[i].pad, (*out)[i].kpad, (int8_t*)&host[off_w[i]], (conv_tap*)&host[off_t[i]]);
   HIPCHK(hipMalloc(&slab->d, total));
   HIPCHK(hipMemcpy(slab->d, host.data(), total, hipMemcpyHostToDevice));
   for (size_t i = 0; i < w.size(); i++)
@@ -180,44 +172,19 @@ static int build_conv_packs(const std::vector<const int8_t*>& w, const std::vect
   return 0;
 }
 
-struct dctfhe_circuit {
+struct dctfhe_circuit : CircuitPlan {      // tensors, ops (one decoded SiteOp per record), input / output tensor
   dctfhe_ctx* ctx = nullptr;
-  std::vector<TensorShape> tensors;
-  std::vector<Op> ops;
   std::vector<void*> d_payload;  // per op, device copy of its payload (weights / tables)
   std::vector<int64_t*> d_split; // per op: the half tables [S | Dt] of a parity-split look-up, each [ntab][2^(w-1)] (nullptr for other ops)
   std::vector<ConvPack> conv;    // per op: the matrix-core form of a convolution's weights (empty for other ops)
   ConvSlab conv_slab;            // ... all of them in one allocation, made when the first encrypted session is created
   std::vector<std::vector<int8_t>> conv_w;          // host copies of the convolution weights until then
-  std::vector<std::array<int, 7>> conv_geom;
-  int input_tensor = 0, output_tensor = 0, max_bit_width = 0;
   ~dctfhe_circuit() {
     if (ctx) hipSetDevice(ctx->device);
     for (void* p : d_payload) if (p) hipFree(p);
     for (int64_t* p : d_split) if (p) hipFree(p);
   }
 };
-
-// ---- look-up modes (ip[9] of an OP_LUT record; dctfhe/compile.py LUT_*)
-enum { LUT_EXACT = 0, LUT_APPROX = 1, LUT_SPLIT = 2, LUT_SPLIT_QUIET = 3 };
-static bool lut_is_split(const Op& o) { return o.ip[9] == LUT_SPLIT || o.ip[9] == LUT_SPLIT_QUIET; }
-// one-bit steps of a look-up op: none with approximate rounding; the r rounding steps, and for a parity split the step that takes the
-// table index's low bit off the working ciphertext
-static int lut_steps(const Op& o) { return o.ip[9] == LUT_APPROX ? 0 : o.ip[1] + (lut_is_split(o) ? 1 : 0); }
-// Parity split of tables [ntab][2^w] (t = 2 t' + b0): S[j] = ((T[2j] + T[2j+1]) mod 2^64) >> 1, Dt[j] = T[2j] - S[j], so that
-// S + Dt = T[2j] and S - Dt = T[2j+1] (mod 2^64) whatever the top bit of S.  out = [S: ntab << (w-1)][Dt: the same].  An odd sum has no
-// half: -1 (the compiler keeps the output exponent of a split site >= 1).
-static int split_tables_host(const int64_t* T, size_t ntab, int w, std::vector<int64_t>* out) {
-  const size_t half = (size_t)1 << (w - 1), n = ntab * half;
-  out->resize(2 * n);
-  for (size_t i = 0; i < n; i++) {
-    const uint64_t a = (uint64_t)T[2 * i], b = (uint64_t)T[2 * i + 1], sum = a + b;
-    if (sum & 1) return -1;
-    (*out)[i] = (int64_t)(sum >> 1);
-    (*out)[n + i] = (int64_t)(a - (sum >> 1));
-  }
-  return 0;
-}
 
 // ---- max pool (OP_MAXPOOL): separable passes, rows then columns; each pass a log-depth tree of pairwise maxima
 // max(a, b) = b + relu(a - b) over the window's in-range taps.  Late pairing: a pass of L = ceil(log2 max taps) levels; at level l an
@@ -236,17 +203,6 @@ struct PoolPlan {
   size_t pairs_per_batch = 0;
   DevBuf maps;
 };
-static int pool_out_size(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
-// pairwise maxima of one image: every output of a pass costs its in-range taps minus one
-static int64_t pool_pairs(int C, int H, int W, int k, int s, int p) {
-  auto pass = [&](int n) {
-    int64_t t = 0;
-    for (int o = 0; o < pool_out_size(n, k, s, p); o++)
-      for (int j = 0; j < k; j++) t += (o * s - p + j >= 0 && o * s - p + j < n) ? 1 : 0;
-    return t - pool_out_size(n, k, s, p);
-  };
-  return (int64_t)C * H * pass(W) + (int64_t)C * pool_out_size(W, k, s, p) * pass(H);
-}
 static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, PoolPlan* P) {
   const int Ho = pool_out_size(H, k, s, p), Wo = pool_out_size(W, k, s, p);
   if ((double)batch * C * H * W >= 2147483647.0) return fail("max pool: %d x %d x %d x %d rows exceed the int32 index maps", batch, C, H, W);
@@ -327,6 +283,10 @@ static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, PoolPl
   return 0;
 }
 
+// key-switch digits and bodies, small ciphertexts and the 64 single-entry tables 2^j of the one-bit steps, for `chunk` ciphertexts at a time
+struct LutScratch { uint8_t* digits = nullptr; uint64_t* bodies = nullptr; uint64_t* small = nullptr; int64_t* bit_tables = nullptr; size_t chunk = 0; };
+struct LutScratchOwner { LutScratch s{}; ~LutScratchOwner() { hipFree(s.digits); hipFree(s.bodies); hipFree(s.small); hipFree(s.bit_tables); } };
+
 struct dctfhe_session {
   dctfhe_ctx* ctx = nullptr;
   dctfhe_circuit* circ = nullptr;
@@ -339,12 +299,7 @@ struct dctfhe_session {
   // encrypted tensors are stored at their effective dimension: row stride t_L[t] words = t_L[t]-1 mask words + the body;
   // t_deff[t] <= t_L[t]-1 is how many leading mask words may be non-zero.  Clear mode: one word per element.
   std::vector<size_t> t_L, t_deff;
-  // scratch for LUT sites
-  size_t chunk = 0;
-  uint8_t* d_digits = nullptr;
-  uint64_t* d_bodies = nullptr;
-  uint64_t* d_small = nullptr;
-  int64_t* d_bit_tables = nullptr;  // 64 single-entry tables: 2^j
+  LutScratchOwner lut;              // scratch for LUT sites
   int* d_overflow = nullptr;
   // `simulate`: per-op noise (fraction of the torus) injected by the clear look-up kernel; empty = noise-free
   std::vector<double> sim_sigma;
@@ -360,7 +315,7 @@ struct dctfhe_session {
     if (ctx) hipSetDevice(ctx->device);
     for (auto& o : owned) hipFree(o.second);
     for (hipEvent_t e : ev_pool) hipEventDestroy(e);
-    hipFree(d_digits); hipFree(d_bodies); hipFree(d_small); hipFree(d_bit_tables); hipFree(d_overflow);
+    hipFree(d_overflow);
   }
 };
 
@@ -1293,87 +1248,64 @@ static int dev_conv2d(hipStream_t st, const uint64_t* in, int batch, int Cin, in
 
 static unsigned ew_grid(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, 16384)); }
 
-// exact rounding + table look-up on `count` ciphertexts, in place on d_work (already shifted / offset)
-struct LutScratch { uint8_t* digits = nullptr; uint64_t* bodies = nullptr; uint64_t* small = nullptr; int64_t* bit_tables = nullptr; size_t chunk = 0; };
-// Tier of rounding step i of a look-up op: ip[5] (bit tier), from step ip[8] on its one-level twin ip[7], from step ip[11] & 255 on the
-// two-bit-rotation twin ip[11] >> 8 (the compiler proves each hand-over safe; dctfhe/compile.py::step_tier is the same rule).
-struct StepTiers {
-  int bit = -1, coarse = -1, coarse_from = 1 << 30, coarse2 = -1, coarse2_from = 1 << 30;
-  int at(int i) const { return (coarse2 >= 0 && i >= coarse2_from) ? coarse2 : (coarse >= 0 && i >= coarse_from) ? coarse : bit; }
+// The rows a look-up site works on.  With one-bit steps: in place on `work` (rows of Lw words, already shifted / offset; the first `deff`
+// mask words may be non-zero).  Without: nothing modifies the input, so the key switch reads `src` (rows of Ls words) directly with the
+// site's shift and body offset applied on the fly, and the table bootstrap writes `work` -- no copy of the tensor at all.  A split needs
+// `par` too, rows of Lp words for the parity bootstrap's output and then the second look-up's (Lw - 1, Lp - 1 >= the rings of both), and
+// the half tables tab_s / tab_d in place of `tables`.  idx: optional table index per ciphertext.
+struct LutRows {
+  const uint64_t* src = nullptr;
+  uint64_t *work = nullptr, *par = nullptr;
+  size_t Ls = 0, Lw = 0, Lp = 0;
+  const int64_t *tables = nullptr, *tab_s = nullptr, *tab_d = nullptr;
+  const int32_t* idx = nullptr;
 };
-static StepTiers step_tiers_of(const Op& o) {
-  StepTiers s;
-  s.bit = o.ip[5]; s.coarse = o.ip[7]; s.coarse_from = o.ip[8];
-  if (o.ip[11] >= 0) { s.coarse2 = o.ip[11] >> 8; s.coarse2_from = o.ip[11] & 255; }
-  return s;
-}
-// Parity split of a w-bit table (7 on the shipped catalogues) into two (w-1)-bit look-ups: tier2 < 0 = no split.  par: rows of Lp words for
-// the parity bootstrap's output and then the second look-up's (Lp - 1 >= the rings of both); tab_s / tab_d: the half tables.
-struct LutSplit { int tier2 = -1; uint64_t* par = nullptr; size_t Lp = 0; const int64_t* tab_s = nullptr; const int64_t* tab_d = nullptr; };
-// r > 0: in place on d_work (rows of Lw words, already shifted / offset; the first `deff` mask words may be non-zero).
-// r == 0: nothing modifies the input, so the key switch reads d_src (rows of Ls words) directly with the site's shift and
-// body offset applied on the fly, and the table bootstrap writes d_work -- no copy of the tensor at all.
-static int dev_round_lut(dctfhe_keys* K, const StepTiers& stp, int tab_tier, const uint64_t* d_src, size_t Ls, int shift,
-                         uint64_t body_add, uint64_t* d_work, size_t Lw, size_t count, int p, int r, const int64_t* d_tables, int w, const int32_t* d_idx,
-                         int hw, int nchan, const LutScratch& sc, Timers* tm, int deff = 0, const LutSplit* sp = nullptr) {
-  const bool split = sp && sp->tier2 >= 0;
+static size_t ring_of(const dctfhe_keys* K, int tier) { return (size_t)K->p.tiers[tier].k << K->p.tiers[tier].logN; }
+static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, size_t count, int hw, const LutScratch& sc, Timers* tm, int deff) {
+  const bool split = L.split();
+  const int p = L.p, steps = L.n_steps(), nchan = L.ntab, tab_tier = L.tab_tier, tier2 = L.tier2(K->p);
+  const size_t Lw = b.Lw, ring2 = split ? ring_of(K, tier2) : 0;
   if (split) {
-    const size_t ring2 = (size_t)K->p.tiers[sp->tier2].k << K->p.tiers[sp->tier2].logN;
-    if (w < 2 || !sp->par || !sp->tab_s || !sp->tab_d) return fail("parity split: needs a table of at least 2 input bits, a parity buffer and the half tables");
-    if (Lw < ring2 + 1 || sp->Lp < ring2 + 1) return fail("parity split: rows of %zu / %zu words cannot hold the second look-up's ring of %zu", Lw, sp->Lp, ring2);
+    if (L.w < 2 || !b.par || !b.tab_s || !b.tab_d) return fail("parity split: needs a table of at least 2 input bits, a parity buffer and the half tables");
+    if (Lw < ring2 + 1 || b.Lp < ring2 + 1) return fail("parity split: rows of %zu / %zu words cannot hold the second look-up's ring of %zu", Lw, b.Lp, ring2);
   }
   for (size_t c0 = 0; c0 < count; c0 += sc.chunk) {
     const size_t cn = std::min(sc.chunk, count - c0);
-    uint64_t* w0 = d_work + c0 * Lw;
-    if (split) {
-      // t = 2 t' + b0 sits under the padding bit once the r rounding steps are done.  Step r is one more of them, on b0: it leaves t' as
-      // a (w-1)-bit message in w0.  The same small ciphertext, bootstrapped with 2^62 and body offset -2^62, gives b0 * 2^63 (par).
-      // Second look-up first, while w0 still holds t': key switch of w0 + par (b0 in the padding bit, never materialised), table Dt
-      // -> (-1)^b0 Dt[t'] into par; then the first look-up S[t'] into w0 as for any site, and the sum.
-      hipStream_t st = K->ctx->stream;
-      for (int i = 0; i <= r; i++) {
-        const int bt = stp.at(i);
-        CHK(dev_keyswitch(K, bt, w0, cn, p - i, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
-        CHK(dev_ms_center(K, bt, sc.small, cn, tm));
-        const int vlog = 62 - p + i;
-        CHK(dev_pbs(K, bt, sc.small, cn, sc.bit_tables + vlog, 0, nullptr, 1, 1, 0, w0, 1, (uint64_t)0 - (1ULL << vlog), tm, Lw));
-        if (i == r) CHK(dev_pbs(K, bt, sc.small, cn, sc.bit_tables + 62, 0, nullptr, 1, 1, 0, sp->par, 0, (uint64_t)0 - (1ULL << 62), tm, sp->Lp));
-      }
-      const int* idx = d_idx ? d_idx + c0 : nullptr;
-      CHK(dev_keyswitch(K, sp->tier2, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw, 0, nullptr, nullptr, sp->par, sp->Lp));
-      CHK(dev_ms_center(K, sp->tier2, sc.small, cn, tm));
-      CHK(dev_pbs(K, sp->tier2, sc.small, cn, sp->tab_d, w - 1, idx, hw, nchan, c0, sp->par, 0, 0, tm, sp->Lp));
-      CHK(dev_keyswitch(K, tab_tier, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
-      CHK(dev_ms_center(K, tab_tier, sc.small, cn, tm));
-      CHK(dev_pbs(K, tab_tier, sc.small, cn, sp->tab_s, w - 1, idx, hw, nchan, c0, w0, 0, 0, tm, Lw));
-      const size_t ring2 = (size_t)K->p.tiers[sp->tier2].k << K->p.tiers[sp->tier2].logN;
-      const int h = tm ? tm->begin(CAT_LINEAR) : -1;
-      hipLaunchKernelGGL(k_acc_rows, dim3(ew_grid(cn * (ring2 + 1))), dim3(256), 0, st, w0, Lw, sp->par, sp->Lp, cn, ring2);
-      HIPCHK(hipGetLastError());
-      if (tm) tm->end(h);
-      continue;
-    }
-    for (int i = 0; i < r; i++) {
-      const int bt = stp.at(i);
+    uint64_t* w0 = b.work + c0 * Lw;
+    const int* idx = b.idx ? b.idx + c0 : nullptr;
+    for (int i = 0; i < steps; i++) {
+      const int bt = L.steps.at(i), vlog = 62 - p + i;
       CHK(dev_keyswitch(K, bt, w0, cn, p - i, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
       CHK(dev_ms_center(K, bt, sc.small, cn, tm));
-      const int vlog = 62 - p + i;
       CHK(dev_pbs(K, bt, sc.small, cn, sc.bit_tables + vlog, 0, nullptr, 1, 1, 0, w0, 1, (uint64_t)0 - (1ULL << vlog), tm, Lw));
     }
-    if (r > 0) CHK(dev_keyswitch(K, tab_tier, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
-    else       CHK(dev_keyswitch(K, tab_tier, d_src + c0 * Ls, cn, shift, sc.digits, sc.bodies, sc.small, tm, deff, Ls, body_add));
+    if (split) {
+      // t = 2 t' + b0 sits under the padding bit once the r rounding steps are done.  The last step was one more of them, on b0: it left
+      // t' as a (w-1)-bit message in w0.  The same small ciphertext, bootstrapped with 2^62 and body offset -2^62, gives b0 * 2^63 (par).
+      // Second look-up first, while w0 still holds t': key switch of w0 + par (b0 in the padding bit, never materialised), table Dt
+      // -> (-1)^b0 Dt[t'] into par; then the first look-up S[t'] into w0 as for any site, and the sum.
+      CHK(dev_pbs(K, L.steps.at(steps - 1), sc.small, cn, sc.bit_tables + 62, 0, nullptr, 1, 1, 0, b.par, 0, (uint64_t)0 - (1ULL << 62), tm, b.Lp));
+      CHK(dev_keyswitch(K, tier2, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw, 0, nullptr, nullptr, b.par, b.Lp));
+      CHK(dev_ms_center(K, tier2, sc.small, cn, tm));
+      CHK(dev_pbs(K, tier2, sc.small, cn, b.tab_d, L.w - 1, idx, hw, nchan, c0, b.par, 0, 0, tm, b.Lp));
+    }
+    if (steps > 0) CHK(dev_keyswitch(K, tab_tier, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
+    else           CHK(dev_keyswitch(K, tab_tier, b.src + c0 * b.Ls, cn, L.shift, sc.digits, sc.bodies, sc.small, tm, deff, b.Ls, L.round_add()));
     CHK(dev_ms_center(K, tab_tier, sc.small, cn, tm));
-    CHK(dev_pbs(K, tab_tier, sc.small, cn, d_tables, w, d_idx ? d_idx + c0 : nullptr, hw, nchan, c0, w0, 0, 0, tm, Lw));
+    CHK(dev_pbs(K, tab_tier, sc.small, cn, split ? b.tab_s : b.tables, L.table_bits(), idx, hw, nchan, c0, w0, 0, 0, tm, Lw));
+    if (split) {
+      const int h = tm ? tm->begin(CAT_LINEAR) : -1;
+      hipLaunchKernelGGL(k_acc_rows, dim3(ew_grid(cn * (ring2 + 1))), dim3(256), 0, K->ctx->stream, w0, Lw, b.par, b.Lp, cn, ring2);
+      HIPCHK(hipGetLastError());
+      if (tm) tm->end(h);
+    }
   }
   return 0;
 }
-// the mask words a rounding chain touches: its input's, and the rings of the bit tiers whose outputs it accumulates
-static int round_chain_deff(const dctfhe_keys* K, int src_deff, const StepTiers& stp, int r) {
-  int d = src_deff;
-  for (int i = 0; i < r; i++) {
-    const int tier = stp.at(i);
-    if (tier >= 0) d = std::max(d, K->p.tiers[tier].k << K->p.tiers[tier].logN);
-  }
+// the mask words a rounding chain touches: its input's, and the rings of the bit tiers whose outputs it accumulates (the step entries)
+static int round_chain_deff(const dctfhe_keys* K, int src_deff, const LutSite& L) {
+  int d = src_deff, left = L.n_steps();
+  for_each_bootstrap(L, K->p, [&](int tier, int, bool) { if (left-- > 0 && tier >= 0) d = std::max(d, (int)ring_of(K, tier)); });
   return d;
 }
 
@@ -1396,19 +1328,14 @@ static int alloc_lut_scratch(dctfhe_keys* K, size_t chunk, LutScratch* sc) {
   HIPCHK(hipMemcpy(sc->bit_tables, bt, sizeof bt, hipMemcpyHostToDevice));
   return 0;
 }
-static void free_lut_scratch(LutScratch* sc) {
-  hipFree(sc->digits); hipFree(sc->bodies); hipFree(sc->small); hipFree(sc->bit_tables);
-  sc->digits = nullptr; sc->bodies = nullptr; sc->small = nullptr; sc->bit_tables = nullptr;
-}
-struct LutScratchOwner { LutScratch s{}; ~LutScratchOwner() { free_lut_scratch(&s); } };
 
 // the levels of a max-pool plan on device rows.  Input rows of stride Ls (first ds mask words meaningful); level buffers and output rows of
 // stride Lo, of which the first `dout` = max(ds, ring of the tier) mask words may be non-zero.  Each level: the gather, then per chunk the
 // key switch of the differences (k_ks_decompose_diff), the centred mod switch and the relu bootstrap accumulated into the gathered b rows.
-static int dev_max_pool(dctfhe_keys* K, int tier, const PoolPlan& P, const uint64_t* d_in, size_t Ls, size_t ds, uint64_t* const bufs[2],
-                        uint64_t* d_out, size_t Lo, size_t dout, int shift, uint64_t body_add, const int64_t* d_table, int p_d,
-                        const LutScratch& sc, Timers* tm) {
+static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, const uint64_t* d_in, size_t Ls, size_t ds, uint64_t* const bufs[2],
+                        uint64_t* d_out, size_t Lo, size_t dout, const int64_t* d_table, const LutScratch& sc, Timers* tm) {
   hipStream_t st = K->ctx->stream;
+  const int tier = S.tier;
   const int32_t* maps = P.maps.as<int32_t>();
   for (const PoolLevel& l : P.lv) {
     const uint64_t* src = l.src == 0 ? d_in : bufs[l.src - 1];
@@ -1420,10 +1347,10 @@ static int dev_max_pool(dctfhe_keys* K, int tier, const PoolPlan& P, const uint6
     if (tm) tm->end(h);
     for (size_t c0 = 0; c0 < l.pairs; c0 += sc.chunk) {
       const size_t cn = std::min(sc.chunk, l.pairs - c0);
-      CHK(dev_keyswitch(K, tier, src, cn, shift, sc.digits, sc.bodies, sc.small, tm, (int)d_src, L_src, body_add, maps + l.a_off + c0,
+      CHK(dev_keyswitch(K, tier, src, cn, S.shift, sc.digits, sc.bodies, sc.small, tm, (int)d_src, L_src, S.body_add, maps + l.a_off + c0,
                         maps + l.b_off + c0));
       CHK(dev_ms_center(K, tier, sc.small, cn, tm));
-      CHK(dev_pbs(K, tier, sc.small, cn, d_table, p_d, nullptr, 1, 1, 0, dst + c0 * Lo, 1, 0, tm, Lo));
+      CHK(dev_pbs(K, tier, sc.small, cn, d_table, S.p_d, nullptr, 1, 1, 0, dst + c0 * Lo, 1, 0, tm, Lo));
     }
   }
   return 0;
@@ -1549,21 +1476,24 @@ extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int 
   }
   LutScratchOwner sc;
   CHK(alloc_lut_scratch(K, std::min<size_t>(count, 4096), &sc.s));
-  LutSplit sp;
+  // the site a record of this look-up would decode to (rows arrive shifted and offset; without an index every ciphertext takes table 0)
+  LutSite site;
+  site.p = p; site.r = r; site.w = w; site.ntab = table_idx ? ntab : 1; site.tab_tier = tab_tier; site.steps.bit = bit_tier;
+  LutRows rows;
+  rows.src = rows.work = d_work.as<uint64_t>(); rows.Ls = rows.Lw = L;
+  rows.tables = d_tab.as<int64_t>(); rows.idx = d_idx.as<int32_t>();
   if (split) {
     HIPCHK(d_par.alloc(sc.s.chunk * L * 8));
-    sp.tier2 = tab_tier2; sp.par = d_par.as<uint64_t>(); sp.Lp = L;
-    sp.tab_s = d_tab.as<int64_t>(); sp.tab_d = d_tab.as<int64_t>() + ((size_t)ntab << (w - 1));
+    site.mode = LUT_SPLIT; site.tier2_named = tab_tier2;
+    rows.par = d_par.as<uint64_t>(); rows.Lp = L;
+    rows.tab_s = d_tab.as<int64_t>(); rows.tab_d = d_tab.as<int64_t>() + ((size_t)ntab << (w - 1));
   }
   if (r > 0) {
     hipLaunchKernelGGL(k_affine, dim3(ew_grid(count * L)), dim3(256), 0, ctx->stream, d_work.as<uint64_t>(), L, L - 1, d_work.as<uint64_t>(), L, count, L - 1, 0,
                        1ULL << (63 - p + r - 1));
     HIPCHK(hipGetLastError());
   }
-  StepTiers stp;
-  stp.bit = bit_tier;
-  CHK(dev_round_lut(K, stp, tab_tier, d_work.as<uint64_t>(), L, 0, 0, d_work.as<uint64_t>(), L, count, p, r, d_tab.as<int64_t>(), w,
-                    d_idx.as<int32_t>(), 1, 1, sc.s, nullptr, 0, &sp));
+  CHK(dev_round_lut(K, site, rows, count, 1, sc.s, nullptr, 0));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipMemcpy(cts_out, d_work.p, count * L * 8, hipMemcpyDeviceToHost));
   return 0;
@@ -1591,7 +1521,7 @@ extern "C" int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int bat
   HIPCHK(hipMemcpy(d_w.p, weight, nw, hipMemcpyHostToDevice));
   ConvSlab slab;
   std::vector<ConvPack> pk;
-  CHK(build_conv_packs({weight}, {{Cout, Cin, H, W, KH, KW, pad}}, &slab, &pk));
+  CHK(build_conv_packs({weight}, {ConvSite{Cout, Cin, H, W, KH, KW, stride, pad}}, &slab, &pk));
   CHK(dev_conv2d(ctx->stream, d_in.as<uint64_t>(), batch, Cin, H, W, L, L - 1, d_w.as<int8_t>(), &pk[0], Cout, KH, KW, stride, pad, d_out.as<uint64_t>(), L));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipMemcpy(out, d_out.p, nout * 8, hipMemcpyDeviceToHost));
@@ -1742,8 +1672,8 @@ extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   LutScratchOwner sc;
   CHK(alloc_lut_scratch(K, std::min<size_t>(std::max<size_t>(P.pairs_per_batch, 1), 4096), &sc.s));
   uint64_t* const bufs[2] = {ba.as<uint64_t>(), bb.as<uint64_t>()};
-  CHK(dev_max_pool(K, tier, P, di.as<uint64_t>(), Li, (size_t)deff_in, bufs, d_o.as<uint64_t>(), Lo, (size_t)dout, 0, 1ULL << 62, d_tab.as<int64_t>(), p_d,
-                   sc.s, nullptr));
+  const PoolSite site{k, s, p, 0, tier, p_d, deff_in, 1ULL << 62};
+  CHK(dev_max_pool(K, site, P, di.as<uint64_t>(), Li, (size_t)deff_in, bufs, d_o.as<uint64_t>(), Lo, (size_t)dout, d_tab.as<int64_t>(), sc.s, nullptr));
   HIPCHK(hipStreamSynchronize(st));
   HIPCHK(hipMemcpy(out, d_o.p, nout * Lo * 8, hipMemcpyDeviceToHost));
   return 0;
@@ -1791,89 +1721,8 @@ extern "C" int dctfhe_dct_frontend(dctfhe_ctx* ctx, const uint8_t* y, const uint
 }
 
 // ------------------------------------------------------------------------------------------ circuit
-struct BlobHeader { uint32_t magic, version; int32_t n_tensors, n_ops, input_tensor, output_tensor, max_bit_width, reserved; };
-
-// parse + validate a circuit blob on the host (no GPU): header, tensor table, op records, payload ranges, per-op shapes
-static int parse_circuit(const void* blob, size_t size, dctfhe_circuit* c) {
-  if (!blob) return fail("null circuit blob");
-  if (size < sizeof(BlobHeader)) return fail("circuit blob too short");
-  BlobHeader h;
-  memcpy(&h, blob, sizeof h);
-  if (h.magic != 0x46544344u /* 'DCTF' */ || h.version != 1) return fail("bad circuit blob magic/version");
-  if (h.n_tensors < 1 || h.n_ops < 0 || h.n_tensors > (1 << 20) || h.n_ops > (1 << 20)) return fail("circuit blob: bad tensor/op count");
-  const size_t need = sizeof h + (size_t)h.n_tensors * sizeof(TensorShape) + (size_t)h.n_ops * sizeof(Op);
-  if (size < need) return fail("circuit blob truncated");
-  auto bad_t = [&](int t) { return t < 0 || t >= h.n_tensors; };
-  if (bad_t(h.input_tensor) || bad_t(h.output_tensor)) return fail("circuit blob: input/output tensor id out of range");
-  c->tensors.resize(h.n_tensors);
-  c->ops.resize(h.n_ops);
-  const char* p = (const char*)blob + sizeof h;
-  memcpy(c->tensors.data(), p, (size_t)h.n_tensors * sizeof(TensorShape));
-  p += (size_t)h.n_tensors * sizeof(TensorShape);
-  memcpy(c->ops.data(), p, (size_t)h.n_ops * sizeof(Op));
-  c->input_tensor = h.input_tensor; c->output_tensor = h.output_tensor; c->max_bit_width = h.max_bit_width;
-  for (const TensorShape& t : c->tensors)
-    if (t.C < 1 || t.H < 1 || t.W < 1) return fail("circuit blob: empty tensor shape");
-  for (int i = 0; i < h.n_ops; i++) {
-    const Op& o = c->ops[i];
-    if (o.type < OP_CONV || o.type > OP_MAXPOOL) return fail("op %d: unknown type %d", i, o.type);
-    if (bad_t(o.src0) || bad_t(o.dst) || (o.type == OP_ADD && bad_t(o.src1))) return fail("op %d: tensor id out of range", i);
-    if (o.payload_len < 0 || (o.payload_len > 0 && (o.payload_off < (int64_t)need || (size_t)o.payload_off + (size_t)o.payload_len > size)))
-      return fail("op %d: payload out of range", i);
-    const TensorShape& a = c->tensors[o.src0];
-    const TensorShape& d = c->tensors[o.dst];
-    switch (o.type) {
-      case OP_CONV: {
-        const int Cout = o.ip[0], KH = o.ip[1], KW = o.ip[2], st = o.ip[3], pad = o.ip[4];
-        if (Cout < 1 || KH < 1 || KW < 1 || st < 1 || pad < 0 || a.H + 2 * pad < KH || a.W + 2 * pad < KW) return fail("op %d: bad convolution geometry", i);
-        if (d.C != Cout || d.H != (a.H + 2 * pad - KH) / st + 1 || d.W != (a.W + 2 * pad - KW) / st + 1) return fail("op %d: convolution output shape mismatch", i);
-        if (o.payload_len != (int64_t)Cout * a.C * KH * KW) return fail("op %d: weight payload of %lld bytes, expected %lld", i, (long long)o.payload_len, (long long)Cout * a.C * KH * KW);
-        break;
-      }
-      case OP_ADD: {
-        const TensorShape& b2 = c->tensors[o.src1];
-        if (a.C != b2.C || a.H != b2.H || a.W != b2.W || a.C != d.C || a.H != d.H || a.W != d.W) return fail("op %d: add operands differ in shape", i);
-        break;
-      }
-      case OP_SUMPOOL: {
-        const int K = o.ip[0];
-        if (K < 1 || d.C != a.C || d.H != a.H / K || d.W != a.W / K || d.H < 1 || d.W < 1) return fail("op %d: bad pooling geometry", i);
-        break;
-      }
-      case OP_LUT: {
-        const int pp = o.ip[0], r = o.ip[1], w = o.ip[2], shift = o.ip[3], ntab = o.ip[6];
-        if (pp < 1 || pp > 62 || r < 0 || r >= pp || w != pp - r || shift < 0 || shift > 63) return fail("op %d: bad look-up precision (p=%d r=%d w=%d shift=%d)", i, pp, r, w, shift);
-        if (ntab != 1 && ntab != a.C) return fail("op %d: %d tables for %d channels", i, ntab, a.C);
-        if (o.payload_len != ((int64_t)ntab << w) * 8) return fail("op %d: table payload of %lld bytes, expected %lld", i, (long long)o.payload_len, (long long)(((int64_t)ntab << w) * 8));
-        if (a.C != d.C || a.H != d.H || a.W != d.W) return fail("op %d: look-up changes the shape", i);
-        if (o.ip[9] < LUT_EXACT || o.ip[9] > LUT_SPLIT_QUIET) return fail("op %d: unknown look-up mode %d (0 exact, 1 approximate, 2 / 3 parity split)", i, o.ip[9]);
-        if (lut_is_split(o)) {
-          if (w < 2 || w > 16) return fail("op %d: a parity split needs a table of 2 to 16 input bits, not %d", i, w);
-          if (o.ip[5] < 0) return fail("op %d: a parity split needs a bit tier", i);
-          std::vector<int64_t> tmp((size_t)ntab << w), halves;
-          memcpy(tmp.data(), (const char*)blob + o.payload_off, (size_t)o.payload_len);
-          if (split_tables_host(tmp.data(), (size_t)ntab, w, &halves)) return fail("op %d: parity split of a table whose entry pairs have an odd sum", i);
-        }
-        break;
-      }
-      case OP_MAXPOOL: {
-        const int k = o.ip[0], st = o.ip[1], pad = o.ip[2], shift = o.ip[3], tier = o.ip[4], pd = o.ip[5];
-        if (k < 1 || k > 32 || st < 1 || pad < 0 || 2 * pad > k || a.H + 2 * pad < k || a.W + 2 * pad < k)
-          return fail("op %d: bad max-pool geometry (k=%d s=%d p=%d: need 1 <= k <= 32, s >= 1, 0 <= p <= k/2, window inside the padded input)", i, k, st, pad);
-        if (d.C != a.C) return fail("op %d: max pool changes the channel count (%d -> %d)", i, a.C, d.C);
-        if (d.H != pool_out_size(a.H, k, st, pad) || d.W != pool_out_size(a.W, k, st, pad)) return fail("op %d: max-pool output shape mismatch", i);
-        if (pd < 2 || pd > 16 || shift < 0 || pd + shift > 63) return fail("op %d: bad max-pool difference precision (p_d=%d shift=%d)", i, pd, shift);
-        if (tier < 0 || tier >= DCTFHE_MAX_TIERS) return fail("op %d: max-pool tier %d out of range", i, tier);
-        if (o.payload_len != ((int64_t)1 << pd) * 8) return fail("op %d: max-pool table payload of %lld bytes, expected %lld", i, (long long)o.payload_len, (long long)(((int64_t)1 << pd) * 8));
-        break;
-      }
-    }
-  }
-  return 0;
-}
-
 extern "C" int dctfhe_circuit_validate(const void* blob, size_t size) {
-  dctfhe_circuit c;
+  CircuitPlan c;
   return parse_circuit(blob, size, &c);
 }
 
@@ -1885,164 +1734,123 @@ extern "C" int dctfhe_circuit_load(dctfhe_ctx* ctx, const void* blob, size_t siz
   c->ctx = ctx;
   c->d_payload.assign(c->ops.size(), nullptr);
   c->d_split.assign(c->ops.size(), nullptr);
-  std::vector<const int8_t*> cw(c->ops.size(), nullptr);
-  std::vector<std::array<int, 7>> cg(c->ops.size());
-  for (size_t i = 0; i < c->ops.size(); i++) {
-    const Op& o = c->ops[i];
-    if (o.payload_len > 0) {
-      HIPCHK(hipMalloc(&c->d_payload[i], (size_t)o.payload_len));
-      HIPCHK(hipMemcpy(c->d_payload[i], (const char*)blob + o.payload_off, (size_t)o.payload_len, hipMemcpyHostToDevice));
-    }
-    if (o.type == OP_LUT && lut_is_split(o)) {      // the half tables of a parity split, once per circuit
-      std::vector<int64_t> tmp((size_t)o.payload_len / 8), halves;
-      memcpy(tmp.data(), (const char*)blob + o.payload_off, (size_t)o.payload_len);
-      if (split_tables_host(tmp.data(), (size_t)o.ip[6], o.ip[2], &halves)) return fail("op %zu: parity split of a table whose entry pairs have an odd sum", i);
-      HIPCHK(hipMalloc(&c->d_split[i], halves.size() * 8));
-      HIPCHK(hipMemcpy(c->d_split[i], halves.data(), halves.size() * 8, hipMemcpyHostToDevice));
-    }
-    if (o.type == OP_CONV) {
-      const TensorShape& a = c->tensors[o.src0];
-      cw[i] = (const int8_t*)blob + o.payload_off;
-      cg[i] = {o.ip[0], a.C, a.H, a.W, o.ip[1], o.ip[2], o.ip[4]};
-    }
-  }
   c->conv.assign(c->ops.size(), ConvPack{});
   c->conv_w.resize(c->ops.size());
-  for (size_t i = 0; i < c->ops.size(); i++)
-    if (cw[i]) c->conv_w[i].assign(cw[i], cw[i] + c->ops[i].payload_len);
-  c->conv_geom = cg;
+  for (size_t i = 0; i < c->ops.size(); i++) {
+    SiteOp& o = c->ops[i];
+    const char* payload = (const char*)blob + o.payload_off;
+    if (o.payload_len > 0) {
+      HIPCHK(hipMalloc(&c->d_payload[i], (size_t)o.payload_len));
+      HIPCHK(hipMemcpy(c->d_payload[i], payload, (size_t)o.payload_len, hipMemcpyHostToDevice));
+    }
+    if (!o.halves.empty()) {      // the half tables of a parity split (parse_circuit made them), once per circuit
+      HIPCHK(hipMalloc(&c->d_split[i], o.halves.size() * 8));
+      HIPCHK(hipMemcpy(c->d_split[i], o.halves.data(), o.halves.size() * 8, hipMemcpyHostToDevice));
+      std::vector<int64_t>().swap(o.halves);
+    }
+    if (o.type == OP_CONV) c->conv_w[i].assign((const int8_t*)payload, (const int8_t*)payload + o.payload_len);
+  }
   *out = c.release();
   return 0;
 }
 extern "C" int dctfhe_circuit_destroy(dctfhe_circuit* c) { delete c; return 0; }
 extern "C" int dctfhe_circuit_io(dctfhe_circuit* c, int64_t* n_in, int64_t* n_out) {
-  const TensorShape& a = c->tensors[c->input_tensor];
-  const TensorShape& b = c->tensors[c->output_tensor];
-  *n_in = (int64_t)a.C * a.H * a.W;
-  *n_out = (int64_t)b.C * b.H * b.W;
+  *n_in = (int64_t)c->tensors[c->input_tensor].elems();
+  *n_out = (int64_t)c->tensors[c->output_tensor].elems();
   return 0;
 }
 
-extern "C" int dctfhe_circuit_stats(dctfhe_circuit* c, const dctfhe_params* P, dctfhe_stats* s) {
-  memset(s, 0, sizeof *s);
-  s->max_bit_width = c->max_bit_width;
-  s->n_ops = (int)c->ops.size();
-  const double Lb = (P->D + 1) * 8.0;
-  auto elems = [&](int t) { const TensorShape& x = c->tensors[t]; return (double)x.C * x.H * x.W; };
-  auto tier_flops = [&](const dctfhe_tier& t) {
-    const double N = (double)(1 << t.logN), M = N / 2;
-    const double fft = 5.0 * M * std::log2(M);
-    if (t.unroll == 2)   // per PAIR of key bits: the same transforms, three key blocks folded with their monomials (22 + 8 flops per
-                         // point and key polynomial), the monomials themselves (18 per point)
-      return (t.n / 2) * ((t.k + 1) * t.l * fft + (t.k + 1) * fft + (double)(t.k + 1) * (t.k + 1) * t.l * M * 30.0 + M * 18.0);
-    return t.n * ((t.k + 1) * t.l * fft + (t.k + 1) * fft + (double)(t.k + 1) * (t.k + 1) * t.l * M * 8.0);
-  };
-  auto key_bytes = [&](const dctfhe_tier& t) {
-    const double N = (double)(1 << t.logN);
-    return (double)(t.unroll == 2 ? 3 * t.n / 2 : t.n) * t.l * (t.k + 1) * (t.k + 1) * N * 8.0 + (double)P->D * t.lk * (t.n + 1) * 8.0;
-  };
-  for (const Op& o : c->ops) {
-    const double ein = elems(o.src0), eout = elems(o.dst);
-    switch (o.type) {
-      case OP_CONV: {
-        const TensorShape& a = c->tensors[o.src0];
-        s->conv_macs += (int64_t)(eout * a.C * o.ip[1] * o.ip[2]);
-        s->bytes_algorithmic += (ein + eout) * Lb;
-        break;
-      }
-      case OP_ADD: s->bytes_algorithmic += 3 * eout * Lb; break;
-      case OP_SUMPOOL: s->bytes_algorithmic += (ein + eout) * Lb; break;
-      case OP_LUT: {
-        const int r = lut_steps(o), tt = o.ip[4];     // approximate rounding: no one-bit steps; parity split: one more
-        s->lut_sites += (int64_t)ein;
-        s->bit_steps += (int64_t)(ein * r);
-        s->bytes_algorithmic += 2 * ein * Lb * (1 + r);
-        if (tt >= 0 && tt < P->n_tiers) {
-          s->pbs_count[tt] += (int64_t)ein; s->ks_count[tt] += (int64_t)ein;
-          s->flops_f64 += ein * tier_flops(P->tiers[tt]);
-          s->key_bytes_per_pass += key_bytes(P->tiers[tt]);
-        }
-        const StepTiers stp = step_tiers_of(o);
-        for (int st = 0; st < r; st++) {
-          const int b2 = stp.at(st);
-          if (b2 < 0 || b2 >= P->n_tiers) continue;
-          s->pbs_count[b2] += (int64_t)ein; s->ks_count[b2] += (int64_t)ein;
-          s->flops_f64 += ein * tier_flops(P->tiers[b2]);
-          s->key_bytes_per_pass += key_bytes(P->tiers[b2]);
-        }
-        if (lut_is_split(o)) {
-          // the parity bootstrap (tier of the last step, its small ciphertext: no key switch) and the second look-up with its key switch
-          const int pt = stp.at(r - 1), t2 = (tt >= 0 && tt < P->n_tiers) ? (o.ip[9] == LUT_SPLIT_QUIET ? P->tiers[tt].ksk_share : tt) : -1;
-          if (pt >= 0 && pt < P->n_tiers) { s->pbs_count[pt] += (int64_t)ein; s->flops_f64 += ein * tier_flops(P->tiers[pt]); }
-          if (t2 >= 0 && t2 < P->n_tiers) {
-            s->pbs_count[t2] += (int64_t)ein; s->ks_count[t2] += (int64_t)ein;
-            s->flops_f64 += ein * tier_flops(P->tiers[t2]);
-            s->key_bytes_per_pass += key_bytes(P->tiers[t2]);
-          }
-          s->bytes_algorithmic += 4 * ein * Lb;
-        }
-        break;
-      }
-      case OP_MAXPOOL: {
-        const TensorShape& a = c->tensors[o.src0];
-        const double n = (double)pool_pairs(a.C, a.H, a.W, o.ip[0], o.ip[1], o.ip[2]);
-        const int tt = o.ip[4];
-        s->bytes_algorithmic += (ein + 3 * n) * Lb;     // gathers, and two rows read per difference
-        if (tt >= 0 && tt < P->n_tiers) {
-          s->pbs_count[tt] += (int64_t)n; s->ks_count[tt] += (int64_t)n;
-          s->flops_f64 += n * tier_flops(P->tiers[tt]);
-          s->key_bytes_per_pass += key_bytes(P->tiers[tt]);
-        }
-        break;
-      }
-      default: break;
-    }
-  }
-  return 0;
-}
+extern "C" int dctfhe_circuit_stats(dctfhe_circuit* c, const dctfhe_params* P, dctfhe_stats* s) { return circuit_stats(*c, *P, s); }
 
 // ------------------------------------------------------------------------------------------ session
-extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctfhe_keys* keys, int batch, dctfhe_session** out) {
-  if (batch < 1) return fail("batch must be >= 1");
-  HIPCHK(hipSetDevice(ctx->device));
-  std::unique_ptr<dctfhe_session> s(new dctfhe_session);
-  s->ctx = ctx; s->circ = circ; s->keys = keys; s->batch = batch;
-  s->D = keys ? keys->p.D : 0;
-  // validate tiers named by the circuit
-  if (keys)
-    for (size_t i = 0; i < circ->ops.size(); i++) {
-      const Op& o = circ->ops[i];
-      if (o.type == OP_MAXPOOL) {
-        if (o.ip[4] >= keys->p.n_tiers) return fail("op %zu names a tier the keys lack", i);
-        if (o.ip[5] > keys->p.tiers[o.ip[4]].logN - 1) return fail("op %zu: max-pool table of 2^%d entries does not fit tier %d", i, o.ip[5], o.ip[4]);
-        continue;
-      }
-      if (o.type != OP_LUT) continue;
-      const int tt = o.ip[4], bt = o.ip[5], r = lut_steps(o), w = o.ip[2] - (lut_is_split(o) ? 1 : 0);
-      if (tt < 0 || tt >= keys->p.n_tiers || (r > 0 && (bt < 0 || bt >= keys->p.n_tiers))) return fail("op %zu names a tier the keys lack", i);
-      if (w > keys->p.tiers[tt].logN - 1) return fail("op %zu: table of 2^%d entries does not fit tier %d", i, w, tt);
-      if (o.ip[9] == LUT_SPLIT_QUIET) {
-        const int t2 = keys->p.tiers[tt].ksk_share;
-        if (t2 < 0 || t2 >= keys->p.n_tiers) return fail("op %zu: parity split on the quiet twin, but tier %d shares no key-switch key", i, tt);
-        if (w > keys->p.tiers[t2].logN - 1) return fail("op %zu: table of 2^%d entries does not fit tier %d", i, w, t2);
-      }
-      const StepTiers stp = step_tiers_of(o);
-      for (int st = 0; st < r; st++)
-        if (stp.at(st) < 0 || stp.at(st) >= keys->p.n_tiers) return fail("op %zu names a coarse bit tier the keys lack", i);
+// 1. every tier the circuit bootstraps on exists in the keys, and its tables fit that tier's ring
+static int session_check_keys(dctfhe_session* s) {
+  const dctfhe_params& P = s->keys->p;
+  auto lacks = [&](int t) { return t < 0 || t >= P.n_tiers; };
+  for (size_t i = 0; i < s->circ->ops.size(); i++) {
+    const SiteOp& o = s->circ->ops[i];
+    const LutSite& L = o.lut;
+    const bool pool = o.type == OP_MAXPOOL;
+    if (o.type == OP_LUT) {
+      if (lacks(L.tab_tier) || (L.n_steps() > 0 && lacks(L.steps.bit))) return fail("op %zu names a tier the keys lack", i);
+      if (L.mode == LUT_SPLIT_QUIET && lacks(L.tier2(P))) return fail("op %zu: parity split on the quiet twin, but tier %d shares no key-switch key", i, L.tab_tier);
     }
-  if (keys && !circ->conv_slab.d) {
-    // the matrix-core form of the convolution weights, once per circuit and only for encrypted evaluation (clear mode runs the VALU
-    // kernel), in one allocation
-    std::vector<const int8_t*> cw(circ->ops.size(), nullptr);
-    for (size_t i = 0; i < circ->ops.size(); i++)
-      if (i < circ->conv_w.size() && !circ->conv_w[i].empty()) cw[i] = circ->conv_w[i].data();
-    CHK(build_conv_packs(cw, circ->conv_geom, &circ->conv_slab, &circ->conv));
+    int err = 0;
+    for_each_bootstrap(o, P, [&](int t, int bits, bool) {
+      if (err) return;
+      if (lacks(t)) err = fail(pool ? "op %zu names a tier the keys lack" : "op %zu names a coarse bit tier the keys lack", i);
+      else if (bits > P.tiers[t].logN - 1) err = fail("op %zu: %stable of 2^%d entries does not fit tier %d", i, pool ? "max-pool " : "", bits, t);
+    });
+    CHK(err);
   }
-  // tensor liveness: free a buffer after its last reader; reuse freed buffers of sufficient size
+  return 0;
+}
+
+// 2. the matrix-core form of the convolution weights, once per circuit and only for encrypted evaluation (clear mode runs the VALU
+// kernel), in one allocation
+static int session_conv_packs(dctfhe_session* s) {
+  dctfhe_circuit* circ = s->circ;
+  std::vector<const int8_t*> cw;
+  std::vector<ConvSite> cg;
+  for (size_t i = 0; i < circ->ops.size(); i++) {
+    cw.push_back(circ->conv_w[i].empty() ? nullptr : circ->conv_w[i].data());
+    cg.push_back(circ->ops[i].conv);
+  }
+  return circ->conv_slab.d ? 0 : build_conv_packs(cw, cg, &circ->conv_slab, &circ->conv);
+}
+
+// 3. row layout per tensor.  Encrypted: a tensor is stored at its effective dimension -- the compiler's `deff_in` of the consuming op
+// (mask words beyond it are zero in every ciphertext of the tensor); the output of a look-up is as wide as its table tier's ring, or as
+// the rounding chain that works in place on it.  75 % of a ResNet tensor used to be stored, written and streamed zeros.
+static int session_row_layout(dctfhe_session* s) {
+  const dctfhe_circuit* circ = s->circ;
+  const dctfhe_keys* keys = s->keys;
   const int nt = (int)circ->tensors.size();
+  s->t_L.assign(nt, 1);
+  s->t_deff.assign(nt, 0);
+  if (!keys) return 0;
+  const size_t D = (size_t)s->D;
+  // (the matrix-core key switch walks the key in steps of 64 rows: an effective dimension it cannot take is kept at full width)
+  // ... and the integer-VALU key switch (betak = 8, or a key the matrix-core tiling does not cover) walks whole rows of D words: a
+  // circuit that uses such a tier keeps every tensor at full width
+  bool all_mfma = true;
+  for (const SiteOp& o : circ->ops)
+    for_each_bootstrap(o, keys->p, [&](int t, int, bool) { all_mfma = all_mfma && keys->tiers[t].d_kskT != nullptr; });
+  auto clampd = [&](int d) { return (size_t)((all_mfma && d > 0 && (size_t)d < D && d % 64 == 0) ? d : D); };
+  std::vector<char> known(nt, 0);
+  auto set = [&](int t, size_t deff, size_t width) { s->t_deff[t] = deff; s->t_L[t] = (all_mfma ? std::max(deff, width) : D) + 1; known[t] = 1; };
+  for (const SiteOp& o : circ->ops)
+    if (o.src0 == circ->input_tensor) { set(circ->input_tensor, clampd(o.deff_in), 0); break; }
+  if (!known[circ->input_tensor]) set(circ->input_tensor, D, 0);
+  for (size_t i = 0; i < circ->ops.size(); i++) {
+    const SiteOp& o = circ->ops[i];
+    if (!known[o.src0] || (o.type == OP_ADD && !known[o.src1])) return fail("op %zu reads a tensor no earlier op wrote", i);
+    if (o.type == OP_LUT) {
+      const LutSite& L = o.lut;
+      size_t ring = ring_of(keys, L.tab_tier);
+      if (L.split()) ring = std::max(ring, ring_of(keys, L.tier2(keys->p)));      // the sum of both look-ups: as wide as the wider ring
+      if (clampd(L.deff_in) < s->t_deff[o.src0]) return fail("op %zu: look-up compiled for effective dimension %d, its input has %zu", i, L.deff_in, s->t_deff[o.src0]);
+      const size_t chain = L.n_steps() > 0 ? (size_t)round_chain_deff(keys, (int)clampd(L.deff_in), L) : 0;
+      set(o.dst, ring, chain);
+    } else if (o.type == OP_MAXPOOL) {      // the relu bootstraps accumulate into the first kN words of copies of the input
+      set(o.dst, std::max(s->t_deff[o.src0], ring_of(keys, o.pool.tier)), 0);
+    } else if (o.type == OP_ADD) {
+      set(o.dst, std::max(s->t_deff[o.src0], s->t_deff[o.src1]), 0);
+    } else {
+      set(o.dst, s->t_deff[o.src0], 0);
+    }
+  }
+  return 0;
+}
+
+// 4. device buffers.  Tensor liveness: free a buffer after its last reader; reuse freed buffers of sufficient size
+static int session_plan_buffers(dctfhe_session* s) {
+  const dctfhe_circuit* circ = s->circ;
+  const bool keys = s->keys != nullptr;
+  const int nt = (int)circ->tensors.size(), batch = s->batch;
   std::vector<int> last_use(nt, -1);
   for (int i = 0; i < (int)circ->ops.size(); i++) {
-    const Op& o = circ->ops[i];
+    const SiteOp& o = circ->ops[i];
     last_use[o.src0] = i;
     if (o.type == OP_ADD) last_use[o.src1] = i;
   }
@@ -2051,61 +1859,9 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   last_use[circ->input_tensor] = 1 << 30;
   s->d_tensor.assign(nt, nullptr);
   s->tensor_words.assign(nt, 0);
-  // row layout per tensor.  Encrypted: a tensor is stored at its effective dimension -- the compiler's `deff` (ip[10] of the
-  // consuming / producing op: mask words beyond it are zero in every ciphertext of the tensor); the output of a look-up is as
-  // wide as its table tier's ring, or as the rounding chain that works in place on it.  75 % of a ResNet tensor used to be
-  // stored, written and streamed zeros.
-  s->t_L.assign(nt, 1);
-  s->t_deff.assign(nt, 0);
-  if (keys) {
-    const size_t D = (size_t)s->D;
-    // (the matrix-core key switch walks the key in steps of 64 rows: an effective dimension it cannot take is kept at full width)
-    // ... and the integer-VALU key switch (betak = 8, or a key the matrix-core tiling does not cover) walks whole rows of D words: a
-    // circuit that uses such a tier keeps every tensor at full width
-    bool all_mfma = true;
-    for (const Op& o : circ->ops) {
-      if (o.type == OP_MAXPOOL) all_mfma = all_mfma && keys->tiers[o.ip[4]].d_kskT != nullptr;
-      if (o.type != OP_LUT) continue;
-      all_mfma = all_mfma && keys->tiers[o.ip[4]].d_kskT != nullptr;
-      const int r = lut_steps(o);
-      if (o.ip[9] == LUT_SPLIT_QUIET) all_mfma = all_mfma && keys->tiers[keys->p.tiers[o.ip[4]].ksk_share].d_kskT != nullptr;
-      const StepTiers stp = step_tiers_of(o);
-      for (int st_i = 0; st_i < r; st_i++) all_mfma = all_mfma && keys->tiers[stp.at(st_i)].d_kskT != nullptr;
-    }
-    auto clampd = [&](int d) { return (size_t)((all_mfma && d > 0 && (size_t)d < D && d % 64 == 0) ? d : D); };
-    std::vector<char> known(nt, 0);
-    auto set = [&](int t, size_t deff, size_t width) { s->t_deff[t] = deff; s->t_L[t] = (all_mfma ? std::max(deff, width) : D) + 1; known[t] = 1; };
-    for (const Op& o : circ->ops)
-      if (o.src0 == circ->input_tensor) { set(circ->input_tensor, clampd(o.ip[10]), 0); break; }
-    if (!known[circ->input_tensor]) set(circ->input_tensor, D, 0);
-    for (size_t i = 0; i < circ->ops.size(); i++) {
-      const Op& o = circ->ops[i];
-      if (!known[o.src0] || (o.type == OP_ADD && !known[o.src1])) return fail("op %zu reads a tensor no earlier op wrote", i);
-      if (o.type == OP_LUT) {
-        const int r = lut_steps(o), tt = o.ip[4];
-        size_t ring = (size_t)keys->p.tiers[tt].k << keys->p.tiers[tt].logN;
-        if (o.ip[9] == LUT_SPLIT_QUIET) {      // the sum of both look-ups: as wide as the wider ring
-          const dctfhe_tier& q = keys->p.tiers[keys->p.tiers[tt].ksk_share];
-          ring = std::max(ring, (size_t)q.k << q.logN);
-        }
-        if (clampd(o.ip[10]) < s->t_deff[o.src0]) return fail("op %zu: look-up compiled for effective dimension %d, its input has %zu", i, o.ip[10], s->t_deff[o.src0]);
-        const size_t chain = r > 0 ? (size_t)round_chain_deff(keys, (int)clampd(o.ip[10]), step_tiers_of(o), r) : 0;
-        set(o.dst, ring, chain);
-      } else if (o.type == OP_MAXPOOL) {      // the relu bootstraps accumulate into the first kN words of copies of the input
-        const size_t ring = (size_t)keys->p.tiers[o.ip[4]].k << keys->p.tiers[o.ip[4]].logN;
-        set(o.dst, std::max(s->t_deff[o.src0], ring), 0);
-      } else if (o.type == OP_ADD) {
-        set(o.dst, std::max(s->t_deff[o.src0], s->t_deff[o.src1]), 0);
-      } else {
-        set(o.dst, s->t_deff[o.src0], 0);
-      }
-    }
-  }
-  for (int t = 0; t < nt; t++) {
-    const TensorShape& x = circ->tensors[t];
-    s->tensor_words[t] = (size_t)batch * x.C * x.H * x.W * s->t_L[t];
-  }
+  for (int t = 0; t < nt; t++) s->tensor_words[t] = (size_t)batch * circ->tensors[t].elems() * s->t_L[t];
   std::vector<std::pair<size_t, uint64_t*>> freelist;
+  std::map<uint64_t*, size_t> cap;      // what each allocation holds
   auto get = [&](size_t words, uint64_t** p) -> int {
     int best = -1;
     for (int i = 0; i < (int)freelist.size(); i++)
@@ -2113,33 +1869,28 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
     if (best >= 0) { *p = freelist[best].second; freelist.erase(freelist.begin() + best); return 0; }
     HIPCHK(hipMalloc(p, words * 8));
     s->owned.push_back({words, *p});
+    cap[*p] = words;
     return 0;
   };
-  std::map<uint64_t*, size_t> cap;
-  auto alloc_t = [&](int t) -> int {
-    if (s->d_tensor[t]) return 0;
-    uint64_t* p = nullptr;
-    CHK(get(s->tensor_words[t], &p));
-    s->d_tensor[t] = p;
-    if (!cap.count(p)) cap[p] = s->tensor_words[t];
-    return 0;
-  };
+  auto alloc_t = [&](int t) -> int { return s->d_tensor[t] ? 0 : get(s->tensor_words[t], &s->d_tensor[t]); };
+  auto give_back = [&](uint64_t* p) { if (p) freelist.push_back({cap[p], p}); };
   CHK(alloc_t(circ->input_tensor));
   s->pool.resize(circ->ops.size());
   s->pool_buf.assign(circ->ops.size(), {nullptr, nullptr});
   for (int i = 0; i < (int)circ->ops.size(); i++) {
-    const Op& o = circ->ops[i];
+    const SiteOp& o = circ->ops[i];
+    const TensorShape& a = circ->tensors[o.src0];
     CHK(alloc_t(o.dst));
     if (o.type == OP_MAXPOOL) {
-      // the tree's level buffers (encrypted) or the row pass's output (clear), held for this op only: back to the free list after it
-      const TensorShape& a = circ->tensors[o.src0];
+      // the tree's level buffers (encrypted) or the row pass's output (clear)
+      const PoolSite& S = o.pool;
       size_t words[2] = {0, 0};
       if (keys) {
         s->pool[i].reset(new PoolPlan);
-        CHK(pool_plan(batch, a.C, a.H, a.W, o.ip[0], o.ip[1], o.ip[2], s->pool[i].get()));
+        CHK(pool_plan(batch, a.C, a.H, a.W, S.k, S.stride, S.pad, s->pool[i].get()));
         for (int b = 0; b < 2; b++) words[b] = s->pool[i]->rows_buf[b] * s->t_L[o.dst];
       } else {
-        words[0] = (size_t)batch * a.C * a.H * pool_out_size(a.W, o.ip[0], o.ip[1], o.ip[2]);
+        words[0] = (size_t)batch * a.C * a.H * pool_out_size(a.W, S.k, S.stride, S.pad);
       }
       for (int b = 0; b < 2; b++) {
         if (!words[b]) continue;
@@ -2151,44 +1902,50 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
           return fail("op %d: the max pool's level buffer needs %.1f GB, %.1f GB of device memory are free (batch %d too large for one device)", i,
                       words[b] * 8e-9, fr * 1e-9, batch);
         CHK(get(words[b], &s->pool_buf[i][b]));
-        if (!cap.count(s->pool_buf[i][b])) cap[s->pool_buf[i][b]] = words[b];
       }
-      for (int b = 0; b < 2; b++)
-        if (s->pool_buf[i][b]) freelist.push_back({cap[s->pool_buf[i][b]], s->pool_buf[i][b]});
     }
-    if (o.type == OP_LUT && keys && lut_is_split(o)) {
-      // the second work buffer of a parity-split site, chunk-sized: the parity bootstrap's output, then the second look-up's.  Held for
-      // this op only, like the level buffers of a max pool
-      const TensorShape& a = circ->tensors[o.src0];
-      const size_t rows = std::min<size_t>((size_t)batch * a.C * a.H * a.W, 16384);      // the look-up scratch's chunk is at most that
-      const size_t words = rows * s->t_L[o.dst];
-      CHK(get(words, &s->pool_buf[i][0]));
-      if (!cap.count(s->pool_buf[i][0])) cap[s->pool_buf[i][0]] = words;
-      freelist.push_back({cap[s->pool_buf[i][0]], s->pool_buf[i][0]});
+    if (o.type == OP_LUT && keys && o.lut.split()) {
+      // the second work buffer of a parity-split site: the parity bootstrap's output, then the second look-up's; chunk-sized (the
+      // look-up scratch's chunk is at most 16384)
+      const size_t rows = std::min<size_t>((size_t)batch * a.elems(), 16384);
+      CHK(get(rows * s->t_L[o.dst], &s->pool_buf[i][0]));
     }
-    auto release = [&](int t) {
-      if (last_use[t] == i && t != o.dst && s->d_tensor[t]) freelist.push_back({cap[s->d_tensor[t]], s->d_tensor[t]});
-    };
+    for (uint64_t* p : s->pool_buf[i]) give_back(p);      // held for this op only: back to the free list after it
+    auto release = [&](int t) { if (last_use[t] == i && t != o.dst) give_back(s->d_tensor[t]); };
     release(o.src0);
     if (o.type == OP_ADD && o.src1 != o.src0) release(o.src1);
   }
-  if (keys) {
-    size_t maxe = 1;
-    for (size_t i = 0; i < circ->ops.size(); i++) {
-      const Op& o = circ->ops[i];
-      if (o.type == OP_LUT) { const TensorShape& x = circ->tensors[o.src0]; maxe = std::max(maxe, (size_t)batch * x.C * x.H * x.W); }
-      if (o.type == OP_MAXPOOL) for (const PoolLevel& l : s->pool[i]->lv) maxe = std::max(maxe, l.pairs);
-    }
-    LutScratchOwner sc;
-    CHK(alloc_lut_scratch(keys, std::min<size_t>(maxe, 16384), &sc.s));
-    s->chunk = sc.s.chunk; s->d_digits = sc.s.digits; s->d_bodies = sc.s.bodies; s->d_small = sc.s.small; s->d_bit_tables = sc.s.bit_tables;
-    sc.s = LutScratch{};      // the session owns them now
+  return 0;
+}
+
+// 5. the look-up scratch: one chunk as large as the largest batch of bootstraps, at most 16384
+static int session_lut_scratch(dctfhe_session* s) {
+  const dctfhe_circuit* circ = s->circ;
+  size_t maxe = 1;
+  for (size_t i = 0; i < circ->ops.size(); i++) {
+    const SiteOp& o = circ->ops[i];
+    if (o.type == OP_LUT) maxe = std::max(maxe, (size_t)s->batch * circ->tensors[o.src0].elems());
+    if (o.type == OP_MAXPOOL) for (const PoolLevel& l : s->pool[i]->lv) maxe = std::max(maxe, l.pairs);
   }
+  return alloc_lut_scratch(s->keys, std::min<size_t>(maxe, 16384), &s->lut.s);
+}
+
+extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctfhe_keys* keys, int batch, dctfhe_session** out) {
+  if (batch < 1) return fail("batch must be >= 1");
+  HIPCHK(hipSetDevice(ctx->device));
+  std::unique_ptr<dctfhe_session> s(new dctfhe_session);
+  s->ctx = ctx; s->circ = circ; s->keys = keys; s->batch = batch;
+  s->D = keys ? keys->p.D : 0;
+  if (keys) CHK(session_check_keys(s.get()));
+  if (keys) CHK(session_conv_packs(s.get()));
+  CHK(session_row_layout(s.get()));
+  CHK(session_plan_buffers(s.get()));
+  if (keys) CHK(session_lut_scratch(s.get()));
   HIPCHK(hipMalloc(&s->d_overflow, sizeof(int)));
   HIPCHK(hipMemset(s->d_overflow, 0, sizeof(int)));
   if (keys) {
     dctfhe_stats stt;
-    dctfhe_circuit_stats(circ, &keys->p, &stt);
+    circuit_stats(*circ, keys->p, &stt);
     for (int i = 0; i < DCTFHE_MAX_TIERS; i++) s->pbs_per_image[i] = stt.pbs_count[i];
   }
   *out = s.release();
@@ -2314,18 +2071,19 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
   const hipEvent_t e0 = tm.take(), e1 = tm.take();
   HIPCHK(hipEventRecord(e0, st));
   if (timing) memset(timing, 0, sizeof *timing);
-  LutScratch sc{s->d_digits, s->d_bodies, s->d_small, s->d_bit_tables, s->chunk};
+  const LutScratch& sc = s->lut.s;
   for (size_t i = 0; i < c->ops.size(); i++) {
-    const Op& o = c->ops[i];
+    const SiteOp& o = c->ops[i];
     const TensorShape& a = c->tensors[o.src0];
     const TensorShape& d = c->tensors[o.dst];
     uint64_t* src = s->d_tensor[o.src0];
     uint64_t* dst = s->d_tensor[o.dst];
     const size_t Ls = s->t_L[o.src0], Ld = s->t_L[o.dst], ds = s->t_deff[o.src0];
+    const double sg = i < s->sim_sigma.size() ? s->sim_sigma[i] : 0.0;      // clear mode: the noise `simulate` injects at this op
     switch (o.type) {
       case OP_CONV: {
         const int h = tm.begin(CAT_LINEAR);
-        CHK(dev_conv2d(st, src, B, a.C, a.H, a.W, Ls, ds, (const int8_t*)c->d_payload[i], &c->conv[i], o.ip[0], o.ip[1], o.ip[2], o.ip[3], o.ip[4], dst, Ld));
+        CHK(dev_conv2d(st, src, B, a.C, a.H, a.W, Ls, ds, (const int8_t*)c->d_payload[i], &c->conv[i], o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride, o.conv.pad, dst, Ld));
         tm.end(h);
         break;
       }
@@ -2341,74 +2099,58 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
       case OP_SUMPOOL: {
         const int h = tm.begin(CAT_LINEAR);
         const size_t tw = s->tensor_words[o.dst];
-        hipLaunchKernelGGL(k_sum_pool, dim3(ew_grid(tw)), dim3(256), 0, st, src, a.C, a.H, a.W, Ls, ds, o.ip[0], d.H, d.W, dst, Ld, tw);
+        hipLaunchKernelGGL(k_sum_pool, dim3(ew_grid(tw)), dim3(256), 0, st, src, a.C, a.H, a.W, Ls, ds, o.sum_k, d.H, d.W, dst, Ld, tw);
         HIPCHK(hipGetLastError());
         tm.end(h);
         break;
       }
       case OP_LUT: {
-        const int p = o.ip[0], r = o.ip[1], w = o.ip[2], shift = o.ip[3], tt = o.ip[4], bt = o.ip[5], nchan = o.ip[6];
-        const size_t E = (size_t)B * a.C * a.H * a.W;
-        const uint64_t body_add = (uint64_t)o.lp[0];
+        const LutSite& L = o.lut;
+        const size_t E = (size_t)B * a.elems();
         const int hw = a.H * a.W;
+        const int64_t* halves = c->d_split[i];      // [S | Dt] of a parity split, else nullptr
+        const int64_t* half_d = halves ? halves + ((size_t)L.ntab << (L.w - 1)) : nullptr;
         if (!K) {
-          const double sg = i < s->sim_sigma.size() ? s->sim_sigma[i] : 0.0;
           const double sg2 = (i < s->sim_sigma2.size() && s->sim_sigma2[i] > 0) ? s->sim_sigma2[i] : sg;
-          const int split = lut_is_split(o);
-          const int64_t* halves = c->d_split[i];
-          hipLaunchKernelGGL(k_lut_clear, dim3(ew_grid(E)), dim3(256), 0, st, src, dst, E, shift, body_add, p, r, w, (const int64_t*)c->d_payload[i],
-                             hw, nchan, s->d_overflow, sg, rng_key{{(uint32_t)s->sim_seed, (uint32_t)(s->sim_seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}},
-                             (uint64_t)(0x51D0000 + (s->sim_run << 12) + i), (int)(o.ip[9] == LUT_APPROX), split, sg2, halves,
-                             halves ? halves + ((size_t)nchan << (w - 1)) : nullptr);
+          hipLaunchKernelGGL(k_lut_clear, dim3(ew_grid(E)), dim3(256), 0, st, src, dst, E, L.shift, L.body_add, L.p, L.r, L.w, (const int64_t*)c->d_payload[i],
+                             hw, L.ntab, s->d_overflow, sg, rng_key{{(uint32_t)s->sim_seed, (uint32_t)(s->sim_seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}},
+                             (uint64_t)(0x51D0000 + (s->sim_run << 12) + i), (int)L.approx(), (int)L.split(), sg2, halves, half_d);
           HIPCHK(hipGetLastError());
         } else {
-          // exact rounding: + half of what is removed, then r one-bit steps clear the low bits, in place on a shifted copy of the
-          // input.  Approximate rounding (ip[9], the reference README's {"method": "approximate"}): no steps -- the low bits stay
-          // and the half-box rotation of the test vector does the rounding; + half an input unit puts the two inputs next to a
-          // rounding boundary at equal distance from it.  Without steps nothing is copied: the key switch reads the input tensor.
-          const bool approx = o.ip[9] == LUT_APPROX && r > 0;
-          const int steps = lut_steps(o);      // one-bit steps on the working copy: the r rounding steps, + 1 for a parity split
-          const uint64_t add = body_add + (approx ? (1ULL << (62 - p)) : (r > 0 ? (1ULL << (63 - p + r - 1)) : 0));
+          // the one-bit steps clear the low bits in place on a shifted copy of the input (+ LutSite::round_add).  Approximate rounding (the
+          // reference README's {"method": "approximate"}): no steps, and without steps nothing is copied: the key switch reads the input.
           int deff = (int)ds;
-          if (steps > 0) {
-            const StepTiers stp = step_tiers_of(o);
-            deff = round_chain_deff(K, (int)ds, stp, steps);
+          if (L.n_steps() > 0) {
+            deff = round_chain_deff(K, (int)ds, L);
             // the work row: the first deff mask words and the body.  What lies between deff and the end of the row is left alone when
-            // every key switch of the chain narrows to deff (the table bootstrap that ends the site rewrites the row); a key switch
+            // every key switch of the site narrows to deff (the table bootstrap that ends the site rewrites the row); a key switch
             // that cannot narrow reads the whole row, so those words are zeroed (they used to be whatever the recycled
             // buffer held)
-            bool narrow = ks_narrows(K, tt, deff);
-            for (int st_i = 0; st_i < steps; st_i++) narrow = narrow && ks_narrows(K, stp.at(st_i), deff);
-            if (o.ip[9] == LUT_SPLIT_QUIET) narrow = narrow && ks_narrows(K, K->p.tiers[tt].ksk_share, deff);
+            bool narrow = true;
+            for_each_bootstrap(L, K->p, [&](int tier, int, bool) { narrow = narrow && ks_narrows(K, tier, deff); });
             const size_t fill = narrow ? (size_t)deff : Ld - 1;
             const int h = tm.begin(CAT_LINEAR);
-            hipLaunchKernelGGL(k_affine, dim3(ew_grid(E * (fill + 1))), dim3(256), 0, st, src, Ls, ds, dst, Ld, E, fill, shift, add);
+            hipLaunchKernelGGL(k_affine, dim3(ew_grid(E * (fill + 1))), dim3(256), 0, st, src, Ls, ds, dst, Ld, E, fill, L.shift, L.round_add());
             HIPCHK(hipGetLastError());
             tm.end(h);
           }
-          LutSplit sp;
-          if (lut_is_split(o)) {
-            sp.tier2 = o.ip[9] == LUT_SPLIT_QUIET ? K->p.tiers[tt].ksk_share : tt;
-            sp.par = s->pool_buf[i][0]; sp.Lp = Ld;
-            sp.tab_s = c->d_split[i]; sp.tab_d = c->d_split[i] + ((size_t)nchan << (w - 1));
-          }
-          CHK(dev_round_lut(K, step_tiers_of(o), tt, src, Ls, shift, add, dst, Ld, E, p, approx ? 0 : r, (const int64_t*)c->d_payload[i], w, nullptr, hw, nchan, sc,
-                            &tm, deff, &sp));
+          LutRows rows;
+          rows.src = src; rows.Ls = Ls; rows.work = dst; rows.Lw = Ld; rows.par = s->pool_buf[i][0]; rows.Lp = Ld;
+          rows.tables = (const int64_t*)c->d_payload[i]; rows.tab_s = halves; rows.tab_d = half_d;
+          CHK(dev_round_lut(K, L, rows, E, hw, sc, &tm, deff));
         }
         break;
       }
       case OP_MAXPOOL: {
-        const int k = o.ip[0], sp = o.ip[1], pad = o.ip[2], shift = o.ip[3], tt = o.ip[4], pd = o.ip[5];
-        const uint64_t body_add = (uint64_t)o.lp[0];
+        const PoolSite& S = o.pool;
         if (!K) {
-          const double sg = i < s->sim_sigma.size() ? s->sim_sigma[i] : 0.0;
           const int h = tm.begin(CAT_LINEAR);
-          CHK(clear_max_pool(st, src, s->pool_buf[i][0], dst, B, a.C, a.H, a.W, k, sp, pad, shift, body_add, pd, (const int64_t*)c->d_payload[i], sg,
+          CHK(clear_max_pool(st, src, s->pool_buf[i][0], dst, B, a.C, a.H, a.W, S.k, S.stride, S.pad, S.shift, S.body_add, S.p_d, (const int64_t*)c->d_payload[i], sg,
                              s->sim_seed, (1ULL << 40) | ((uint64_t)(0x51D0000 + (s->sim_run << 12) + i) << 1)));
           tm.end(h);
         } else {
           uint64_t* const bufs[2] = {s->pool_buf[i][0], s->pool_buf[i][1]};
-          CHK(dev_max_pool(K, tt, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], shift, body_add, (const int64_t*)c->d_payload[i], pd, sc, &tm));
+          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], (const int64_t*)c->d_payload[i], sc, &tm));
         }
         break;
       }

@@ -62,6 +62,10 @@ struct DevBuf {
   DevBuf& operator=(const DevBuf&) = delete;
   ~DevBuf() { if (p) hipFree(p); }
   hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+  hipError_t upload(const void* host, size_t bytes) {      // alloc + blocking copy of a host operand
+    const hipError_t e = alloc(bytes);
+    return e != hipSuccess ? e : hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+  }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
@@ -600,6 +604,13 @@ static size_t tier_bsk_elems(const dctfhe_tier& t) {   // complex values of the 
   return tier_bsk_blocks(t) * (size_t)(t.k + 1) * t.l * (t.k + 1) * ((size_t)1 << (t.logN - 1));
 }
 static size_t tier_ksk_words(const dctfhe_params& p, const dctfhe_tier& t) { return (size_t)p.D * t.lk * (t.n + 1); }
+// standard domain: a block is (k+1) l rows of k mask polynomials and a body polynomial; the compressed forms keep the bodies only
+static size_t tier_bsk_body_words(const dctfhe_tier& t) { return tier_bsk_blocks(t) * (size_t)(t.k + 1) * t.l << t.logN; }
+// blocks per pass through a 64 MB staging buffer that holds `polys` polynomials per row
+static int tier_bsk_chunk(const dctfhe_tier& t, int polys) {
+  const size_t block_bytes = ((size_t)(t.k + 1) * t.l * polys << t.logN) * 8;
+  return std::max(1, (int)std::min(tier_bsk_blocks(t), ((size_t)64 << 20) / block_bytes));
+}
 
 // allocate every array of the evaluation keys and fill what depends on the parameters only (twiddles, root tables)
 static int eval_alloc(dctfhe_ctx* ctx, const dctfhe_params* params, std::unique_ptr<dctfhe_eval_keys>& E) {
@@ -704,8 +715,7 @@ extern "C" int dctfhe_eval_keys_generate(dctfhe_client_key* C, dctfhe_eval_keys*
     }
     const int N = 1 << t.logN, M = N / 2;
     const size_t per_bit_polys = (size_t)(t.k + 1) * t.l * (t.k + 1);
-    const int blocks = (int)tier_bsk_blocks(t);
-    const int chunk = std::max(1, (int)std::min<size_t>(blocks, ((size_t)64 << 20) / (per_bit_polys * N * 8)));
+    const int blocks = (int)tier_bsk_blocks(t), chunk = tier_bsk_chunk(t, t.k + 1);
     DevBuf d_std;
     HIPCHK(d_std.alloc((size_t)chunk * per_bit_polys * N * 8));
     for (int i0 = 0; i0 < blocks; i0 += chunk) {
@@ -780,7 +790,7 @@ static size_t eval_cblob_size(const dctfhe_params& p) {
   for (int ti = 0; ti < p.n_tiers; ti++) {
     const dctfhe_tier& t = p.tiers[ti];
     if (t.ksk_share < 0) n += (size_t)p.D * t.lk * 8;
-    n += tier_bsk_blocks(t) * (t.k + 1) * t.l * ((size_t)1 << t.logN) * 8;
+    n += tier_bsk_body_words(t) * 8;
   }
   return n;
 }
@@ -832,8 +842,7 @@ extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* bu
       q += rows * 8;
     }
     const int N = 1 << t.logN, rows = (t.k + 1) * t.l;
-    const int blocks = (int)tier_bsk_blocks(t);
-    const int chunk = std::max(1, (int)std::min<size_t>(blocks, ((size_t)64 << 20) / ((size_t)rows * N * 8)));
+    const int blocks = (int)tier_bsk_blocks(t), chunk = tier_bsk_chunk(t, 1);
     const uint8_t* bits = t.unroll == 2 ? C->d_spair[ti] : C->d_s;
     DevBuf d_b;
     HIPCHK(d_b.alloc((size_t)chunk * rows * N * 8));
@@ -895,8 +904,7 @@ static int import_compressed(dctfhe_ctx* ctx, const void* buf, size_t size, dctf
     }
     const int N = 1 << t.logN, M = N / 2, rows = (t.k + 1) * t.l;
     const size_t per_bit_polys = (size_t)rows * (t.k + 1);
-    const int blocks = (int)tier_bsk_blocks(t);
-    const int chunk = std::max(1, (int)std::min<size_t>(blocks, ((size_t)64 << 20) / (per_bit_polys * N * 8)));
+    const int blocks = (int)tier_bsk_blocks(t), chunk = tier_bsk_chunk(t, t.k + 1);
     DevBuf d_std, d_b;
     HIPCHK(d_std.alloc((size_t)chunk * per_bit_polys * N * 8));
     HIPCHK(d_b.alloc((size_t)chunk * rows * N * 8));
@@ -923,19 +931,18 @@ extern "C" int dctfhe_eval_keys_decompress_bsk(dctfhe_ctx* ctx, const void* buf,
   for (int ti = 0; ti < tier; ti++) {
     const dctfhe_tier& t = h.params.tiers[ti];
     if (t.ksk_share < 0) q += (size_t)h.params.D * t.lk * 8;
-    q += tier_bsk_blocks(t) * (t.k + 1) * t.l * ((size_t)1 << t.logN) * 8;
+    q += tier_bsk_body_words(t) * 8;
   }
   const dctfhe_tier& t = h.params.tiers[tier];
   if (t.ksk_share < 0) q += (size_t)h.params.D * t.lk * 8;
   HIPCHK(hipSetDevice(ctx->device));
-  const int blocks = (int)tier_bsk_blocks(t);
-  const size_t N = (size_t)1 << t.logN, rows = (size_t)blocks * (t.k + 1) * t.l;
+  const size_t body_bytes = tier_bsk_body_words(t) * 8;
   DevBuf d_b, d_std;
-  HIPCHK(d_b.alloc(rows * N * 8));
-  HIPCHK(d_std.alloc(rows * (t.k + 1) * N * 8));
-  CHK(expand_bsk_chunk(pub, tier, t, 0, blocks, (const uint64_t*)q, d_b.as<uint64_t>(), d_std.as<uint64_t>(), ctx->stream));
+  HIPCHK(d_b.alloc(body_bytes));
+  HIPCHK(d_std.alloc(body_bytes * (t.k + 1)));
+  CHK(expand_bsk_chunk(pub, tier, t, 0, (int)tier_bsk_blocks(t), (const uint64_t*)q, d_b.as<uint64_t>(), d_std.as<uint64_t>(), ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(out, d_std.p, rows * (t.k + 1) * N * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, d_std.p, body_bytes * (t.k + 1), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -984,12 +991,10 @@ extern "C" int dctfhe_client_key_export_bsk(dctfhe_client_key* C, int tier, uint
   if (tier < 0 || tier >= C->p.n_tiers) return fail("tier out of range");
   const dctfhe_tier& t = C->p.tiers[tier];
   HIPCHK(hipSetDevice(C->ctx->device));
-  const int N = 1 << t.logN;
-  const int blocks = (int)tier_bsk_blocks(t);     // unroll 2: the key of the pair secret
-  const size_t words = (size_t)blocks * (t.k + 1) * t.l * (t.k + 1) * N;
+  const size_t words = tier_bsk_body_words(t) * (t.k + 1);
   DevBuf d;
   HIPCHK(d.alloc(words * 8));
-  CHK(gen_bsk_std_chunk(C, tier, 0, blocks, d.as<uint64_t>()));
+  CHK(gen_bsk_std_chunk(C, tier, 0, (int)tier_bsk_blocks(t), d.as<uint64_t>()));     // unroll 2: the key of the pair secret
   HIPCHK(hipStreamSynchronize(C->ctx->stream));
   HIPCHK(hipMemcpy(out, d.p, words * 8, hipMemcpyDeviceToHost));
   return 0;
@@ -1138,16 +1143,24 @@ struct Timers {
 };
 enum { CAT_LINEAR = 100, CAT_KS = 101 };  // 0..7: bootstrap of tier i
 
-// key switch of `count` ciphertexts (D+1 words each) into small ciphertexts of tier `tier`
+// The ciphertexts a key switch reads: rows of L words (body at L-1), shifted left by `shift` with body_add on the body, on the fly.
 // deff: mask words beyond it are known to be zero in every input (0 or >= D: no such knowledge).  The key switch then
 // runs on the first deff rows of the key only -- the same result bit for bit, deff/D of the work.
-static int dev_keyswitch(dctfhe_keys* K, int tier, const uint64_t* d_cts, size_t count, int shift, uint8_t* d_digits, uint64_t* d_bodies,
-                         uint64_t* d_small, Timers* tm, int deff = 0, size_t L = 0, uint64_t body_add = 0, const int32_t* d_ia = nullptr,
-                         const int32_t* d_ib = nullptr, const uint64_t* d_sum = nullptr, size_t L_sum = 0) {
+// Ciphertext c is row c (KS_ROWS), row ia[c] - row ib[c] (KS_DIFF: the pairwise maxima of a max pool) or row c + row c of `rows_b`, rows
+// of Lb words (KS_SUM: the second look-up of a parity-split site): kernels.h ks_src_*.
+enum KsSource { KS_ROWS, KS_DIFF, KS_SUM };
+struct KsInput {
+  const uint64_t* rows = nullptr; size_t L = 0; int deff = 0, shift = 0; uint64_t body_add = 0;
+  KsSource source = KS_ROWS;
+  const int32_t *ia = nullptr, *ib = nullptr;
+  const uint64_t* rows_b = nullptr; size_t Lb = 0;
+};
+// key switch of `count` ciphertexts into small ciphertexts of tier `tier` (sc.small; sc.digits and sc.bodies in between)
+static int dev_keyswitch(dctfhe_keys* K, int tier, const KsInput& in, size_t count, const LutScratch& sc, Timers* tm) {
   const dctfhe_tier& t = K->p.tiers[tier];
   TierKeys& tk = K->tiers[tier];
-  const int D = K->p.D;
-  if (L == 0) L = (size_t)D + 1;                 // row stride of the input ciphertexts (body at L-1); host format by default
+  const int D = K->p.D, deff = in.deff;
+  const size_t L = in.L;                         // row stride of the input ciphertexts (body at L-1)
   const int Dmax = (int)std::min<size_t>(L - 1, (size_t)D);
   hipStream_t st = K->ctx->stream;
   int De = (deff > 0 && deff < Dmax && tk.d_kskT && (deff * t.lk) % 64 == 0) ? deff : Dmax;
@@ -1168,24 +1181,25 @@ static int dev_keyswitch(dctfhe_keys* K, int tier, const uint64_t* d_cts, size_t
   const int h = tm ? tm->begin(CAT_KS) : -1;
   const size_t total = count * (size_t)De;
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
-  if (d_ia)    // ciphertext c is row ia[c] - row ib[c] of d_cts (the pairwise maxima of a max pool)
-    hipLaunchKernelGGL(k_ks_decompose_diff, dim3(grid), dim3(256), 0, st, d_cts, L, d_ia, d_ib, count, De, shift, body_add, t.lk, t.betak, d_digits, d_bodies);
-  else if (d_sum)   // ciphertext c is row c of d_cts + row c of d_sum (rows of L_sum words): the second look-up of a parity-split site
-    hipLaunchKernelGGL(k_ks_decompose_sum, dim3(grid), dim3(256), 0, st, d_cts, L, d_sum, L_sum, L_sum - 1, count, De, shift, body_add, t.lk, t.betak, d_digits,
-                       d_bodies);
-  else
-    hipLaunchKernelGGL(k_ks_decompose, dim3(grid), dim3(256), 0, st, d_cts, count, L, De, shift, body_add, t.lk, t.betak, d_digits, d_bodies);
+#define KS_DECOMPOSE(SRC, ...) \
+  hipLaunchKernelGGL(k_ks_decompose<SRC>, dim3(grid), dim3(256), 0, st, SRC{__VA_ARGS__}, count, De, in.shift, in.body_add, t.lk, t.betak, sc.digits, sc.bodies)
+  switch (in.source) {
+    case KS_ROWS: KS_DECOMPOSE(ks_src_rows, in.rows, L); break;
+    case KS_DIFF: KS_DECOMPOSE(ks_src_diff, in.rows, L, in.ia, in.ib); break;
+    case KS_SUM:  KS_DECOMPOSE(ks_src_sum, in.rows, L, in.rows_b, in.Lb, in.Lb - 1); break;
+  }
+#undef KS_DECOMPOSE
   if (tk.d_kskT) {   // matrix-core path: i8 digits x signed byte limbs of the key
     const unsigned ncb = (unsigned)(tk.ncol_pad / 128), nrb = (unsigned)((count + 127) / 128), cpx = (ncb + 7) / 8;
 #define KS_LAUNCH(LB)                                                                                                                      \
-    hipLaunchKernelGGL(k_ks_mfma<LB>, dim3(8 * cpx * nrb), dim3(256), 0, st, d_digits, d_bodies, count, De * t.lk, tk.d_kskT, D * t.lk, tk.ncol_pad, \
-                       colsum, t.n, t.betak, d_small)
+    hipLaunchKernelGGL(k_ks_mfma<LB>, dim3(8 * cpx * nrb), dim3(256), 0, st, sc.digits, sc.bodies, count, De * t.lk, tk.d_kskT, D * t.lk, tk.ncol_pad, \
+                       colsum, t.n, t.betak, sc.small)
     if (tk.limbs == 2) KS_LAUNCH(2); else if (tk.limbs == 4) KS_LAUNCH(4); else KS_LAUNCH(8);
 #undef KS_LAUNCH
   } else {           // shapes the MFMA tiling does not cover (D*lk not a multiple of 64, betak = 8): integer VALU GEMM
     constexpr int CT = 16;
     dim3 g2((t.n + 1 + 255) / 256, (unsigned)((count + CT - 1) / CT));
-    hipLaunchKernelGGL(k_ks_gemm<CT>, g2, dim3(256), 0, st, d_digits, d_bodies, count, D * t.lk, tk.d_ksk, tk.d_colsum, t.n, t.betak, d_small);
+    hipLaunchKernelGGL(k_ks_gemm<CT>, g2, dim3(256), 0, st, sc.digits, sc.bodies, count, D * t.lk, tk.d_ksk, tk.d_colsum, t.n, t.betak, sc.small);
   }
   HIPCHK(hipGetLastError());
   if (tm) tm->end(h);
@@ -1203,17 +1217,20 @@ static int dev_ms_center(dctfhe_keys* K, int tier, uint64_t* d_small, size_t cou
   return 0;
 }
 
-static int dev_pbs(dctfhe_keys* K, int tier, const uint64_t* d_small, size_t count, const int64_t* d_tables, int w, const int32_t* d_idx,
-                   int hw, int nchan, size_t e_offset, uint64_t* d_out, int accumulate, uint64_t body_add, Timers* tm, size_t L_out = 0) {
+// What a bootstrap looks up: tables of 2^w entries; ciphertext c takes table idx[c] (idx: optional), or, of `nchan` per-channel tables,
+// the one of element e_offset + c of a tensor with hw elements per channel.  The defaults mean one table.
+struct PbsLut { const int64_t* tables = nullptr; int w = 0; const int32_t* idx = nullptr; int hw = 1, nchan = 1; size_t e_offset = 0; };
+// Where its result goes: rows of L words, stored or added to what the rows hold, body_add on the body.
+struct PbsOut { uint64_t* rows = nullptr; size_t L = 0; bool accumulate = false; uint64_t body_add = 0; };
+static int dev_pbs(dctfhe_keys* K, int tier, const uint64_t* d_small, size_t count, const PbsLut& lut, const PbsOut& out, Timers* tm) {
   const dctfhe_tier& t = K->p.tiers[tier];
   pbs_launch a;
   a.cts_small = d_small; a.count = count; a.n = t.n; a.beta = t.beta;
   a.bsk = K->tiers[tier].d_bsk; a.tw = K->tiers[tier].d_tw; a.wtab = K->tiers[tier].d_wtab;
-  a.tables = d_tables; a.w = w; a.table_idx = d_idx; a.hw = hw; a.nchan = nchan; a.e_offset = e_offset;
+  a.tables = lut.tables; a.w = lut.w; a.table_idx = lut.idx; a.hw = lut.hw; a.nchan = lut.nchan; a.e_offset = lut.e_offset;
   const int ring = t.k << t.logN;
-  if (L_out == 0) L_out = (size_t)K->p.D + 1;
-  if (L_out < (size_t)ring + 1) return fail("bootstrap output rows of %zu words cannot hold a ring of %d", L_out, ring);
-  a.out = d_out; a.D_out = (int)L_out - 1; a.accumulate = accumulate; a.body_add = body_add; a.dummy = K->d_dummy; a.bsk_wrap = 0;
+  if (out.L < (size_t)ring + 1) return fail("bootstrap output rows of %zu words cannot hold a ring of %d", out.L, ring);
+  a.out = out.rows; a.D_out = (int)out.L - 1; a.accumulate = out.accumulate; a.body_add = out.body_add; a.dummy = K->d_dummy; a.bsk_wrap = 0;
   // L2 warm-up: each workgroup touches 1/pf_parts of the next key blocks; the paired two-bit kernel at N = 2048 measures 3 % better
   // without (profiles/r02_exp_ablations.log: 22.5 vs 23.2 ms), every other barrier-coupled kernel better with (T4r 82.4 vs 86.3, T5a 25.7
   // vs 26.6).  The parts are dealt by blockIdx / 8, i.e. per XCD: with one 512-thread workgroup per CU an XCD holds 32 of them, and 32
@@ -1224,6 +1241,12 @@ static int dev_pbs(dctfhe_keys* K, int tier, const uint64_t* d_small, size_t cou
   CHK(launch_pbs(t, a, K->ctx->stream));
   if (tm) tm->end(h);
   return 0;
+}
+// key switch of `in` to tier `tier`, centred mod switch, bootstrap: what every look-up with a key switch of its own runs on a chunk
+static int dev_ks_pbs(dctfhe_keys* K, int tier, const KsInput& in, size_t count, const PbsLut& lut, const PbsOut& out, const LutScratch& sc, Timers* tm) {
+  CHK(dev_keyswitch(K, tier, in, count, sc, tm));
+  CHK(dev_ms_center(K, tier, sc.small, count, tm));
+  return dev_pbs(K, tier, sc.small, count, lut, out, tm);
 }
 
 static int dev_conv2d(hipStream_t st, const uint64_t* in, int batch, int Cin, int H, int W, size_t Lin, size_t deff, const int8_t* d_w, const ConvPack* pk, int Cout,
@@ -1272,27 +1295,29 @@ static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, siz
   for (size_t c0 = 0; c0 < count; c0 += sc.chunk) {
     const size_t cn = std::min(sc.chunk, count - c0);
     uint64_t* w0 = b.work + c0 * Lw;
-    const int* idx = b.idx ? b.idx + c0 : nullptr;
+    KsInput work;            // the working rows as they stand
+    work.rows = w0; work.L = Lw; work.deff = deff;
+    PbsLut tab;              // the site's table look-up
+    tab.tables = split ? b.tab_s : b.tables; tab.w = L.table_bits(); tab.idx = b.idx ? b.idx + c0 : nullptr; tab.hw = hw; tab.nchan = nchan; tab.e_offset = c0;
     for (int i = 0; i < steps; i++) {
-      const int bt = L.steps.at(i), vlog = 62 - p + i;
-      CHK(dev_keyswitch(K, bt, w0, cn, p - i, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
-      CHK(dev_ms_center(K, bt, sc.small, cn, tm));
-      CHK(dev_pbs(K, bt, sc.small, cn, sc.bit_tables + vlog, 0, nullptr, 1, 1, 0, w0, 1, (uint64_t)0 - (1ULL << vlog), tm, Lw));
+      const int vlog = 62 - p + i;
+      KsInput in = work; in.shift = p - i;
+      PbsOut bit{w0, Lw}; bit.accumulate = true; bit.body_add = (uint64_t)0 - (1ULL << vlog);
+      CHK(dev_ks_pbs(K, L.steps.at(i), in, cn, PbsLut{sc.bit_tables + vlog}, bit, sc, tm));
     }
     if (split) {
       // t = 2 t' + b0 sits under the padding bit once the r rounding steps are done.  The last step was one more of them, on b0: it left
       // t' as a (w-1)-bit message in w0.  The same small ciphertext, bootstrapped with 2^62 and body offset -2^62, gives b0 * 2^63 (par).
       // Second look-up first, while w0 still holds t': key switch of w0 + par (b0 in the padding bit, never materialised), table Dt
       // -> (-1)^b0 Dt[t'] into par; then the first look-up S[t'] into w0 as for any site, and the sum.
-      CHK(dev_pbs(K, L.steps.at(steps - 1), sc.small, cn, sc.bit_tables + 62, 0, nullptr, 1, 1, 0, b.par, 0, (uint64_t)0 - (1ULL << 62), tm, b.Lp));
-      CHK(dev_keyswitch(K, tier2, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw, 0, nullptr, nullptr, b.par, b.Lp));
-      CHK(dev_ms_center(K, tier2, sc.small, cn, tm));
-      CHK(dev_pbs(K, tier2, sc.small, cn, b.tab_d, L.w - 1, idx, hw, nchan, c0, b.par, 0, 0, tm, b.Lp));
+      PbsOut par{b.par, b.Lp}; par.body_add = (uint64_t)0 - (1ULL << 62);
+      CHK(dev_pbs(K, L.steps.at(steps - 1), sc.small, cn, PbsLut{sc.bit_tables + 62}, par, tm));
+      KsInput sum = work; sum.source = KS_SUM; sum.rows_b = b.par; sum.Lb = b.Lp;
+      PbsLut tab2 = tab; tab2.tables = b.tab_d;
+      CHK(dev_ks_pbs(K, tier2, sum, cn, tab2, PbsOut{b.par, b.Lp}, sc, tm));
     }
-    if (steps > 0) CHK(dev_keyswitch(K, tab_tier, w0, cn, 0, sc.digits, sc.bodies, sc.small, tm, deff, Lw));
-    else           CHK(dev_keyswitch(K, tab_tier, b.src + c0 * b.Ls, cn, L.shift, sc.digits, sc.bodies, sc.small, tm, deff, b.Ls, L.round_add()));
-    CHK(dev_ms_center(K, tab_tier, sc.small, cn, tm));
-    CHK(dev_pbs(K, tab_tier, sc.small, cn, split ? b.tab_s : b.tables, L.table_bits(), idx, hw, nchan, c0, w0, 0, 0, tm, Lw));
+    if (steps == 0) { work.rows = b.src + c0 * b.Ls; work.L = b.Ls; work.shift = L.shift; work.body_add = L.round_add(); }   // nothing modified the input
+    CHK(dev_ks_pbs(K, tab_tier, work, cn, tab, PbsOut{w0, Lw}, sc, tm));
     if (split) {
       const int h = tm ? tm->begin(CAT_LINEAR) : -1;
       hipLaunchKernelGGL(k_acc_rows, dim3(ew_grid(cn * (ring2 + 1))), dim3(256), 0, K->ctx->stream, w0, Lw, b.par, b.Lp, cn, ring2);
@@ -1331,7 +1356,7 @@ static int alloc_lut_scratch(dctfhe_keys* K, size_t chunk, LutScratch* sc) {
 
 // the levels of a max-pool plan on device rows.  Input rows of stride Ls (first ds mask words meaningful); level buffers and output rows of
 // stride Lo, of which the first `dout` = max(ds, ring of the tier) mask words may be non-zero.  Each level: the gather, then per chunk the
-// key switch of the differences (k_ks_decompose_diff), the centred mod switch and the relu bootstrap accumulated into the gathered b rows.
+// key switch of the differences (KS_DIFF), the centred mod switch and the relu bootstrap accumulated into the gathered b rows.
 static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, const uint64_t* d_in, size_t Ls, size_t ds, uint64_t* const bufs[2],
                         uint64_t* d_out, size_t Lo, size_t dout, const int64_t* d_table, const LutScratch& sc, Timers* tm) {
   hipStream_t st = K->ctx->stream;
@@ -1347,10 +1372,11 @@ static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, co
     if (tm) tm->end(h);
     for (size_t c0 = 0; c0 < l.pairs; c0 += sc.chunk) {
       const size_t cn = std::min(sc.chunk, l.pairs - c0);
-      CHK(dev_keyswitch(K, tier, src, cn, S.shift, sc.digits, sc.bodies, sc.small, tm, (int)d_src, L_src, S.body_add, maps + l.a_off + c0,
-                        maps + l.b_off + c0));
-      CHK(dev_ms_center(K, tier, sc.small, cn, tm));
-      CHK(dev_pbs(K, tier, sc.small, cn, d_table, S.p_d, nullptr, 1, 1, 0, dst + c0 * Lo, 1, 0, tm, Lo));
+      KsInput diff;
+      diff.rows = src; diff.L = L_src; diff.deff = (int)d_src; diff.shift = S.shift; diff.body_add = S.body_add;
+      diff.source = KS_DIFF; diff.ia = maps + l.a_off + c0; diff.ib = maps + l.b_off + c0;
+      PbsOut acc{dst + c0 * Lo, Lo}; acc.accumulate = true;
+      CHK(dev_ks_pbs(K, tier, diff, cn, PbsLut{d_table, S.p_d}, acc, sc, tm));
     }
   }
   return 0;
@@ -1381,15 +1407,15 @@ extern "C" int dctfhe_keyswitch_prefix(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
   HIPCHK(hipSetDevice(ctx->device));
   const dctfhe_tier& t = K->p.tiers[tier];
   const size_t L = (size_t)K->p.D + 1;
-  DevBuf d_in, d_small, d_bodies, d_dig;
-  HIPCHK(d_in.alloc(count * L * 8));
-  HIPCHK(d_small.alloc(count * (size_t)(t.n + 1) * 8));
-  HIPCHK(d_bodies.alloc(count * 8));
-  HIPCHK(d_dig.alloc(count * (size_t)K->p.D * t.lk));
-  HIPCHK(hipMemcpy(d_in.p, cts, count * L * 8, hipMemcpyHostToDevice));
-  CHK(dev_keyswitch(K, tier, d_in.as<uint64_t>(), count, shift, d_dig.as<uint8_t>(), d_bodies.as<uint64_t>(), d_small.as<uint64_t>(), nullptr, deff));
+  DevBuf d_in;
+  HIPCHK(d_in.upload(cts, count * L * 8));
+  LutScratchOwner sc;
+  CHK(alloc_lut_scratch(K, count, &sc.s));
+  KsInput in;
+  in.rows = d_in.as<uint64_t>(); in.L = L; in.deff = deff; in.shift = shift;
+  CHK(dev_keyswitch(K, tier, in, count, sc.s, nullptr));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(cts_small, d_small.p, count * (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cts_small, sc.s.small, count * (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 extern "C" int dctfhe_keyswitch(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, int shift, uint64_t* cts_small) {
@@ -1404,8 +1430,7 @@ extern "C" int dctfhe_modswitch_center(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
   HIPCHK(hipSetDevice(ctx->device));
   const size_t bytes = count * (size_t)(K->p.tiers[tier].n + 1) * 8;
   DevBuf d;
-  HIPCHK(d.alloc(bytes));
-  HIPCHK(hipMemcpy(d.p, cts_small, bytes, hipMemcpyHostToDevice));
+  HIPCHK(d.upload(cts_small, bytes));
   CHK(dev_ms_center(K, tier, d.as<uint64_t>(), count, nullptr));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipMemcpy(cts_small, d.p, bytes, hipMemcpyDeviceToHost));
@@ -1426,16 +1451,13 @@ extern "C" int dctfhe_pbs(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const 
       if (table_idx[i] < 0 || table_idx[i] >= ntab) return fail("table_idx[%zu] = %d out of range (%d tables)", i, table_idx[i], ntab);
   const size_t L = (size_t)K->p.D + 1;
   DevBuf d_small, d_out, d_tab, d_idx;
-  HIPCHK(d_small.alloc(count * (size_t)(t.n + 1) * 8));
+  HIPCHK(d_small.upload(cts_small, count * (size_t)(t.n + 1) * 8));
   HIPCHK(d_out.alloc(count * L * 8));
-  HIPCHK(d_tab.alloc(((size_t)ntab << w) * 8));
-  HIPCHK(hipMemcpy(d_small.p, cts_small, count * (size_t)(t.n + 1) * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_tab.p, tables, ((size_t)ntab << w) * 8, hipMemcpyHostToDevice));
-  if (table_idx) {
-    HIPCHK(d_idx.alloc(count * 4));
-    HIPCHK(hipMemcpy(d_idx.p, table_idx, count * 4, hipMemcpyHostToDevice));
-  }
-  CHK(dev_pbs(K, tier, d_small.as<uint64_t>(), count, d_tab.as<int64_t>(), w, d_idx.as<int32_t>(), 1, 1, 0, d_out.as<uint64_t>(), 0, 0, nullptr));
+  HIPCHK(d_tab.upload(tables, ((size_t)ntab << w) * 8));
+  if (table_idx) HIPCHK(d_idx.upload(table_idx, count * 4));
+  PbsLut lut;
+  lut.tables = d_tab.as<int64_t>(); lut.w = w; lut.idx = d_idx.as<int32_t>();
+  CHK(dev_pbs(K, tier, d_small.as<uint64_t>(), count, lut, PbsOut{d_out.as<uint64_t>(), L}, nullptr));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   HIPCHK(hipMemcpy(cts_out, d_out.p, count * L * 8, hipMemcpyDeviceToHost));
   return 0;
@@ -1466,14 +1488,9 @@ extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int 
   HIPCHK(hipSetDevice(ctx->device));
   const size_t L = (size_t)K->p.D + 1;
   DevBuf d_work, d_tab, d_idx, d_par;
-  HIPCHK(d_work.alloc(count * L * 8));
-  HIPCHK(d_tab.alloc(((size_t)ntab << w) * 8));
-  HIPCHK(hipMemcpy(d_work.p, cts, count * L * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_tab.p, split ? halves.data() : tables, ((size_t)ntab << w) * 8, hipMemcpyHostToDevice));
-  if (table_idx) {
-    HIPCHK(d_idx.alloc(count * 4));
-    HIPCHK(hipMemcpy(d_idx.p, table_idx, count * 4, hipMemcpyHostToDevice));
-  }
+  HIPCHK(d_work.upload(cts, count * L * 8));
+  HIPCHK(d_tab.upload(split ? halves.data() : tables, ((size_t)ntab << w) * 8));
+  if (table_idx) HIPCHK(d_idx.upload(table_idx, count * 4));
   LutScratchOwner sc;
   CHK(alloc_lut_scratch(K, std::min<size_t>(count, 4096), &sc.s));
   // the site a record of this look-up would decode to (rows arrive shifted and offset; without an index every ciphertext takes table 0)
@@ -1611,19 +1628,18 @@ extern "C" int dctfhe_keyswitch_diff(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int t
   HIPCHK(hipSetDevice(ctx->device));
   const dctfhe_tier& t = K->p.tiers[tier];
   const size_t L = (size_t)K->p.D + 1;
-  DevBuf d_in, d_small, d_bodies, d_dig, d_idx;
-  HIPCHK(d_in.alloc(count * L * 8));
-  HIPCHK(d_small.alloc(count * (size_t)(t.n + 1) * 8));
-  HIPCHK(d_bodies.alloc(count * 8));
-  HIPCHK(d_dig.alloc(count * (size_t)K->p.D * t.lk));
-  HIPCHK(d_idx.alloc(count * 8));
-  HIPCHK(hipMemcpy(d_in.p, cts, count * L * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_idx.p, ia, count * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_idx.as<int32_t>() + count, ib, count * 4, hipMemcpyHostToDevice));
-  CHK(dev_keyswitch(K, tier, d_in.as<uint64_t>(), count, shift, d_dig.as<uint8_t>(), d_bodies.as<uint64_t>(), d_small.as<uint64_t>(), nullptr, deff, L,
-                    body_add, d_idx.as<int32_t>(), d_idx.as<int32_t>() + count));
+  DevBuf d_in, d_ia, d_ib;
+  HIPCHK(d_in.upload(cts, count * L * 8));
+  HIPCHK(d_ia.upload(ia, count * 4));
+  HIPCHK(d_ib.upload(ib, count * 4));
+  LutScratchOwner sc;
+  CHK(alloc_lut_scratch(K, count, &sc.s));
+  KsInput in;
+  in.rows = d_in.as<uint64_t>(); in.L = L; in.deff = deff; in.shift = shift; in.body_add = body_add;
+  in.source = KS_DIFF; in.ia = d_ia.as<int32_t>(); in.ib = d_ib.as<int32_t>();
+  CHK(dev_keyswitch(K, tier, in, count, sc.s, nullptr));
   HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(cts_small, d_small.p, count * (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cts_small, sc.s.small, count * (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1664,11 +1680,9 @@ extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   PoolPlan P;
   CHK(pool_plan(batch, C, H, W, k, s, p, &P));
   DevBuf di, d_o, ba, bb, d_tab;
-  HIPCHK(di.alloc(nin * Li * 8)); HIPCHK(d_o.alloc(nout * Lo * 8));
+  HIPCHK(di.upload(in, nin * Li * 8)); HIPCHK(d_o.alloc(nout * Lo * 8));
   HIPCHK(ba.alloc(P.rows_buf[0] * Lo * 8)); HIPCHK(bb.alloc(P.rows_buf[1] * Lo * 8));
-  HIPCHK(d_tab.alloc(((size_t)1 << p_d) * 8));
-  HIPCHK(hipMemcpy(di.p, in, nin * Li * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_tab.p, table, ((size_t)1 << p_d) * 8, hipMemcpyHostToDevice));
+  HIPCHK(d_tab.upload(table, ((size_t)1 << p_d) * 8));
   LutScratchOwner sc;
   CHK(alloc_lut_scratch(K, std::min<size_t>(std::max<size_t>(P.pairs_per_batch, 1), 4096), &sc.s));
   uint64_t* const bufs[2] = {ba.as<uint64_t>(), bb.as<uint64_t>()};
@@ -2220,9 +2234,11 @@ extern "C" int dctfhe_bench_pbs(dctfhe_ctx* ctx, dctfhe_keys* K, int tier, size_
   HIPCHK(hipMemcpy(d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
   hipEvent_t a, b;
   hipEventCreate(&a); hipEventCreate(&b);
-  CHK(dev_pbs(K, tier, d_small, count, d_tab, 4, nullptr, 1, 1, 0, d_out, 0, 0, nullptr));
+  const PbsLut lut{d_tab, 4};
+  const PbsOut out{d_out, L};
+  CHK(dev_pbs(K, tier, d_small, count, lut, out, nullptr));
   hipEventRecord(a, ctx->stream);
-  for (int r = 0; r < reps; r++) CHK(dev_pbs(K, tier, d_small, count, d_tab, 4, nullptr, 1, 1, 0, d_out, 0, 0, nullptr));
+  for (int r = 0; r < reps; r++) CHK(dev_pbs(K, tier, d_small, count, lut, out, nullptr));
   hipEventRecord(b, ctx->stream);
   HIPCHK(hipEventSynchronize(b));
   float ms = 0;

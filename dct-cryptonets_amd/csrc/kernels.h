@@ -209,25 +209,27 @@ __global__ void k_pair_secret(const uint8_t* __restrict__ s, int n, uint8_t* __r
   out[3 * i] = a && !b; out[3 * i + 1] = !a && b; out[3 * i + 2] = a && b;
 }
 
-// bootstrap key, standard domain, rows [i0, i0+ni) x rows_per_bit: GLWE(0) + s_i * gadget.
-// One block per row; the mask polynomial is parked in LDS while the body accumulates A * S.
-__global__ void k_bsk_gen_std(const uint8_t* __restrict__ s_small, const uint8_t* __restrict__ S_glwe, int i0, int k, int N, int l,
-                              int beta, double sigma, rng_key pub, rng_key sec, uint64_t stream, uint64_t* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  uint64_t* A = reinterpret_cast<uint64_t*>(smem_raw);
-  const int rows = (k + 1) * l;
-  const int i = i0 + (int)(blockIdx.x / rows), r = (int)(blockIdx.x % rows);
-  const uint64_t grow = (uint64_t)i * rows + r;  // global row id: randomness does not depend on chunking
-  uint64_t* row = out + (size_t)blockIdx.x * (k + 1) * N;
-  uint64_t* B = row + (size_t)k * N;
+// What every bootstrap-key row starts from, whichever form it is stored in: the noise draw into the body polynomial B, then per mask
+// polynomial j < k the draw into LDS (A; a ChaCha block, eight words, per thread: N is a multiple of 8, so a polynomial starts a block)
+// and B += A * S_j (negacyclic).  grow is the global row id: the randomness does not depend on chunking.  masks: where the k mask
+// polynomials go ([k][N]), or nullptr for a row that keeps its body only.
+__device__ __forceinline__ void bsk_row_zero(const uint8_t* __restrict__ S_glwe, uint64_t grow, int k, int N, double sigma, const rng_key& pub,
+                                             const rng_key& sec, uint64_t stream, uint64_t* __restrict__ A, uint64_t* __restrict__ B,
+                                             uint64_t* __restrict__ masks) {
   for (int c = threadIdx.x; c < N; c += blockDim.x)
     B[c] = (uint64_t)gauss_torus(sec, stream + 1, grow * (uint64_t)N + c, sigma);
   for (int j = 0; j < k; j++) {
     __syncthreads();
-    for (int c = threadIdx.x; c < N; c += blockDim.x) {
-      const uint64_t a = rnd64(pub, stream, (grow * (uint64_t)k + j) * (uint64_t)N + c);
-      A[c] = a;
-      row[(size_t)j * N + c] = a;
+    const uint64_t blk0 = ((grow * (uint64_t)k + j) * (uint64_t)N) >> 3;
+    for (int q = threadIdx.x; q < N / 8; q += blockDim.x) {
+      uint32_t o[16];
+      chacha20_block(pub, stream, blk0 + q, o);
+#pragma unroll
+      for (int w = 0; w < 8; w++) {
+        const uint64_t a = (uint64_t)o[2 * w] | ((uint64_t)o[2 * w + 1] << 32);
+        A[8 * q + w] = a;
+        if (masks) masks[(size_t)j * N + 8 * q + w] = a;
+      }
     }
     __syncthreads();
     const uint8_t* Sj = S_glwe + (size_t)j * N;
@@ -241,6 +243,17 @@ __global__ void k_bsk_gen_std(const uint8_t* __restrict__ s_small, const uint8_t
       B[c] += acc;
     }
   }
+}
+
+// bootstrap key, standard domain, rows [i0, i0+ni) x rows_per_bit: GLWE(0) + s_i * gadget.
+// One block per row; the mask polynomial is parked in LDS while the body accumulates A * S.
+__global__ void k_bsk_gen_std(const uint8_t* __restrict__ s_small, const uint8_t* __restrict__ S_glwe, int i0, int k, int N, int l,
+                              int beta, double sigma, rng_key pub, rng_key sec, uint64_t stream, uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int rows = (k + 1) * l;
+  const int i = i0 + (int)(blockIdx.x / rows), r = (int)(blockIdx.x % rows);
+  uint64_t* row = out + (size_t)blockIdx.x * (k + 1) * N;
+  bsk_row_zero(S_glwe, (uint64_t)i * rows + r, k, N, sigma, pub, sec, stream, reinterpret_cast<uint64_t*>(smem_raw), row + (size_t)k * N, row);
   __syncthreads();
   if (threadIdx.x == 0 && s_small[i]) {
     const int p = r / l, lev = r % l;
@@ -251,38 +264,14 @@ __global__ void k_bsk_gen_std(const uint8_t* __restrict__ s_small, const uint8_t
 // the same rows in BODY FORM, bodies only ([ni * rows][N]): the masks stay the pure draws of `pub` (k_seeded_expand rebuilds them), so
 // the s_i * gadget term that k_bsk_gen_std adds to mask polynomial p < k moves into the body as - s_i g S_p (same phase, same noise
 // draw); rows with p = k are k_bsk_gen_std's bodies bit for bit.  Covers the pair secret of unroll 2 like k_bsk_gen_std (s_small = the
-// derived bits).  One block per row; masks drawn a ChaCha block (eight words) per thread into LDS.
+// derived bits).  One block per row.
 __global__ void k_bsk_gen_bodies(const uint8_t* __restrict__ s_small, const uint8_t* __restrict__ S_glwe, int i0, int k, int N, int l,
                                  int beta, double sigma, rng_key pub, rng_key sec, uint64_t stream, uint64_t* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  uint64_t* A = reinterpret_cast<uint64_t*>(smem_raw);
   const int rows = (k + 1) * l;
   const int i = i0 + (int)(blockIdx.x / rows), r = (int)(blockIdx.x % rows);
-  const uint64_t grow = (uint64_t)i * rows + r;
   uint64_t* B = out + (size_t)blockIdx.x * N;
-  for (int c = threadIdx.x; c < N; c += blockDim.x)
-    B[c] = (uint64_t)gauss_torus(sec, stream + 1, grow * (uint64_t)N + c, sigma);
-  for (int j = 0; j < k; j++) {
-    __syncthreads();
-    const uint64_t blk0 = ((grow * (uint64_t)k + j) * (uint64_t)N) >> 3;     // N is a multiple of 8: the polynomial starts a block
-    for (int q = threadIdx.x; q < N / 8; q += blockDim.x) {
-      uint32_t o[16];
-      chacha20_block(pub, stream, blk0 + q, o);
-#pragma unroll
-      for (int w = 0; w < 8; w++) A[8 * q + w] = (uint64_t)o[2 * w] | ((uint64_t)o[2 * w + 1] << 32);
-    }
-    __syncthreads();
-    const uint8_t* Sj = S_glwe + (size_t)j * N;
-    for (int c = threadIdx.x; c < N; c += blockDim.x) {
-      uint64_t acc = 0;
-      for (int m = 0; m < N; m++) {
-        if (!Sj[m]) continue;  // uniform branch
-        const int src = c - m;
-        acc += (src >= 0) ? A[src] : (uint64_t)0 - A[src + N];
-      }
-      B[c] += acc;
-    }
-  }
+  bsk_row_zero(S_glwe, (uint64_t)i * rows + r, k, N, sigma, pub, sec, stream, reinterpret_cast<uint64_t*>(smem_raw), B, nullptr);
   if (!s_small[i]) return;
   const int p = r / l, lev = r % l;
   const uint64_t g = 1ULL << (64 - beta * (lev + 1));
@@ -318,88 +307,55 @@ k_bsk_fourier(const uint64_t* __restrict__ polys, size_t npoly, const cplx* __re
 // Layout digits[c][i*lk + lev] (u8).  Also copies the (shifted) body.
 // Only the first Deff mask words are decomposed (digits [count][Deff*lk]): the caller knows the rest to be zero (nested
 // keys: a ciphertext that came out of a ring of dimension kN <= Deff has a zero tail), and a zero word contributes nothing.
-__global__ void k_ks_decompose(const uint64_t* __restrict__ cts, size_t count, size_t L /* row stride in words; body at L-1 */, int Deff, int shift,
-                               uint64_t body_add, int lk, int betak, uint8_t* __restrict__ digits, uint64_t* __restrict__ bodies) {
-  const size_t total = count * (size_t)Deff;
-  const int half = 1 << (betak - 1);
-  for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t)gridDim.x * blockDim.x) {
-    const size_t c = x / Deff;
-    const int i = (int)(x % Deff);
-    const uint64_t v = cts[c * L + i] << shift;
-    const int tot = lk * betak;
-    uint64_t xx = (v + (1ULL << (63 - tot))) >> (64 - tot);
-    const uint64_t B = 1ULL << betak, mask = B - 1;
-    uint64_t carry = 0;
-    uint8_t* dst = digits + (c * (size_t)Deff + i) * lk;
-    for (int lev = lk - 1; lev >= 0; lev--) {
-      uint64_t d = (xx & mask) + carry;
-      xx >>= betak;
-      int dv;
-      if (d >= (uint64_t)half) { dv = (int)d - (int)B; carry = 1; } else { dv = (int)d; carry = 0; }
-      dst[lev] = (uint8_t)(dv + half);
-    }
-    if (i == 0) bodies[c] = (cts[c * L + L - 1] << shift) + body_add;      // the affine step of a look-up without rounding steps rides along
+// Where ciphertext c comes from is a row source: word(c, i) is its mask word i < Deff, body(c) its body.
+
+// the ciphertexts are the rows themselves (stride L words, body at L-1)
+struct ks_src_rows {
+  const uint64_t* cts; size_t L;
+  __device__ __forceinline__ uint64_t word(size_t c, int i) const { return cts[c * L + i]; }
+  __device__ __forceinline__ uint64_t body(size_t c) const { return cts[c * L + L - 1]; }
+};
+// the difference of two rows, for the pairwise maxima of a max pool: ciphertext c is rows[ia[c]] - rows[ib[c]] (rows of stride L, the
+// first Deff mask words meaningful) -- no difference tensor is ever written
+struct ks_src_diff {
+  const uint64_t* rows; size_t L; const int32_t *ia, *ib;
+  __device__ __forceinline__ uint64_t word(size_t c, int i) const { return rows[(size_t)ia[c] * L + i] - rows[(size_t)ib[c] * L + i]; }
+  __device__ __forceinline__ uint64_t body(size_t c) const { return rows[(size_t)ia[c] * L + L - 1] - rows[(size_t)ib[c] * L + L - 1]; }
+};
+// the sum of two row sets, for the second look-up of a parity-split site (7-bit tables): ciphertext c is rows_a[c] + rows_b[c] -- the
+// working ciphertext (rows of stride La) plus the parity bootstrap's output (rows of stride Lb, whose db stored mask words hold a ring and
+// zeros; a word beyond them counts as zero) -- so the copy with the parity in its padding bit is never written
+struct ks_src_sum {
+  const uint64_t* rows_a; size_t La; const uint64_t* rows_b; size_t Lb, db;
+  __device__ __forceinline__ uint64_t word(size_t c, int i) const { return rows_a[c * La + i] + ((size_t)i < db ? rows_b[c * Lb + i] : 0); }
+  __device__ __forceinline__ uint64_t body(size_t c) const { return rows_a[c * La + La - 1] + rows_b[c * Lb + Lb - 1]; }
+};
+
+// the lk balanced base-2^betak digits of v, rounded at 2^-(lk betak), most significant first, each offset by half a base
+__device__ __forceinline__ void ks_split_digits(uint64_t v, int lk, int betak, uint8_t* __restrict__ dst) {
+  const int half = 1 << (betak - 1), tot = lk * betak;
+  uint64_t xx = (v + (1ULL << (63 - tot))) >> (64 - tot);
+  const uint64_t B = 1ULL << betak, mask = B - 1;
+  uint64_t carry = 0;
+  for (int lev = lk - 1; lev >= 0; lev--) {
+    uint64_t d = (xx & mask) + carry;
+    xx >>= betak;
+    int dv;
+    if (d >= (uint64_t)half) { dv = (int)d - (int)B; carry = 1; } else { dv = (int)d; carry = 0; }
+    dst[lev] = (uint8_t)(dv + half);
   }
 }
 
-// Step 1 on the difference of two rows, for the pairwise maxima of a max pool: ciphertext c is rows[ia[c]] - rows[ib[c]] (rows of
-// stride L, the first Deff mask words meaningful), shifted and body-offset on the fly -- no difference tensor is ever written.  The digit
-// split is k_ks_decompose's.
-__global__ void k_ks_decompose_diff(const uint64_t* __restrict__ rows, size_t L, const int32_t* __restrict__ ia, const int32_t* __restrict__ ib,
-                                    size_t count, int Deff, int shift, uint64_t body_add, int lk, int betak, uint8_t* __restrict__ digits,
-                                    uint64_t* __restrict__ bodies) {
+// lanes run over consecutive words of a ciphertext
+template <class Src>
+__global__ void k_ks_decompose(Src src, size_t count, int Deff, int shift, uint64_t body_add, int lk, int betak, uint8_t* __restrict__ digits,
+                               uint64_t* __restrict__ bodies) {
   const size_t total = count * (size_t)Deff;
-  const int half = 1 << (betak - 1);
   for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t)gridDim.x * blockDim.x) {
     const size_t c = x / Deff;
     const int i = (int)(x % Deff);
-    const uint64_t* ra = rows + (size_t)ia[c] * L;
-    const uint64_t* rb = rows + (size_t)ib[c] * L;
-    const uint64_t v = (ra[i] - rb[i]) << shift;
-    const int tot = lk * betak;
-    uint64_t xx = (v + (1ULL << (63 - tot))) >> (64 - tot);
-    const uint64_t B = 1ULL << betak, mask = B - 1;
-    uint64_t carry = 0;
-    uint8_t* dst = digits + (c * (size_t)Deff + i) * lk;
-    for (int lev = lk - 1; lev >= 0; lev--) {
-      uint64_t d = (xx & mask) + carry;
-      xx >>= betak;
-      int dv;
-      if (d >= (uint64_t)half) { dv = (int)d - (int)B; carry = 1; } else { dv = (int)d; carry = 0; }
-      dst[lev] = (uint8_t)(dv + half);
-    }
-    if (i == 0) bodies[c] = ((ra[L - 1] - rb[L - 1]) << shift) + body_add;
-  }
-}
-
-// Step 1 on the sum of two row sets, for the second look-up of a parity-split site (7-bit tables): ciphertext c is rows_a[c] + rows_b[c]
-// -- the working ciphertext (rows of stride La) plus the parity bootstrap's output (rows of stride Lb, whose db stored mask words hold a
-// ring and zeros; a word beyond them counts as zero) -- so the copy with the parity in its padding bit is never written.  Lanes run over
-// consecutive words of a row; the digit split is k_ks_decompose's.
-__global__ void k_ks_decompose_sum(const uint64_t* __restrict__ rows_a, size_t La, const uint64_t* __restrict__ rows_b, size_t Lb, size_t db,
-                                   size_t count, int Deff, int shift, uint64_t body_add, int lk, int betak, uint8_t* __restrict__ digits,
-                                   uint64_t* __restrict__ bodies) {
-  const size_t total = count * (size_t)Deff;
-  const int half = 1 << (betak - 1);
-  for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t)gridDim.x * blockDim.x) {
-    const size_t c = x / Deff;
-    const int i = (int)(x % Deff);
-    const uint64_t* ra = rows_a + c * La;
-    const uint64_t* rb = rows_b + c * Lb;
-    const uint64_t v = (ra[i] + ((size_t)i < db ? rb[i] : 0)) << shift;
-    const int tot = lk * betak;
-    uint64_t xx = (v + (1ULL << (63 - tot))) >> (64 - tot);
-    const uint64_t B = 1ULL << betak, mask = B - 1;
-    uint64_t carry = 0;
-    uint8_t* dst = digits + (c * (size_t)Deff + i) * lk;
-    for (int lev = lk - 1; lev >= 0; lev--) {
-      uint64_t d = (xx & mask) + carry;
-      xx >>= betak;
-      int dv;
-      if (d >= (uint64_t)half) { dv = (int)d - (int)B; carry = 1; } else { dv = (int)d; carry = 0; }
-      dst[lev] = (uint8_t)(dv + half);
-    }
-    if (i == 0) bodies[c] = ((ra[La - 1] + rb[Lb - 1]) << shift) + body_add;
+    ks_split_digits(src.word(c, i) << shift, lk, betak, digits + (c * (size_t)Deff + i) * lk);
+    if (i == 0) bodies[c] = (src.body(c) << shift) + body_add;      // the affine step of a look-up without rounding steps rides along
   }
 }
 

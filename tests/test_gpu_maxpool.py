@@ -35,14 +35,17 @@ def _oracle(qm, q):
 def test_keyswitch_diff_equals_keyswitch_of_the_difference(keys):
     rng = np.random.default_rng(0)
     cts = keys.encrypt(rng.integers(0, 16, 40).astype(np.uint64) << np.uint64(58))
-    ia, ib = rng.integers(0, 40, 40).astype(np.int32), rng.integers(0, 40, 40).astype(np.int32)
-    for tier in (0, 1):
-        for shift, body_add in ((0, 1 << 62), (2, 0)):
-            got = keys.keyswitch_diff(tier, cts, ia, ib, shift, body_add)
-            diff = cts[ia] - cts[ib]
-            diff[:, -1] += np.uint64(body_add >> shift)          # body_add lands after the shift: pre-divide (exact for these values)
-            want = keys.keyswitch(tier, diff, shift=shift)
-            assert np.array_equal(got, want), (tier, shift)
+    assert cts[:, :512].any() and not cts[:, 512:1024].any()     # input_dim: the rows mask 512 of the 1024 key words
+    # all 40 rows and 37 of them (not a multiple of the decompose kernel's 256-thread block), at full width and narrowed to the 512 words
+    for n, deff in ((40, 0), (40, 512), (37, 0), (37, 512)):
+        ia, ib = rng.integers(0, n, n).astype(np.int32), rng.integers(0, n, n).astype(np.int32)
+        for tier in (0, 1):
+            for shift, body_add in ((0, 1 << 62), (2, 0)):
+                got = keys.keyswitch_diff(tier, cts[:n], ia, ib, shift, body_add, deff=deff)
+                diff = cts[:n][ia] - cts[:n][ib]
+                diff[:, -1] += np.uint64(body_add >> shift)          # body_add lands after the shift: pre-divide (exact for these values)
+                want = keys.keyswitch(tier, diff, shift=shift, deff=deff)
+                assert np.array_equal(got, want), (n, deff, tier, shift)
 
 
 @pytest.mark.parametrize("pool,H,W", GEOMS)

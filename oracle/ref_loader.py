@@ -134,6 +134,14 @@ def pbs(cts_small, bsk_f, bsk, k, N, l, beta, tables, w, table_idx, D_out, exact
     return out
 
 
+def build_testvector(table, w, N):
+    """the N coefficients the blind rotation starts from (ref_build_testvector): table[(j + N/2^(w+1)) >> (logN - w)], wrapped negated"""
+    table = np.ascontiguousarray(table, np.int64).reshape(1 << w)
+    tv = np.zeros(N, np.uint64)
+    lib().ref_build_testvector(table, w, N, tv)
+    return tv
+
+
 def ms_center(cts_small, N):
     """centred mod switch (ref_ms_center): returns the adjusted copy"""
     out = np.ascontiguousarray(cts_small, np.uint64).copy()

@@ -89,3 +89,60 @@ def test_round_lut_is_round_half_up(kit, oracle):
     out = oracle.round_lut(cts, kit["D"], p, r, bt, bt, table, w, None)
     got = np.round(_cent(oracle.lwe_phase(kit["S"], kit["D"], out)) * 64).astype(np.int64)
     assert np.array_equal(got, ((msgs + np.uint64(2)) >> np.uint64(2)).astype(np.int64))
+
+
+@pytest.mark.parametrize("logN", [8, 9, 10])
+def test_level_grid_rotation_matches_exact_pbs(oracle, logN):
+    """What tests/test_gpu_pbs_matrix.py sweeps the GPU kernels against: a small ciphertext on the 2N-level grid (pbs_matrix_ref
+    level_grid_cts) turns the test vector by exactly its level t, so the bootstrap leaves tv[t] for t < N and -tv[t - N] above.  Confirmed
+    here on the oracle's exact-arithmetic bootstrap at every one of the 2N levels, for the narrowest table (w = 0) and the widest
+    (w = logN - 1: boxes of two coefficients), three tables picked per ciphertext.  A three-bit key and one level of 20-bit digits keep the
+    schoolbook products quick; the gadget rounding they leave (sigma ~2^-16) is far inside the 2^-8 half-box of the table entries."""
+    import pbs_matrix_ref as R
+    N = 1 << logN
+    s = np.array([1, 0, 1], np.uint8)
+    S = oracle.gen_binary_key(21, N)
+    bsk = oracle.bsk_gen(s, S, 1, N, 1, 20, 2.0 ** -45, 22)
+    rng = np.random.default_rng(logN)
+    levels = np.arange(2 * N)
+    idx = (np.arange(levels.size) % 3).astype(np.int32)
+    small = R.level_grid_cts(s, logN, levels, rng)
+    for w in (0, logN - 1):
+        tables = rng.integers(-8, 8, (3, 1 << w)).astype(np.int64) << 57
+        out = oracle.pbs(small, None, bsk, 1, N, 1, 20, tables, w, idx, N, exact=True)
+        ph = oracle.lwe_phase(S, N, out)
+        want = R.level_grid_expected(oracle, tables, idx, w, N, levels)
+        dec = lambda p: ((p + (np.uint64(1) << np.uint64(56))) >> np.uint64(57)) & np.uint64(127)
+        assert np.array_equal(dec(ph), dec(want)), (w, np.flatnonzero(dec(ph) != dec(want))[:10])
+        assert np.abs(_cent(ph - want)).max() < 2.0 ** -12, w
+
+
+F64_SHAPES = [(10, 1, 1, 20), (11, 1, 3, 12), (10, 2, 2, 14), (11, 1, 4, 10), (12, 1, 2, 16)]
+
+
+@pytest.mark.parametrize("logN,k,l,beta", F64_SHAPES, ids=["N%d-k%d-l%d-b%d" % (1 << a, b, c, d) for a, b, c, d in F64_SHAPES])
+def test_f64_path_inside_the_difference_bound(oracle, logN, k, l, beta):
+    """The bound tests/test_gpu_pbs_matrix.py holds (device - oracle) to is sqrt(2) x 1.6 x sqrt(n (fft + dec)) of params.var_pbs_out.
+    The reference itself must sit inside it: the oracle's f64 bootstrap against its exact-arithmetic one, same keys and inputs (n = 40,
+    noisy inputs on box centres), fixed seeds.  Measured rms / sqrt(n (fft + dec)) with these seeds: 1.11, 0.84, 0.84, 0.96, 0.45 (8, 8, 8, 8 and 4 ciphertexts); the bound is at 2.26."""
+    import math
+    import pbs_matrix_ref as R
+    N, n = 1 << logN, 40
+    t = R.tier_spec(n, k, logN, l, beta, 1, 2.0 ** (-62 if logN >= 12 else -52))
+    s, S = oracle.gen_binary_key(31, n), oracle.gen_binary_key(32, k * N)
+    bsk = oracle.bsk_gen(s, S, k, N, l, beta, t.glwe_sigma, 33)
+    w, count = min(6, logN - 5), 8 if logN <= 11 else 4
+    msgs = (np.arange(count, dtype=np.uint64) * np.uint64(37)) % np.uint64(2 << w)
+    small = oracle.lwe_encrypt(s, n, msgs << np.uint64(63 - w), 2.0 ** -30, 34)
+    table = np.random.default_rng(35).integers(-8, 8, 1 << w).astype(np.int64) << 57
+    a = oracle.pbs(small, oracle.bsk_to_fourier(bsk), None, k, N, l, beta, table, w, None, k * N)
+    b = oracle.pbs(small, None, bsk, k, N, l, beta, table, w, None, k * N, exact=True)
+    ph_a, ph_b = oracle.lwe_phase(S, k * N, a), oracle.lwe_phase(S, k * N, b)
+    want = R.message_expected(table, np.zeros(count, np.int64), w, msgs)
+    dec = lambda p: ((p + (np.uint64(1) << np.uint64(56))) >> np.uint64(57)) & np.uint64(127)
+    assert np.array_equal(dec(ph_a), dec(want)) and np.array_equal(dec(ph_b), dec(want))
+    rms = math.sqrt(np.mean(_cent(ph_a - ph_b) ** 2))
+    unit = R.diff_bound(t) / (math.sqrt(2.0) * R.FFT_WINDOW)
+    print("f64 - exact, rms / sqrt(n (fft + dec)): %.3f" % (rms / unit))
+    assert rms < R.diff_bound(t), (rms, R.diff_bound(t))
+    assert max(np.abs(_cent(ph_a - want)).max(), np.abs(_cent(ph_b - want)).max()) < R.max_bound(t)

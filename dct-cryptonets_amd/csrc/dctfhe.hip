@@ -1078,6 +1078,23 @@ extern "C" int dctfhe_decrypt(dctfhe_ctx* ctx, dctfhe_client_key* C, const uint6
   if (!C) return fail("dctfhe_decrypt: null argument");
   return dctfhe_decrypt_rows(ctx, C, cts, count, C->p.D, phases);
 }
+// packed results (dctfhe_keyswitch_pack, dctfhe_session_download_packed): rows of n + 1 u16 under the first n bits of the small key
+extern "C" int dctfhe_decrypt_packed(dctfhe_ctx* ctx, dctfhe_client_key* C, int n, const uint16_t* rows, size_t count, uint64_t* phases) {
+  if (!ctx || !C || (count && (!rows || !phases))) return fail("dctfhe_decrypt_packed: null argument");
+  if (n < 1 || n > C->p.n_max) return fail("dctfhe_decrypt_packed: rows of %d mask words, the small key has %d", n, C->p.n_max);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t bytes = count * (size_t)(n + 1) * sizeof(uint16_t);
+  DevBuf d_ph, d_rows;
+  HIPCHK(d_ph.alloc(count * 8));
+  HIPCHK(d_rows.alloc(bytes));
+  HIPCHK(hipMemcpyAsync(d_rows.p, rows, bytes, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_phase16, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, C->d_s, n, d_rows.as<uint16_t>(), count, d_ph.as<uint64_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(phases, d_ph.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
 
 // ---- seeded input ciphertexts: the mask of ciphertext c is the draw (enc_pub, stream, c (D + 1) + j), j < input_dim, and enc_pub is one
 // ChaCha20 block of the handle's secret encryption key -- the client ships (enc_pub, stream, bodies), the server regenerates the masks
@@ -1420,6 +1437,42 @@ extern "C" int dctfhe_keyswitch_prefix(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
 }
 extern "C" int dctfhe_keyswitch(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, int shift, uint64_t* cts_small) {
   return dctfhe_keyswitch_prefix(ctx, K, tier, cts, count, shift, 0, cts_small);
+}
+
+// Packed results: `count` device rows of stride L words (the first deff mask words may be non-zero) key-switched
+// to `tier` at shift 0 and rounded to 16-bit rows [count][n + 1] in HOST memory, sc.chunk ciphertexts at a time.  The packed chunk goes
+// through a device buffer of its own: a chunk of odd-length rows need not end on the 8-byte boundary k_pack16 stores at.
+static int dev_keyswitch_pack(dctfhe_keys* K, int tier, const uint64_t* d_rows, size_t L, int deff, size_t count, const LutScratch& sc, uint16_t* rows) {
+  const size_t n1 = (size_t)K->p.tiers[tier].n + 1;
+  hipStream_t st = K->ctx->stream;
+  DevBuf d_pack;
+  HIPCHK(d_pack.alloc(std::min(sc.chunk, count) * n1 * sizeof(uint16_t)));
+  for (size_t c0 = 0; c0 < count; c0 += sc.chunk) {
+    const size_t cn = std::min(sc.chunk, count - c0), words = cn * n1;
+    KsInput in;
+    in.rows = d_rows + c0 * L; in.L = L; in.deff = deff;
+    CHK(dev_keyswitch(K, tier, in, cn, sc, nullptr));
+    hipLaunchKernelGGL(k_pack16, dim3(ew_grid(words / 4)), dim3(256), 0, st, sc.small, words, d_pack.as<uint16_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rows + c0 * n1, d_pack.p, words * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+extern "C" int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, int dim, int deff,
+                                     uint16_t* rows) {
+  if (!ctx || !K || (count && (!cts || !rows))) return fail("dctfhe_keyswitch_pack: null argument");
+  if (tier < 0 || tier >= K->p.n_tiers) return fail("dctfhe_keyswitch_pack: tier %d out of range (%d tiers)", tier, K->p.n_tiers);
+  if (dim < 1 || dim > K->p.D) return fail("dctfhe_keyswitch_pack: rows of %d mask words, the key has %d", dim, K->p.D);
+  if (deff < 0 || deff > dim) return fail("dctfhe_keyswitch_pack: effective dimension %d outside [0, dim = %d]", deff, dim);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t L = (size_t)dim + 1;
+  DevBuf d_in;
+  HIPCHK(d_in.upload(cts, count * L * 8));
+  LutScratchOwner sc;
+  CHK(alloc_lut_scratch(K, std::min<size_t>(count, 16384), &sc.s));
+  return dev_keyswitch_pack(K, tier, d_in.as<uint64_t>(), L, deff ? deff : dim, count, sc.s, rows);
 }
 
 // the centred mod switch on host buffers (the scheduler applies it between every key switch and its bootstrap)
@@ -2073,6 +2126,17 @@ extern "C" int dctfhe_session_download_rows(dctfhe_session* s, uint64_t* cts_out
 extern "C" int dctfhe_session_download(dctfhe_session* s, uint64_t* cts_out) {
   if (!s) return fail("dctfhe_session_download: null argument");
   return dctfhe_session_download_rows(s, cts_out, s->D);
+}
+// the outputs as packed rows: key-switched to `tier` straight from the output tensor (its stored stride and effective dimension) with the
+// session's look-up scratch, at download time -- dctfhe_session_run and its timing do not know about it
+extern "C" int dctfhe_session_download_packed(dctfhe_session* s, int tier, uint16_t* rows) {
+  if (!s || !rows) return fail("dctfhe_session_download_packed: null argument");
+  if (!s->keys) return fail("dctfhe_session_download_packed: a clear-mode session holds phases, not ciphertexts (dctfhe_session_download)");
+  if (tier < 0 || tier >= s->keys->p.n_tiers) return fail("dctfhe_session_download_packed: tier %d out of range (%d tiers)", tier, s->keys->p.n_tiers);
+  HIPCHK(hipSetDevice(s->ctx->device));
+  const int t = s->circ->output_tensor;
+  const size_t Ls = s->t_L[t];
+  return dev_keyswitch_pack(s->keys, tier, s->d_tensor[t], Ls, (int)s->t_deff[t], s->tensor_words[t] / Ls, s->lut.s, rows);
 }
 
 extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {

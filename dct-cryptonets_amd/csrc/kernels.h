@@ -556,6 +556,41 @@ __global__ void __launch_bounds__(256) k_ms_center(uint64_t* __restrict__ small,
   if (lane == 0) ct[n] -= (uint64_t)(part >> 1);
 }
 
+// ---- packed results: key-switched ciphertexts as 16-bit rows ---------------------------------------
+// A result only has to survive the decode margin 2^-(out_bits + 3), so once it is key-switched to a small key the top 16 bits of every
+// word are all the client needs: word -> (word + 2^47) >> 48, round to nearest on the 2^-16 grid, a tie goes up, a carry out of the top
+// wraps to 0 (the u64 sum wraps).
+__device__ __forceinline__ uint64_t round16(uint64_t v) { return (v + (1ULL << 47)) >> 48; }
+
+// small [words] u64 -> rows [words] u16.  A row has n + 1 words, odd for even n, so rows are not 4-byte aligned: lanes run over the FLAT
+// array, four consecutive results each, one 8-byte store per lane; the words % 4 results at the end go out as single u16 stores.
+__global__ void k_pack16(const uint64_t* __restrict__ small, size_t words, uint16_t* __restrict__ rows) {
+  const size_t quads = words / 4;
+  uint64_t* __restrict__ out4 = reinterpret_cast<uint64_t*>(rows);
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
+    const uint64_t* p = small + 4 * q;
+    out4[q] = round16(p[0]) | (round16(p[1]) << 16) | (round16(p[2]) << 32) | (round16(p[3]) << 48);
+  }
+  const size_t tail = 4 * quads + threadIdx.x;
+  if (blockIdx.x == 0 && tail < words) rows[tail] = (uint16_t)round16(small[tail]);
+}
+
+// client: phase of a packed row under the first n bits of the small key, on the 16-bit torus: (row[n] - sum_{j<n} s_j row[j]) mod 2^16,
+// returned as phase16 << 48.  One wave per row as in k_ms_center: lane-strided u16 loads, 32-bit partial sums (wrapping mod 2^32 keeps
+// the low 16 bits exact), butterfly reduction.
+__global__ void __launch_bounds__(256) k_phase16(const uint8_t* __restrict__ s, int n, const uint16_t* __restrict__ rows, size_t count,
+                                                 uint64_t* __restrict__ phases) {
+  const size_t c = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (c >= count) return;
+  const uint16_t* row = rows + c * (size_t)(n + 1);
+  uint32_t part = 0;
+  for (int j = lane; j < n; j += 64)
+    if (s[j]) part += row[j];
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+  if (lane == 0) phases[c] = (uint64_t)(((uint32_t)row[n] - part) & 0xFFFFu) << 48;
+}
+
 // ------------------------------------------------------------------------------------------ K4-K6 bootstrap
 struct pbs_launch {
   const uint64_t* cts_small;  // count x (n+1)

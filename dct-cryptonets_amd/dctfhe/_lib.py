@@ -49,6 +49,7 @@ EXPORTS = [
     "dctfhe_encrypt_seeded", "dctfhe_expand_seeded", "dctfhe_session_upload_seeded", "dctfhe_eval_keys_export_compressed",
     "dctfhe_eval_keys_decompress_bsk", "dctfhe_keyswitch_diff", "dctfhe_max_pool_rows",
     "dctfhe_round_lut_split", "dctfhe_session_set_noise_split",
+    "dctfhe_session_download_packed", "dctfhe_keyswitch_pack", "dctfhe_decrypt_packed",
 ]
 
 _lib = None
@@ -127,6 +128,9 @@ def load():
     L.dctfhe_eval_keys_decompress_bsk.argtypes = [vp, vp, sz, i32, vp]
     L.dctfhe_keyswitch_diff.argtypes = [vp, vp, i32, vp, sz, vp, vp, i32, u64, i32, vp]
     L.dctfhe_max_pool_rows.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]
+    L.dctfhe_session_download_packed.argtypes = [vp, i32, vp]
+    L.dctfhe_keyswitch_pack.argtypes = [vp, vp, i32, vp, sz, i32, i32, vp]
+    L.dctfhe_decrypt_packed.argtypes = [vp, vp, i32, vp, sz, vp]
     _lib = L
     return L
 

@@ -282,6 +282,34 @@ class CompiledCircuit:
         return "\n".join(lines)
 
 
+@dataclass
+class OutputCompaction:
+    """how a circuit's results travel packed (include/dctfhe.h dctfhe_session_download_packed): key-switched to `tier`, 16 bits per word"""
+    tier: int
+    name: str
+    n: int
+    bytes_per_ciphertext: int      # 2 (n + 1)
+    var: float                     # what the key switch and the 16-bit rounding add (torus^2)
+    pfail: float                   # per result, against the decode margin 2^-(out_bits + 3)
+
+
+def output_compaction(circ):
+    """The tier whose key-switch key packs this circuit's results: among the tiers that own one (ksk_share < 0), the least
+    var_keyswitch(deff_out, t) + var_round16(t.n).  Raises ValueError when a packed result would leave the catalogue's failure budget."""
+    ps, out = circ.param_set, circ.tensors[circ.output_tensor]
+    deff = out.deff or ps.D
+    var, ti = min((P.var_keyswitch(deff, t) + P.var_round16(t.n), i) for i, t in enumerate(ps.tiers) if t.ksk_share < 0)
+    t = ps.tiers[ti]
+    margin = 2.0 ** -(circ.out_bits + 3)
+    pfail = P.p_fail(margin, out.var + var)
+    budget = getattr(ps, "p_budget", 1e-12)
+    if pfail > budget:
+        raise ValueError(f"packed results leave the budget: best tier {t.name} (n = {t.n}) adds sigma 2^{0.5 * math.log2(var):.1f} to an output of "
+                         f"sigma 2^{0.5 * math.log2(max(out.var, 2.0 ** -128)):.1f} at effective dimension {deff}; margin 2^-{circ.out_bits + 3}, "
+                         f"p_fail {pfail:.1e} per result > {budget:.1e}")
+    return OutputCompaction(tier=ti, name=t.name, n=t.n, bytes_per_ciphertext=2 * (t.n + 1), var=var, pfail=pfail)
+
+
 def step_tier(o, i):
     """tier index of rounding step i of look-up op `o`: bit tier, from ip[8] on the coarse twin ip[7], from ip[11] & 255 on ip[11] >> 8"""
     t = o.ip[5]

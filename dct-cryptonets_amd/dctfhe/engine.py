@@ -184,6 +184,46 @@ class SeededCiphertexts:
         return cls(blob[H:H + 32], stream, D, input_dim, np.frombuffer(blob, np.uint64, count, H + 32).copy())
 
 
+class PackedCiphertexts:
+    """Result ciphertexts in PACKED form (include/dctfhe.h dctfhe_session_download_packed): key-switched to a small key of n bits and
+    rounded to 16 bits per word, rows [count, n + 1] of uint16.  Wire form: to_bytes / from_bytes (little-endian)."""
+
+    MAGIC, VERSION = b"DPCT", 1
+    _HDR = struct.Struct("<4sIiQ")            # magic, version, n, count; then count x (n + 1) u16
+
+    def __init__(self, n, rows):
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"packed ciphertexts need n >= 1 (got {n})")
+        rows = np.ascontiguousarray(rows, np.uint16)
+        if rows.size % (n + 1):
+            raise ValueError(f"{rows.size} words are not rows of n + 1 = {n + 1}")
+        self.n, self.rows = n, rows.reshape(-1, n + 1)
+
+    def __len__(self):
+        return self.rows.shape[0]
+
+    @property
+    def nbytes(self):
+        return self._HDR.size + self.rows.nbytes
+
+    def to_bytes(self):
+        return self._HDR.pack(self.MAGIC, self.VERSION, self.n, self.rows.shape[0]) + self.rows.astype("<u2", copy=False).tobytes()
+
+    @classmethod
+    def from_bytes(cls, blob):
+        blob = bytes(blob)
+        H = cls._HDR.size
+        if len(blob) < H:
+            raise ValueError("packed-ciphertext blob too short")
+        magic, version, n, count = cls._HDR.unpack_from(blob)
+        if magic != cls.MAGIC or version != cls.VERSION:
+            raise ValueError("not a packed-ciphertext blob (magic / version)")
+        if n < 1 or len(blob) != H + 2 * count * (n + 1):
+            raise ValueError(f"packed-ciphertext blob of {len(blob)} bytes, its header says n = {n}, {count} rows")
+        return cls(n, np.frombuffer(blob, "<u2", count * (n + 1), H).astype(np.uint16))
+
+
 class ClientKey:
     """Secret side (include/dctfhe.h dctfhe_client_key): encrypts, decrypts, generates evaluation keys."""
 
@@ -265,6 +305,12 @@ class ClientKey:
         check(self.L.dctfhe_decrypt_rows(self.ctx.h, self.h, ptr(cts), cts.shape[0], dim, ptr(out)))
         return out
 
+    def decrypt_packed(self, packed):
+        """PackedCiphertexts -> phases (phase16 << 48: QuantizedModule.decode_output reads them like decrypt's)"""
+        out = np.empty(len(packed), np.uint64)
+        check(self.L.dctfhe_decrypt_packed(self.ctx.h, self.h, packed.n, ptr(packed.rows), len(packed), ptr(out)))
+        return out
+
     def close(self):
         if self.h:
             self.L.dctfhe_client_key_destroy(self.h)
@@ -313,6 +359,14 @@ class EvalKeys:
         out = np.empty((cts.shape[0], self.tier(tier).n + 1), np.uint64)
         check(self.L.dctfhe_keyswitch_prefix(self.ctx.h, self.h, tier, ptr(cts), cts.shape[0], shift, deff, ptr(out)))
         return out
+
+    def keyswitch_pack(self, tier, cts, dim, deff=0):
+        """rows of dim mask words + body -> PackedCiphertexts under tier's small key (dctfhe_keyswitch_pack); deff as in keyswitch"""
+        cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, int(dim) + 1)
+        n = self.tier(tier).n
+        out = np.empty((cts.shape[0], n + 1), np.uint16)
+        check(self.L.dctfhe_keyswitch_pack(self.ctx.h, self.h, tier, ptr(cts), cts.shape[0], int(dim), int(deff), ptr(out)))
+        return PackedCiphertexts(n, out)
 
     def keyswitch_diff(self, tier, cts, ia, ib, shift=0, body_add=0, deff=0):
         """key switch of cts[ia[c]] - cts[ib[c]] (dctfhe_keyswitch_diff): small ciphertexts [len(ia), n + 1]"""
@@ -388,9 +442,9 @@ class Keys:
 
     def __getattr__(self, name):
         if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter",
-                    "encrypt_seeded", "export_eval_keys_compressed"):
+                    "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed"):
             return getattr(self.client, name)
-        if name in ("export_ksk", "keyswitch", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
+        if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
         raise AttributeError(name)
 
@@ -482,6 +536,14 @@ class Session:
             out = np.empty((self.batch, self.circuit.n_out, dim + 1), np.uint64)
             check(self.L.dctfhe_session_download_rows(self.h, ptr(out), int(dim)))
         return out
+
+    def download_packed(self, tier):
+        """the outputs key-switched to `tier` and packed to 16 bits per word (dctfhe_session_download_packed): PackedCiphertexts of
+        batch x n_out rows; encrypted sessions only"""
+        n = self.keys.tier(tier).n if (self.keys is not None and 0 <= tier < self.keys.params.n_tiers) else 0      # the library refuses the rest
+        out = np.empty((self.batch * self.circuit.n_out, n + 1), np.uint16)
+        check(self.L.dctfhe_session_download_packed(self.h, int(tier), ptr(out)))
+        return PackedCiphertexts(n, out)
 
     def close(self):
         if self.h:

@@ -119,6 +119,12 @@ def var_pbs_out(t, fft_c=2.0):
     return t.n * (ext + fft)
 
 
+def var_round16(n):
+    """packed results (csrc/kernels.h k_pack16): every word of a small ciphertext rounded to the 2^-16 torus grid.  The phase keeps
+    sum_i s_i e_i + e_b with e uniform on +-2^-17: n/2 + 1 units of 2^-32 / 12 (binary key, half the bits set; plain rounding)."""
+    return (n / 2.0 + 1.0) * 2.0 ** -32 / 12.0
+
+
 def p_fail(margin, var):
     """two-sided Gaussian tail beyond `margin`"""
     if var <= 0:

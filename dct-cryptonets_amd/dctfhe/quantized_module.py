@@ -4,7 +4,8 @@
     compile_brevitas_qat_model(...)  homomorphic_eval.py:276    compile_brevitas_qat_model -> QuantizedModule
     compile_torch_model(...)         homomorphic_eval.py:287    compile_torch_model (same circuit builder)
     Configuration(...)               homomorphic_eval.py:266    Configuration (progress flags kept, inert; compress_input_ciphertexts,
-                                                                compress_evaluation_keys: seeded inputs / compressed evaluation keys)
+                                                                compress_evaluation_keys: seeded inputs / compressed evaluation keys;
+                                                                compress_output_ciphertexts: packed 16-bit results)
     q.fhe_circuit.graph.maximum_integer_bit_width()    :301     FHECircuit.graph.maximum_integer_bit_width()
     q.fhe_circuit.mlir                                 :311     FHECircuit.mlir  (text dump of the compiled circuit)
     q.fhe_circuit.keygen()                             :315     FHECircuit.keygen()  (keys generated on the GPU)
@@ -20,19 +21,22 @@ import numpy as np
 
 from . import compile as cc
 from . import params as P
-from .engine import Circuit, Context, Keys, SeededCiphertexts, Session
+from .engine import Circuit, Context, Keys, PackedCiphertexts, SeededCiphertexts, Session
 
 
 class Configuration:
     """Stand-in for concrete.fhe.Configuration (reference homomorphic_eval.py:266-273)."""
 
     def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
-                 compress_evaluation_keys=False, **kwargs):
+                 compress_evaluation_keys=False, compress_output_ciphertexts=False, **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
         # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
         # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
         self.compress_input_ciphertexts = bool(compress_input_ciphertexts)
         self.compress_evaluation_keys = bool(compress_evaluation_keys)
+        # dctfhe addition (like tier_policy): results come back key-switched to a small key and rounded to 16 bits per word
+        # (include/dctfhe.h dctfhe_session_download_packed; the tier is dctfhe.compile.output_compaction's).  Off by default.
+        self.compress_output_ciphertexts = bool(compress_output_ciphertexts)
         self.extra = kwargs
 
 
@@ -65,8 +69,8 @@ class FHECircuit:
     def load_evaluation_keys(self, blob):
         return self._o.load_evaluation_keys(blob)
 
-    def evaluate_encrypted(self, cts, batch, dim=None):
-        return self._o.evaluate_encrypted(cts, batch, dim)
+    def evaluate_encrypted(self, cts, batch, dim=None, packed=None):
+        return self._o.evaluate_encrypted(cts, batch, dim, packed)
 
     @property
     def statistics(self):
@@ -88,6 +92,7 @@ class QuantizedModule:
         self.last_timing = None
         self.last_io = None
         self.sim_seed = 977
+        self._compaction = None
 
     # -- lazy device objects -------------------------------------------------------------
     def _context(self):
@@ -115,6 +120,13 @@ class QuantizedModule:
             self._sessions[key] = Session(ctx, self._circuit, self._keys if mode == "execute" else None, batch)
         return self._sessions[key]
 
+    def output_compaction(self):
+        """the tier packed results are key-switched to (dctfhe.compile.output_compaction); raises ValueError where packing would leave
+        the catalogue's failure budget"""
+        if self._compaction is None:
+            self._compaction = cc.output_compaction(self.compiled)
+        return self._compaction
+
     # -- client / server split (reference homomorphic_eval.py:313-317 keeps both halves in one process) ------------
     def export_evaluation_keys(self, compressed=None):
         """client side: the evaluation keys as a flat uint8 blob to ship to the server (no secret inside).  compressed (default:
@@ -140,18 +152,24 @@ class QuantizedModule:
             self._keys.close()
         self._keys = EvalKeys.from_blob(ctx, blob)
 
-    def evaluate_encrypted(self, cts, batch, dim=None):
+    def evaluate_encrypted(self, cts, batch, dim=None, packed=None):
         """server side: input ciphertexts [batch * n_in, D+1] -> output ciphertexts [batch * n_out, D+1]; dim: the compact wire
         form instead -- input rows of dim mask words + body, output rows of Session.dims()[1] mask words + body.  cts may also be
-        SeededCiphertexts (or their to_bytes() form): the masks are regenerated on the GPU; dim then only selects the output form"""
+        SeededCiphertexts (or their to_bytes() form): the masks are regenerated on the GPU; dim then only selects the output form.
+        packed (default: Configuration.compress_output_ciphertexts): the outputs as PackedCiphertexts instead, whatever dim says"""
         if isinstance(cts, (bytes, bytearray, memoryview)):
             cts = SeededCiphertexts.from_bytes(cts)
+        if packed is None:
+            packed = self.configuration.compress_output_ciphertexts
+        tier = self.output_compaction().tier if packed else None
         sess = self._session("execute", batch)
         if isinstance(cts, SeededCiphertexts):
             sess.upload_seeded(cts)
         else:
             sess.upload(cts, dim)
         sess.run()
+        if packed:
+            return sess.download_packed(tier)
         if dim is None:
             return sess.download().reshape(-1, self._keys.D + 1)
         out_dim = sess.dims()[1]
@@ -173,6 +191,20 @@ class QuantizedModule:
         e = self.compiled.e_out
         v = (phases + (np.uint64(1) << np.uint64(e - 1))).view(np.int64) >> np.int64(e)     # signed, rounded
         return v
+
+    def decrypt_result(self, x):
+        """client side: what evaluate_encrypted returned -> decoded integers [B, F].  x: PackedCiphertexts or their to_bytes() form, or
+        rows [B * F, dim + 1] of uint64 (full width or the compact wire form)"""
+        if self._keys is None or not hasattr(self._keys, "decrypt"):
+            raise RuntimeError("decrypting needs the client key (fhe_circuit.keygen); this module holds evaluation keys only")
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            x = PackedCiphertexts.from_bytes(x)
+        if isinstance(x, PackedCiphertexts):
+            ph = self._keys.decrypt_packed(x)
+        else:
+            x = np.asarray(x)
+            ph = self._keys.decrypt(x, x.shape[-1] - 1)
+        return self.decode_output(ph.reshape(-1, self.compiled.n_out()))
 
     def dequantize_output(self, q):
         return q.astype(np.float64) * self.compiled.out_scale
@@ -208,6 +240,9 @@ class QuantizedModule:
             # Configuration(compress_input_ciphertexts=True): only the bodies travel (seeded form), the GPU regenerates the masks
             in_dim, out_dim = sess.dims()
             seeded = self.configuration.compress_input_ciphertexts
+            # Configuration(compress_output_ciphertexts=True): results come back packed (refused here, before anything is encrypted,
+            # where the compiler's price for it leaves the budget)
+            pack_tier = self.output_compaction().tier if self.configuration.compress_output_ciphertexts else None
             t1 = time.time()
             cts = self._keys.encrypt_seeded(phases.reshape(-1)) if seeded else self._keys.encrypt(phases.reshape(-1), in_dim)
             t2 = time.time()
@@ -218,9 +253,15 @@ class QuantizedModule:
             t3 = time.time()
             timing = sess.run(timing=True)
             t4 = time.time()
-            out = sess.download(out_dim).reshape(-1, out_dim + 1)
-            t5 = time.time()
-            out_ph = self._keys.decrypt(out, out_dim).reshape(B, -1)
+            if pack_tier is None:
+                out = sess.download(out_dim).reshape(-1, out_dim + 1)
+                t5 = time.time()
+                out_ph = self._keys.decrypt(out, out_dim).reshape(B, -1)
+            else:
+                pk = sess.download_packed(pack_tier)
+                out = pk.rows
+                t5 = time.time()
+                out_ph = self._keys.decrypt_packed(pk).reshape(B, -1)
             self.last_io = dict(encrypt_s=t2 - t1, upload_s=t3 - t2, run_s=t4 - t3, download_s=t5 - t4, decrypt_s=time.time() - t5,
                                 input_bytes=int(cts.nbytes), output_bytes=int(out.nbytes),
                                 upload_bytes=int(cts.bodies.nbytes if seeded else cts.nbytes))

@@ -277,6 +277,28 @@ int dctfhe_session_set_noise(dctfhe_session* s, uint64_t seed, const double* sig
 int dctfhe_session_set_noise_split(dctfhe_session* s, const double* sigma2_per_op, int n_ops);
 int dctfhe_session_download(dctfhe_session* s, uint64_t* cts_out /* batch x n_out x (D+1) */);
 
+/* PACKED result ciphertexts.  A result carries a signed out_bits-bit value plus padding: its decode margin is
+ * 2^-(out_bits + 3), far wider than a 64-bit word resolves.  The server therefore key-switches each result to the small key of `tier`
+ * with the key-switch key it already holds (the tier's own, or the one it shares: ksk_share) -- shift 0, the sum over the first deff key
+ * rows, exactly the n + 1 words dctfhe_keyswitch_prefix(tier, shift = 0, deff) returns -- and keeps the top 16 bits of every word:
+ *     row[j] = (uint16_t)((small[j] + 2^47) >> 48),  j = 0 .. n
+ * (round to nearest on the 2^-16 torus grid, a tie goes up, a carry out of the top wraps to 0; plain rounding, not centred).  Host form:
+ * count x (n + 1) little-endian uint16_t, rows contiguous (odd row length for even n: rows are not 4-byte aligned).  2 (n + 1) bytes per
+ * result instead of 8 (out_dim + 1).  Which tier keeps the result inside its margin is the compiler's call (dctfhe.compile
+ * output_compaction); no new key material is involved.
+ *
+ * dctfhe_session_download_packed: the session's outputs in that form.  Runs at download time with the session's look-up scratch, in chunks
+ * of at most 16384 ciphertexts; dctfhe_session_run and dctfhe_timing do not see it.  Encrypted sessions only. */
+int dctfhe_session_download_packed(dctfhe_session* s, int tier, uint16_t* rows /* batch x n_out x (n+1) */);
+/* The primitive on host rows of dim mask words + body (words from deff on count as zero; deff = 0: dim), 1 <= dim <= D, 0 <= deff <= dim,
+ * with dctfhe_keyswitch_prefix's contract for deff: the caller knows every mask word from deff on to be zero. */
+int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, const uint64_t* cts /* count x (dim+1) */, size_t count, int dim,
+                          int deff, uint16_t* rows /* count x (n+1) */);
+/* CLIENT: phases of packed rows under the first n bits of the small key (n = the tier's small dimension, 1 <= n <= n_max):
+ *     phase16 = (row[n] - sum_{j<n} s_j row[j]) mod 2^16,  returned as (uint64_t)phase16 << 48
+ * so that whatever decodes dctfhe_decrypt's phases decodes these. */
+int dctfhe_decrypt_packed(dctfhe_ctx* ctx, dctfhe_client_key* client, int n, const uint16_t* rows, size_t count, uint64_t* phases);
+
 /* f64 FMA peak micro-benchmark (TFLOP/s) used to price the blind-rotate kernel in bench.py. */
 int dctfhe_fp64_peak(dctfhe_ctx* ctx, double* tflops);
 /* stand-alone timing of the blind-rotate kernel: count ciphertexts of tier `tier`, average ms per launch */

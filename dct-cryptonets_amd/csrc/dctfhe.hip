@@ -8,6 +8,7 @@
 #include <array>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -315,8 +316,22 @@ struct dctfhe_session {
   // per op: the tree of a max pool (index maps in device memory) and its two level buffers (planner-owned, reused after the op)
   std::vector<std::unique_ptr<PoolPlan>> pool;
   std::vector<std::array<uint64_t*, 2>> pool_buf;
+  // margin audit (dctfhe_session_set_audit): off unless d_audit_key is set.  The session's own copy of the small key, one slot per
+  // (op, bootstrap with a key switch of its own) on the device, their fixed fields, each op's first slot, and the last run's slots
+  uint8_t* d_audit_key = nullptr;
+  size_t audit_key_bytes = 0;
+  margin_slot* d_audit = nullptr;
+  std::vector<dctfhe_margin_stats> audit_slots, audit_last;
+  std::vector<int> audit_first;
+  void audit_off() {
+    if (d_audit_key) { hipMemset(d_audit_key, 0, audit_key_bytes); hipFree(d_audit_key); }    // the secret does not outlive the audit
+    hipFree(d_audit);
+    d_audit_key = nullptr; d_audit = nullptr; audit_key_bytes = 0;
+    audit_slots.clear(); audit_last.clear(); audit_first.clear();
+  }
   ~dctfhe_session() {
     if (ctx) hipSetDevice(ctx->device);
+    audit_off();
     for (auto& o : owned) hipFree(o.second);
     for (hipEvent_t e : ev_pool) hipEventDestroy(e);
     hipFree(d_overflow);
@@ -1259,10 +1274,29 @@ static int dev_pbs(dctfhe_keys* K, int tier, const uint64_t* d_small, size_t cou
   if (tm) tm->end(h);
   return 0;
 }
-// key switch of `in` to tier `tier`, centred mod switch, bootstrap: what every look-up with a key switch of its own runs on a chunk
-static int dev_ks_pbs(dctfhe_keys* K, int tier, const KsInput& in, size_t count, const PbsLut& lut, const PbsOut& out, const LutScratch& sc, Timers* tm) {
+// margin audit: where a probe of the switched small ciphertexts goes -- the secret small key (device bytes) and the slot of the site's
+// FIRST bootstrap with a key switch of its own; dev_round_lut / dev_max_pool pass the slot of the one they launch to dev_ks_pbs
+struct MarginProbe {
+  const uint8_t* key = nullptr; margin_slot* slot = nullptr;
+  MarginProbe at(int entry) const { return MarginProbe{key, slot + entry}; }
+};
+static unsigned margin_grid(size_t count) { return (unsigned)std::max<size_t>(1, std::min<size_t>((count + 3) / 4, 1024)); }
+// the probe kernel on `count` small ciphertexts of `tier` about to meet a table of w input bits; outside every Timers span
+static int dev_margin_probe(hipStream_t st, const dctfhe_tier& t, const uint8_t* d_key, const uint64_t* d_small, size_t count, int w, int32_t* d_err,
+                            margin_slot* d_slot) {
+  if (count == 0) return 0;
+  if (w < 0 || t.logN - w < 1) return fail("margin probe: a table of %d input bits leaves no box on a ring of 2^%d", w, t.logN);
+  hipLaunchKernelGGL(k_margin_probe, dim3(margin_grid(count)), dim3(256), 0, st, d_key, d_small, count, t.n, t.logN, w, d_err, d_slot);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// key switch of `in` to tier `tier`, centred mod switch, bootstrap: what every look-up with a key switch of its own runs on a chunk.
+// probe (the margin audit; nullptr everywhere else): the switched small ciphertexts are measured on the way
+static int dev_ks_pbs(dctfhe_keys* K, int tier, const KsInput& in, size_t count, const PbsLut& lut, const PbsOut& out, const LutScratch& sc, Timers* tm,
+                      const MarginProbe* probe = nullptr) {
   CHK(dev_keyswitch(K, tier, in, count, sc, tm));
   CHK(dev_ms_center(K, tier, sc.small, count, tm));
+  if (probe) CHK(dev_margin_probe(K->ctx->stream, K->p.tiers[tier], probe->key, sc.small, count, lut.w, nullptr, probe->slot));
   return dev_pbs(K, tier, sc.small, count, lut, out, tm);
 }
 
@@ -1301,7 +1335,9 @@ struct LutRows {
   const int32_t* idx = nullptr;
 };
 static size_t ring_of(const dctfhe_keys* K, int tier) { return (size_t)K->p.tiers[tier].k << K->p.tiers[tier].logN; }
-static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, size_t count, int hw, const LutScratch& sc, Timers* tm, int deff) {
+// probe: the margin audit's slots of this site in for_each_bootstrap order -- steps, a split's second look-up, the table
+static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, size_t count, int hw, const LutScratch& sc, Timers* tm, int deff,
+                         const MarginProbe* probe = nullptr) {
   const bool split = L.split();
   const int p = L.p, steps = L.n_steps(), nchan = L.ntab, tab_tier = L.tab_tier, tier2 = L.tier2(K->p);
   const size_t Lw = b.Lw, ring2 = split ? ring_of(K, tier2) : 0;
@@ -1320,7 +1356,8 @@ static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, siz
       const int vlog = 62 - p + i;
       KsInput in = work; in.shift = p - i;
       PbsOut bit{w0, Lw}; bit.accumulate = true; bit.body_add = (uint64_t)0 - (1ULL << vlog);
-      CHK(dev_ks_pbs(K, L.steps.at(i), in, cn, PbsLut{sc.bit_tables + vlog}, bit, sc, tm));
+      const MarginProbe pr = probe ? probe->at(i) : MarginProbe{};
+      CHK(dev_ks_pbs(K, L.steps.at(i), in, cn, PbsLut{sc.bit_tables + vlog}, bit, sc, tm, probe ? &pr : nullptr));
     }
     if (split) {
       // t = 2 t' + b0 sits under the padding bit once the r rounding steps are done.  The last step was one more of them, on b0: it left
@@ -1331,10 +1368,12 @@ static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, siz
       CHK(dev_pbs(K, L.steps.at(steps - 1), sc.small, cn, PbsLut{sc.bit_tables + 62}, par, tm));
       KsInput sum = work; sum.source = KS_SUM; sum.rows_b = b.par; sum.Lb = b.Lp;
       PbsLut tab2 = tab; tab2.tables = b.tab_d;
-      CHK(dev_ks_pbs(K, tier2, sum, cn, tab2, PbsOut{b.par, b.Lp}, sc, tm));
+      const MarginProbe pr = probe ? probe->at(steps) : MarginProbe{};
+      CHK(dev_ks_pbs(K, tier2, sum, cn, tab2, PbsOut{b.par, b.Lp}, sc, tm, probe ? &pr : nullptr));
     }
     if (steps == 0) { work.rows = b.src + c0 * b.Ls; work.L = b.Ls; work.shift = L.shift; work.body_add = L.round_add(); }   // nothing modified the input
-    CHK(dev_ks_pbs(K, tab_tier, work, cn, tab, PbsOut{w0, Lw}, sc, tm));
+    const MarginProbe pr = probe ? probe->at(steps + (split ? 1 : 0)) : MarginProbe{};
+    CHK(dev_ks_pbs(K, tab_tier, work, cn, tab, PbsOut{w0, Lw}, sc, tm, probe ? &pr : nullptr));
     if (split) {
       const int h = tm ? tm->begin(CAT_LINEAR) : -1;
       hipLaunchKernelGGL(k_acc_rows, dim3(ew_grid(cn * (ring2 + 1))), dim3(256), 0, K->ctx->stream, w0, Lw, b.par, b.Lp, cn, ring2);
@@ -1375,7 +1414,8 @@ static int alloc_lut_scratch(dctfhe_keys* K, size_t chunk, LutScratch* sc) {
 // stride Lo, of which the first `dout` = max(ds, ring of the tier) mask words may be non-zero.  Each level: the gather, then per chunk the
 // key switch of the differences (KS_DIFF), the centred mod switch and the relu bootstrap accumulated into the gathered b rows.
 static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, const uint64_t* d_in, size_t Ls, size_t ds, uint64_t* const bufs[2],
-                        uint64_t* d_out, size_t Lo, size_t dout, const int64_t* d_table, const LutScratch& sc, Timers* tm) {
+                        uint64_t* d_out, size_t Lo, size_t dout, const int64_t* d_table, const LutScratch& sc, Timers* tm,
+                        const MarginProbe* probe = nullptr) {
   hipStream_t st = K->ctx->stream;
   const int tier = S.tier;
   const int32_t* maps = P.maps.as<int32_t>();
@@ -1393,7 +1433,7 @@ static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, co
       diff.rows = src; diff.L = L_src; diff.deff = (int)d_src; diff.shift = S.shift; diff.body_add = S.body_add;
       diff.source = KS_DIFF; diff.ia = maps + l.a_off + c0; diff.ib = maps + l.b_off + c0;
       PbsOut acc{dst + c0 * Lo, Lo}; acc.accumulate = true;
-      CHK(dev_ks_pbs(K, tier, diff, cn, PbsLut{d_table, S.p_d}, acc, sc, tm));
+      CHK(dev_ks_pbs(K, tier, diff, cn, PbsLut{d_table, S.p_d}, acc, sc, tm, probe));
     }
   }
   return 0;
@@ -2139,6 +2179,77 @@ extern "C" int dctfhe_session_download_packed(dctfhe_session* s, int tier, uint1
   return dev_keyswitch_pack(s->keys, tier, s->d_tensor[t], Ls, (int)s->t_deff[t], s->tensor_words[t] / Ls, s->lut.s, rows);
 }
 
+// ---- margin audit (include/dctfhe.h): the slots are those of for_each_bootstrap, the kernel k_margin_probe
+static_assert(sizeof(margin_slot) == sizeof(dctfhe_margin_stats) && offsetof(margin_slot, max_abs) == offsetof(dctfhe_margin_stats, max_abs) &&
+              offsetof(margin_slot, count) == offsetof(dctfhe_margin_stats, count) && offsetof(margin_slot, sum_sq) == offsetof(dctfhe_margin_stats, sum_sq) &&
+              offsetof(margin_slot, hist) == offsetof(dctfhe_margin_stats, hist) && DCTFHE_MARGIN_BINS == 16, "k_margin_probe accumulates into dctfhe_margin_stats");
+static dctfhe_margin_stats margin_header(int op, int entry, int tier, int logN, int w) {
+  dctfhe_margin_stats m;
+  memset(&m, 0, sizeof m);
+  m.op = op; m.entry = entry; m.tier = tier; m.table_bits = w; m.half_box = 1 << (logN - w - 1);
+  return m;
+}
+// the run's accumulated fields under the slots' fixed ones
+static int session_audit_collect(dctfhe_session* s) {
+  s->audit_last = s->audit_slots;
+  if (s->audit_slots.empty()) return 0;
+  std::vector<dctfhe_margin_stats> dev(s->audit_slots.size());
+  HIPCHK(hipMemcpy(dev.data(), s->d_audit, dev.size() * sizeof(dctfhe_margin_stats), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < dev.size(); i++) {
+    dctfhe_margin_stats& m = s->audit_last[i];
+    m.max_abs = dev[i].max_abs; m.count = dev[i].count; m.sum = dev[i].sum; m.sum_sq = dev[i].sum_sq;
+    memcpy(m.hist, dev[i].hist, sizeof m.hist);
+  }
+  return 0;
+}
+extern "C" int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* C) {
+  if (!s) return fail("dctfhe_session_set_audit: null session");
+  HIPCHK(hipSetDevice(s->ctx->device));
+  if (!C) { s->audit_off(); return 0; }
+  if (!s->keys) return fail("dctfhe_session_set_audit: a clear-mode session holds phases, not ciphertexts: there is no decision noise to measure");
+  const dctfhe_params &P = s->keys->p, &Q = C->p;
+  if (C->ctx->device != s->ctx->device) return fail("dctfhe_session_set_audit: the client key lives on device %d, the session on %d", C->ctx->device, s->ctx->device);
+  if (P.D != Q.D || P.n_max != Q.n_max || P.n_tiers != Q.n_tiers)
+    return fail("dctfhe_session_set_audit: the client key (D = %d, n_max = %d, %d tiers) is of another parameter set than the session's keys (D = %d, n_max = %d, %d tiers)",
+                Q.D, Q.n_max, Q.n_tiers, P.D, P.n_max, P.n_tiers);
+  for (int t = 0; t < P.n_tiers; t++)
+    if (P.tiers[t].n != Q.tiers[t].n || P.tiers[t].k != Q.tiers[t].k || P.tiers[t].logN != Q.tiers[t].logN)
+      return fail("dctfhe_session_set_audit: tier %d of the client key (n = %d, k = %d, logN = %d) differs from the session's (n = %d, k = %d, logN = %d)", t,
+                  Q.tiers[t].n, Q.tiers[t].k, Q.tiers[t].logN, P.tiers[t].n, P.tiers[t].k, P.tiers[t].logN);
+  std::vector<dctfhe_margin_stats> slots;
+  std::vector<int> first;
+  for (size_t i = 0; i < s->circ->ops.size(); i++) {
+    const SiteOp& o = s->circ->ops[i];
+    if (o.type == OP_LUT && o.lut.approx())
+      return fail("dctfhe_session_set_audit: op %zu rounds approximately: the low bits ride along into its look-up, the distance from the box centre is not noise", i);
+    first.push_back((int)slots.size());
+    int entry = 0, err = 0;
+    for_each_bootstrap(o, P, [&](int tier, int bits, bool own_ks) {
+      if (!own_ks || err) return;
+      if (P.tiers[tier].logN - bits < 1) { err = fail("dctfhe_session_set_audit: op %zu: a table of %d input bits leaves no box on tier %d", i, bits, tier); return; }
+      slots.push_back(margin_header((int)i, entry++, tier, P.tiers[tier].logN, bits));
+    });
+    CHK(err);
+  }
+  s->audit_off();
+  s->audit_key_bytes = (size_t)P.n_max;
+  HIPCHK(hipMalloc(&s->d_audit_key, s->audit_key_bytes));
+  HIPCHK(hipMemcpy(s->d_audit_key, C->d_s, s->audit_key_bytes, hipMemcpyDeviceToDevice));
+  HIPCHK(hipMalloc(&s->d_audit, std::max<size_t>(1, slots.size()) * sizeof(margin_slot)));
+  HIPCHK(hipMemset(s->d_audit, 0, std::max<size_t>(1, slots.size()) * sizeof(margin_slot)));
+  s->audit_slots = slots; s->audit_last = slots; s->audit_first = first;
+  return 0;
+}
+extern "C" int dctfhe_session_audit(dctfhe_session* s, dctfhe_margin_stats* out, int capacity, int* n_slots) {
+  if (!s || !n_slots) return fail("dctfhe_session_audit: null argument");
+  const int n = s->d_audit_key ? (int)s->audit_last.size() : 0;
+  *n_slots = n;
+  if (!out) return 0;
+  if (capacity < n) return fail("dctfhe_session_audit: room for %d slots, the circuit has %d", capacity, n);
+  if (n) memcpy(out, s->audit_last.data(), (size_t)n * sizeof(dctfhe_margin_stats));
+  return 0;
+}
+
 extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
   HIPCHK(hipSetDevice(s->ctx->device));
   hipStream_t st = s->ctx->stream;
@@ -2150,8 +2261,13 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
   HIPCHK(hipEventRecord(e0, st));
   if (timing) memset(timing, 0, sizeof *timing);
   const LutScratch& sc = s->lut.s;
+  const bool audit = s->d_audit_key != nullptr;
+  if (audit && !s->audit_slots.empty())      // every run starts from zeroed slots
+    HIPCHK(hipMemsetAsync(s->d_audit, 0, s->audit_slots.size() * sizeof(margin_slot), st));
   for (size_t i = 0; i < c->ops.size(); i++) {
     const SiteOp& o = c->ops[i];
+    const MarginProbe probe_i = audit ? MarginProbe{s->d_audit_key, s->d_audit + s->audit_first[i]} : MarginProbe{};
+    const MarginProbe* probe = audit ? &probe_i : nullptr;
     const TensorShape& a = c->tensors[o.src0];
     const TensorShape& d = c->tensors[o.dst];
     uint64_t* src = s->d_tensor[o.src0];
@@ -2215,7 +2331,7 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
           LutRows rows;
           rows.src = src; rows.Ls = Ls; rows.work = dst; rows.Lw = Ld; rows.par = s->pool_buf[i][0]; rows.Lp = Ld;
           rows.tables = (const int64_t*)c->d_payload[i]; rows.tab_s = halves; rows.tab_d = half_d;
-          CHK(dev_round_lut(K, L, rows, E, hw, sc, &tm, deff));
+          CHK(dev_round_lut(K, L, rows, E, hw, sc, &tm, deff, probe));
         }
         break;
       }
@@ -2228,7 +2344,7 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
           tm.end(h);
         } else {
           uint64_t* const bufs[2] = {s->pool_buf[i][0], s->pool_buf[i][1]};
-          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], (const int64_t*)c->d_payload[i], sc, &tm));
+          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], (const int64_t*)c->d_payload[i], sc, &tm, probe));
         }
         break;
       }
@@ -2251,6 +2367,7 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
     }
     for (int i = 0; i < DCTFHE_MAX_TIERS; i++) timing->pbs_cts[i] = s->pbs_per_image[i] * B;
   }
+  if (audit) CHK(session_audit_collect(s));
   if (!K) {
     int ov = 0;
     HIPCHK(hipMemcpy(&ov, s->d_overflow, sizeof ov, hipMemcpyDeviceToHost));
@@ -2260,6 +2377,59 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
 }
 
 // ------------------------------------------------------------------------------------------ probes
+// ---- margin audit, the primitives (include/dctfhe.h): the definition on the host, and the session's kernel on host rows
+static void margin_accumulate(dctfhe_margin_stats* m, int32_t e) {
+  const int32_t a = e < 0 ? -e : e;
+  m->count++; m->sum += e; m->sum_sq += (uint64_t)((int64_t)e * e);
+  m->max_abs = std::max(m->max_abs, a);
+  m->hist[margin_bin(e, m->half_box)]++;
+}
+extern "C" int dctfhe_margin_probe_host(const uint8_t* small_key, int n, int logN, const uint64_t* cts_small, size_t count, int table_bits, int32_t* err,
+                                        dctfhe_margin_stats* stats) {
+  if (n < 1) return fail("dctfhe_margin_probe_host: small ciphertexts of %d mask words", n);
+  if (logN < 1 || logN > 31) return fail("dctfhe_margin_probe_host: ring of 2^%d", logN);
+  if (table_bits < 0 || logN - table_bits < 1) return fail("dctfhe_margin_probe_host: a table of %d input bits leaves no box on a ring of 2^%d (need 0 <= table_bits < logN)", table_bits, logN);
+  if (!small_key || (count && !cts_small)) return fail("dctfhe_margin_probe_host: null argument");
+  if (stats) *stats = margin_header(-1, -1, -1, logN, table_bits);
+  for (size_t c = 0; c < count; c++) {
+    const uint64_t* ct = cts_small + c * (size_t)(n + 1);
+    uint32_t acc = 0;
+    for (int i = 0; i < n; i++)
+      if (small_key[i]) acc += margin_level(ct[i], logN);
+    const int32_t e = margin_error(margin_level(ct[n], logN) - acc, logN, table_bits);
+    if (err) err[c] = e;
+    if (stats) margin_accumulate(stats, e);
+  }
+  return 0;
+}
+extern "C" int dctfhe_margin_probe(dctfhe_ctx* ctx, dctfhe_client_key* C, int tier, const uint64_t* cts_small, size_t count, int table_bits, int32_t* err,
+                                   dctfhe_margin_stats* stats) {
+  if (!ctx || !C || (count && !cts_small)) return fail("dctfhe_margin_probe: null argument");
+  if (tier < 0 || tier >= C->p.n_tiers) return fail("dctfhe_margin_probe: tier %d out of range (%d tiers)", tier, C->p.n_tiers);
+  const dctfhe_tier& t = C->p.tiers[tier];
+  if (table_bits < 0 || t.logN - table_bits < 1)
+    return fail("dctfhe_margin_probe: a table of %d input bits leaves no box on a ring of 2^%d (need 0 <= table_bits < logN)", table_bits, t.logN);
+  if (stats) *stats = margin_header(-1, -1, tier, t.logN, table_bits);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t bytes = count * (size_t)(t.n + 1) * 8;
+  DevBuf d_ct, d_err, d_slot;
+  HIPCHK(d_ct.alloc(bytes));
+  HIPCHK(hipMemcpyAsync(d_ct.p, cts_small, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (err) HIPCHK(d_err.alloc(count * 4));
+  if (stats) { HIPCHK(d_slot.alloc(sizeof(margin_slot))); HIPCHK(hipMemsetAsync(d_slot.p, 0, sizeof(margin_slot), ctx->stream)); }
+  CHK(dev_margin_probe(ctx->stream, t, C->d_s, d_ct.as<uint64_t>(), count, table_bits, err ? d_err.as<int32_t>() : nullptr, stats ? d_slot.as<margin_slot>() : nullptr));
+  if (err) HIPCHK(hipMemcpyAsync(err, d_err.p, count * 4, hipMemcpyDeviceToHost, ctx->stream));
+  dctfhe_margin_stats dev;
+  if (stats) HIPCHK(hipMemcpyAsync(&dev, d_slot.p, sizeof dev, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (stats) {
+    stats->max_abs = dev.max_abs; stats->count = dev.count; stats->sum = dev.sum; stats->sum_sq = dev.sum_sq;
+    memcpy(stats->hist, dev.hist, sizeof dev.hist);
+  }
+  return 0;
+}
+
 extern "C" int dctfhe_fp64_peak(dctfhe_ctx* ctx, double* tflops) {
   HIPCHK(hipSetDevice(ctx->device));
   const int blocks = ctx->prop.multiProcessorCount * 8, threads = 256, iters = 1 << 14;

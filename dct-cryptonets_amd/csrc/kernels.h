@@ -591,6 +591,66 @@ __global__ void __launch_bounds__(256) k_phase16(const uint8_t* __restrict__ s, 
   if (lane == 0) phases[c] = (uint64_t)(((uint32_t)row[n] - part) & 0xFFFFu) << 48;
 }
 
+// ---- margin audit: how far from its box centre every bootstrap decides ------------------------------------
+// The bootstrap rounds each word of a small ciphertext to the 2N levels of its ring (pbs_core.h: ((x >> msh) + 1) >> 1 with msh =
+// 62 - logN, the expression k_ms_center uses) and reads the box of G = 2^(logN - w) levels its switched phase lands in; boxes are
+// centred on the multiples of G (testvec_coeff: half a box of rotation).  margin_error is the signed distance, in levels, of a
+// switched phase from the centre of its box: in [-h, h), h = G / 2 >= 1.  While a run is correct this is the noise of the decision.
+HD uint32_t margin_level(uint64_t x, int logN) { return (uint32_t)(((x >> (62 - logN)) + 1) >> 1); }
+HD int32_t margin_error(uint32_t phase_levels, int logN, int w) {
+  const uint32_t G = 1u << (logN - w), h = G >> 1;
+  return (int32_t)((phase_levels + h) & (G - 1)) - (int32_t)h;
+}
+HD int margin_bin(int32_t e, int32_t h) { const int32_t a = e < 0 ? -e : e, b = 16 * a / h; return b < 15 ? b : 15; }
+// the layout of dctfhe_margin_stats (include/dctfhe.h; dctfhe.hip asserts it), with the accumulated fields as the atomics take them
+struct margin_slot {
+  int32_t op, entry, tier, table_bits, half_box, max_abs;
+  unsigned long long count, sum, sum_sq, hist[16];
+};
+constexpr int MARGIN_WORDS = 3 + 16;      // count, sum, sum_sq, hist[16]: the words a block adds to a slot
+
+// The probe: `count` small ciphertexts of n + 1 words under the first n key bytes of s (0 / 1), a table of w input bits on a ring of
+// 2^logN.  One wave per ciphertext as in k_ms_center and k_phase16 -- lane-strided loads, 32-bit partial sums (the phase is taken mod
+// 2N, a power of two), butterfly reduction, after which every lane holds the phase -- but a wave walks ciphertexts grid-strided and
+// keeps its statistics in registers: lane b < 16 counts histogram bin b, the sums are wave-uniform.  The four waves of a block meet in
+// LDS and the block issues one set of integer atomics on the slot, so the result does not depend on the order of anything.  No thread
+// leaves before the barrier.  err (optional): e per ciphertext; slot (optional): the accumulated statistics.
+__global__ void __launch_bounds__(256) k_margin_probe(const uint8_t* __restrict__ s, const uint64_t* __restrict__ small, size_t count, int n,
+                                                      int logN, int w, int32_t* __restrict__ err, margin_slot* __restrict__ slot) {
+  __shared__ unsigned long long part[4][MARGIN_WORDS];
+  __shared__ int part_max[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int32_t h = (int32_t)1 << (logN - w - 1);
+  unsigned long long cnt = 0, sum = 0, sq = 0, bin_count = 0;
+  int32_t mx = 0;
+  for (size_t c = (size_t)blockIdx.x * 4 + wave; c < count; c += (size_t)gridDim.x * 4) {
+    const uint64_t* ct = small + c * (size_t)(n + 1);
+    uint32_t acc = 0;
+    for (int i = lane; i < n; i += 64)
+      if (s[i]) acc += margin_level(ct[i], logN);
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    const int32_t e = margin_error(margin_level(ct[n], logN) - acc, logN, w);
+    if (err && lane == 0) err[c] = e;
+    const int32_t a = e < 0 ? -e : e;
+    cnt++;
+    sum += (unsigned long long)(long long)e;
+    sq += (unsigned long long)((long long)e * e);
+    mx = a > mx ? a : mx;
+    if (lane == margin_bin(e, h)) bin_count++;
+  }
+  if (lane == 0) { part[wave][0] = cnt; part[wave][1] = sum; part[wave][2] = sq; part_max[wave] = mx; }
+  if (lane < 16) part[wave][3 + lane] = bin_count;
+  __syncthreads();
+  if (!slot) return;
+  if (threadIdx.x < MARGIN_WORDS) {
+    const unsigned long long v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (v) atomicAdd(&slot->count + threadIdx.x, v);
+  } else if (threadIdx.x == MARGIN_WORDS) {
+    const int m = max(max(part_max[0], part_max[1]), max(part_max[2], part_max[3]));
+    if (m) atomicMax(&slot->max_abs, m);
+  }
+}
+
 // ------------------------------------------------------------------------------------------ K4-K6 bootstrap
 struct pbs_launch {
   const uint64_t* cts_small;  // count x (n+1)

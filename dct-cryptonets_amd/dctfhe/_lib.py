@@ -38,6 +38,15 @@ class Timing(C.Structure):
                 ("linear_ms", C.c_double), ("pbs_launches", C.c_int64 * MAX_TIERS), ("pbs_cts", C.c_int64 * MAX_TIERS)]
 
 
+MARGIN_BINS = 16
+
+
+class MarginStats(C.Structure):
+    """dctfhe_margin_stats: one slot of the margin audit (include/dctfhe.h)"""
+    _fields_ = [("op", C.c_int32), ("entry", C.c_int32), ("tier", C.c_int32), ("table_bits", C.c_int32), ("half_box", C.c_int32),
+                ("max_abs", C.c_int32), ("count", C.c_int64), ("sum", C.c_int64), ("sum_sq", C.c_uint64), ("hist", C.c_int64 * MARGIN_BINS)]
+
+
 EXPORTS = [
     "dctfhe_last_error", "dctfhe_version", "dctfhe_ctx_create", "dctfhe_ctx_destroy", "dctfhe_ctx_set_stream",
     "dctfhe_ctx_synchronize", "dctfhe_keygen", "dctfhe_client_key_create", "dctfhe_client_key_destroy", "dctfhe_eval_keys_generate",
@@ -50,6 +59,7 @@ EXPORTS = [
     "dctfhe_eval_keys_decompress_bsk", "dctfhe_keyswitch_diff", "dctfhe_max_pool_rows",
     "dctfhe_round_lut_split", "dctfhe_session_set_noise_split",
     "dctfhe_session_download_packed", "dctfhe_keyswitch_pack", "dctfhe_decrypt_packed",
+    "dctfhe_margin_probe_host", "dctfhe_margin_probe", "dctfhe_session_set_audit", "dctfhe_session_audit",
 ]
 
 _lib = None
@@ -131,6 +141,10 @@ def load():
     L.dctfhe_session_download_packed.argtypes = [vp, i32, vp]
     L.dctfhe_keyswitch_pack.argtypes = [vp, vp, i32, vp, sz, i32, i32, vp]
     L.dctfhe_decrypt_packed.argtypes = [vp, vp, i32, vp, sz, vp]
+    L.dctfhe_margin_probe_host.argtypes = [vp, i32, i32, vp, sz, i32, vp, C.POINTER(MarginStats)]
+    L.dctfhe_margin_probe.argtypes = [vp, vp, i32, vp, sz, i32, vp, C.POINTER(MarginStats)]
+    L.dctfhe_session_set_audit.argtypes = [vp, vp]
+    L.dctfhe_session_audit.argtypes = [vp, C.POINTER(MarginStats), i32, C.POINTER(C.c_int)]
     _lib = L
     return L
 

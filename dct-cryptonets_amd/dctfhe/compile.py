@@ -173,6 +173,9 @@ class OpInfo:
     pool_geom: list = None
     n_max: int = 0
     levels: int = 0
+    # margin audit: (kind, tier, table bits, variance) of every bootstrap with a key switch of its own, in the engine's order
+    # (csrc/circuit.h for_each_bootstrap), as _estimate_noise priced them
+    margin: list = None
 
 
 @dataclass
@@ -224,6 +227,22 @@ class CompiledCircuit:
     def simulation_sigmas_split(self):
         """per op, the noise std `simulate` injects at the SECOND look-up of a parity-split site (0 elsewhere)"""
         return [o.sim_sigma2 if (o.type == OP_LUT and is_split(o)) else 0.0 for o in self.ops]
+
+    def margin_model(self):
+        """One record per slot of the margin audit (include/dctfhe.h dctfhe_session_audit), in the same enumeration: per look-up op its
+        one-bit steps, for a parity split the second look-up, then the table; one record per max pool (its worst tree level).  The
+        parity bootstrap has no key switch of its own and no record.  sigma (fraction of the torus) is the very figure _estimate_noise
+        put into p_fail for that decision.  elements: decisions per image."""
+        ps, out = self.param_set, []
+        for i, o in enumerate(self.ops):
+            if o.type not in (OP_LUT, OP_MAXPOOL):
+                continue
+            s = self.tensors[o.src0]
+            n = o.n_max if o.type == OP_MAXPOOL else s.C * s.H * s.W
+            for e, (kind, tier, bits, var) in enumerate(o.margin or []):
+                out.append(dict(op=i, entry=e, kind=kind, tier=tier, tier_name=ps.tiers[tier].name, table_bits=bits, elements=n,
+                                sigma=math.sqrt(var), note=o.note))
+        return out
 
     def pbs_counts(self):
         """{tier name: programmable bootstraps per image} -- table lookups on the site's table tier, rounding steps
@@ -733,16 +752,17 @@ def _estimate_noise(circ):
             # bootstrap output to b.  The column pass starts from the row pass's output.
             tt = ps.tiers[o.ip[4]]
             ring = tt.k << tt.logN
-            v, d_in, worst, v_tab = s.var, s.deff or ps.D, 0.0, 0.0
+            v, d_in, worst, v_tab, v_worst = s.var, s.deff or ps.D, 0.0, 0.0, 0.0
             for mult, pairs in o.pool_geom:
                 for npair in pairs:
                     v_tab = 2.0 * v * 4.0 ** o.ip[3] + P.var_keyswitch(d_in, tt) + P.var_modswitch(tt)
                     pf = P.p_fail(2.0 ** -(o.p + 2), v_tab)
-                    worst = max(worst, pf)
+                    worst, v_worst = max(worst, pf), max(v_worst, v_tab)
                     total += pf * mult * npair
                     v += P.var_pbs_out(tt, ps.fft_noise_c)
                     d_in = max(d_in, ring)
             o.pfail = worst
+            o.margin = [("pool", o.ip[4], o.p, v_worst)]
             o.sim_sigma = math.sqrt(v_tab)
             T[o.dst].var = v
         else:
@@ -761,9 +781,12 @@ def _estimate_noise(circ):
 
             c2 = getattr(ps, "bit_tier_coarse2", None)
 
-            def site_pfail(coarse_from, coarse2_from=None):
+            def site_pfail(coarse_from, coarse2_from=None, rec=None):
+                """rec (a list): the variance at every decision is appended, for CompiledCircuit.margin_model"""
                 pf_, v_ = 0.0, v_in0
                 if approx:
+                    if rec is not None:
+                        rec.append(("table", o.ip[4], o.w, v_ + v_tab_in))      # listed for completeness: the audit refuses such a site
                     # no rounding steps: the low r bits ride along; a failure is noise beyond the half-box.  (The two inputs
                     # next to a rounding boundary, 2 of 2^r, sit half an input unit from it and take the neighbouring
                     # entry far more often: the method's own inexactness, reported apart as boundary flips.)
@@ -771,19 +794,29 @@ def _estimate_noise(circ):
                 step = None
                 if R_ > 0:
                     for i in range(R_):
-                        step = ps.tiers[o.ip[5]]
+                        ti = o.ip[5]
                         if i >= coarse_from and o.ip[7] >= 0:
-                            step = ps.tiers[o.ip[7]]
+                            ti = o.ip[7]
                         if coarse2_from is not None and i >= coarse2_from:
-                            step = ps.tiers[c2]
+                            ti = c2
+                        step = ps.tiers[ti]
                         # the tier that runs the step key-switches to its own small key (own length, own noise) and mod-switches on its ring
                         v_bit_in = P.var_keyswitch(max(d_in, step.k << step.logN), step) + P.var_modswitch(step)
-                        pf_ += P.p_fail(0.25, 4.0 ** (o.p - i) * v_ + v_bit_in)
+                        v_step = 4.0 ** (o.p - i) * v_ + v_bit_in
+                        pf_ += P.p_fail(0.25, v_step)
+                        if rec is not None:
+                            rec.append((f"step {i}", ti, 0, v_step))
                         v_ += P.var_pbs_out(step, ps.fft_noise_c)
-                second = P.p_fail(2.0 ** -(W_ + 2), v_ + P.var_pbs_out(step, ps.fft_noise_c) + v_tab2_in) if split else 0.0
+                v_second = (v_ + P.var_pbs_out(step, ps.fft_noise_c) + v_tab2_in) if split else 0.0
+                second = P.p_fail(2.0 ** -(W_ + 2), v_second) if split else 0.0
+                if rec is not None:
+                    if split:
+                        rec.append(("second", second_tier(ps, o), W_, v_second))
+                    rec.append(("table", o.ip[4], W_, v_ + v_tab_in))
                 return pf_ + P.p_fail(2.0 ** -(W_ + 2), v_ + v_tab_in) + second
 
             pf = site_pfail(R_)
+            chosen = (R_, None)       # the arguments of the site_pfail call whose result stays in o.pfail
             if R_ > 0 and o.ip[7] >= 0 and not approx:
                 # earliest step from which the one-level bit tier keeps the site within 2x of its all-precise failure rate
                 budget = max(2.0 * pf, getattr(ps, "p_budget", 1e-12))
@@ -792,14 +825,18 @@ def _estimate_noise(circ):
                     cf -= 1
                 o.coarse_from = o.ip[8] = cf
                 pf = site_pfail(cf)
+                chosen = (cf, None)
                 if c2 is not None:      # ... and, inside that budget, the earliest step from which the two-bit-rotation tier will do
                     cf2 = R_
                     while cf2 > cf and site_pfail(cf, cf2 - 1) <= budget:
                         cf2 -= 1
                     o.coarse2_from = cf2
                     o.ip[11] = (c2 << 8) | cf2 if cf2 < R_ else -1
-                    pf = site_pfail(cf, cf2 if cf2 < R_ else None)
+                    chosen = (cf, cf2 if cf2 < R_ else None)
+                    pf = site_pfail(*chosen)
             o.pfail = pf
+            o.margin = []
+            site_pfail(*chosen, rec=o.margin)
             v_sim = v_in0
             if R_ > 0 and not approx:                       # what the one-bit steps leave on the working ciphertext
                 for i in range(R_):

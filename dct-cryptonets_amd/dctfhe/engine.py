@@ -7,7 +7,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._lib import Params, Stats, Tier, Timing, check, ptr
+from ._lib import MarginStats, Params, Stats, Tier, Timing, check, ptr
 
 
 def make_params(D, n_max, tiers, input_sigma, input_dim=0):
@@ -18,6 +18,26 @@ def make_params(D, n_max, tiers, input_sigma, input_dim=0):
         p.tiers[i] = Tier(t["n"], t["k"], t["logN"], t["l"], t["beta"], t["lk"], t["betak"], t.get("ksk_share", -1),
                           t.get("unroll", 1), 0, t["lwe_sigma"], t["glwe_sigma"])
     return p
+
+
+def margin_stats_dict(m):
+    """a dctfhe_margin_stats as a dict of Python ints (hist: a list of 16)"""
+    return dict(op=m.op, entry=m.entry, tier=m.tier, table_bits=m.table_bits, half_box=m.half_box, max_abs=m.max_abs, count=m.count,
+                sum=m.sum, sum_sq=m.sum_sq, hist=list(m.hist))
+
+
+def margin_probe_host(small_key, n, logN, cts_small, table_bits, want_err=True, want_stats=True):
+    """the margin audit's definition on the CPU (include/dctfhe.h dctfhe_margin_probe_host; no GPU): small ciphertexts [count, n + 1]
+    under the first n bytes of small_key -> (e per ciphertext as int32 or None, statistics dict or None)"""
+    L = _lib.load()
+    key = np.ascontiguousarray(small_key, np.uint8)
+    cts = None if cts_small is None else np.ascontiguousarray(cts_small, np.uint64)
+    count = 0 if cts is None else cts.size // (max(int(n), 0) + 1)
+    err = np.empty(count, np.int32) if want_err else None
+    st = MarginStats() if want_stats else None
+    check(L.dctfhe_margin_probe_host(ptr(key), int(n), int(logN), None if cts is None else ptr(cts), count, int(table_bits),
+                                     None if err is None else ptr(err), None if st is None else C.byref(st)))
+    return err, (None if st is None else margin_stats_dict(st))
 
 
 class Context:
@@ -311,6 +331,19 @@ class ClientKey:
         check(self.L.dctfhe_decrypt_packed(self.ctx.h, self.h, packed.n, ptr(packed.rows), len(packed), ptr(out)))
         return out
 
+    def margin_probe(self, tier, cts_small, table_bits, want_err=True, want_stats=True):
+        """the margin audit's kernel on small ciphertexts [count, n + 1] of `tier`, already key-switched and mod-switched, about to meet
+        a table of table_bits input bits (dctfhe_margin_probe): (signed distance from the box centre per ciphertext, in levels of 2N,
+        or None; statistics dict or None)"""
+        cts = np.ascontiguousarray(cts_small, np.uint64)
+        n = self.tier(tier).n if 0 <= tier < self.params.n_tiers else 0      # the library refuses the rest
+        count = cts.size // (n + 1)
+        err = np.empty(count, np.int32) if want_err else None
+        st = MarginStats() if want_stats else None
+        check(self.L.dctfhe_margin_probe(self.ctx.h, self.h, int(tier), ptr(cts), count, int(table_bits), None if err is None else ptr(err),
+                                         None if st is None else C.byref(st)))
+        return err, (None if st is None else margin_stats_dict(st))
+
     def close(self):
         if self.h:
             self.L.dctfhe_client_key_destroy(self.h)
@@ -442,7 +475,7 @@ class Keys:
 
     def __getattr__(self, name):
         if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter",
-                    "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed"):
+                    "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed", "margin_probe"):
             return getattr(self.client, name)
         if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
@@ -536,6 +569,23 @@ class Session:
             out = np.empty((self.batch, self.circuit.n_out, dim + 1), np.uint64)
             check(self.L.dctfhe_session_download_rows(self.h, ptr(out), int(dim)))
         return out
+
+    def set_audit(self, client):
+        """margin audit (dctfhe_session_set_audit): client -- a ClientKey, or a Keys pair whose client half is used -- turns it on for the
+        following runs, None turns it off.  The session keeps its own copy of the small key; it needs the SECRET, so this is a
+        development and assurance tool, never a server path"""
+        client = getattr(client, "client", client)
+        check(self.L.dctfhe_session_set_audit(self.h, None if client is None else client.h))
+
+    def audit(self):
+        """the slots of the last run (dctfhe_session_audit): a list of dicts, empty when the audit is off"""
+        n = C.c_int()
+        check(self.L.dctfhe_session_audit(self.h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return []
+        out = (MarginStats * n.value)()
+        check(self.L.dctfhe_session_audit(self.h, out, n.value, C.byref(n)))
+        return [margin_stats_dict(m) for m in out]
 
     def download_packed(self, tier):
         """the outputs key-switched to `tier` and packed to 16 bits per word (dctfhe_session_download_packed): PackedCiphertexts of

@@ -15,6 +15,7 @@ fhe="execute": quantise -> encrypt -> circuit on ciphertexts -> decrypt -> dequa
 libdctfhe.so.  fhe="simulate" / "disable": the same integer circuit on plaintext phases (1-word
 "ciphertexts"), also on the GPU through the same scheduler -- the noise-free circuit.  There is no CPU path.
 """
+import math
 import time
 
 import numpy as np
@@ -38,6 +39,51 @@ class Configuration:
         # (include/dctfhe.h dctfhe_session_download_packed; the tier is dctfhe.compile.output_compaction's).  Off by default.
         self.compress_output_ciphertexts = bool(compress_output_ciphertexts)
         self.extra = kwargs
+
+
+class MarginReport:
+    """What a margin audit measured (QuantizedModule.audit), slot by slot beside the compiler's model (CompiledCircuit.margin_model).
+    rows: one dict per slot -- op, entry, kind, tier, tier_name, table_bits, note, the slot's count, sum, sum_sq, half_box and max_abs
+    (levels of the tier's 2N), mean (levels), sigma_measured = sqrt(sum_sq / count) / 2N and sigma_model (fractions of the torus), ratio = measured / model,
+    max_over_half_box = max_abs / half_box, z = the half-box in measured sigmas, hist (16 bins of 16 |e| / half_box).
+    It validates the variance model at every decision of this run; it does not observe a 1e-13 tail."""
+
+    def __init__(self, rows):
+        self.rows = rows
+
+    @classmethod
+    def from_slots(cls, slots, model, params):
+        if [(m["op"], m["entry"], m["tier"], m["table_bits"]) for m in model] != [(s["op"], s["entry"], s["tier"], s["table_bits"]) for s in slots]:
+            raise RuntimeError("margin audit: the engine's slots are not the compiler's margin_model()")
+        rows = []
+        for s, m in zip(slots, model):
+            two_n = 2.0 * (1 << params.tiers[s["tier"]].logN)
+            cnt = s["count"]
+            sig = math.sqrt(s["sum_sq"] / cnt) / two_n if cnt else float("nan")
+            rows.append(dict(op=s["op"], entry=s["entry"], kind=m["kind"], tier=s["tier"], tier_name=m["tier_name"], table_bits=s["table_bits"],
+                             note=m["note"], count=cnt, half_box=s["half_box"], max_abs=s["max_abs"], sum=s["sum"], sum_sq=s["sum_sq"], mean=(s["sum"] / cnt if cnt else float("nan")),
+                             sigma_measured=sig, sigma_model=m["sigma"], ratio=sig / m["sigma"] if cnt else float("nan"),
+                             max_over_half_box=s["max_abs"] / s["half_box"],
+                             z=(s["half_box"] / two_n / sig) if (cnt and sig > 0) else float("inf"), hist=list(s["hist"])))
+        return cls(rows)
+
+    def worst(self):
+        """the slot whose half-box is the fewest measured sigmas wide (None for a circuit without look-ups)"""
+        probed = [r for r in self.rows if r["count"]]
+        return min(probed, key=lambda r: r["z"]) if probed else None
+
+    def text(self):
+        lines = ["// margin audit: sigma at the point of decision, measured against the compiler's model (fractions of the torus, log2)"]
+        for r in self.rows:
+            lg = lambda v: f"{math.log2(v):7.2f}" if (v == v and v > 0) else "    n/a"
+            lines.append(f"op {r['op']:3d}.{r['entry']} {r['kind']:<7} tier={r['tier_name']:<5} bits={r['table_bits']} count={r['count']:8d} "
+                         f"measured=2^{lg(r['sigma_measured'])} model=2^{lg(r['sigma_model'])} ratio={r['ratio']:.2f} "
+                         f"max|e|/half_box={r['max_over_half_box']:.3f} z={r['z']:.1f}  // {r['note']}")
+        w = self.worst()
+        if w is not None:
+            lines.append(f"// narrowest decision: op {w['op']}.{w['entry']} ({w['kind']}, {w['note']}): half-box = {w['z']:.1f} measured sigma, "
+                         f"largest ratio measured / model {max(r['ratio'] for r in self.rows if r['count']):.2f}")
+        return "\n".join(lines)
 
 
 class _Graph:
@@ -272,6 +318,32 @@ class QuantizedModule:
         self.last_timing = dict(total_ms=timing.total_ms, pbs_ms=list(timing.pbs_ms), ks_ms=timing.ks_ms, linear_ms=timing.linear_ms,
                                 wall_s=time.time() - t0)
         return self.decode_output(out_ph)
+
+    # -- margin audit (include/dctfhe.h dctfhe_session_set_audit): a development and assurance tool ------------------
+    def audit_quantized(self, q):
+        """An encrypted pass over integer inputs q [B, C, H, W] with the margin audit on: (decoded outputs [B, F], MarginReport).  Every
+        bootstrap decision of the run is measured with the client's secret key, so it runs where the client key is."""
+        if self._keys is not None and not hasattr(self._keys, "decrypt"):
+            raise RuntimeError("the margin audit needs the client key (fhe_circuit.keygen); this module holds evaluation keys only")
+        phases = self.encode_input(q)
+        B = q.shape[0]
+        sess = self._session("execute", B)
+        in_dim, out_dim = sess.dims()
+        sess.set_audit(self._keys.client)
+        try:
+            sess.upload(self._keys.encrypt(phases.reshape(-1), in_dim), in_dim)
+            sess.run()
+            slots = sess.audit()
+            out = sess.download(out_dim).reshape(-1, out_dim + 1)
+        finally:
+            sess.set_audit(None)
+        report = MarginReport.from_slots(slots, self.compiled.margin_model(), self.compiled.param_set)
+        return self.decode_output(self._keys.decrypt(out, out_dim).reshape(B, -1)), report
+
+    def audit(self, x):
+        """x: float [B, C, H, W] -> (float outputs [B, F] of an encrypted pass, MarginReport)"""
+        out_q, report = self.audit_quantized(self.quantize_input(np.asarray(x)))
+        return self.dequantize_output(out_q), report
 
     def close(self):
         for s in self._sessions.values():

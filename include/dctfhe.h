@@ -299,6 +299,50 @@ int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, con
  * so that whatever decodes dctfhe_decrypt's phases decodes these. */
 int dctfhe_decrypt_packed(dctfhe_ctx* ctx, dctfhe_client_key* client, int n, const uint16_t* rows, size_t count, uint64_t* phases);
 
+/* MARGIN AUDIT: the decision noise of every bootstrap that has a key switch of its own, measured in a real run.
+ * A development and assurance tool: it needs the client's SECRET key, so it is never a server path.
+ *
+ * Take a small ciphertext (a_0 .. a_{n-1}, b) of a tier with ring N = 2^logN, key-switched and mod-switched (centred), about to be
+ * bootstrapped with a table of w input bits (w = 0: a one-bit step).  With lv(x) = ((x >> (62 - logN)) + 1) >> 1, the bootstrap's own
+ * rounding to 2N levels,
+ *     phi = (lv(b) - sum_{i<n} s_i lv(a_i)) mod 2N          the switched phase under the first n bits of the small key
+ *     G = 2^(logN - w), h = G / 2                           box width and half-box in levels; boxes are centred on the multiples of G
+ *     e = ((phi + h) mod G) - h,  -h <= e < h               the signed distance from the centre of the box the bootstrap will read
+ * While the run is correct, e is exactly the noise the compiler prices at that decision (dctfhe.compile margin_model).  It is an
+ * integer: every statistic below is exact and does not depend on the order of summation.
+ * A WRONG SECRET CANNOT BE DETECTED: the statistics then read as uniform noise (max_abs near half_box, a flat histogram). */
+#define DCTFHE_MARGIN_BINS 16
+typedef struct {
+  int32_t op, entry;          /* circuit op; index among that op's bootstraps that have a key switch of their own (-1, -1: a primitive call) */
+  int32_t tier, table_bits;   /* tier -1: the host form */
+  int32_t half_box, max_abs;  /* h and the largest |e|, in levels of the tier's 2N */
+  int64_t count, sum;         /* decisions probed; sum of e */
+  uint64_t sum_sq;            /* sum of e^2 */
+  int64_t hist[DCTFHE_MARGIN_BINS];   /* bin min(15, 16 |e| / half_box) */
+} dctfhe_margin_stats;
+
+/* no GPU (like dctfhe_rng_host): the definition, on host rows of n + 1 words.  small_key: n bytes, 0 or 1.  1 <= n, 1 <= logN <= 31,
+ * 0 <= table_bits < logN.  err (count values) and stats may each be NULL. */
+int dctfhe_margin_probe_host(const uint8_t* small_key, int n, int logN, const uint64_t* cts_small, size_t count,
+                             int table_bits, int32_t* err, dctfhe_margin_stats* stats);
+/* the session's kernel on host rows of `tier`, key bits from the client handle */
+int dctfhe_margin_probe(dctfhe_ctx* ctx, dctfhe_client_key* client, int tier, const uint64_t* cts_small, size_t count,
+                        int table_bits, int32_t* err, dctfhe_margin_stats* stats);
+/* encrypted sessions: client != NULL turns the audit on for the following runs, NULL turns it off.  The session copies the small key's
+ * n_max bytes into a device buffer of its own (cleared before it is freed, on destroy and when the audit is turned off): the client
+ * handle may be destroyed afterwards.  While the audit is on, every bootstrap launch with a key switch of its own is followed by one
+ * small streaming kernel over its small ciphertexts; dctfhe_timing.total_ms of such a run includes them (the per-category spans do
+ * not).  Off -- the default -- a run launches exactly what it did before this call existed.
+ * Refused: a clear-mode session; a client whose D, n_max, tier count or any tier's n, k, logN differ from the session's keys; a circuit
+ * with an approximate-rounding site (the low bits ride along there: e is not noise). */
+int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* client);
+/* The slots of the last run: one per (op, bootstrap with a key switch of its own), ops in circuit order, a look-up's one-bit steps,
+ * then for a parity split its second look-up, then its table; a max pool has one slot over all its levels.  (The parity bootstrap
+ * reuses the last step's small ciphertext: no slot.  The order is that of the enumeration, not of execution.)  The chunks of a site
+ * accumulate into its slot; every dctfhe_session_run starts from zeroed slots.  out == NULL: only *n_slots is written; audit off:
+ * *n_slots = 0.  capacity < *n_slots is refused. */
+int dctfhe_session_audit(dctfhe_session* s, dctfhe_margin_stats* out, int capacity, int* n_slots);
+
 /* f64 FMA peak micro-benchmark (TFLOP/s) used to price the blind-rotate kernel in bench.py. */
 int dctfhe_fp64_peak(dctfhe_ctx* ctx, double* tflops);
 /* stand-alone timing of the blind-rotate kernel: count ciphertexts of tier `tier`, average ms per launch */

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstddef>
@@ -53,35 +54,76 @@ struct dctfhe_ctx {
   int device = 0;
   hipStream_t stream = nullptr, own = nullptr;
   hipDeviceProp_t prop;
+  ~dctfhe_ctx() { if (own) hipStreamDestroy(own); }
 };
 
-// device buffer that frees itself unless released: every early return of an entry point cleans up after itself
+// The two owners: every piece of device memory and every event of the library is held by one of them, and nothing else frees any.
+// g_dev_bytes: the bytes all live DevBufs were allocated with (dctfhe_device_bytes_live)
+static std::atomic<size_t> g_dev_bytes{0};
 struct DevBuf {
   void* p = nullptr;
+  size_t bytes = 0;
   DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  hipError_t upload(const void* host, size_t bytes) {      // alloc + blocking copy of a host operand
-    const hipError_t e = alloc(bytes);
-    return e != hipSuccess ? e : hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p) { hipFree(p); g_dev_bytes -= bytes; }
+    p = nullptr; bytes = 0;
+  }
+  hipError_t alloc(size_t n) {
+    reset();
+    const hipError_t e = hipMalloc(&p, n ? n : 1);
+    if (e != hipSuccess) { p = nullptr; return e; }
+    bytes = n; g_dev_bytes += n;
+    return e;
+  }
+  hipError_t upload(const void* host, size_t n) {      // alloc + blocking copy of a host operand
+    const hipError_t e = alloc(n);
+    return e != hipSuccess ? e : hipMemcpy(p, host, n, hipMemcpyHostToDevice);
+  }
+  hipError_t download(void* host, size_t n, hipStream_t st) const {      // what `st` computed into the first n bytes, to the host
+    const hipError_t e = hipStreamSynchronize(st);
+    return e != hipSuccess ? e : hipMemcpy(host, p, n, hipMemcpyDeviceToHost);
   }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+struct DevEvent {
+  hipEvent_t e = nullptr;
+  DevEvent() = default;
+  DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+  DevEvent& operator=(DevEvent&& o) noexcept {
+    if (this != &o) { reset(); e = o.e; o.e = nullptr; }
+    return *this;
+  }
+  ~DevEvent() { reset(); }
+  void reset() {
+    if (e) hipEventDestroy(e);
+    e = nullptr;
+  }
+  hipError_t create() { reset(); return hipEventCreate(&e); }
+};
+extern "C" size_t dctfhe_device_bytes_live(void) { return g_dev_bytes.load(); }
 
-struct TierKeys {
-  dctfhe_tier t{};
-  uint64_t* d_ksk = nullptr;     // [D][lk][n+1]
-  uint64_t* d_colsum = nullptr;  // [n+1], over all D*lk rows
-  std::map<int, uint64_t*>* colsum_eff = nullptr;   // column sums over the first Deff*lk rows (shared with the key's owner)
-  int8_t* d_kskT = nullptr;      // signed byte limbs, [limbs(n+1) padded to 128][D*lk], for the MFMA key switch
+// a key-switch key and everything derived from it: made by the tier that owns it, read through TierKeys::ks by every tier that shares it
+struct KskKey {
+  DevBuf ksk;                    // u64 [D][lk][n+1]
+  DevBuf colsum;                 // u64 [n+1], over all D*lk rows
+  std::map<int, DevBuf> colsum_eff;   // ... over the first Deff*lk rows, filled on the first key switch at that Deff
+  DevBuf kskT;                   // signed byte limbs, [limbs(n+1) padded to 128][D*lk], for the MFMA key switch (empty: integer-VALU GEMM)
   int ncol_pad = 0;
   int limbs = 8;                 // byte limbs kept per key word (ks_limbs): the key lives on the 2^-(8 limbs) torus grid
-  bool own_ksk = false;
-  cplx* d_bsk = nullptr;         // [n][rows][k+1][P][T]; unroll 2: [3n/2 blocks] for the pair secret
-  cplx* d_wtab = nullptr;        // unroll 2: e^{i pi m/N}, m < 2N, then e^{2 pi i k/8}, k < 8
-  cplx* d_tw = nullptr;
+};
+struct TierKeys {
+  dctfhe_tier t{};
+  KskKey* ks = nullptr;          // dctfhe_eval_keys::ksk[this tier], or [t.ksk_share]
+  DevBuf bsk;                    // cplx [n][rows][k+1][P][T]; unroll 2: [3n/2 blocks] for the pair secret
+  DevBuf wtab;                   // cplx, unroll 2: e^{i pi m/N}, m < 2N, then e^{2 pi i k/8}, k < 8
+  DevBuf tw;                     // cplx
+  bool mfma() const { return ks->kskT.p != nullptr; }
 };
 
 // CLIENT side: everything secret.  The whole handle is a function of (params, 32-byte seed): persist the seed to persist it.
@@ -96,34 +138,22 @@ struct dctfhe_client_key {
   // (0, m1 - m2).  ADVICE r2.)
   uint8_t nonce[16] = {};
   rng_key enc_sec{}, enc_pub{};
-  uint8_t *d_S = nullptr, *d_s = nullptr;
-  uint8_t* d_spair[DCTFHE_MAX_TIERS] = {};   // unroll 2: derived secret (s1(1-s2), (1-s1)s2, s1 s2) per pair
+  DevBuf d_S, d_s;               // key bits, one byte each
+  DevBuf d_spair[DCTFHE_MAX_TIERS];          // unroll 2: derived secret (s1(1-s2), (1-s1)s2, s1 s2) per pair
   uint64_t enc_calls = 0;        // every dctfhe_encrypt call draws from fresh streams
-  ~dctfhe_client_key() {
-    if (ctx) hipSetDevice(ctx->device);
-    hipFree(d_S); hipFree(d_s);
-    for (auto q : d_spair) hipFree(q);
-  }
+  const uint8_t* S() const { return d_S.as<uint8_t>(); }
+  const uint8_t* s() const { return d_s.as<uint8_t>(); }
+  ~dctfhe_client_key() { if (ctx) hipSetDevice(ctx->device); }      // ... before the members free themselves
 };
 
 // SERVER side: evaluation keys only (key-switch keys, Fourier bootstrap keys); nothing here depends on the secret at run time.
 struct dctfhe_eval_keys {
   dctfhe_ctx* ctx = nullptr;
   dctfhe_params p{};
+  KskKey ksk[DCTFHE_MAX_TIERS];  // per tier with a key-switch key of its own (ksk_share < 0)
   TierKeys tiers[DCTFHE_MAX_TIERS];
-  uint64_t* d_dummy = nullptr;   // D+1 words, sink of padded bootstrap groups
-  ~dctfhe_eval_keys() {
-    if (ctx) hipSetDevice(ctx->device);
-    hipFree(d_dummy);
-    for (int i = 0; i < DCTFHE_MAX_TIERS; i++) {
-      TierKeys& tk = tiers[i];
-      if (tk.own_ksk) {
-        hipFree(tk.d_ksk); hipFree(tk.d_colsum); hipFree(tk.d_kskT);
-        if (tk.colsum_eff) { for (auto& kv : *tk.colsum_eff) hipFree(kv.second); delete tk.colsum_eff; }
-      }
-      hipFree(tk.d_bsk); hipFree(tk.d_tw); hipFree(tk.d_wtab);
-    }
-  }
+  DevBuf d_dummy;                // D+1 words, sink of padded bootstrap groups
+  ~dctfhe_eval_keys() { if (ctx) hipSetDevice(ctx->device); }
 };
 using dctfhe_keys = dctfhe_eval_keys;   // the server-side code below says K for the evaluation keys
 
@@ -151,11 +181,7 @@ static void pack_conv_host(const int8_t* w, int Cout, int Cin, int H, int W, int
   }
 }
 // every pack of a circuit (or the single one of the dctfhe_conv2d primitive) lives in ONE device allocation
-struct ConvSlab {
-  void* d = nullptr;
-  ~ConvSlab() { hipFree(d); }
-};
-static int build_conv_packs(const std::vector<const int8_t*>& w, const std::vector<ConvSite>& g, ConvSlab* slab, std::vector<ConvPack>* out) {
+static int build_conv_packs(const std::vector<const int8_t*>& w, const std::vector<ConvSite>& g, DevBuf* slab, std::vector<ConvPack>* out) {
   size_t total = 0;
   std::vector<size_t> off_w(w.size()), off_t(w.size());
   out->assign(w.size(), ConvPack{});
@@ -170,25 +196,20 @@ static int build_conv_packs(const std::vector<const int8_t*>& w, const std::vect
   std::vector<char> host(total, 0);
   for (size_t i = 0; i < w.size(); i++)
     if (w[i]) pack_conv_host(w[i], g[i].Cout, g[i].Cin, g[i].H, g[i].W, g[i].KH, g[i].KW, g[i].pad, (*out)[i].kpad, (int8_t*)&host[off_w[i]], (conv_tap*)&host[off_t[i]]);
-  HIPCHK(hipMalloc(&slab->d, total));
-  HIPCHK(hipMemcpy(slab->d, host.data(), total, hipMemcpyHostToDevice));
+  HIPCHK(slab->upload(host.data(), total));
   for (size_t i = 0; i < w.size(); i++)
-    if (w[i]) { (*out)[i].d_w = (int8_t*)slab->d + off_w[i]; (*out)[i].d_taps = (conv_tap*)((char*)slab->d + off_t[i]); }
+    if (w[i]) { (*out)[i].d_w = slab->as<int8_t>() + off_w[i]; (*out)[i].d_taps = (conv_tap*)(slab->as<char>() + off_t[i]); }
   return 0;
 }
 
 struct dctfhe_circuit : CircuitPlan {      // tensors, ops (one decoded SiteOp per record), input / output tensor
   dctfhe_ctx* ctx = nullptr;
-  std::vector<void*> d_payload;  // per op, device copy of its payload (weights / tables)
-  std::vector<int64_t*> d_split; // per op: the half tables [S | Dt] of a parity-split look-up, each [ntab][2^(w-1)] (nullptr for other ops)
+  std::vector<DevBuf> d_payload; // per op, device copy of its payload (weights / tables)
+  std::vector<DevBuf> d_split;   // per op: the half tables [S | Dt] of a parity-split look-up, each i64 [ntab][2^(w-1)] (empty for other ops)
   std::vector<ConvPack> conv;    // per op: the matrix-core form of a convolution's weights (empty for other ops)
-  ConvSlab conv_slab;            // ... all of them in one allocation, made when the first encrypted session is created
+  DevBuf conv_slab;              // ... all of them in one allocation, made when the first encrypted session is created
   std::vector<std::vector<int8_t>> conv_w;          // host copies of the convolution weights until then
-  ~dctfhe_circuit() {
-    if (ctx) hipSetDevice(ctx->device);
-    for (void* p : d_payload) if (p) hipFree(p);
-    for (int64_t* p : d_split) if (p) hipFree(p);
-  }
+  ~dctfhe_circuit() { if (ctx) hipSetDevice(ctx->device); }
 };
 
 // ---- max pool (OP_MAXPOOL): separable passes, rows then columns; each pass a log-depth tree of pairwise maxima
@@ -289,8 +310,14 @@ static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, PoolPl
 }
 
 // key-switch digits and bodies, small ciphertexts and the 64 single-entry tables 2^j of the one-bit steps, for `chunk` ciphertexts at a time
-struct LutScratch { uint8_t* digits = nullptr; uint64_t* bodies = nullptr; uint64_t* small = nullptr; int64_t* bit_tables = nullptr; size_t chunk = 0; };
-struct LutScratchOwner { LutScratch s{}; ~LutScratchOwner() { hipFree(s.digits); hipFree(s.bodies); hipFree(s.small); hipFree(s.bit_tables); } };
+struct LutScratch {
+  DevBuf d_digits, d_bodies, d_small, d_bit_tables;
+  size_t chunk = 0;
+  uint8_t* digits() const { return d_digits.as<uint8_t>(); }
+  uint64_t* bodies() const { return d_bodies.as<uint64_t>(); }
+  uint64_t* small() const { return d_small.as<uint64_t>(); }
+  const int64_t* bit_tables() const { return d_bit_tables.as<int64_t>(); }
+};
 
 struct dctfhe_session {
   dctfhe_ctx* ctx = nullptr;
@@ -299,42 +326,37 @@ struct dctfhe_session {
   int batch = 0;
   int D = 0;
   std::vector<uint64_t*> d_tensor;
-  std::vector<std::pair<size_t, uint64_t*>> owned;
+  std::vector<DevBuf> owned;        // the planner's allocations; d_tensor and pool_buf point into them
   std::vector<size_t> tensor_words;
   // encrypted tensors are stored at their effective dimension: row stride t_L[t] words = t_L[t]-1 mask words + the body;
   // t_deff[t] <= t_L[t]-1 is how many leading mask words may be non-zero.  Clear mode: one word per element.
   std::vector<size_t> t_L, t_deff;
-  LutScratchOwner lut;              // scratch for LUT sites
-  int* d_overflow = nullptr;
+  LutScratch lut;                   // scratch for LUT sites
+  DevBuf d_overflow;                // one int
   // `simulate`: per-op noise (fraction of the torus) injected by the clear look-up kernel; empty = noise-free
   std::vector<double> sim_sigma;
   std::vector<double> sim_sigma2;   // parity-split sites: the second look-up's (0 or absent: the first one's)
   uint64_t sim_seed = 0, sim_run = 0;
   // timing: events are created once and reused by every run; bootstraps per tier and image are fixed by the circuit
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<DevEvent> ev_pool;
   int64_t pbs_per_image[DCTFHE_MAX_TIERS] = {};
   // per op: the tree of a max pool (index maps in device memory) and its two level buffers (planner-owned, reused after the op)
   std::vector<std::unique_ptr<PoolPlan>> pool;
   std::vector<std::array<uint64_t*, 2>> pool_buf;
   // margin audit (dctfhe_session_set_audit): off unless d_audit_key is set.  The session's own copy of the small key, one slot per
   // (op, bootstrap with a key switch of its own) on the device, their fixed fields, each op's first slot, and the last run's slots
-  uint8_t* d_audit_key = nullptr;
-  size_t audit_key_bytes = 0;
-  margin_slot* d_audit = nullptr;
+  DevBuf d_audit_key, d_audit;      // bytes of the small key; margin_slot per slot
   std::vector<dctfhe_margin_stats> audit_slots, audit_last;
   std::vector<int> audit_first;
+  void wipe_audit_key() { if (d_audit_key.p) hipMemset(d_audit_key.p, 0, d_audit_key.bytes); }      // the secret does not outlive the audit
   void audit_off() {
-    if (d_audit_key) { hipMemset(d_audit_key, 0, audit_key_bytes); hipFree(d_audit_key); }    // the secret does not outlive the audit
-    hipFree(d_audit);
-    d_audit_key = nullptr; d_audit = nullptr; audit_key_bytes = 0;
+    wipe_audit_key();
+    d_audit_key.reset(); d_audit.reset();
     audit_slots.clear(); audit_last.clear(); audit_first.clear();
   }
   ~dctfhe_session() {
     if (ctx) hipSetDevice(ctx->device);
-    audit_off();
-    for (auto& o : owned) hipFree(o.second);
-    for (hipEvent_t e : ev_pool) hipEventDestroy(e);
-    hipFree(d_overflow);
+    wipe_audit_key();
   }
 };
 
@@ -454,18 +476,17 @@ extern "C" int dctfhe_ctx_create(int device_id, dctfhe_ctx** out) {
     return fail("dctfhe: no HIP device visible -- this engine has no CPU path");
   if (device_id < 0 || device_id >= ndev) return fail("dctfhe: device %d out of range (%d visible)", device_id, ndev);
   HIPCHK(hipSetDevice(device_id));
-  auto* c = new dctfhe_ctx;
+  std::unique_ptr<dctfhe_ctx> c(new dctfhe_ctx);
   c->device = device_id;
   HIPCHK(hipGetDeviceProperties(&c->prop, device_id));
   HIPCHK(hipStreamCreate(&c->own));
   c->stream = c->own;
-  *out = c;
+  *out = c.release();
   return 0;
 }
 extern "C" int dctfhe_ctx_destroy(dctfhe_ctx* c) {
   if (!c) return 0;
   hipSetDevice(c->device);
-  if (c->own) hipStreamDestroy(c->own);
   delete c;
   return 0;
 }
@@ -573,16 +594,16 @@ extern "C" int dctfhe_client_key_create(dctfhe_ctx* ctx, const dctfhe_params* pa
   }
   hipStream_t st = ctx->stream;
   const int D = params->D;
-  HIPCHK(hipMalloc(&C->d_S, D));
-  HIPCHK(hipMalloc(&C->d_s, params->n_max));
-  hipLaunchKernelGGL(k_gen_bits, dim3((D + 255) / 256), dim3(256), 0, st, C->sec, (uint64_t)STREAM_BIGKEY, C->d_S, D);
-  hipLaunchKernelGGL(k_gen_bits, dim3((params->n_max + 255) / 256), dim3(256), 0, st, C->sec, (uint64_t)STREAM_SMALLKEY, C->d_s, params->n_max);
+  HIPCHK(C->d_S.alloc(D));
+  HIPCHK(C->d_s.alloc(params->n_max));
+  hipLaunchKernelGGL(k_gen_bits, dim3((D + 255) / 256), dim3(256), 0, st, C->sec, (uint64_t)STREAM_BIGKEY, C->d_S.as<uint8_t>(), D);
+  hipLaunchKernelGGL(k_gen_bits, dim3((params->n_max + 255) / 256), dim3(256), 0, st, C->sec, (uint64_t)STREAM_SMALLKEY, C->d_s.as<uint8_t>(), params->n_max);
   HIPCHK(hipGetLastError());
   for (int ti = 0; ti < params->n_tiers; ti++) {
     const dctfhe_tier& t = params->tiers[ti];
     if (t.unroll != 2) continue;
-    HIPCHK(hipMalloc(&C->d_spair[ti], (size_t)(3 * t.n / 2)));
-    hipLaunchKernelGGL(k_pair_secret, dim3((t.n / 2 + 255) / 256), dim3(256), 0, st, C->d_s, t.n, C->d_spair[ti]);
+    HIPCHK(C->d_spair[ti].alloc((size_t)(3 * t.n / 2)));
+    hipLaunchKernelGGL(k_pair_secret, dim3((t.n / 2 + 255) / 256), dim3(256), 0, st, C->s(), t.n, C->d_spair[ti].as<uint8_t>());
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(st));
@@ -597,8 +618,8 @@ static int gen_bsk_std_chunk(dctfhe_client_key* C, int tier, int i0, int ni, uin
   const int N = 1 << t.logN, rows = (t.k + 1) * t.l;
   SET_LDS_ATTR(k_bsk_gen_std, 8192 * 8);
   // unroll 2: the "secret" is the pair secret of 3n/2 bits, i0/ni count its blocks
-  const uint8_t* bits = t.unroll == 2 ? C->d_spair[tier] : C->d_s;
-  hipLaunchKernelGGL(k_bsk_gen_std, dim3((unsigned)(ni * rows)), dim3(256), (size_t)N * 8, C->ctx->stream, bits, C->d_S, i0, t.k, N,
+  const uint8_t* bits = t.unroll == 2 ? C->d_spair[tier].as<uint8_t>() : C->s();
+  hipLaunchKernelGGL(k_bsk_gen_std, dim3((unsigned)(ni * rows)), dim3(256), (size_t)N * 8, C->ctx->stream, bits, C->S(), i0, t.k, N,
                      t.l, t.beta, t.glwe_sigma, C->pub, C->sec, (uint64_t)(STREAM_BSK_MASK + 2 * tier), d_out);
   HIPCHK(hipGetLastError());
   return 0;
@@ -635,32 +656,31 @@ static int eval_alloc(dctfhe_ctx* ctx, const dctfhe_params* params, std::unique_
   E->ctx = ctx; E->p = *params;
   hipStream_t st = ctx->stream;
   const int D = params->D;
-  HIPCHK(hipMalloc(&E->d_dummy, (size_t)(D + 1) * 8));
+  HIPCHK(E->d_dummy.alloc((size_t)(D + 1) * 8));
   for (int ti = 0; ti < params->n_tiers; ti++) {
     const dctfhe_tier& t = params->tiers[ti];
     TierKeys& tk = E->tiers[ti];
     tk.t = t;
     if (t.ksk_share >= 0) {
-      const TierKeys& o = E->tiers[t.ksk_share];
-      tk.d_ksk = o.d_ksk; tk.d_colsum = o.d_colsum; tk.d_kskT = o.d_kskT; tk.ncol_pad = o.ncol_pad; tk.colsum_eff = o.colsum_eff; tk.limbs = o.limbs;
+      tk.ks = E->tiers[t.ksk_share].ks;
     } else {
-      tk.own_ksk = true;
-      tk.limbs = ks_limbs(t);
-      tk.colsum_eff = new std::map<int, uint64_t*>();
+      KskKey& ks = E->ksk[ti];
+      tk.ks = &ks;
+      ks.limbs = ks_limbs(t);
       const size_t rows = (size_t)D * t.lk;
-      HIPCHK(hipMalloc(&tk.d_ksk, rows * (t.n + 1) * 8));
-      HIPCHK(hipMalloc(&tk.d_colsum, (size_t)(t.n + 1) * 8));
+      HIPCHK(ks.ksk.alloc(rows * (t.n + 1) * 8));
+      HIPCHK(ks.colsum.alloc((size_t)(t.n + 1) * 8));
       // the i8 MFMA key switch reads digits as SIGNED bytes: offset digits in [0, 2^betak) need betak <= 7;
       // wider gadgets and shapes the tiling does not cover go to the integer-VALU GEMM
       if (rows % 64 == 0 && rows <= (1u << 17) && t.betak <= 7) {
-        tk.ncol_pad = ((tk.limbs * (t.n + 1) + 127) / 128) * 128;
-        HIPCHK(hipMalloc(&tk.d_kskT, (size_t)tk.ncol_pad * rows));
+        ks.ncol_pad = ((ks.limbs * (t.n + 1) + 127) / 128) * 128;
+        HIPCHK(ks.kskT.alloc((size_t)ks.ncol_pad * rows));
       }
     }
     std::vector<cplx> tw;
     CHK(make_twiddles(t, tw));
-    HIPCHK(hipMalloc(&tk.d_tw, tw.size() * sizeof(cplx)));
-    HIPCHK(hipMemcpyAsync(tk.d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, st));
+    HIPCHK(tk.tw.alloc(tw.size() * sizeof(cplx)));
+    HIPCHK(hipMemcpyAsync(tk.tw.p, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     const int N = 1 << t.logN, M = N / 2;
     if (t.unroll == 2) {
@@ -672,16 +692,16 @@ static int eval_alloc(dctfhe_ctx* ctx, const dctfhe_params* params, std::unique_
       // maps with one large page (a 262 KB allocation lands wherever the sub-allocator has room, and the N = 8192 bootstrap measured
       // 0 / +4 / +5 / +11 % at table addresses that were 256 / 64 / 128 / 32 KB-aligned: profiles/r02_exp_ablations.log)
       const size_t wt_bytes = (((wt.size() * sizeof(cplx)) + (2u << 20) - 1) >> 21) << 21;
-      HIPCHK(hipMalloc(&tk.d_wtab, wt_bytes));
-      HIPCHK(hipMemcpyAsync(tk.d_wtab, wt.data(), wt.size() * sizeof(cplx), hipMemcpyHostToDevice, st));
+      HIPCHK(tk.wtab.alloc(wt_bytes));
+      HIPCHK(hipMemcpyAsync(tk.wtab.p, wt.data(), wt.size() * sizeof(cplx), hipMemcpyHostToDevice, st));
       HIPCHK(hipStreamSynchronize(st));
     }
     // PBS_PF_DIST iterations' worth of extra (zero) key blocks: the L2 warm-up of the last iterations reads past the key
     // (launch_pbs checks this contract: pbs_core.h, "L2 warm-up geometry")
     const size_t per_block = (size_t)(t.k + 1) * t.l * (t.k + 1) * M;
     const size_t pad = (size_t)PBS_PF_DIST * (t.unroll == 2 ? 3 : 1) * per_block;
-    HIPCHK(hipMalloc(&tk.d_bsk, (tier_bsk_elems(t) + pad) * sizeof(cplx)));
-    HIPCHK(hipMemsetAsync(tk.d_bsk + tier_bsk_elems(t), 0, pad * sizeof(cplx), st));
+    HIPCHK(tk.bsk.alloc((tier_bsk_elems(t) + pad) * sizeof(cplx)));
+    HIPCHK(hipMemsetAsync(tk.bsk.as<cplx>() + tier_bsk_elems(t), 0, pad * sizeof(cplx), st));
   }
   HIPCHK(hipStreamSynchronize(st));
   return 0;
@@ -692,21 +712,21 @@ static int eval_finish(dctfhe_eval_keys* E) {
   hipStream_t st = E->ctx->stream;
   for (int ti = 0; ti < E->p.n_tiers; ti++) {
     const dctfhe_tier& t = E->p.tiers[ti];
-    TierKeys& tk = E->tiers[ti];
-    if (!tk.own_ksk) continue;
+    if (t.ksk_share >= 0) continue;
+    KskKey& ks = E->ksk[ti];
     const size_t rows = (size_t)E->p.D * t.lk;
-    hipLaunchKernelGGL(k_ksk_colsum, dim3((t.n + 256) / 256), dim3(256), 0, st, tk.d_ksk, (int)rows, t.n, tk.d_colsum);
-    if (tk.d_kskT) {
+    hipLaunchKernelGGL(k_ksk_colsum, dim3((t.n + 256) / 256), dim3(256), 0, st, ks.ksk.as<uint64_t>(), (int)rows, t.n, ks.colsum.as<uint64_t>());
+    if (ks.kskT.p) {
       // the limb form keeps the top tk.limbs bytes of every word: make sure nothing sits below them (an imported key must be on the grid)
       DevBuf flag;
       HIPCHK(flag.alloc(sizeof(int)));
       HIPCHK(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-      hipLaunchKernelGGL(k_ksk_off_grid, dim3(2048), dim3(256), 0, st, tk.d_ksk, rows * (size_t)(t.n + 1), tk.limbs, flag.as<int>());
+      hipLaunchKernelGGL(k_ksk_off_grid, dim3(2048), dim3(256), 0, st, ks.ksk.as<uint64_t>(), rows * (size_t)(t.n + 1), ks.limbs, flag.as<int>());
       int bad = 0;
       HIPCHK(hipMemcpyAsync(&bad, flag.p, sizeof bad, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
-      if (bad) return fail("tier %d: key-switch key words off the 2^-%d torus grid (a key made by another build?)", ti, 8 * tk.limbs);
-      hipLaunchKernelGGL(k_ksk_to_limbs, dim3(4096), dim3(256), 0, st, tk.d_ksk, (int)rows, t.n, tk.limbs, tk.ncol_pad, tk.d_kskT);
+      if (bad) return fail("tier %d: key-switch key words off the 2^-%d torus grid (a key made by another build?)", ti, 8 * ks.limbs);
+      hipLaunchKernelGGL(k_ksk_to_limbs, dim3(4096), dim3(256), 0, st, ks.ksk.as<uint64_t>(), (int)rows, t.n, ks.limbs, ks.ncol_pad, ks.kskT.as<int8_t>());
     }
     HIPCHK(hipGetLastError());
   }
@@ -723,9 +743,9 @@ extern "C" int dctfhe_eval_keys_generate(dctfhe_client_key* C, dctfhe_eval_keys*
   for (int ti = 0; ti < C->p.n_tiers; ti++) {
     const dctfhe_tier& t = C->p.tiers[ti];
     TierKeys& tk = E->tiers[ti];
-    if (tk.own_ksk) {
-      hipLaunchKernelGGL(k_ksk_gen, dim3((unsigned)((size_t)D * t.lk)), dim3(256), 0, st, C->d_S, C->d_s, t.n, t.lk, t.betak, ks_limbs(t), t.lwe_sigma, C->pub, C->sec,
-                         (uint64_t)(STREAM_KSK + 2 * ti), tk.d_ksk);
+    if (t.ksk_share < 0) {
+      hipLaunchKernelGGL(k_ksk_gen, dim3((unsigned)((size_t)D * t.lk)), dim3(256), 0, st, C->S(), C->s(), t.n, t.lk, t.betak, ks_limbs(t), t.lwe_sigma, C->pub, C->sec,
+                         (uint64_t)(STREAM_KSK + 2 * ti), tk.ks->ksk.as<uint64_t>());
       HIPCHK(hipGetLastError());
     }
     const int N = 1 << t.logN, M = N / 2;
@@ -736,7 +756,7 @@ extern "C" int dctfhe_eval_keys_generate(dctfhe_client_key* C, dctfhe_eval_keys*
     for (int i0 = 0; i0 < blocks; i0 += chunk) {
       const int ni = std::min(chunk, blocks - i0);
       CHK(gen_bsk_std_chunk(C, ti, i0, ni, d_std.as<uint64_t>()));
-      CHK(launch_bsk_fourier(t, d_std.as<uint64_t>(), (size_t)ni * per_bit_polys, tk.d_tw, tk.d_bsk + (size_t)i0 * per_bit_polys * M, st));
+      CHK(launch_bsk_fourier(t, d_std.as<uint64_t>(), (size_t)ni * per_bit_polys, tk.tw.as<cplx>(), tk.bsk.as<cplx>() + (size_t)i0 * per_bit_polys * M, st));
     }
     HIPCHK(hipStreamSynchronize(st));
   }
@@ -785,10 +805,10 @@ extern "C" int dctfhe_eval_keys_export(dctfhe_eval_keys* E, void* buf, size_t ca
   for (int ti = 0; ti < E->p.n_tiers; ti++) {
     const dctfhe_tier& t = E->p.tiers[ti];
     if (t.ksk_share < 0) {
-      HIPCHK(hipMemcpy(q, E->tiers[ti].d_ksk, tier_ksk_words(E->p, t) * 8, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(q, E->ksk[ti].ksk.p, tier_ksk_words(E->p, t) * 8, hipMemcpyDeviceToHost));
       q += tier_ksk_words(E->p, t) * 8;
     }
-    HIPCHK(hipMemcpy(q, E->tiers[ti].d_bsk, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(q, E->tiers[ti].bsk.p, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyDeviceToHost));
     q += tier_bsk_elems(t) * sizeof(cplx);
   }
   return 0;
@@ -849,7 +869,7 @@ extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* bu
       const size_t rows = (size_t)P.D * t.lk;
       DevBuf d_ksk;
       HIPCHK(d_ksk.alloc(rows * (t.n + 1) * 8));
-      hipLaunchKernelGGL(k_ksk_gen, dim3((unsigned)rows), dim3(256), 0, st, C->d_S, C->d_s, t.n, t.lk, t.betak, ks_limbs(t), t.lwe_sigma, C->pub, C->sec,
+      hipLaunchKernelGGL(k_ksk_gen, dim3((unsigned)rows), dim3(256), 0, st, C->S(), C->s(), t.n, t.lk, t.betak, ks_limbs(t), t.lwe_sigma, C->pub, C->sec,
                          (uint64_t)(STREAM_KSK + 2 * ti), d_ksk.as<uint64_t>());
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(st));
@@ -858,18 +878,17 @@ extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* bu
     }
     const int N = 1 << t.logN, rows = (t.k + 1) * t.l;
     const int blocks = (int)tier_bsk_blocks(t), chunk = tier_bsk_chunk(t, 1);
-    const uint8_t* bits = t.unroll == 2 ? C->d_spair[ti] : C->d_s;
+    const uint8_t* bits = t.unroll == 2 ? C->d_spair[ti].as<uint8_t>() : C->s();
     DevBuf d_b;
     HIPCHK(d_b.alloc((size_t)chunk * rows * N * 8));
     SET_LDS_ATTR(k_bsk_gen_bodies, 8192 * 8);
     for (int i0 = 0; i0 < blocks; i0 += chunk) {
       const int ni = std::min(chunk, blocks - i0);
-      hipLaunchKernelGGL(k_bsk_gen_bodies, dim3((unsigned)(ni * rows)), dim3(256), (size_t)N * 8, st, bits, C->d_S, i0, t.k, N, t.l, t.beta, t.glwe_sigma,
+      hipLaunchKernelGGL(k_bsk_gen_bodies, dim3((unsigned)(ni * rows)), dim3(256), (size_t)N * 8, st, bits, C->S(), i0, t.k, N, t.l, t.beta, t.glwe_sigma,
                          C->pub, C->sec, (uint64_t)(STREAM_BSK_MASK + 2 * ti), d_b.as<uint64_t>());
       HIPCHK(hipGetLastError());
-      HIPCHK(hipStreamSynchronize(st));
       const size_t bytes = (size_t)ni * rows * N * 8;
-      HIPCHK(hipMemcpy(q, d_b.p, bytes, hipMemcpyDeviceToHost));
+      HIPCHK(d_b.download(q, bytes, st));
       q += bytes;
     }
   }
@@ -913,7 +932,7 @@ static int import_compressed(dctfhe_ctx* ctx, const void* buf, size_t size, dctf
       HIPCHK(d_b.alloc(rows * 8));
       HIPCHK(hipMemcpyAsync(d_b.p, q, rows * 8, hipMemcpyHostToDevice, st));
       CHK(launch_expand(pub, (uint64_t)(STREAM_KSK + 2 * ti), 0, (uint64_t)t.n + 1, t.n, ksk_grid_mask(t), d_b.as<uint64_t>(), 1, rows, (size_t)t.n + 1,
-                        tk.d_ksk, st));
+                        tk.ks->ksk.as<uint64_t>(), st));
       HIPCHK(hipStreamSynchronize(st));
       q += rows * 8;
     }
@@ -926,7 +945,7 @@ static int import_compressed(dctfhe_ctx* ctx, const void* buf, size_t size, dctf
     for (int i0 = 0; i0 < blocks; i0 += chunk) {
       const int ni = std::min(chunk, blocks - i0);
       CHK(expand_bsk_chunk(pub, ti, t, i0, ni, (const uint64_t*)q, d_b.as<uint64_t>(), d_std.as<uint64_t>(), st));
-      CHK(launch_bsk_fourier(t, d_std.as<uint64_t>(), (size_t)ni * per_bit_polys, tk.d_tw, tk.d_bsk + (size_t)i0 * per_bit_polys * M, st));
+      CHK(launch_bsk_fourier(t, d_std.as<uint64_t>(), (size_t)ni * per_bit_polys, tk.tw.as<cplx>(), tk.bsk.as<cplx>() + (size_t)i0 * per_bit_polys * M, st));
       HIPCHK(hipStreamSynchronize(st));      // the next chunk's copy reuses d_b and d_std
       q += (size_t)ni * rows * N * 8;
     }
@@ -956,8 +975,7 @@ extern "C" int dctfhe_eval_keys_decompress_bsk(dctfhe_ctx* ctx, const void* buf,
   HIPCHK(d_b.alloc(body_bytes));
   HIPCHK(d_std.alloc(body_bytes * (t.k + 1)));
   CHK(expand_bsk_chunk(pub, tier, t, 0, (int)tier_bsk_blocks(t), (const uint64_t*)q, d_b.as<uint64_t>(), d_std.as<uint64_t>(), ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(out, d_std.p, body_bytes * (t.k + 1), hipMemcpyDeviceToHost));
+  HIPCHK(d_std.download(out, body_bytes * (t.k + 1), ctx->stream));
   return 0;
 }
 
@@ -976,10 +994,10 @@ extern "C" int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t 
   for (int ti = 0; ti < h.params.n_tiers; ti++) {
     const dctfhe_tier& t = h.params.tiers[ti];
     if (t.ksk_share < 0) {
-      HIPCHK(hipMemcpy(E->tiers[ti].d_ksk, q, tier_ksk_words(h.params, t) * 8, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(E->ksk[ti].ksk.p, q, tier_ksk_words(h.params, t) * 8, hipMemcpyHostToDevice));
       q += tier_ksk_words(h.params, t) * 8;
     }
-    HIPCHK(hipMemcpy(E->tiers[ti].d_bsk, q, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(E->tiers[ti].bsk.p, q, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyHostToDevice));
     q += tier_bsk_elems(t) * sizeof(cplx);
   }
   CHK(eval_finish(E.get()));
@@ -990,15 +1008,15 @@ extern "C" int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t 
 // ---- test / client views ---------------------------------------------------------------------------
 extern "C" int dctfhe_client_key_export_secret(dctfhe_client_key* C, uint8_t* big_key, uint8_t* small_key) {
   HIPCHK(hipSetDevice(C->ctx->device));
-  HIPCHK(hipMemcpy(big_key, C->d_S, C->p.D, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(small_key, C->d_s, C->p.n_max, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(big_key, C->S(), C->p.D, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(small_key, C->s(), C->p.n_max, hipMemcpyDeviceToHost));
   return 0;
 }
 extern "C" int dctfhe_eval_keys_export_ksk(dctfhe_eval_keys* K, int tier, uint64_t* out) {
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   const dctfhe_tier& t = K->p.tiers[tier];
   HIPCHK(hipSetDevice(K->ctx->device));
-  HIPCHK(hipMemcpy(out, K->tiers[tier].d_ksk, (size_t)K->p.D * t.lk * (t.n + 1) * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, K->tiers[tier].ks->ksk.p, (size_t)K->p.D * t.lk * (t.n + 1) * 8, hipMemcpyDeviceToHost));
   return 0;
 }
 // the standard-domain bootstrap key, regenerated from the client's streams (what dctfhe_eval_keys_generate transformed)
@@ -1010,8 +1028,7 @@ extern "C" int dctfhe_client_key_export_bsk(dctfhe_client_key* C, int tier, uint
   DevBuf d;
   HIPCHK(d.alloc(words * 8));
   CHK(gen_bsk_std_chunk(C, tier, 0, (int)tier_bsk_blocks(t), d.as<uint64_t>()));     // unroll 2: the key of the pair secret
-  HIPCHK(hipStreamSynchronize(C->ctx->stream));
-  HIPCHK(hipMemcpy(out, d.p, words * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d.download(out, words * 8, C->ctx->stream));
   return 0;
 }
 
@@ -1028,8 +1045,7 @@ extern "C" int dctfhe_rng_device(dctfhe_ctx* ctx, const uint8_t* key32, uint64_t
   HIPCHK(d.alloc(count * 8));
   hipLaunchKernelGGL(k_rng_fill, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, key_from_bytes(key32), stream, idx0, d.as<uint64_t>(), count);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(out, d.p, count * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d.download(out, count * 8, ctx->stream));
   return 0;
 }
 
@@ -1048,7 +1064,7 @@ extern "C" int dctfhe_encrypt_rows(dctfhe_ctx* ctx, dctfhe_client_key* C, const 
   HIPCHK(hipMemcpyAsync(d_ph.p, phases, count * 8, hipMemcpyHostToDevice, ctx->stream));
   // fresh streams per call: a (mask, noise) pair is never drawn twice under one handle; handles differ by their nonce
   const uint64_t stream = (uint64_t)STREAM_ENC + ((++C->enc_calls) << 16);
-  hipLaunchKernelGGL(k_lwe_encrypt, dim3((unsigned)count), dim3(256), 0, ctx->stream, C->d_S, D, dim, dim_eff, d_ph.as<uint64_t>(),
+  hipLaunchKernelGGL(k_lwe_encrypt, dim3((unsigned)count), dim3(256), 0, ctx->stream, C->S(), D, dim, dim_eff, d_ph.as<uint64_t>(),
                      C->p.input_sigma, C->enc_pub, C->enc_sec, stream, d_ct.as<uint64_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(cts, d_ct.p, count * L * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1083,7 +1099,7 @@ extern "C" int dctfhe_decrypt_rows(dctfhe_ctx* ctx, dctfhe_client_key* C, const 
   HIPCHK(d_ph.alloc(count * 8));
   HIPCHK(d_ct.alloc(count * L * 8));
   HIPCHK(hipMemcpyAsync(d_ct.p, cts, count * L * 8, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_lwe_phase, dim3((unsigned)count), dim3(256), 0, ctx->stream, C->d_S, dim, d_ct.as<uint64_t>(), d_ph.as<uint64_t>());
+  hipLaunchKernelGGL(k_lwe_phase, dim3((unsigned)count), dim3(256), 0, ctx->stream, C->S(), dim, d_ct.as<uint64_t>(), d_ph.as<uint64_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(phases, d_ph.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1104,7 +1120,7 @@ extern "C" int dctfhe_decrypt_packed(dctfhe_ctx* ctx, dctfhe_client_key* C, int 
   HIPCHK(d_ph.alloc(count * 8));
   HIPCHK(d_rows.alloc(bytes));
   HIPCHK(hipMemcpyAsync(d_rows.p, rows, bytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_phase16, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, C->d_s, n, d_rows.as<uint16_t>(), count, d_ph.as<uint64_t>());
+  hipLaunchKernelGGL(k_phase16, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx->stream, C->s(), n, d_rows.as<uint16_t>(), count, d_ph.as<uint64_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(phases, d_ph.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1125,7 +1141,7 @@ extern "C" int dctfhe_encrypt_seeded(dctfhe_ctx* ctx, dctfhe_client_key* C, cons
   HIPCHK(d_b.alloc(count * 8));
   HIPCHK(hipMemcpyAsync(d_ph.p, phases, count * 8, hipMemcpyHostToDevice, ctx->stream));
   const uint64_t stream = (uint64_t)STREAM_ENC + ((++C->enc_calls) << 16);      // the step dctfhe_encrypt_rows takes
-  hipLaunchKernelGGL(k_lwe_encrypt_seeded, dim3((unsigned)count), dim3(256), 0, ctx->stream, C->d_S, D, dim_eff, d_ph.as<uint64_t>(), C->p.input_sigma,
+  hipLaunchKernelGGL(k_lwe_encrypt_seeded, dim3((unsigned)count), dim3(256), 0, ctx->stream, C->S(), D, dim_eff, d_ph.as<uint64_t>(), C->p.input_sigma,
                      C->enc_pub, C->enc_sec, stream, d_b.as<uint64_t>());
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(bodies, d_b.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1155,13 +1171,13 @@ extern "C" int dctfhe_expand_seeded(dctfhe_ctx* ctx, const uint8_t* mask_key, ui
 struct Timers {
   hipStream_t st;
   bool on;
-  std::vector<hipEvent_t>* pool;     // owned by the session (or by nobody: primitives pass on = false)
+  std::vector<DevEvent>* pool;       // owned by the session (or by nobody: primitives pass on = false)
   struct Span { hipEvent_t a, b; int cat; };
   std::vector<Span> spans;
   size_t used = 0;
   hipEvent_t take() {
-    if (used == pool->size()) { hipEvent_t e; hipEventCreate(&e); pool->push_back(e); }
-    return (*pool)[used++];
+    if (used == pool->size()) { pool->emplace_back(); pool->back().create(); }
+    return (*pool)[used++].e;
   }
   int begin(int cat) {
     if (!on) return -1;
@@ -1190,48 +1206,50 @@ struct KsInput {
 // key switch of `count` ciphertexts into small ciphertexts of tier `tier` (sc.small; sc.digits and sc.bodies in between)
 static int dev_keyswitch(dctfhe_keys* K, int tier, const KsInput& in, size_t count, const LutScratch& sc, Timers* tm) {
   const dctfhe_tier& t = K->p.tiers[tier];
-  TierKeys& tk = K->tiers[tier];
+  KskKey& ks = *K->tiers[tier].ks;
+  const uint64_t* ksk = ks.ksk.as<uint64_t>();
+  const int8_t* kskT = ks.kskT.as<int8_t>();
   const int D = K->p.D, deff = in.deff;
   const size_t L = in.L;                         // row stride of the input ciphertexts (body at L-1)
   const int Dmax = (int)std::min<size_t>(L - 1, (size_t)D);
   hipStream_t st = K->ctx->stream;
-  int De = (deff > 0 && deff < Dmax && tk.d_kskT && (deff * t.lk) % 64 == 0) ? deff : Dmax;
-  if (!tk.d_kskT && De != D) return fail("key switch: the integer-VALU path needs full-width rows");
-  if (tk.d_kskT && (De * t.lk) % 64 != 0) return fail("key switch: %d rows x %d levels is not a multiple of 64", De, t.lk);
-  const uint64_t* colsum = tk.d_colsum;
+  int De = (deff > 0 && deff < Dmax && kskT && (deff * t.lk) % 64 == 0) ? deff : Dmax;
+  if (!kskT && De != D) return fail("key switch: the integer-VALU path needs full-width rows");
+  if (kskT && (De * t.lk) % 64 != 0) return fail("key switch: %d rows x %d levels is not a multiple of 64", De, t.lk);
+  const uint64_t* colsum = ks.colsum.as<uint64_t>();
   if (De < D) {
-    auto it = tk.colsum_eff->find(De);
-    if (it == tk.colsum_eff->end()) {
-      uint64_t* cs = nullptr;
-      HIPCHK(hipMalloc(&cs, (size_t)(t.n + 1) * 8));
-      hipLaunchKernelGGL(k_ksk_colsum, dim3((t.n + 256) / 256), dim3(256), 0, st, tk.d_ksk, De * t.lk, t.n, cs);
+    auto it = ks.colsum_eff.find(De);
+    if (it == ks.colsum_eff.end()) {      // filled here, entered into the cache only once the fill is under way without an error
+      DevBuf cs;
+      HIPCHK(cs.alloc((size_t)(t.n + 1) * 8));
+      hipLaunchKernelGGL(k_ksk_colsum, dim3((t.n + 256) / 256), dim3(256), 0, st, ksk, De * t.lk, t.n, cs.as<uint64_t>());
       HIPCHK(hipGetLastError());
-      it = tk.colsum_eff->emplace(De, cs).first;
+      it = ks.colsum_eff.emplace(De, std::move(cs)).first;
     }
-    colsum = it->second;
+    colsum = it->second.as<uint64_t>();
   }
   const int h = tm ? tm->begin(CAT_KS) : -1;
   const size_t total = count * (size_t)De;
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 65536);
 #define KS_DECOMPOSE(SRC, ...) \
-  hipLaunchKernelGGL(k_ks_decompose<SRC>, dim3(grid), dim3(256), 0, st, SRC{__VA_ARGS__}, count, De, in.shift, in.body_add, t.lk, t.betak, sc.digits, sc.bodies)
+  hipLaunchKernelGGL(k_ks_decompose<SRC>, dim3(grid), dim3(256), 0, st, SRC{__VA_ARGS__}, count, De, in.shift, in.body_add, t.lk, t.betak, sc.digits(), sc.bodies())
   switch (in.source) {
     case KS_ROWS: KS_DECOMPOSE(ks_src_rows, in.rows, L); break;
     case KS_DIFF: KS_DECOMPOSE(ks_src_diff, in.rows, L, in.ia, in.ib); break;
     case KS_SUM:  KS_DECOMPOSE(ks_src_sum, in.rows, L, in.rows_b, in.Lb, in.Lb - 1); break;
   }
 #undef KS_DECOMPOSE
-  if (tk.d_kskT) {   // matrix-core path: i8 digits x signed byte limbs of the key
-    const unsigned ncb = (unsigned)(tk.ncol_pad / 128), nrb = (unsigned)((count + 127) / 128), cpx = (ncb + 7) / 8;
+  if (kskT) {   // matrix-core path: i8 digits x signed byte limbs of the key
+    const unsigned ncb = (unsigned)(ks.ncol_pad / 128), nrb = (unsigned)((count + 127) / 128), cpx = (ncb + 7) / 8;
 #define KS_LAUNCH(LB)                                                                                                                      \
-    hipLaunchKernelGGL(k_ks_mfma<LB>, dim3(8 * cpx * nrb), dim3(256), 0, st, sc.digits, sc.bodies, count, De * t.lk, tk.d_kskT, D * t.lk, tk.ncol_pad, \
-                       colsum, t.n, t.betak, sc.small)
-    if (tk.limbs == 2) KS_LAUNCH(2); else if (tk.limbs == 4) KS_LAUNCH(4); else KS_LAUNCH(8);
+    hipLaunchKernelGGL(k_ks_mfma<LB>, dim3(8 * cpx * nrb), dim3(256), 0, st, sc.digits(), sc.bodies(), count, De * t.lk, kskT, D * t.lk, ks.ncol_pad, \
+                       colsum, t.n, t.betak, sc.small())
+    if (ks.limbs == 2) KS_LAUNCH(2); else if (ks.limbs == 4) KS_LAUNCH(4); else KS_LAUNCH(8);
 #undef KS_LAUNCH
   } else {           // shapes the MFMA tiling does not cover (D*lk not a multiple of 64, betak = 8): integer VALU GEMM
     constexpr int CT = 16;
     dim3 g2((t.n + 1 + 255) / 256, (unsigned)((count + CT - 1) / CT));
-    hipLaunchKernelGGL(k_ks_gemm<CT>, g2, dim3(256), 0, st, sc.digits, sc.bodies, count, D * t.lk, tk.d_ksk, tk.d_colsum, t.n, t.betak, sc.small);
+    hipLaunchKernelGGL(k_ks_gemm<CT>, g2, dim3(256), 0, st, sc.digits(), sc.bodies(), count, D * t.lk, ksk, colsum, t.n, t.betak, sc.small());
   }
   HIPCHK(hipGetLastError());
   if (tm) tm->end(h);
@@ -1258,11 +1276,11 @@ static int dev_pbs(dctfhe_keys* K, int tier, const uint64_t* d_small, size_t cou
   const dctfhe_tier& t = K->p.tiers[tier];
   pbs_launch a;
   a.cts_small = d_small; a.count = count; a.n = t.n; a.beta = t.beta;
-  a.bsk = K->tiers[tier].d_bsk; a.tw = K->tiers[tier].d_tw; a.wtab = K->tiers[tier].d_wtab;
+  a.bsk = K->tiers[tier].bsk.as<cplx>(); a.tw = K->tiers[tier].tw.as<cplx>(); a.wtab = K->tiers[tier].wtab.as<cplx>();
   a.tables = lut.tables; a.w = lut.w; a.table_idx = lut.idx; a.hw = lut.hw; a.nchan = lut.nchan; a.e_offset = lut.e_offset;
   const int ring = t.k << t.logN;
   if (out.L < (size_t)ring + 1) return fail("bootstrap output rows of %zu words cannot hold a ring of %d", out.L, ring);
-  a.out = out.rows; a.D_out = (int)out.L - 1; a.accumulate = out.accumulate; a.body_add = out.body_add; a.dummy = K->d_dummy; a.bsk_wrap = 0;
+  a.out = out.rows; a.D_out = (int)out.L - 1; a.accumulate = out.accumulate; a.body_add = out.body_add; a.dummy = K->d_dummy.as<uint64_t>(); a.bsk_wrap = 0;
   // L2 warm-up: each workgroup touches 1/pf_parts of the next key blocks; the paired two-bit kernel at N = 2048 measures 3 % better
   // without (profiles/r02_exp_ablations.log: 22.5 vs 23.2 ms), every other barrier-coupled kernel better with (T4r 82.4 vs 86.3, T5a 25.7
   // vs 26.6).  The parts are dealt by blockIdx / 8, i.e. per XCD: with one 512-thread workgroup per CU an XCD holds 32 of them, and 32
@@ -1295,9 +1313,9 @@ static int dev_margin_probe(hipStream_t st, const dctfhe_tier& t, const uint8_t*
 static int dev_ks_pbs(dctfhe_keys* K, int tier, const KsInput& in, size_t count, const PbsLut& lut, const PbsOut& out, const LutScratch& sc, Timers* tm,
                       const MarginProbe* probe = nullptr) {
   CHK(dev_keyswitch(K, tier, in, count, sc, tm));
-  CHK(dev_ms_center(K, tier, sc.small, count, tm));
-  if (probe) CHK(dev_margin_probe(K->ctx->stream, K->p.tiers[tier], probe->key, sc.small, count, lut.w, nullptr, probe->slot));
-  return dev_pbs(K, tier, sc.small, count, lut, out, tm);
+  CHK(dev_ms_center(K, tier, sc.small(), count, tm));
+  if (probe) CHK(dev_margin_probe(K->ctx->stream, K->p.tiers[tier], probe->key, sc.small(), count, lut.w, nullptr, probe->slot));
+  return dev_pbs(K, tier, sc.small(), count, lut, out, tm);
 }
 
 static int dev_conv2d(hipStream_t st, const uint64_t* in, int batch, int Cin, int H, int W, size_t Lin, size_t deff, const int8_t* d_w, const ConvPack* pk, int Cout,
@@ -1357,7 +1375,7 @@ static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, siz
       KsInput in = work; in.shift = p - i;
       PbsOut bit{w0, Lw}; bit.accumulate = true; bit.body_add = (uint64_t)0 - (1ULL << vlog);
       const MarginProbe pr = probe ? probe->at(i) : MarginProbe{};
-      CHK(dev_ks_pbs(K, L.steps.at(i), in, cn, PbsLut{sc.bit_tables + vlog}, bit, sc, tm, probe ? &pr : nullptr));
+      CHK(dev_ks_pbs(K, L.steps.at(i), in, cn, PbsLut{sc.bit_tables() + vlog}, bit, sc, tm, probe ? &pr : nullptr));
     }
     if (split) {
       // t = 2 t' + b0 sits under the padding bit once the r rounding steps are done.  The last step was one more of them, on b0: it left
@@ -1365,7 +1383,7 @@ static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, siz
       // Second look-up first, while w0 still holds t': key switch of w0 + par (b0 in the padding bit, never materialised), table Dt
       // -> (-1)^b0 Dt[t'] into par; then the first look-up S[t'] into w0 as for any site, and the sum.
       PbsOut par{b.par, b.Lp}; par.body_add = (uint64_t)0 - (1ULL << 62);
-      CHK(dev_pbs(K, L.steps.at(steps - 1), sc.small, cn, PbsLut{sc.bit_tables + 62}, par, tm));
+      CHK(dev_pbs(K, L.steps.at(steps - 1), sc.small(), cn, PbsLut{sc.bit_tables() + 62}, par, tm));
       KsInput sum = work; sum.source = KS_SUM; sum.rows_b = b.par; sum.Lb = b.Lp;
       PbsLut tab2 = tab; tab2.tables = b.tab_d;
       const MarginProbe pr = probe ? probe->at(steps) : MarginProbe{};
@@ -1393,20 +1411,19 @@ static int round_chain_deff(const dctfhe_keys* K, int src_deff, const LutSite& L
 // can the key switch of `tier` run on the first deff rows of its key only?  (matrix-core path, whole 64-row steps; otherwise it walks the
 // whole stored row and every word of it has to be meaningful)
 static bool ks_narrows(const dctfhe_keys* K, int tier, int deff) {
-  return K->tiers[tier].d_kskT != nullptr && ((size_t)deff * (size_t)K->p.tiers[tier].lk) % 64 == 0;
+  return K->tiers[tier].mfma() && ((size_t)deff * (size_t)K->p.tiers[tier].lk) % 64 == 0;
 }
 
 static int alloc_lut_scratch(dctfhe_keys* K, size_t chunk, LutScratch* sc) {
   int lkmax = 1, nmax = 1;
   for (int i = 0; i < K->p.n_tiers; i++) { lkmax = std::max(lkmax, K->p.tiers[i].lk); nmax = std::max(nmax, K->p.tiers[i].n); }
   sc->chunk = chunk;
-  HIPCHK(hipMalloc(&sc->digits, chunk * (size_t)K->p.D * lkmax));
-  HIPCHK(hipMalloc(&sc->bodies, chunk * 8));
-  HIPCHK(hipMalloc(&sc->small, chunk * (size_t)(nmax + 1) * 8));
-  HIPCHK(hipMalloc(&sc->bit_tables, 64 * 8));
+  HIPCHK(sc->d_digits.alloc(chunk * (size_t)K->p.D * lkmax));
+  HIPCHK(sc->d_bodies.alloc(chunk * 8));
+  HIPCHK(sc->d_small.alloc(chunk * (size_t)(nmax + 1) * 8));
   int64_t bt[64];
   for (int j = 0; j < 64; j++) bt[j] = (int64_t)(1ULL << j);
-  HIPCHK(hipMemcpy(sc->bit_tables, bt, sizeof bt, hipMemcpyHostToDevice));
+  HIPCHK(sc->d_bit_tables.upload(bt, sizeof bt));
   return 0;
 }
 
@@ -1466,13 +1483,12 @@ extern "C" int dctfhe_keyswitch_prefix(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
   const size_t L = (size_t)K->p.D + 1;
   DevBuf d_in;
   HIPCHK(d_in.upload(cts, count * L * 8));
-  LutScratchOwner sc;
-  CHK(alloc_lut_scratch(K, count, &sc.s));
+  LutScratch sc;
+  CHK(alloc_lut_scratch(K, count, &sc));
   KsInput in;
   in.rows = d_in.as<uint64_t>(); in.L = L; in.deff = deff; in.shift = shift;
-  CHK(dev_keyswitch(K, tier, in, count, sc.s, nullptr));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(cts_small, sc.s.small, count * (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost));
+  CHK(dev_keyswitch(K, tier, in, count, sc, nullptr));
+  HIPCHK(sc.d_small.download(cts_small, count * (size_t)(t.n + 1) * 8, ctx->stream));
   return 0;
 }
 extern "C" int dctfhe_keyswitch(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, int shift, uint64_t* cts_small) {
@@ -1492,7 +1508,7 @@ static int dev_keyswitch_pack(dctfhe_keys* K, int tier, const uint64_t* d_rows, 
     KsInput in;
     in.rows = d_rows + c0 * L; in.L = L; in.deff = deff;
     CHK(dev_keyswitch(K, tier, in, cn, sc, nullptr));
-    hipLaunchKernelGGL(k_pack16, dim3(ew_grid(words / 4)), dim3(256), 0, st, sc.small, words, d_pack.as<uint16_t>());
+    hipLaunchKernelGGL(k_pack16, dim3(ew_grid(words / 4)), dim3(256), 0, st, sc.small(), words, d_pack.as<uint16_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(rows + c0 * n1, d_pack.p, words * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
   }
@@ -1510,9 +1526,9 @@ extern "C" int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int t
   const size_t L = (size_t)dim + 1;
   DevBuf d_in;
   HIPCHK(d_in.upload(cts, count * L * 8));
-  LutScratchOwner sc;
-  CHK(alloc_lut_scratch(K, std::min<size_t>(count, 16384), &sc.s));
-  return dev_keyswitch_pack(K, tier, d_in.as<uint64_t>(), L, deff ? deff : dim, count, sc.s, rows);
+  LutScratch sc;
+  CHK(alloc_lut_scratch(K, std::min<size_t>(count, 16384), &sc));
+  return dev_keyswitch_pack(K, tier, d_in.as<uint64_t>(), L, deff ? deff : dim, count, sc, rows);
 }
 
 // the centred mod switch on host buffers (the scheduler applies it between every key switch and its bootstrap)
@@ -1525,8 +1541,7 @@ extern "C" int dctfhe_modswitch_center(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
   DevBuf d;
   HIPCHK(d.upload(cts_small, bytes));
   CHK(dev_ms_center(K, tier, d.as<uint64_t>(), count, nullptr));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(cts_small, d.p, bytes, hipMemcpyDeviceToHost));
+  HIPCHK(d.download(cts_small, bytes, ctx->stream));
   return 0;
 }
 
@@ -1551,8 +1566,7 @@ extern "C" int dctfhe_pbs(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const 
   PbsLut lut;
   lut.tables = d_tab.as<int64_t>(); lut.w = w; lut.idx = d_idx.as<int32_t>();
   CHK(dev_pbs(K, tier, d_small.as<uint64_t>(), count, lut, PbsOut{d_out.as<uint64_t>(), L}, nullptr));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(cts_out, d_out.p, count * L * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d_out.download(cts_out, count * L * 8, ctx->stream));
   return 0;
 }
 
@@ -1584,8 +1598,8 @@ extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int 
   HIPCHK(d_work.upload(cts, count * L * 8));
   HIPCHK(d_tab.upload(split ? halves.data() : tables, ((size_t)ntab << w) * 8));
   if (table_idx) HIPCHK(d_idx.upload(table_idx, count * 4));
-  LutScratchOwner sc;
-  CHK(alloc_lut_scratch(K, std::min<size_t>(count, 4096), &sc.s));
+  LutScratch sc;
+  CHK(alloc_lut_scratch(K, std::min<size_t>(count, 4096), &sc));
   // the site a record of this look-up would decode to (rows arrive shifted and offset; without an index every ciphertext takes table 0)
   LutSite site;
   site.p = p; site.r = r; site.w = w; site.ntab = table_idx ? ntab : 1; site.tab_tier = tab_tier; site.steps.bit = bit_tier;
@@ -1593,7 +1607,7 @@ extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int 
   rows.src = rows.work = d_work.as<uint64_t>(); rows.Ls = rows.Lw = L;
   rows.tables = d_tab.as<int64_t>(); rows.idx = d_idx.as<int32_t>();
   if (split) {
-    HIPCHK(d_par.alloc(sc.s.chunk * L * 8));
+    HIPCHK(d_par.alloc(sc.chunk * L * 8));
     site.mode = LUT_SPLIT; site.tier2_named = tab_tier2;
     rows.par = d_par.as<uint64_t>(); rows.Lp = L;
     rows.tab_s = d_tab.as<int64_t>(); rows.tab_d = d_tab.as<int64_t>() + ((size_t)ntab << (w - 1));
@@ -1603,9 +1617,8 @@ extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int 
                        1ULL << (63 - p + r - 1));
     HIPCHK(hipGetLastError());
   }
-  CHK(dev_round_lut(K, site, rows, count, 1, sc.s, nullptr, 0));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(cts_out, d_work.p, count * L * 8, hipMemcpyDeviceToHost));
+  CHK(dev_round_lut(K, site, rows, count, 1, sc, nullptr, 0));
+  HIPCHK(d_work.download(cts_out, count * L * 8, ctx->stream));
   return 0;
 }
 // A table of 7 input bits is split inside (both look-ups on tab_tier): at the half-box of a 6-bit table instead of half of it
@@ -1624,17 +1637,14 @@ extern "C" int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int bat
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   const size_t nin = (size_t)batch * Cin * H * W * L, nout = (size_t)batch * Cout * Ho * Wo * L, nw = (size_t)Cout * Cin * KH * KW;
   DevBuf d_in, d_out, d_w;
-  HIPCHK(d_in.alloc(nin * 8));
+  HIPCHK(d_in.upload(in, nin * 8));
   HIPCHK(d_out.alloc(nout * 8));
-  HIPCHK(d_w.alloc(nw));
-  HIPCHK(hipMemcpy(d_in.p, in, nin * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_w.p, weight, nw, hipMemcpyHostToDevice));
-  ConvSlab slab;
+  HIPCHK(d_w.upload(weight, nw));
+  DevBuf slab;
   std::vector<ConvPack> pk;
   CHK(build_conv_packs({weight}, {ConvSite{Cout, Cin, H, W, KH, KW, stride, pad}}, &slab, &pk));
   CHK(dev_conv2d(ctx->stream, d_in.as<uint64_t>(), batch, Cin, H, W, L, L - 1, d_w.as<int8_t>(), &pk[0], Cout, KH, KW, stride, pad, d_out.as<uint64_t>(), L));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(out, d_out.p, nout * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d_out.download(out, nout * 8, ctx->stream));
   return 0;
 }
 
@@ -1655,14 +1665,11 @@ extern "C" int dctfhe_add_rows(dctfhe_ctx* ctx, const uint64_t* a, int dim_a, in
   HIPCHK(hipSetDevice(ctx->device));
   const size_t La = (size_t)dim_a + 1, Lb = (size_t)dim_b + 1, Lo = (size_t)dim_o + 1;
   DevBuf da, db, d_o;
-  HIPCHK(da.alloc(count * La * 8)); HIPCHK(db.alloc(count * Lb * 8)); HIPCHK(d_o.alloc(count * Lo * 8));
-  HIPCHK(hipMemcpy(da.p, a, count * La * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(db.p, b, count * Lb * 8, hipMemcpyHostToDevice));
+  HIPCHK(da.upload(a, count * La * 8)); HIPCHK(db.upload(b, count * Lb * 8)); HIPCHK(d_o.alloc(count * Lo * 8));
   hipLaunchKernelGGL(k_add, dim3(ew_grid(count * Lo)), dim3(256), 0, ctx->stream, da.as<uint64_t>(), La, (size_t)deff_a, db.as<uint64_t>(), Lb, (size_t)deff_b,
                      d_o.as<uint64_t>(), Lo, count);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(out, d_o.p, count * Lo * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d_o.download(out, count * Lo * 8, ctx->stream));
   return 0;
 }
 // inout: rows of dim_o + 1 words; the kernel writes the first nwords mask words (a << shift; zero from deff_a on) and the body
@@ -1676,14 +1683,11 @@ extern "C" int dctfhe_affine_rows(dctfhe_ctx* ctx, const uint64_t* a, int dim_a,
   HIPCHK(hipSetDevice(ctx->device));
   const size_t La = (size_t)dim_a + 1, Lo = (size_t)dim_o + 1;
   DevBuf da, d_o;
-  HIPCHK(da.alloc(count * La * 8)); HIPCHK(d_o.alloc(count * Lo * 8));
-  HIPCHK(hipMemcpy(da.p, a, count * La * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_o.p, inout, count * Lo * 8, hipMemcpyHostToDevice));
+  HIPCHK(da.upload(a, count * La * 8)); HIPCHK(d_o.upload(inout, count * Lo * 8));
   hipLaunchKernelGGL(k_affine, dim3(ew_grid(count * ((size_t)nwords + 1))), dim3(256), 0, ctx->stream, da.as<uint64_t>(), La, (size_t)deff_a, d_o.as<uint64_t>(), Lo, count,
                      (size_t)nwords, shift, body_add);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(inout, d_o.p, count * Lo * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d_o.download(inout, count * Lo * 8, ctx->stream));
   return 0;
 }
 // in [batch][C][H][W] rows -> out [batch][C][H/K][W/K] rows: window sums with floor semantics (border rows / columns dropped)
@@ -1697,12 +1701,10 @@ extern "C" int dctfhe_sum_pool_rows(dctfhe_ctx* ctx, const uint64_t* in, int dim
   const int Ho = H / K, Wo = W / K;
   const size_t nin = (size_t)batch * C * H * W * Li, nout = (size_t)batch * C * Ho * Wo * Lo;
   DevBuf di, d_o;
-  HIPCHK(di.alloc(nin * 8)); HIPCHK(d_o.alloc(nout * 8));
-  HIPCHK(hipMemcpy(di.p, in, nin * 8, hipMemcpyHostToDevice));
+  HIPCHK(di.upload(in, nin * 8)); HIPCHK(d_o.alloc(nout * 8));
   hipLaunchKernelGGL(k_sum_pool, dim3(ew_grid(nout)), dim3(256), 0, ctx->stream, di.as<uint64_t>(), C, H, W, Li, (size_t)deff_in, K, Ho, Wo, d_o.as<uint64_t>(), Lo, nout);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(out, d_o.p, nout * 8, hipMemcpyDeviceToHost));
+  HIPCHK(d_o.download(out, nout * 8, ctx->stream));
   return 0;
 }
 
@@ -1725,14 +1727,13 @@ extern "C" int dctfhe_keyswitch_diff(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int t
   HIPCHK(d_in.upload(cts, count * L * 8));
   HIPCHK(d_ia.upload(ia, count * 4));
   HIPCHK(d_ib.upload(ib, count * 4));
-  LutScratchOwner sc;
-  CHK(alloc_lut_scratch(K, count, &sc.s));
+  LutScratch sc;
+  CHK(alloc_lut_scratch(K, count, &sc));
   KsInput in;
   in.rows = d_in.as<uint64_t>(); in.L = L; in.deff = deff; in.shift = shift; in.body_add = body_add;
   in.source = KS_DIFF; in.ia = d_ia.as<int32_t>(); in.ib = d_ib.as<int32_t>();
-  CHK(dev_keyswitch(K, tier, in, count, sc.s, nullptr));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(cts_small, sc.s.small, count * (size_t)(t.n + 1) * 8, hipMemcpyDeviceToHost));
+  CHK(dev_keyswitch(K, tier, in, count, sc, nullptr));
+  HIPCHK(sc.d_small.download(cts_small, count * (size_t)(t.n + 1) * 8, ctx->stream));
   return 0;
 }
 
@@ -1751,11 +1752,9 @@ extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   hipStream_t st = ctx->stream;
   if (!K) {
     DevBuf di, dm, d_o;
-    HIPCHK(di.alloc(nin * 8)); HIPCHK(dm.alloc((size_t)batch * C * H * Wo * 8)); HIPCHK(d_o.alloc(nout * 8));
-    HIPCHK(hipMemcpy(di.p, in, nin * 8, hipMemcpyHostToDevice));
+    HIPCHK(di.upload(in, nin * 8)); HIPCHK(dm.alloc((size_t)batch * C * H * Wo * 8)); HIPCHK(d_o.alloc(nout * 8));
     CHK(clear_max_pool(st, di.as<uint64_t>(), dm.as<uint64_t>(), d_o.as<uint64_t>(), batch, C, H, W, k, s, p, 0, 1ULL << 62, p_d, nullptr, 0.0, 0, 0));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(out, d_o.p, nout * 8, hipMemcpyDeviceToHost));
+    HIPCHK(d_o.download(out, nout * 8, st));
     return 0;
   }
   if (!table) return fail("dctfhe_max_pool_rows: null table");
@@ -1776,13 +1775,12 @@ extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   HIPCHK(di.upload(in, nin * Li * 8)); HIPCHK(d_o.alloc(nout * Lo * 8));
   HIPCHK(ba.alloc(P.rows_buf[0] * Lo * 8)); HIPCHK(bb.alloc(P.rows_buf[1] * Lo * 8));
   HIPCHK(d_tab.upload(table, ((size_t)1 << p_d) * 8));
-  LutScratchOwner sc;
-  CHK(alloc_lut_scratch(K, std::min<size_t>(std::max<size_t>(P.pairs_per_batch, 1), 4096), &sc.s));
+  LutScratch sc;
+  CHK(alloc_lut_scratch(K, std::min<size_t>(std::max<size_t>(P.pairs_per_batch, 1), 4096), &sc));
   uint64_t* const bufs[2] = {ba.as<uint64_t>(), bb.as<uint64_t>()};
   const PoolSite site{k, s, p, 0, tier, p_d, deff_in, 1ULL << 62};
-  CHK(dev_max_pool(K, site, P, di.as<uint64_t>(), Li, (size_t)deff_in, bufs, d_o.as<uint64_t>(), Lo, (size_t)dout, d_tab.as<int64_t>(), sc.s, nullptr));
-  HIPCHK(hipStreamSynchronize(st));
-  HIPCHK(hipMemcpy(out, d_o.p, nout * Lo * 8, hipMemcpyDeviceToHost));
+  CHK(dev_max_pool(K, site, P, di.as<uint64_t>(), Li, (size_t)deff_in, bufs, d_o.as<uint64_t>(), Lo, (size_t)dout, d_tab.as<int64_t>(), sc, nullptr));
+  HIPCHK(d_o.download(out, nout * Lo * 8, st));
   return 0;
 }
 
@@ -1802,11 +1800,8 @@ extern "C" int dctfhe_dct_frontend(dctfhe_ctx* ctx, const uint8_t* y, const uint
   const int C = ny + n1 + n2;
   const size_t by = (size_t)batch * S * fs * S * fs, bc = (size_t)batch * Sc * fs * Sc * fs, nout = (size_t)batch * C * S * S;
   DevBuf d_y, d_c1, d_c2, d_idx, d_ms, d_out;
-  HIPCHK(d_y.alloc(by)); HIPCHK(d_c1.alloc(bc)); HIPCHK(d_c2.alloc(bc));
+  HIPCHK(d_y.upload(y, by)); HIPCHK(d_c1.upload(c1, bc)); HIPCHK(d_c2.upload(c2, bc));
   HIPCHK(d_idx.alloc((size_t)C * 4)); HIPCHK(d_ms.alloc((size_t)C * 8)); HIPCHK(d_out.alloc(nout * 4));
-  HIPCHK(hipMemcpy(d_y.p, y, by, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_c1.p, c1, bc, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_c2.p, c2, bc, hipMemcpyHostToDevice));
   dct_args a;
   a.plane[0] = d_y.as<uint8_t>(); a.plane[1] = d_c1.as<uint8_t>(); a.plane[2] = d_c2.as<uint8_t>();
   a.S = S; a.Sc = Sc; a.fs = fs; a.round_coeffs = round_coeffs; a.batch = batch;
@@ -1822,8 +1817,7 @@ extern "C" int dctfhe_dct_frontend(dctfhe_ctx* ctx, const uint8_t* y, const uint
   a.mean = d_ms.as<float>(); a.stdv = d_ms.as<float>() + C; a.out = d_out.as<float>();
   hipLaunchKernelGGL(k_dct_frontend, dim3(ew_grid(nout)), dim3(256), 0, ctx->stream, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  HIPCHK(hipMemcpy(out, d_out.p, nout * 4, hipMemcpyDeviceToHost));
+  HIPCHK(d_out.download(out, nout * 4, ctx->stream));
   return 0;
 }
 
@@ -1839,20 +1833,16 @@ extern "C" int dctfhe_circuit_load(dctfhe_ctx* ctx, const void* blob, size_t siz
   CHK(parse_circuit(blob, size, c.get()));
   HIPCHK(hipSetDevice(ctx->device));
   c->ctx = ctx;
-  c->d_payload.assign(c->ops.size(), nullptr);
-  c->d_split.assign(c->ops.size(), nullptr);
+  c->d_payload.resize(c->ops.size());
+  c->d_split.resize(c->ops.size());
   c->conv.assign(c->ops.size(), ConvPack{});
   c->conv_w.resize(c->ops.size());
   for (size_t i = 0; i < c->ops.size(); i++) {
     SiteOp& o = c->ops[i];
     const char* payload = (const char*)blob + o.payload_off;
-    if (o.payload_len > 0) {
-      HIPCHK(hipMalloc(&c->d_payload[i], (size_t)o.payload_len));
-      HIPCHK(hipMemcpy(c->d_payload[i], payload, (size_t)o.payload_len, hipMemcpyHostToDevice));
-    }
+    if (o.payload_len > 0) HIPCHK(c->d_payload[i].upload(payload, (size_t)o.payload_len));
     if (!o.halves.empty()) {      // the half tables of a parity split (parse_circuit made them), once per circuit
-      HIPCHK(hipMalloc(&c->d_split[i], o.halves.size() * 8));
-      HIPCHK(hipMemcpy(c->d_split[i], o.halves.data(), o.halves.size() * 8, hipMemcpyHostToDevice));
+      HIPCHK(c->d_split[i].upload(o.halves.data(), o.halves.size() * 8));
       std::vector<int64_t>().swap(o.halves);
     }
     if (o.type == OP_CONV) c->conv_w[i].assign((const int8_t*)payload, (const int8_t*)payload + o.payload_len);
@@ -1903,7 +1893,7 @@ static int session_conv_packs(dctfhe_session* s) {
     cw.push_back(circ->conv_w[i].empty() ? nullptr : circ->conv_w[i].data());
     cg.push_back(circ->ops[i].conv);
   }
-  return circ->conv_slab.d ? 0 : build_conv_packs(cw, cg, &circ->conv_slab, &circ->conv);
+  return circ->conv_slab.p ? 0 : build_conv_packs(cw, cg, &circ->conv_slab, &circ->conv);
 }
 
 // 3. row layout per tensor.  Encrypted: a tensor is stored at its effective dimension -- the compiler's `deff_in` of the consuming op
@@ -1922,7 +1912,7 @@ static int session_row_layout(dctfhe_session* s) {
   // circuit that uses such a tier keeps every tensor at full width
   bool all_mfma = true;
   for (const SiteOp& o : circ->ops)
-    for_each_bootstrap(o, keys->p, [&](int t, int, bool) { all_mfma = all_mfma && keys->tiers[t].d_kskT != nullptr; });
+    for_each_bootstrap(o, keys->p, [&](int t, int, bool) { all_mfma = all_mfma && keys->tiers[t].mfma(); });
   auto clampd = [&](int d) { return (size_t)((all_mfma && d > 0 && (size_t)d < D && d % 64 == 0) ? d : D); };
   std::vector<char> known(nt, 0);
   auto set = [&](int t, size_t deff, size_t width) { s->t_deff[t] = deff; s->t_L[t] = (all_mfma ? std::max(deff, width) : D) + 1; known[t] = 1; };
@@ -1967,20 +1957,24 @@ static int session_plan_buffers(dctfhe_session* s) {
   s->d_tensor.assign(nt, nullptr);
   s->tensor_words.assign(nt, 0);
   for (int t = 0; t < nt; t++) s->tensor_words[t] = (size_t)batch * circ->tensors[t].elems() * s->t_L[t];
-  std::vector<std::pair<size_t, uint64_t*>> freelist;
-  std::map<uint64_t*, size_t> cap;      // what each allocation holds
+  std::vector<size_t> freelist;      // indices into s->owned
+  auto size_of = [&](size_t f) { return s->owned[freelist[f]].bytes; };
   auto get = [&](size_t words, uint64_t** p) -> int {
     int best = -1;
     for (int i = 0; i < (int)freelist.size(); i++)
-      if (freelist[i].first >= words && (best < 0 || freelist[i].first < freelist[best].first)) best = i;
-    if (best >= 0) { *p = freelist[best].second; freelist.erase(freelist.begin() + best); return 0; }
-    HIPCHK(hipMalloc(p, words * 8));
-    s->owned.push_back({words, *p});
-    cap[*p] = words;
+      if (size_of(i) >= words * 8 && (best < 0 || size_of(i) < size_of(best))) best = i;
+    if (best >= 0) { *p = s->owned[freelist[best]].as<uint64_t>(); freelist.erase(freelist.begin() + best); return 0; }
+    DevBuf b;
+    HIPCHK(b.alloc(words * 8));
+    *p = b.as<uint64_t>();
+    s->owned.push_back(std::move(b));
     return 0;
   };
   auto alloc_t = [&](int t) -> int { return s->d_tensor[t] ? 0 : get(s->tensor_words[t], &s->d_tensor[t]); };
-  auto give_back = [&](uint64_t* p) { if (p) freelist.push_back({cap[p], p}); };
+  auto give_back = [&](uint64_t* p) {
+    for (size_t i = 0; p && i < s->owned.size(); i++)
+      if (s->owned[i].p == p) freelist.push_back(i);
+  };
   CHK(alloc_t(circ->input_tensor));
   s->pool.resize(circ->ops.size());
   s->pool_buf.assign(circ->ops.size(), {nullptr, nullptr});
@@ -2004,7 +1998,7 @@ static int session_plan_buffers(dctfhe_session* s) {
         size_t fr = 0, tot = 0;
         hipMemGetInfo(&fr, &tot);
         bool reuse = false;
-        for (auto& f : freelist) reuse = reuse || f.first >= words[b];
+        for (size_t f = 0; f < freelist.size(); f++) reuse = reuse || size_of(f) >= words[b] * 8;
         if (!reuse && words[b] * 8 > fr)
           return fail("op %d: the max pool's level buffer needs %.1f GB, %.1f GB of device memory are free (batch %d too large for one device)", i,
                       words[b] * 8e-9, fr * 1e-9, batch);
@@ -2034,7 +2028,7 @@ static int session_lut_scratch(dctfhe_session* s) {
     if (o.type == OP_LUT) maxe = std::max(maxe, (size_t)s->batch * circ->tensors[o.src0].elems());
     if (o.type == OP_MAXPOOL) for (const PoolLevel& l : s->pool[i]->lv) maxe = std::max(maxe, l.pairs);
   }
-  return alloc_lut_scratch(s->keys, std::min<size_t>(maxe, 16384), &s->lut.s);
+  return alloc_lut_scratch(s->keys, std::min<size_t>(maxe, 16384), &s->lut);
 }
 
 extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctfhe_keys* keys, int batch, dctfhe_session** out) {
@@ -2048,8 +2042,8 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   CHK(session_row_layout(s.get()));
   CHK(session_plan_buffers(s.get()));
   if (keys) CHK(session_lut_scratch(s.get()));
-  HIPCHK(hipMalloc(&s->d_overflow, sizeof(int)));
-  HIPCHK(hipMemset(s->d_overflow, 0, sizeof(int)));
+  HIPCHK(s->d_overflow.alloc(sizeof(int)));
+  HIPCHK(hipMemset(s->d_overflow.p, 0, sizeof(int)));
   if (keys) {
     dctfhe_stats stt;
     circuit_stats(*circ, keys->p, &stt);
@@ -2082,11 +2076,11 @@ extern "C" int dctfhe_session_upload_rows(dctfhe_session* s, const uint64_t* cts
   HIPCHK(tmp.alloc(count * Lh * 8));
   HIPCHK(hipMemcpyAsync(tmp.p, cts_in, count * Lh * 8, hipMemcpyHostToDevice, st));
   if (deff < (size_t)dim) {
-    HIPCHK(hipMemsetAsync(s->d_overflow, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_tail_nonzero, dim3(ew_grid(count * ((size_t)dim - deff))), dim3(256), 0, st, tmp.as<uint64_t>(), count, dim, (int)deff, s->d_overflow);
+    HIPCHK(hipMemsetAsync(s->d_overflow.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_tail_nonzero, dim3(ew_grid(count * ((size_t)dim - deff))), dim3(256), 0, st, tmp.as<uint64_t>(), count, dim, (int)deff, s->d_overflow.as<int>());
     HIPCHK(hipGetLastError());
     int bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, s->d_overflow, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&bad, s->d_overflow.p, sizeof bad, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (bad) return fail("input ciphertexts have non-zero mask words beyond %zu: encrypt them with these parameters (input_dim)", deff);
   }
@@ -2176,7 +2170,7 @@ extern "C" int dctfhe_session_download_packed(dctfhe_session* s, int tier, uint1
   HIPCHK(hipSetDevice(s->ctx->device));
   const int t = s->circ->output_tensor;
   const size_t Ls = s->t_L[t];
-  return dev_keyswitch_pack(s->keys, tier, s->d_tensor[t], Ls, (int)s->t_deff[t], s->tensor_words[t] / Ls, s->lut.s, rows);
+  return dev_keyswitch_pack(s->keys, tier, s->d_tensor[t], Ls, (int)s->t_deff[t], s->tensor_words[t] / Ls, s->lut, rows);
 }
 
 // ---- margin audit (include/dctfhe.h): the slots are those of for_each_bootstrap, the kernel k_margin_probe
@@ -2194,7 +2188,7 @@ static int session_audit_collect(dctfhe_session* s) {
   s->audit_last = s->audit_slots;
   if (s->audit_slots.empty()) return 0;
   std::vector<dctfhe_margin_stats> dev(s->audit_slots.size());
-  HIPCHK(hipMemcpy(dev.data(), s->d_audit, dev.size() * sizeof(dctfhe_margin_stats), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(dev.data(), s->d_audit.p, dev.size() * sizeof(dctfhe_margin_stats), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < dev.size(); i++) {
     dctfhe_margin_stats& m = s->audit_last[i];
     m.max_abs = dev[i].max_abs; m.count = dev[i].count; m.sum = dev[i].sum; m.sum_sq = dev[i].sum_sq;
@@ -2232,17 +2226,24 @@ extern "C" int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* C)
     CHK(err);
   }
   s->audit_off();
-  s->audit_key_bytes = (size_t)P.n_max;
-  HIPCHK(hipMalloc(&s->d_audit_key, s->audit_key_bytes));
-  HIPCHK(hipMemcpy(s->d_audit_key, C->d_s, s->audit_key_bytes, hipMemcpyDeviceToDevice));
-  HIPCHK(hipMalloc(&s->d_audit, std::max<size_t>(1, slots.size()) * sizeof(margin_slot)));
-  HIPCHK(hipMemset(s->d_audit, 0, std::max<size_t>(1, slots.size()) * sizeof(margin_slot)));
+  // the new key copy and slot array are built in locals and enter the session together: a step that fails leaves the audit off.  The
+  // key is copied last, so that no error path frees a copy of the secret unwiped
+  DevBuf key, slot;
+  HIPCHK(key.alloc((size_t)P.n_max));
+  HIPCHK(slot.alloc(std::max<size_t>(1, slots.size()) * sizeof(margin_slot)));
+  HIPCHK(hipMemset(slot.p, 0, slot.bytes));
+  const hipError_t e = hipMemcpy(key.p, C->s(), key.bytes, hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) {
+    hipMemset(key.p, 0, key.bytes);
+    return fail("dctfhe_session_set_audit: copy of the small key -> %s", hipGetErrorString(e));
+  }
+  s->d_audit_key = std::move(key); s->d_audit = std::move(slot);
   s->audit_slots = slots; s->audit_last = slots; s->audit_first = first;
   return 0;
 }
 extern "C" int dctfhe_session_audit(dctfhe_session* s, dctfhe_margin_stats* out, int capacity, int* n_slots) {
   if (!s || !n_slots) return fail("dctfhe_session_audit: null argument");
-  const int n = s->d_audit_key ? (int)s->audit_last.size() : 0;
+  const int n = s->d_audit_key.p ? (int)s->audit_last.size() : 0;
   *n_slots = n;
   if (!out) return 0;
   if (capacity < n) return fail("dctfhe_session_audit: room for %d slots, the circuit has %d", capacity, n);
@@ -2260,13 +2261,13 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
   const hipEvent_t e0 = tm.take(), e1 = tm.take();
   HIPCHK(hipEventRecord(e0, st));
   if (timing) memset(timing, 0, sizeof *timing);
-  const LutScratch& sc = s->lut.s;
-  const bool audit = s->d_audit_key != nullptr;
+  const LutScratch& sc = s->lut;
+  const bool audit = s->d_audit_key.p != nullptr;
   if (audit && !s->audit_slots.empty())      // every run starts from zeroed slots
-    HIPCHK(hipMemsetAsync(s->d_audit, 0, s->audit_slots.size() * sizeof(margin_slot), st));
+    HIPCHK(hipMemsetAsync(s->d_audit.p, 0, s->audit_slots.size() * sizeof(margin_slot), st));
   for (size_t i = 0; i < c->ops.size(); i++) {
     const SiteOp& o = c->ops[i];
-    const MarginProbe probe_i = audit ? MarginProbe{s->d_audit_key, s->d_audit + s->audit_first[i]} : MarginProbe{};
+    const MarginProbe probe_i = audit ? MarginProbe{s->d_audit_key.as<uint8_t>(), s->d_audit.as<margin_slot>() + s->audit_first[i]} : MarginProbe{};
     const MarginProbe* probe = audit ? &probe_i : nullptr;
     const TensorShape& a = c->tensors[o.src0];
     const TensorShape& d = c->tensors[o.dst];
@@ -2277,7 +2278,7 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
     switch (o.type) {
       case OP_CONV: {
         const int h = tm.begin(CAT_LINEAR);
-        CHK(dev_conv2d(st, src, B, a.C, a.H, a.W, Ls, ds, (const int8_t*)c->d_payload[i], &c->conv[i], o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride, o.conv.pad, dst, Ld));
+        CHK(dev_conv2d(st, src, B, a.C, a.H, a.W, Ls, ds, c->d_payload[i].as<int8_t>(), &c->conv[i], o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride, o.conv.pad, dst, Ld));
         tm.end(h);
         break;
       }
@@ -2302,12 +2303,12 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
         const LutSite& L = o.lut;
         const size_t E = (size_t)B * a.elems();
         const int hw = a.H * a.W;
-        const int64_t* halves = c->d_split[i];      // [S | Dt] of a parity split, else nullptr
+        const int64_t* halves = c->d_split[i].as<int64_t>();      // [S | Dt] of a parity split, else nullptr
         const int64_t* half_d = halves ? halves + ((size_t)L.ntab << (L.w - 1)) : nullptr;
         if (!K) {
           const double sg2 = (i < s->sim_sigma2.size() && s->sim_sigma2[i] > 0) ? s->sim_sigma2[i] : sg;
-          hipLaunchKernelGGL(k_lut_clear, dim3(ew_grid(E)), dim3(256), 0, st, src, dst, E, L.shift, L.body_add, L.p, L.r, L.w, (const int64_t*)c->d_payload[i],
-                             hw, L.ntab, s->d_overflow, sg, rng_key{{(uint32_t)s->sim_seed, (uint32_t)(s->sim_seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}},
+          hipLaunchKernelGGL(k_lut_clear, dim3(ew_grid(E)), dim3(256), 0, st, src, dst, E, L.shift, L.body_add, L.p, L.r, L.w, c->d_payload[i].as<int64_t>(),
+                             hw, L.ntab, s->d_overflow.as<int>(), sg, rng_key{{(uint32_t)s->sim_seed, (uint32_t)(s->sim_seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}},
                              (uint64_t)(0x51D0000 + (s->sim_run << 12) + i), (int)L.approx(), (int)L.split(), sg2, halves, half_d);
           HIPCHK(hipGetLastError());
         } else {
@@ -2330,7 +2331,7 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
           }
           LutRows rows;
           rows.src = src; rows.Ls = Ls; rows.work = dst; rows.Lw = Ld; rows.par = s->pool_buf[i][0]; rows.Lp = Ld;
-          rows.tables = (const int64_t*)c->d_payload[i]; rows.tab_s = halves; rows.tab_d = half_d;
+          rows.tables = c->d_payload[i].as<int64_t>(); rows.tab_s = halves; rows.tab_d = half_d;
           CHK(dev_round_lut(K, L, rows, E, hw, sc, &tm, deff, probe));
         }
         break;
@@ -2339,12 +2340,12 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
         const PoolSite& S = o.pool;
         if (!K) {
           const int h = tm.begin(CAT_LINEAR);
-          CHK(clear_max_pool(st, src, s->pool_buf[i][0], dst, B, a.C, a.H, a.W, S.k, S.stride, S.pad, S.shift, S.body_add, S.p_d, (const int64_t*)c->d_payload[i], sg,
+          CHK(clear_max_pool(st, src, s->pool_buf[i][0], dst, B, a.C, a.H, a.W, S.k, S.stride, S.pad, S.shift, S.body_add, S.p_d, c->d_payload[i].as<int64_t>(), sg,
                              s->sim_seed, (1ULL << 40) | ((uint64_t)(0x51D0000 + (s->sim_run << 12) + i) << 1)));
           tm.end(h);
         } else {
           uint64_t* const bufs[2] = {s->pool_buf[i][0], s->pool_buf[i][1]};
-          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], (const int64_t*)c->d_payload[i], sc, &tm, probe));
+          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], c->d_payload[i].as<int64_t>(), sc, &tm, probe));
         }
         break;
       }
@@ -2370,8 +2371,8 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
   if (audit) CHK(session_audit_collect(s));
   if (!K) {
     int ov = 0;
-    HIPCHK(hipMemcpy(&ov, s->d_overflow, sizeof ov, hipMemcpyDeviceToHost));
-    if (ov) { HIPCHK(hipMemset(s->d_overflow, 0, sizeof(int))); return fail("clear run: a message left its padded range (calibration too tight)"); }
+    HIPCHK(hipMemcpy(&ov, s->d_overflow.p, sizeof ov, hipMemcpyDeviceToHost));
+    if (ov) { HIPCHK(hipMemset(s->d_overflow.p, 0, sizeof(int))); return fail("clear run: a message left its padded range (calibration too tight)"); }
   }
   return 0;
 }
@@ -2418,7 +2419,7 @@ extern "C" int dctfhe_margin_probe(dctfhe_ctx* ctx, dctfhe_client_key* C, int ti
   HIPCHK(hipMemcpyAsync(d_ct.p, cts_small, bytes, hipMemcpyHostToDevice, ctx->stream));
   if (err) HIPCHK(d_err.alloc(count * 4));
   if (stats) { HIPCHK(d_slot.alloc(sizeof(margin_slot))); HIPCHK(hipMemsetAsync(d_slot.p, 0, sizeof(margin_slot), ctx->stream)); }
-  CHK(dev_margin_probe(ctx->stream, t, C->d_s, d_ct.as<uint64_t>(), count, table_bits, err ? d_err.as<int32_t>() : nullptr, stats ? d_slot.as<margin_slot>() : nullptr));
+  CHK(dev_margin_probe(ctx->stream, t, C->s(), d_ct.as<uint64_t>(), count, table_bits, err ? d_err.as<int32_t>() : nullptr, stats ? d_slot.as<margin_slot>() : nullptr));
   if (err) HIPCHK(hipMemcpyAsync(err, d_err.p, count * 4, hipMemcpyDeviceToHost, ctx->stream));
   dctfhe_margin_stats dev;
   if (stats) HIPCHK(hipMemcpyAsync(&dev, d_slot.p, sizeof dev, hipMemcpyDeviceToHost, ctx->stream));
@@ -2433,20 +2434,18 @@ extern "C" int dctfhe_margin_probe(dctfhe_ctx* ctx, dctfhe_client_key* C, int ti
 extern "C" int dctfhe_fp64_peak(dctfhe_ctx* ctx, double* tflops) {
   HIPCHK(hipSetDevice(ctx->device));
   const int blocks = ctx->prop.multiProcessorCount * 8, threads = 256, iters = 1 << 14;
-  double* d;
-  HIPCHK(hipMalloc(&d, (size_t)blocks * threads * 8));
-  hipEvent_t a, b;
-  hipEventCreate(&a); hipEventCreate(&b);
-  hipLaunchKernelGGL(k_fp64_peak, dim3(blocks), dim3(threads), 0, ctx->stream, d, iters);
-  hipEventRecord(a, ctx->stream);
-  for (int r = 0; r < 4; r++) hipLaunchKernelGGL(k_fp64_peak, dim3(blocks), dim3(threads), 0, ctx->stream, d, iters);
-  hipEventRecord(b, ctx->stream);
-  HIPCHK(hipEventSynchronize(b));
+  DevBuf d;
+  HIPCHK(d.alloc((size_t)blocks * threads * 8));
+  DevEvent a, b;
+  HIPCHK(a.create()); HIPCHK(b.create());
+  hipLaunchKernelGGL(k_fp64_peak, dim3(blocks), dim3(threads), 0, ctx->stream, d.as<double>(), iters);
+  hipEventRecord(a.e, ctx->stream);
+  for (int r = 0; r < 4; r++) hipLaunchKernelGGL(k_fp64_peak, dim3(blocks), dim3(threads), 0, ctx->stream, d.as<double>(), iters);
+  hipEventRecord(b.e, ctx->stream);
+  HIPCHK(hipEventSynchronize(b.e));
   float ms = 0;
-  hipEventElapsedTime(&ms, a, b);
+  hipEventElapsedTime(&ms, a.e, b.e);
   *tflops = 4.0 * blocks * threads * (double)iters * 8 * 2 / (ms * 1e-3) / 1e12;
-  hipEventDestroy(a); hipEventDestroy(b);
-  hipFree(d);
   return 0;
 }
 
@@ -2455,30 +2454,26 @@ extern "C" int dctfhe_bench_pbs(dctfhe_ctx* ctx, dctfhe_keys* K, int tier, size_
   HIPCHK(hipSetDevice(ctx->device));
   const dctfhe_tier& t = K->p.tiers[tier];
   const size_t L = (size_t)K->p.D + 1;
-  uint64_t *d_small, *d_out; int64_t* d_tab;
-  HIPCHK(hipMalloc(&d_small, count * (size_t)(t.n + 1) * 8));
-  HIPCHK(hipMalloc(&d_out, count * L * 8));
-  HIPCHK(hipMalloc(&d_tab, 8 * 16));
   std::vector<uint64_t> h(count * (size_t)(t.n + 1));
   uint64_t stt = 12345;
   for (auto& v : h) { stt = stt * 6364136223846793005ULL + 1442695040888963407ULL; v = stt; }
-  HIPCHK(hipMemcpy(d_small, h.data(), h.size() * 8, hipMemcpyHostToDevice));
   int64_t tab[16];
   for (int i = 0; i < 16; i++) tab[i] = (int64_t)i << 58;
-  HIPCHK(hipMemcpy(d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
-  hipEvent_t a, b;
-  hipEventCreate(&a); hipEventCreate(&b);
-  const PbsLut lut{d_tab, 4};
-  const PbsOut out{d_out, L};
-  CHK(dev_pbs(K, tier, d_small, count, lut, out, nullptr));
-  hipEventRecord(a, ctx->stream);
-  for (int r = 0; r < reps; r++) CHK(dev_pbs(K, tier, d_small, count, lut, out, nullptr));
-  hipEventRecord(b, ctx->stream);
-  HIPCHK(hipEventSynchronize(b));
+  DevBuf d_small, d_out, d_tab;
+  HIPCHK(d_small.upload(h.data(), h.size() * 8));
+  HIPCHK(d_out.alloc(count * L * 8));
+  HIPCHK(d_tab.upload(tab, sizeof tab));
+  DevEvent a, b;
+  HIPCHK(a.create()); HIPCHK(b.create());
+  const PbsLut lut{d_tab.as<int64_t>(), 4};
+  const PbsOut out{d_out.as<uint64_t>(), L};
+  CHK(dev_pbs(K, tier, d_small.as<uint64_t>(), count, lut, out, nullptr));
+  hipEventRecord(a.e, ctx->stream);
+  for (int r = 0; r < reps; r++) CHK(dev_pbs(K, tier, d_small.as<uint64_t>(), count, lut, out, nullptr));
+  hipEventRecord(b.e, ctx->stream);
+  HIPCHK(hipEventSynchronize(b.e));
   float ms = 0;
-  hipEventElapsedTime(&ms, a, b);
+  hipEventElapsedTime(&ms, a.e, b.e);
   *ms_per_launch = ms / reps;
-  hipEventDestroy(a); hipEventDestroy(b);
-  hipFree(d_small); hipFree(d_out); hipFree(d_tab);
   return 0;
 }

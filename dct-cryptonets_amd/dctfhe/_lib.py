@@ -60,6 +60,7 @@ EXPORTS = [
     "dctfhe_round_lut_split", "dctfhe_session_set_noise_split",
     "dctfhe_session_download_packed", "dctfhe_keyswitch_pack", "dctfhe_decrypt_packed",
     "dctfhe_margin_probe_host", "dctfhe_margin_probe", "dctfhe_session_set_audit", "dctfhe_session_audit",
+    "dctfhe_device_bytes_live",
 ]
 
 _lib = None
@@ -145,6 +146,8 @@ def load():
     L.dctfhe_margin_probe.argtypes = [vp, vp, i32, vp, sz, i32, vp, C.POINTER(MarginStats)]
     L.dctfhe_session_set_audit.argtypes = [vp, vp]
     L.dctfhe_session_audit.argtypes = [vp, C.POINTER(MarginStats), i32, C.POINTER(C.c_int)]
+    L.dctfhe_device_bytes_live.argtypes = []
+    L.dctfhe_device_bytes_live.restype = sz
     _lib = L
     return L
 

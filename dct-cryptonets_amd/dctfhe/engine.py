@@ -40,6 +40,11 @@ def margin_probe_host(small_key, n, logN, cts_small, table_bits, want_err=True, 
     return err, (None if st is None else margin_stats_dict(st))
 
 
+def device_bytes_live():
+    """bytes of device memory the library holds in this process right now (dctfhe_device_bytes_live): handles, caches, calls in flight"""
+    return int(_lib.load().dctfhe_device_bytes_live())
+
+
 class Context:
     def __init__(self, device=0):
         self.L = _lib.load()

@@ -136,6 +136,9 @@ int dctfhe_client_key_export_bsk(dctfhe_client_key* client, int tier, uint64_t* 
 /* the generator itself: `count` 64-bit outputs (key, stream, idx0 + i).  _host runs on the CPU (known-answer tests need no GPU) */
 int dctfhe_rng_host(const uint8_t key[32], uint64_t stream, uint64_t idx0, size_t count, uint64_t* out);
 int dctfhe_rng_device(dctfhe_ctx* ctx, const uint8_t key[32], uint64_t stream, uint64_t idx0, size_t count, uint64_t* out);
+/* bytes of device memory the library holds in this process right now: the sum over every live allocation of the size it was made with
+ * (handles, caches and the buffers of calls in flight).  Host-only: an atomic counter, no device needed. */
+size_t dctfhe_device_bytes_live(void);
 
 /* R4, client half: encrypt phases (already encoded) / return phases b - <a,s>.  Host buffers.  Every dctfhe_encrypt call
  * draws masks and noise from fresh generator streams (a per-handle call counter). */

@@ -20,11 +20,14 @@ e = 63 - p first, so that t sits in the top w+1 bits with the padding bit clear.
 A table of 7 input bits is evaluated by a PARITY SPLIT on the 6-bit tiers: one more one-bit step takes the
 low bit b0 of t = 2 t' + b0 off the working ciphertext, a second sign bootstrap of the same small ciphertext puts b0 into the
 padding bit of a copy, and two 6-bit look-ups give  S[t'] + (-1)^b0 Dt[t'] = T[t]  with  S = (T[2j] + T[2j+1]) / 2,
-Dt = T[2j] - S  (split_tables).  The blob keeps one LUT record with w = 7 and the 128-entry tables; ip[9] says how it runs.
+Dt = T[2j] - S  (split_tables).  The blob keeps one LUT record with w = 7 and the 128-entry tables; the site's mode says how it runs.
+
+Every op carries the typed site of its kind (ConvSite, LutSite, PoolSite: the names and rules of csrc/circuit.h, which decodes what
+this module writes).  Which slot of a blob record holds which field is known to _encode_record alone.
 """
 import math
 import struct
-from dataclasses import dataclass, field
+from dataclasses import dataclass, replace
 
 import numpy as np
 import torch
@@ -35,10 +38,10 @@ from . import params as P
 OP_CONV, OP_ADD, OP_SUMPOOL, OP_LUT = 1, 2, 3, 4
 OP_MAXPOOL = 5            # not 9: the ABI tests use 9 as the unknown type
 MAGIC = 0x46544344
-# ip[9] of a LUT record: how the site is evaluated
+# LutSite.mode: how the site is evaluated
 LUT_EXACT, LUT_APPROX = 0, 1
-LUT_SPLIT = 2             # parity split, both look-ups on the site's table tier ip[4]
-LUT_SPLIT_QUIET = 3       # parity split, the second look-up on the quiet twin: the tier whose key-switch key ip[4] shares (ksk_share)
+LUT_SPLIT = 2             # parity split, both look-ups on the site's table tier
+LUT_SPLIT_QUIET = 3       # parity split, the second look-up on the quiet twin: the tier whose key-switch key the table tier shares (ksk_share)
 
 
 def split_tables(enc):
@@ -148,34 +151,109 @@ class TensorInfo:
 
 
 @dataclass
+class ConvSite:
+    Cout: int
+    KH: int
+    KW: int
+    stride: int
+    pad: int
+
+
+@dataclass
+class LutSite:
+    """one look-up: p-bit accumulator, r bits rounded away, w = p - r table bits (csrc/circuit.h LutSite and StepTiers hold the same rules)"""
+    p: int
+    r: int
+    w: int
+    signed: bool
+    ntab: int                 # tables: 1, or one per channel
+    body_add: int             # added to the shifted body: 2^62 puts a signed value's index at m + 2^(p-1)
+    shift: int = 0            # from the input's encoding up to 63 - p
+    mode: int = LUT_EXACT
+    tab_tier: int = -1
+    bit_tier: int = -1        # one-bit step i runs here ...
+    coarse: int = -1          # ... from step coarse_from on, on the one-level twin ...
+    coarse_from: int = 0
+    coarse2: int = -1         # ... and from step coarse2_from on, on the two-bit-rotation twin (< 0: no hand-over)
+    coarse2_from: int = 0
+
+    def split(self): return self.mode in (LUT_SPLIT, LUT_SPLIT_QUIET)
+    def approx(self): return self.mode == LUT_APPROX
+    def table_bits(self): return self.w - 1 if self.split() else self.w
+
+    def n_steps(self):
+        """one-bit steps: the r rounding steps, plus the step that takes the parity bit off a split site; none when the table rounds"""
+        return 0 if self.approx() else self.r + (1 if self.split() else 0)
+
+    def step_tier(self, i):
+        if self.coarse2 >= 0 and i >= self.coarse2_from:
+            return self.coarse2
+        return self.coarse if (self.coarse >= 0 and i >= self.coarse_from) else self.bit_tier
+
+    def tier2(self, ps):
+        """tier of a split's second look-up"""
+        return ps.tiers[self.tab_tier].ksk_share if self.mode == LUT_SPLIT_QUIET else self.tab_tier
+
+
+@dataclass
+class PoolSite:
+    k: int
+    stride: int
+    pad: int
+    p_d: int                  # bits of the signed difference of two operands: the relu table's input
+    body_add: int
+    pool_geom: list           # [(multiplicity, pairs per level)] per pass (pool_geometry)
+    n_max: int                # pairwise maxima per image
+    levels: int               # tree levels of both passes
+    shift: int = 0            # of the differences, up to 63 - p_d
+    tier: int = -1            # of the relu table
+
+
+@dataclass
 class OpInfo:
     type: int
     src0: int
     src1: int
     dst: int
-    ip: list = field(default_factory=lambda: [0] * 12)
-    lp: list = field(default_factory=lambda: [0, 0])
+    conv: ConvSite = None             # the site of the op's type (OP_ADD has none; OP_SUMPOOL: its window sum_k)
+    lut: LutSite = None
+    pool: PoolSite = None
+    sum_k: int = 0
+    deff_in: int = 0                  # effective dimension of what the op reads (mask words beyond it are zero)
     payload: np.ndarray = None
-    # LUT metadata
-    p: int = 0
-    r: int = 0
-    w: int = 0
-    signed: bool = False
     table_values: np.ndarray = None   # [ntab, 2^w] integer outputs (before encoding)
     nu2: float = 1.0
     note: str = ""
     pfail: float = 0.0
-    coarse_from: int = -1             # rounding steps i >= coarse_from run on the one-level bit tier
-    coarse2_from: int = -1            # ... and steps i >= coarse2_from on the two-bit-rotation bit tier (ip[11] = tier << 8 | from)
     sim_sigma: float = 0.0            # modelled noise std at the input of the site's table bootstrap (fraction of the torus)
     sim_sigma2: float = 0.0           # parity-split sites: the same at the second look-up (one more bit-tier output on its input)
-    # MAXPOOL metadata: [(multiplicity, pairs per level)] per pass (pool_geometry), pairwise maxima per image, tree levels
-    pool_geom: list = None
-    n_max: int = 0
-    levels: int = 0
-    # margin audit: (kind, tier, table bits, variance) of every bootstrap with a key switch of its own, in the engine's order
-    # (csrc/circuit.h for_each_bootstrap), as _estimate_noise priced them
-    margin: list = None
+    margin: list = None               # margin audit: the variance _estimate_noise priced every bootstrap with a key switch of its own at
+
+    # what a look-up reads, for either kind of table site (a max pool looks its p_d-bit differences up unrounded)
+    p = property(lambda o: o.lut.p if o.lut else o.pool.p_d if o.pool else 0)
+    r = property(lambda o: o.lut.r if o.lut else 0)
+    w = property(lambda o: o.lut.w if o.lut else o.pool.p_d if o.pool else 0)
+    signed = property(lambda o: o.lut.signed if o.lut else o.pool is not None)
+    n_max = property(lambda o: o.pool.n_max)
+    # the blob record, for readers that count in slots (bench.py, the tests): encoded on demand, never written
+    ip = property(lambda o: _encode_record(o)[0])
+    lp = property(lambda o: _encode_record(o)[1])
+
+
+def for_each_bootstrap(o, ps):
+    """The bootstraps one element of op `o` takes, in execution order (csrc/circuit.h for_each_bootstrap): (kind, tier, table_bits,
+    own_keyswitch).  Look-up: the one-bit steps; for a split the parity bootstrap, on the last step's small ciphertext, and the second
+    look-up; the table.  Max pool: one relu bootstrap per pairwise maximum.  Nothing for the levelled ops."""
+    if o.type == OP_LUT:
+        L, n = o.lut, o.lut.n_steps()
+        for i in range(n):
+            yield f"step {i}", L.step_tier(i), 0, True
+        if L.split():
+            yield "parity", L.step_tier(n - 1), 0, False
+            yield "second", L.tier2(ps), L.w - 1, True
+        yield "table", L.tab_tier, L.table_bits(), True
+    elif o.type == OP_MAXPOOL:
+        yield "pool", o.pool.tier, o.pool.p_d, True
 
 
 @dataclass
@@ -226,7 +304,7 @@ class CompiledCircuit:
 
     def simulation_sigmas_split(self):
         """per op, the noise std `simulate` injects at the SECOND look-up of a parity-split site (0 elsewhere)"""
-        return [o.sim_sigma2 if (o.type == OP_LUT and is_split(o)) else 0.0 for o in self.ops]
+        return [o.sim_sigma2 if (o.type == OP_LUT and o.lut.split()) else 0.0 for o in self.ops]
 
     def margin_model(self):
         """One record per slot of the margin audit (include/dctfhe.h dctfhe_session_audit), in the same enumeration: per look-up op its
@@ -235,36 +313,26 @@ class CompiledCircuit:
         put into p_fail for that decision.  elements: decisions per image."""
         ps, out = self.param_set, []
         for i, o in enumerate(self.ops):
-            if o.type not in (OP_LUT, OP_MAXPOOL):
-                continue
-            s = self.tensors[o.src0]
-            n = o.n_max if o.type == OP_MAXPOOL else s.C * s.H * s.W
-            for e, (kind, tier, bits, var) in enumerate(o.margin or []):
-                out.append(dict(op=i, entry=e, kind=kind, tier=tier, tier_name=ps.tiers[tier].name, table_bits=bits, elements=n,
+            boots = [b for b in for_each_bootstrap(o, ps) if b[3]]
+            for e, ((kind, tier, bits, _), var) in enumerate(zip(boots, o.margin or [])):
+                out.append(dict(op=i, entry=e, kind=kind, tier=tier, tier_name=ps.tiers[tier].name, table_bits=bits, elements=self._decisions(o),
                                 sigma=math.sqrt(var), note=o.note))
         return out
+
+    def _decisions(self, o):
+        """bootstraps per image and entry of for_each_bootstrap"""
+        s = self.tensors[o.src0]
+        return o.pool.n_max if o.type == OP_MAXPOOL else s.C * s.H * s.W
 
     def pbs_counts(self):
         """{tier name: programmable bootstraps per image} -- table lookups on the site's table tier, rounding steps
         on the bit tier (steps below coarse_from) or the one-level bit tier (steps from coarse_from on)."""
         ps, out = self.param_set, {}
         for o in self.ops:
-            if o.type == OP_MAXPOOL:
-                nm = ps.tiers[o.ip[4]].name
-                out[nm] = out.get(nm, 0) + o.n_max
-                continue
-            if o.type != OP_LUT:
-                continue
-            s = self.tensors[o.src0]
-            n = s.C * s.H * s.W
-            out[ps.tiers[o.ip[4]].name] = out.get(ps.tiers[o.ip[4]].name, 0) + n
-            if o.ip[9] != LUT_APPROX:
-                for st in range(chain_steps(o)):
-                    nm = ps.tiers[step_tier(o, st)].name
-                    out[nm] = out.get(nm, 0) + n
-            if is_split(o):      # the parity bootstrap (tier of step r, no key switch of its own) and the second look-up
-                for nm in (ps.tiers[step_tier(o, o.r)].name, ps.tiers[second_tier(ps, o)].name):
-                    out[nm] = out.get(nm, 0) + n
+            boots = list(for_each_bootstrap(o, ps))
+            for _, tier, _, _ in boots[-1:] + boots[:-1]:      # a site's table first: the order in which the tier names appear
+                nm = ps.tiers[tier].name
+                out[nm] = out.get(nm, 0) + self._decisions(o)
         return out
 
     def report(self):
@@ -279,21 +347,22 @@ class CompiledCircuit:
             s, d = self.tensors[o.src0], self.tensors[o.dst]
             head = f"%{o.dst} = {names[o.type]}(%{o.src0}" + (f", %{o.src1}" if o.type == OP_ADD else "") + ")"
             if o.type == OP_CONV:
-                head += f" {{cout={o.ip[0]}, k={o.ip[1]}x{o.ip[2]}, stride={o.ip[3]}, pad={o.ip[4]}, nu2={o.nu2:.0f}}}"
+                head += f" {{cout={o.conv.Cout}, k={o.conv.KH}x{o.conv.KW}, stride={o.conv.stride}, pad={o.conv.pad}, nu2={o.nu2:.0f}}}"
             elif o.type == OP_SUMPOOL:
-                head += f" {{k={o.ip[0]}}}"
+                head += f" {{k={o.sum_k}}}"
             elif o.type == OP_MAXPOOL:
-                head = (f"%{o.dst} = max_pool2d(%{o.src0}, {o.ip[0]}, {o.ip[1]}, {o.ip[2]}) {{p_d={o.ip[5]}, shift={o.ip[3]}, "
-                        f"tier={ps.tiers[o.ip[4]].name}, levels={o.levels}, pairwise_max={o.n_max}, p_fail/max={o.pfail:.1e}}}  // {o.note}")
+                S = o.pool
+                head = (f"%{o.dst} = max_pool2d(%{o.src0}, {S.k}, {S.stride}, {S.pad}) {{p_d={S.p_d}, shift={S.shift}, "
+                        f"tier={ps.tiers[S.tier].name}, levels={S.levels}, pairwise_max={S.n_max}, p_fail/max={o.pfail:.1e}}}  // {o.note}")
             elif o.type == OP_LUT:
-                nst = 0 if o.ip[9] == LUT_APPROX else chain_steps(o)
-                head += (f" {{p={o.p}, lsbs_removed={o.r}, table_bits={o.w}, signed={int(o.signed)}, shift={o.ip[3]}, "
-                         f"tier={ps.tiers[o.ip[4]].name}" + (", rounding=approximate" if o.ip[9] == LUT_APPROX else "") +
-                         (f", parity_split={ps.tiers[o.ip[4]].name}+{ps.tiers[second_tier(ps, o)].name}, steps={o.r}+1" if is_split(o) else "") +
-                         (f", bit_tier={ps.tiers[o.ip[5]].name}" if nst else "") +
-                         (f", steps>={o.ip[8]}:{ps.tiers[o.ip[7]].name}" if (nst and o.ip[7] >= 0 and o.ip[8] < nst) else "") +
-                         (f", steps>={o.ip[11] & 255}:{ps.tiers[o.ip[11] >> 8].name}" if (nst and o.ip[11] >= 0 and (o.ip[11] & 255) < nst) else "") +
-                         f", tables={o.ip[6]}, p_fail/elt={o.pfail:.1e}}}  // {o.note}")
+                L, nst, tab = o.lut, o.lut.n_steps(), ps.tiers[o.lut.tab_tier].name
+                head += (f" {{p={L.p}, lsbs_removed={L.r}, table_bits={L.w}, signed={int(L.signed)}, shift={L.shift}, "
+                         f"tier={tab}" + (", rounding=approximate" if L.approx() else "") +
+                         (f", parity_split={tab}+{ps.tiers[L.tier2(ps)].name}, steps={L.r}+1" if L.split() else "") +
+                         (f", bit_tier={ps.tiers[L.bit_tier].name}" if nst else "") +
+                         (f", steps>={L.coarse_from}:{ps.tiers[L.coarse].name}" if (nst and L.coarse >= 0 and L.coarse_from < nst) else "") +
+                         (f", steps>={L.coarse2_from}:{ps.tiers[L.coarse2].name}" if (nst and L.coarse2 >= 0 and L.coarse2_from < nst) else "") +
+                         f", tables={L.ntab}, p_fail/elt={o.pfail:.1e}}}  // {o.note}")
             lines.append(f"{head} : [{s.C}x{s.H}x{s.W}] -> [{d.C}x{d.H}x{d.W}] e={d.e}")
         lines.append(f"// expected table failures per image (noise model): {self.expected_failures_per_image:.2e}")
         if self.rounding_method == "approximate":
@@ -329,29 +398,11 @@ def output_compaction(circ):
     return OutputCompaction(tier=ti, name=t.name, n=t.n, bytes_per_ciphertext=2 * (t.n + 1), var=var, pfail=pfail)
 
 
-def step_tier(o, i):
-    """tier index of rounding step i of look-up op `o`: bit tier, from ip[8] on the coarse twin ip[7], from ip[11] & 255 on ip[11] >> 8"""
-    t = o.ip[5]
-    if o.ip[7] >= 0 and i >= o.ip[8]:
-        t = o.ip[7]
-    if o.ip[11] >= 0 and i >= (o.ip[11] & 255):
-        t = o.ip[11] >> 8
-    return t
-
-
-def is_split(o):
-    """look-up op evaluated by the parity split (ip[9] = LUT_SPLIT / LUT_SPLIT_QUIET)"""
-    return o.ip[9] in (LUT_SPLIT, LUT_SPLIT_QUIET)
-
-
-def chain_steps(o):
-    """one-bit steps of an exact look-up op: the r rounding steps, plus the step that takes the parity bit off a split site"""
-    return o.r + (1 if is_split(o) else 0)
-
-
-def second_tier(ps, o):
-    """tier of the second look-up of a parity-split site"""
-    return ps.tiers[o.ip[4]].ksk_share if o.ip[9] == LUT_SPLIT_QUIET else o.ip[4]
+# the site's own rules, for callers that hold a look-up op
+def step_tier(o, i): return o.lut.step_tier(i)
+def is_split(o): return o.lut.split()
+def chain_steps(o): return o.lut.n_steps()
+def second_tier(ps, o): return o.lut.tier2(ps)
 
 
 class _Act:
@@ -405,9 +456,7 @@ class _Builder:
         acc = conv_int(a.q, wq, layer.stride, layer.pad)
         Cout, _, KH, KW = wq.shape
         tid = self.tensor(Cout, acc.shape[2], acc.shape[3], int(acc.min()), int(acc.max()))
-        op = OpInfo(OP_CONV, a.tid, -1, tid)
-        op.ip[:5] = [Cout, KH, KW, layer.stride, layer.pad]
-        op.payload = wq.astype(np.int8)
+        op = OpInfo(OP_CONV, a.tid, -1, tid, conv=ConvSite(Cout, KH, KW, layer.stride, layer.pad), payload=wq.astype(np.int8))
         op.nu2 = float((wq.astype(np.float64) ** 2).sum(axis=(1, 2, 3)).max())
         self.ops.append(op)
         return _Act(acc, a.scale * sw, tid, int(acc.min()), int(acc.max()))
@@ -423,9 +472,7 @@ class _Builder:
         Ho, Wo = H // K, W // K     # floor mode drops the border (reference backbone.py:276 nn.AvgPool2d)
         q = a.q[:, :, :Ho * K, :Wo * K].reshape(B, C, Ho, K, Wo, K).sum(axis=(3, 5))
         tid = self.tensor(C, Ho, Wo, a.lo * K * K, a.hi * K * K)
-        op = OpInfo(OP_SUMPOOL, a.tid, -1, tid)
-        op.ip[0] = K
-        self.ops.append(op)
+        self.ops.append(OpInfo(OP_SUMPOOL, a.tid, -1, tid, sum_k=K))
         return _Act(q, a.scale, tid, a.lo * K * K, a.hi * K * K)
 
     def max_pool(self, a, k, s, p, note):
@@ -434,24 +481,19 @@ class _Builder:
         _, C, H, W = a.q.shape
         tid = self.tensor(C, q.shape[2], q.shape[3], a.lo, a.hi)
         p_d = max(1, (a.hi - a.lo).bit_length()) + 1               # the signed difference of two operands
-        op = OpInfo(OP_MAXPOOL, a.tid, -1, tid, p=p_d, w=p_d, signed=True, note=note)
-        op.ip[:3] = [k, s, p]
-        op.ip[5] = p_d
-        op.ip[6] = 1
+        geom = pool_geometry(C, H, W, k, s, p)
+        site = PoolSite(k, s, p, p_d, body_add=1 << 62,            # signed body offset: index = d + 2^(p_d - 1)
+                        pool_geom=geom, n_max=sum(m * sum(pl) for m, pl in geom), levels=sum(len(pl) for _, pl in geom))
         centres = lut_centers(p_d, 0, p_d, True)
-        op.table_values = np.maximum(centres, 0).reshape(1, -1)     # relu(d): max(a, b) = b + relu(a - b)
-        op.pool_geom = pool_geometry(C, H, W, k, s, p)
-        op.n_max = sum(m * sum(pl) for m, pl in op.pool_geom)
-        op.levels = sum(len(pl) for _, pl in op.pool_geom)
-        self.ops.append(op)
+        self.ops.append(OpInfo(OP_MAXPOOL, a.tid, -1, tid, pool=site, note=note,
+                               table_values=np.maximum(centres, 0).reshape(1, -1)))     # relu(d): max(a, b) = b + relu(a - b)
         return _Act(q, a.scale, tid, a.lo, a.hi)
 
     def lut_to_conv(self, a, fn, per_channel, rounding, out_scale, note):
         """table site whose output feeds a convolution; wide sites are split into a cheap noisy look-up followed by an
         identity 'refresh' bootstrap on a small ring (ParamSet.refresh_min_w)"""
         y = self.lut(a, fn, per_channel, rounding, out_scale, note)
-        op = self.ops[-1]
-        if self.ps.refresh_min_w is not None and op.w >= self.ps.refresh_min_w:
+        if self.ps.refresh_min_w is not None and self.ops[-1].lut.w >= self.ps.refresh_min_w:
             y = self.lut(y, lambda vals: vals, False, False, out_scale, note + " (refresh)")
         return y
 
@@ -477,8 +519,8 @@ class _Builder:
         q = table[np.broadcast_to(ch, idx.shape), idx]
         lo, hi = int(table.min()), int(table.max())
         tid = self.tensor(*a.q.shape[1:], lo, hi)
-        op = OpInfo(OP_LUT, a.tid, -1, tid, p=p, r=r, w=w, signed=signed, table_values=table, note=note)
-        self.ops.append(op)
+        site = LutSite(p, r, w, signed, ntab, body_add=(1 << 62) if signed else 0)
+        self.ops.append(OpInfo(OP_LUT, a.tid, -1, tid, lut=site, table_values=table, note=note))
         return _Act(q, out_scale, tid, lo, hi)
 
 
@@ -614,25 +656,18 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
                            out_scale=s_f, out_bits=bits, max_bit_width=bld.max_bits, param_set=ps,
                            rounding_threshold_bits=rounding_threshold_bits, n_bits=n_bits, rounding_method=rounding_method,
                            tier_policy=tier_policy, calib_out=out.q.reshape(out.q.shape[0], -1))
-    _assign_encodings(circ)
-    _estimate_noise(circ)
-    if getattr(ps, "table_tier_fallback_for_w", None) and circ.worst_site_failure > ps.p_budget:
-        # a faster, noisier tier (two-bit refresh) took a site out of the budget: take the quiet twins and price again
-        ps.table_tier_for_w = {**ps.table_tier_for_w, **ps.table_tier_fallback_for_w}
-        ps.table_tier_fallback_for_w = None
-        _assign_encodings(circ)
-        _estimate_noise(circ)
+    _price(circ)
     # parity-split sites: both look-ups on the site's (one-level) table tier where the budget holds; where the site's consumer -- the
     # refresh that reads the sum of two bootstrap outputs -- leaves it, the second look-up moves to the quiet twin, site by site
     budget = getattr(ps, "p_budget", 1e-12)
     while True:
         reader = {o.src0: o for o in circ.ops if o.type == OP_LUT}
-        move = [o for o in circ.ops if o.type == OP_LUT and o.ip[9] == LUT_SPLIT and ps.tiers[o.ip[4]].ksk_share >= 0
+        move = [o for o in circ.ops if o.type == OP_LUT and o.lut.mode == LUT_SPLIT and ps.tiers[o.lut.tab_tier].ksk_share >= 0
                 and max(o.pfail, reader[o.dst].pfail if o.dst in reader else 0.0) > budget]
         if not move:
             break
         for o in move:
-            o.ip[9] = LUT_SPLIT_QUIET
+            o.lut.mode = LUT_SPLIT_QUIET
         _estimate_noise(circ)
     if own_catalogue and tier_policy == "exact" and circ.worst_site_failure > 1e-10:
         import warnings
@@ -643,21 +678,39 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
 
 
 # ------------------------------------------------------------------------------------------ encodings
+def _price(circ):
+    """encodings and tiers, then the noise budget; a catalogue whose faster, noisier tiers (two-bit refresh) take a site out of the
+    budget falls back to their quiet twins, once, and is priced again"""
+    ps = circ.param_set
+    _assign_encodings(circ)
+    _estimate_noise(circ)
+    if getattr(ps, "table_tier_fallback_for_w", None) and circ.worst_site_failure > ps.p_budget:
+        ps.table_tier_for_w = {**ps.table_tier_for_w, **ps.table_tier_fallback_for_w}
+        ps.table_tier_fallback_for_w = None
+        _assign_encodings(circ)
+        _estimate_noise(circ)
+
+
+def _encode_tables(o, e):
+    enc = (o.table_values.astype(object) * (1 << e)) % (1 << 64)
+    return np.array(enc, dtype=np.uint64).view(np.int64)
+
+
 def _assign_encodings(circ):
-    T, ops = circ.tensors, circ.ops
+    T, ops, ps = circ.tensors, circ.ops, circ.param_set
     req = [None] * len(T)
     req[circ.output_tensor] = 63 - (circ.out_bits + 1)          # signed out_bits value + padding
     for o in reversed(ops):
         if o.type == OP_LUT:
-            need = 63 - o.p
+            need = 63 - o.lut.p
         elif o.type == OP_MAXPOOL:               # the output shares the input's encoding; the difference needs p_d bits
-            need = 63 - o.p if req[o.dst] is None else min(req[o.dst], 63 - o.p)
+            need = 63 - o.pool.p_d if req[o.dst] is None else min(req[o.dst], 63 - o.pool.p_d)
         else:
             need = req[o.dst]
         for s in ([o.src0, o.src1] if o.type == OP_ADD else [o.src0]):
             req[s] = need if req[s] is None else min(req[s], need)
     T[circ.input_tensor].e = req[circ.input_tensor]
-    T[circ.input_tensor].deff = circ.param_set.input_dim or circ.param_set.D
+    T[circ.input_tensor].deff = ps.input_dim or ps.D
     # a table whose output is only ever added (or decrypted) tolerates a noisier, cheaper tier
     amplified = [False] * len(T)
     for o in ops:
@@ -667,67 +720,60 @@ def _assign_encodings(circ):
         if o.type == OP_ADD and amplified[o.dst]:
             amplified[o.src0] = amplified[o.src1] = True
     for o in ops:
+        o.deff_in = max(T[o.src0].deff, T[o.src1].deff) if o.type == OP_ADD else T[o.src0].deff
         if o.type == OP_LUT:
+            L = o.lut
             T[o.dst].e = req[o.dst]
-            shift = (63 - o.p) - T[o.src0].e
-            assert shift >= 0
-            ps = circ.param_set
+            L.shift = (63 - L.p) - T[o.src0].e
+            assert L.shift >= 0
             # a table one bit wider than the catalogue's widest (7 bits on the shipped ones) runs as a parity split: two look-ups of
             # w - 1 bits on the tier a (w - 1)-bit site takes
             coarse, split = not amplified[o.dst], False
             try:
-                tier = ps.tier_for_width(o.w, coarse=coarse)
+                tier = ps.tier_for_width(L.w, coarse=coarse)
             except ValueError:
                 try:
-                    tier = ps.tier_for_width(o.w - 1, coarse=coarse)
+                    tier = ps.tier_for_width(L.w - 1, coarse=coarse)
                 except ValueError:
-                    raise ValueError(f"{o.note}: no tier for a table of {o.w} input bits: the parity split reaches one bit beyond the catalogue's "
+                    raise ValueError(f"{o.note}: no tier for a table of {L.w} input bits: the parity split reaches one bit beyond the catalogue's "
                                      f"widest tables, more would need a larger ring (N = 16384 for 8 bits: DESIGN.md section 9)") from None
                 split = True
                 if circ.rounding_method == "approximate":
-                    raise ValueError(f"{o.note}: a table of {o.w} input bits needs the exact method: the parity split takes the table's low bit "
+                    raise ValueError(f"{o.note}: a table of {L.w} input bits needs the exact method: the parity split takes the table's low bit "
                                      f"with a step of the one-bit rounding chain, which approximate rounding does not run")
                 if circ.tier_policy == "p_error":
-                    raise ValueError(f"{o.note}: a table of {o.w} input bits needs tier_policy='exact': the p_error catalogue has no tier with "
-                                     f"the 2^-{o.w + 1} half-box both look-ups of a parity split need")
-            if (o.w - 1 if split else o.w) > ps.tiers[tier].logN - 1:
+                    raise ValueError(f"{o.note}: a table of {L.w} input bits needs tier_policy='exact': the p_error catalogue has no tier with "
+                                     f"the 2^-{L.w + 1} half-box both look-ups of a parity split need")
+            if (L.w - 1 if split else L.w) > ps.tiers[tier].logN - 1:
                 raise ValueError("table wider than the ring")
-            o.ip[:7] = [o.p, o.r, o.w, shift, tier, ps.bit_tier if (o.r > 0 or split) else -1, o.table_values.shape[0]]
-            o.ip[7], o.ip[8] = (ps.bit_tier_coarse if ps.bit_tier_coarse is not None else -1), o.r + int(split)      # refined by _estimate_noise
-            o.ip[11] = -1
+            L.tab_tier, L.bit_tier = tier, ps.bit_tier if (L.r > 0 or split) else -1
+            # no hand-over yet: _estimate_noise finds the steps from which the coarser bit tiers will do
+            L.coarse, L.coarse_from, L.coarse2 = (ps.bit_tier_coarse if ps.bit_tier_coarse is not None else -1), L.r + int(split), -1
             if split:      # keeps a choice of the quiet second tier made by compile_model across a re-assignment
-                o.ip[9] = o.ip[9] if is_split(o) else LUT_SPLIT
+                L.mode = L.mode if L.split() else LUT_SPLIT
             else:
-                o.ip[9] = LUT_APPROX if (circ.rounding_method == "approximate" and o.r > 0) else LUT_EXACT
-            o.ip[10] = T[o.src0].deff
+                L.mode = LUT_APPROX if (circ.rounding_method == "approximate" and L.r > 0) else LUT_EXACT
             T[o.dst].deff = ps.tiers[tier].k << ps.tiers[tier].logN
             if split and ps.tiers[tier].ksk_share >= 0:      # the second look-up may move to the quiet twin: room for its ring too
                 q = ps.tiers[ps.tiers[tier].ksk_share]
                 T[o.dst].deff = max(T[o.dst].deff, q.k << q.logN)
-            o.lp[0] = (1 << 62) if o.signed else 0
-            enc = (o.table_values.astype(object) * (1 << T[o.dst].e)) % (1 << 64)
-            o.payload = np.array(enc, dtype=np.uint64).view(np.int64)
+            o.payload = _encode_tables(o, T[o.dst].e)
             if split:
                 split_tables(o.payload)       # refuses a table whose pairs have no exact half (e = 0 with an odd sum)
         elif o.type == OP_MAXPOOL:
-            ps = circ.param_set
+            S = o.pool
             T[o.dst].e = T[o.src0].e
-            shift = (63 - o.p) - T[o.src0].e
-            assert shift >= 0
-            tier = ps.tier_for_width(o.p, coarse=not amplified[o.dst])
-            if o.p > ps.tiers[tier].logN - 1:
+            S.shift = (63 - S.p_d) - T[o.src0].e
+            assert S.shift >= 0
+            S.tier = ps.tier_for_width(S.p_d, coarse=not amplified[o.dst])
+            if S.p_d > ps.tiers[S.tier].logN - 1:
                 raise ValueError("max-pool difference table wider than the ring")
-            o.ip[3], o.ip[4] = shift, tier
-            o.ip[10] = T[o.src0].deff
             # the pairwise maxima accumulate a bootstrap output into the first kN words of a copy of `b`
-            T[o.dst].deff = max(T[o.src0].deff, ps.tiers[tier].k << ps.tiers[tier].logN)
-            o.lp[0] = 1 << 62                        # signed body offset: index = d + 2^(p_d - 1)
-            enc = (o.table_values.astype(object) * (1 << T[o.dst].e)) % (1 << 64)
-            o.payload = np.array(enc, dtype=np.uint64).view(np.int64)
+            T[o.dst].deff = max(T[o.src0].deff, ps.tiers[S.tier].k << ps.tiers[S.tier].logN)
+            o.payload = _encode_tables(o, T[o.dst].e)
         else:
             T[o.dst].e = T[o.src0].e
-            T[o.dst].deff = max(T[o.src0].deff, T[o.src1].deff) if o.type == OP_ADD else T[o.src0].deff
-            o.ip[10] = T[o.dst].deff
+            T[o.dst].deff = o.deff_in
             if o.type == OP_ADD:
                 assert T[o.src1].e == T[o.src0].e, "residual operands must share an encoding"
 
@@ -739,119 +785,137 @@ def _estimate_noise(circ):
     total, flips = 0.0, 0.0
     for o in circ.ops:
         s = T[o.src0]
-        n_elt = s.C * s.H * s.W
         if o.type == OP_CONV:
             T[o.dst].var = o.nu2 * s.var
         elif o.type == OP_ADD:
             T[o.dst].var = s.var + T[o.src1].var
         elif o.type == OP_SUMPOOL:
-            T[o.dst].var = o.ip[0] ** 2 * s.var
+            T[o.dst].var = o.sum_k ** 2 * s.var
         elif o.type == OP_MAXPOOL:
-            # every tree level: the difference of two candidates (variance var(a) + var(b), bounded by twice the level's worst),
-            # key-switched over the level's effective dimension, mod-switched, one signed p_d-bit table; b + relu(a - b) adds one
-            # bootstrap output to b.  The column pass starts from the row pass's output.
-            tt = ps.tiers[o.ip[4]]
-            ring = tt.k << tt.logN
-            v, d_in, worst, v_tab, v_worst = s.var, s.deff or ps.D, 0.0, 0.0, 0.0
-            for mult, pairs in o.pool_geom:
-                for npair in pairs:
-                    v_tab = 2.0 * v * 4.0 ** o.ip[3] + P.var_keyswitch(d_in, tt) + P.var_modswitch(tt)
-                    pf = P.p_fail(2.0 ** -(o.p + 2), v_tab)
-                    worst, v_worst = max(worst, pf), max(v_worst, v_tab)
-                    total += pf * mult * npair
-                    v += P.var_pbs_out(tt, ps.fft_noise_c)
-                    d_in = max(d_in, ring)
-            o.pfail = worst
-            o.margin = [("pool", o.ip[4], o.p, v_worst)]
-            o.sim_sigma = math.sqrt(v_tab)
-            T[o.dst].var = v
+            for fail in _price_max_pool(ps, o, s, T[o.dst]):       # one by one: the sum keeps its order
+                total += fail
         else:
-            tt = ps.tiers[o.ip[4]]
-            v_in0 = s.var * 4.0 ** o.ip[3]
-            d_in = s.deff or ps.D                                     # the key switch only sums over the non-zero mask words
-            v_tab_in = P.var_keyswitch(d_in, tt) + P.var_modswitch(tt)
-
-            approx = o.ip[9] == LUT_APPROX
-            # parity split: r + 1 one-bit steps, two look-ups of w - 1 bits; the second one's input carries the parity bootstrap's
-            # output (tier of the last step) on top of the chain's, its key switch and mod switch are its own tier's
-            split = is_split(o)
-            R_, W_ = chain_steps(o), o.w - (1 if split else 0)
-            t2 = ps.tiers[second_tier(ps, o)] if split else None
-            v_tab2_in = (P.var_keyswitch(d_in, t2) + P.var_modswitch(t2)) if split else 0.0
-
-            c2 = getattr(ps, "bit_tier_coarse2", None)
-
-            def site_pfail(coarse_from, coarse2_from=None, rec=None):
-                """rec (a list): the variance at every decision is appended, for CompiledCircuit.margin_model"""
-                pf_, v_ = 0.0, v_in0
-                if approx:
-                    if rec is not None:
-                        rec.append(("table", o.ip[4], o.w, v_ + v_tab_in))      # listed for completeness: the audit refuses such a site
-                    # no rounding steps: the low r bits ride along; a failure is noise beyond the half-box.  (The two inputs
-                    # next to a rounding boundary, 2 of 2^r, sit half an input unit from it and take the neighbouring
-                    # entry far more often: the method's own inexactness, reported apart as boundary flips.)
-                    return P.p_fail(2.0 ** -(o.w + 2), v_ + v_tab_in)
-                step = None
-                if R_ > 0:
-                    for i in range(R_):
-                        ti = o.ip[5]
-                        if i >= coarse_from and o.ip[7] >= 0:
-                            ti = o.ip[7]
-                        if coarse2_from is not None and i >= coarse2_from:
-                            ti = c2
-                        step = ps.tiers[ti]
-                        # the tier that runs the step key-switches to its own small key (own length, own noise) and mod-switches on its ring
-                        v_bit_in = P.var_keyswitch(max(d_in, step.k << step.logN), step) + P.var_modswitch(step)
-                        v_step = 4.0 ** (o.p - i) * v_ + v_bit_in
-                        pf_ += P.p_fail(0.25, v_step)
-                        if rec is not None:
-                            rec.append((f"step {i}", ti, 0, v_step))
-                        v_ += P.var_pbs_out(step, ps.fft_noise_c)
-                v_second = (v_ + P.var_pbs_out(step, ps.fft_noise_c) + v_tab2_in) if split else 0.0
-                second = P.p_fail(2.0 ** -(W_ + 2), v_second) if split else 0.0
-                if rec is not None:
-                    if split:
-                        rec.append(("second", second_tier(ps, o), W_, v_second))
-                    rec.append(("table", o.ip[4], W_, v_ + v_tab_in))
-                return pf_ + P.p_fail(2.0 ** -(W_ + 2), v_ + v_tab_in) + second
-
-            pf = site_pfail(R_)
-            chosen = (R_, None)       # the arguments of the site_pfail call whose result stays in o.pfail
-            if R_ > 0 and o.ip[7] >= 0 and not approx:
-                # earliest step from which the one-level bit tier keeps the site within 2x of its all-precise failure rate
-                budget = max(2.0 * pf, getattr(ps, "p_budget", 1e-12))
-                cf = R_
-                while cf > 0 and site_pfail(cf - 1) <= budget:
-                    cf -= 1
-                o.coarse_from = o.ip[8] = cf
-                pf = site_pfail(cf)
-                chosen = (cf, None)
-                if c2 is not None:      # ... and, inside that budget, the earliest step from which the two-bit-rotation tier will do
-                    cf2 = R_
-                    while cf2 > cf and site_pfail(cf, cf2 - 1) <= budget:
-                        cf2 -= 1
-                    o.coarse2_from = cf2
-                    o.ip[11] = (c2 << 8) | cf2 if cf2 < R_ else -1
-                    chosen = (cf, cf2 if cf2 < R_ else None)
-                    pf = site_pfail(*chosen)
-            o.pfail = pf
-            o.margin = []
-            site_pfail(*chosen, rec=o.margin)
-            v_sim = v_in0
-            if R_ > 0 and not approx:                       # what the one-bit steps leave on the working ciphertext
-                for i in range(R_):
-                    v_sim += P.var_pbs_out(ps.tiers[step_tier(o, i)], ps.fft_noise_c)
-            o.sim_sigma = math.sqrt(v_sim + v_tab_in)
-            o.sim_sigma2 = math.sqrt(v_sim + P.var_pbs_out(ps.tiers[step_tier(o, o.r)], ps.fft_noise_c) + v_tab2_in) if split else 0.0
-            if approx:
-                flips += (2.0 / 2 ** o.r) * P.p_fail(2.0 ** -(o.p + 2), v_in0 + v_tab_in) * n_elt
-            total += pf * n_elt
-            T[o.dst].var = P.var_pbs_out(tt, ps.fft_noise_c) + (P.var_pbs_out(t2, ps.fft_noise_c) if split else 0.0)
+            fail, flip = _price_lut(ps, o, s, T[o.dst])
+            total += fail
+            flips += flip
     circ.expected_failures_per_image = total
     circ.expected_boundary_flips_per_image = flips
 
 
+def _price_max_pool(ps, o, s, d):
+    """-> expected failures per image, one term per tree level.  Every level: the difference of two candidates (variance var(a) + var(b),
+    bounded by twice the level's worst), key-switched over the level's effective dimension, mod-switched, one signed p_d-bit table;
+    b + relu(a - b) adds one bootstrap output to b.  The column pass starts from the row pass's output."""
+    S = o.pool
+    tt = ps.tiers[S.tier]
+    ring = tt.k << tt.logN
+    v, d_in, worst, v_tab, v_worst, fails = s.var, s.deff or ps.D, 0.0, 0.0, 0.0, []
+    for mult, pairs in S.pool_geom:
+        for npair in pairs:
+            v_tab = 2.0 * v * 4.0 ** S.shift + P.var_keyswitch(d_in, tt) + P.var_modswitch(tt)
+            pf = P.p_fail(2.0 ** -(S.p_d + 2), v_tab)
+            worst, v_worst = max(worst, pf), max(v_worst, v_tab)
+            fails.append(pf * mult * npair)
+            v += P.var_pbs_out(tt, ps.fft_noise_c)
+            d_in = max(d_in, ring)
+    o.pfail = worst
+    o.margin = [v_worst]
+    o.sim_sigma = math.sqrt(v_tab)
+    d.var = v
+    return fails
+
+
+def _price_lut(ps, o, s, d):
+    """-> (expected failures, expected boundary flips) per image; settles the site's hand-over steps (LutSite.coarse_from, coarse2,
+    coarse2_from)"""
+    L = o.lut
+    n_elt = s.C * s.H * s.W
+    tt = ps.tiers[L.tab_tier]
+    v_in0 = s.var * 4.0 ** L.shift
+    d_in = s.deff or ps.D                                     # the key switch only sums over the non-zero mask words
+    v_tab_in = P.var_keyswitch(d_in, tt) + P.var_modswitch(tt)
+    # parity split: r + 1 one-bit steps, two look-ups of w - 1 bits; the second one's input carries the parity bootstrap's
+    # output (tier of the last step) on top of the chain's, its key switch and mod switch are its own tier's
+    split, R_, W_ = L.split(), L.n_steps(), L.table_bits()
+    t2 = ps.tiers[L.tier2(ps)] if split else None
+    v_tab2_in = (P.var_keyswitch(d_in, t2) + P.var_modswitch(t2)) if split else 0.0
+    c2 = getattr(ps, "bit_tier_coarse2", None)
+
+    def handed_over(cf, cf2=None):
+        """the site with its hand-overs at steps cf (one-level twin) and cf2 (two-bit-rotation twin; None: not at all)"""
+        return replace(L, coarse_from=cf, coarse2=-1 if cf2 is None else c2, coarse2_from=cf2 or 0)
+
+    def site_pfail(C):
+        """candidate site C -> (failure probability per element, the variance at every decision that has a key switch of its own, in
+        for_each_bootstrap's order)"""
+        pf_, v_, step, var = 0.0, v_in0, None, []
+        # an approximate site has no steps: the low r bits ride along; a failure is noise beyond the table's half-box.  (The two inputs
+        # next to a rounding boundary, 2 of 2^r, sit half an input unit from it and take the neighbouring entry far more often: the
+        # method's own inexactness, reported apart as boundary flips.  Its variance is listed for completeness: the audit refuses the site.)
+        for i in range(R_):
+            step = ps.tiers[C.step_tier(i)]
+            # the tier that runs the step key-switches to its own small key (own length, own noise) and mod-switches on its ring
+            v_bit_in = P.var_keyswitch(max(d_in, step.k << step.logN), step) + P.var_modswitch(step)
+            v_step = 4.0 ** (L.p - i) * v_ + v_bit_in
+            pf_ += P.p_fail(0.25, v_step)
+            var.append(v_step)
+            v_ += P.var_pbs_out(step, ps.fft_noise_c)
+        v_second = (v_ + P.var_pbs_out(step, ps.fft_noise_c) + v_tab2_in) if split else 0.0
+        second = P.p_fail(2.0 ** -(W_ + 2), v_second) if split else 0.0
+        return pf_ + P.p_fail(2.0 ** -(W_ + 2), v_ + v_tab_in) + second, var + ([v_second] if split else []) + [v_ + v_tab_in]
+
+    chosen = handed_over(R_)
+    pf = site_pfail(chosen)[0]
+    if R_ > 0 and L.coarse >= 0:
+        # earliest step from which the one-level bit tier keeps the site within 2x of its all-precise failure rate
+        budget = max(2.0 * pf, getattr(ps, "p_budget", 1e-12))
+        cf = R_
+        while cf > 0 and site_pfail(handed_over(cf - 1))[0] <= budget:
+            cf -= 1
+        chosen = handed_over(cf)
+        if c2 is not None:      # ... and, inside that budget, the earliest step from which the two-bit-rotation tier will do
+            cf2 = R_
+            while cf2 > cf and site_pfail(handed_over(cf, cf2 - 1))[0] <= budget:
+                cf2 -= 1
+            if cf2 < R_:
+                chosen = handed_over(cf, cf2)
+        L = o.lut = chosen
+    o.pfail, o.margin = site_pfail(chosen)
+    # what `simulate` injects: the priced noise at the table, on top of what the one-bit steps left, and at a split's second look-up
+    o.sim_sigma = math.sqrt(o.margin[-1])
+    o.sim_sigma2 = math.sqrt(o.margin[-2]) if split else 0.0
+    d.var = P.var_pbs_out(tt, ps.fft_noise_c) + (P.var_pbs_out(t2, ps.fft_noise_c) if split else 0.0)
+    flip = (2.0 / 2 ** L.r) * P.p_fail(2.0 ** -(L.p + 2), v_in0 + v_tab_in) * n_elt if L.approx() else 0.0
+    return o.pfail * n_elt, flip
+
+
 # ------------------------------------------------------------------------------------------ blob
+# The op record (struct Op of csrc/circuit.h, whose parse_circuit is the decoder): type, src0, src1, dst, ip[12], lp[2], payload range.
+#   every op    ip[10] = effective dimension of what the op reads
+#   OP_CONV     ip[0..4] = Cout, KH, KW, stride, pad
+#   OP_SUMPOOL  ip[0] = window K
+#   OP_LUT      ip[0..3] = p, r, w, shift; ip[4] = table tier; ip[5] = bit tier; ip[6] = tables; ip[7], ip[8] = one-level twin of the bit
+#               tier and the step it takes over from; ip[9] = mode; ip[11] = two-bit-rotation twin << 8 | its step; lp[0] = body offset
+#   OP_MAXPOOL  ip[0..2] = k, stride, pad; ip[3] = shift; ip[4] = tier of the relu table; ip[5] = p_d; ip[6] = 1 table; lp[0] = body offset
+# A tier slot < 0 (ip[11]: the whole slot -1): no such hand-over.  lp words travel as signed 64-bit; src1 of a one-input op as 0.
+def _encode_record(o):
+    """-> (ip[12], lp[2]) of op `o`: the one place that knows which slot holds which field"""
+    ip, body_add = [0] * 12, 0
+    if o.type == OP_CONV:
+        ip[:5] = [o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride, o.conv.pad]
+    elif o.type == OP_SUMPOOL:
+        ip[0] = o.sum_k
+    elif o.type == OP_LUT:
+        L, body_add = o.lut, o.lut.body_add
+        ip[:10] = [L.p, L.r, L.w, L.shift, L.tab_tier, L.bit_tier, L.ntab, L.coarse, L.coarse_from, L.mode]
+        ip[11] = (L.coarse2 << 8 | L.coarse2_from) if L.coarse2 >= 0 else -1
+    elif o.type == OP_MAXPOOL:
+        S, body_add = o.pool, o.pool.body_add
+        ip[:7] = [S.k, S.stride, S.pad, S.shift, S.tier, S.p_d, 1]
+    ip[10] = o.deff_in
+    return [int(x) for x in ip], [body_add - (1 << 64) if body_add >= (1 << 63) else body_add, 0]
+
+
 def _serialize(circ):
     nT, nO = len(circ.tensors), len(circ.ops)
     head = struct.pack("<IIiiiiii", MAGIC, 1, nT, nO, circ.input_tensor, circ.output_tensor, circ.max_bit_width, 0)
@@ -861,8 +925,8 @@ def _serialize(circ):
     for o in circ.ops:
         pl = b"" if o.payload is None else np.ascontiguousarray(o.payload).tobytes()
         pad = (-len(pl)) % 16
-        recs.append(struct.pack("<iiii12i2qqq", o.type, o.src0, max(o.src1, 0), o.dst, *[int(x) for x in o.ip],
-                                *[int(x) - (1 << 64) if int(x) >= (1 << 63) else int(x) for x in o.lp], off if pl else 0, len(pl)))
+        ip, lp = _encode_record(o)
+        recs.append(struct.pack("<iiii12i2qqq", o.type, o.src0, max(o.src1, 0), o.dst, *ip, *lp, off if pl else 0, len(pl)))
         payloads.append(pl + b"\0" * pad)
         off += len(pl) + pad
     return head + tens + b"".join(recs) + b"".join(payloads)

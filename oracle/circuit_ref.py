@@ -11,7 +11,7 @@ import struct
 
 import numpy as np
 
-OP_CONV, OP_ADD, OP_SUMPOOL, OP_LUT = 1, 2, 3, 4
+OP_CONV, OP_ADD, OP_SUMPOOL, OP_LUT, OP_MAXPOOL = 1, 2, 3, 4, 5
 
 
 def parse_blob(blob):
@@ -45,37 +45,63 @@ def _conv_u64(x, w, stride, pad):
     return out
 
 
-def run_clear(blob, phases_in):
-    """phases_in: uint64 [B, n_in] -> (uint64 [B, n_out], overflow flag)"""
+def max_pool_words(x, k, s, p):
+    """x uint64 [B, C, H, W] -> signed-word maximum over the in-range taps of every k x k window (the MaxPool2d contract: floor mode,
+    out-of-range taps ignored)"""
+    B, C, H, W = x.shape
+    Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+    xs = x.view(np.int64)
+    out = np.empty((B, C, Ho, Wo), np.int64)
+    for yo in range(Ho):
+        ys = [y for y in range(yo * s - p, yo * s - p + k) if 0 <= y < H]
+        for xo in range(Wo):
+            xs_ = [xx for xx in range(xo * s - p, xo * s - p + k) if 0 <= xx < W]
+            out[:, :, yo, xo] = xs[:, :, ys][:, :, :, xs_].max(axis=(2, 3))
+    return out.view(np.uint64)
+
+
+def eval_op(o, x, vals):
+    """one parsed op on the phases x of its first input (vals: every tensor so far, by id) -> (phases of its output, overflow flag)"""
+    B = x.shape[0]
+    ip = o["ip"]
+    overflow = False
+    if o["type"] == OP_CONV:
+        Cout, KH, KW, stride, pad = ip[:5]
+        w = np.frombuffer(o["payload"], np.int8).reshape(Cout, x.shape[1], KH, KW)
+        y = _conv_u64(x, w, stride, pad)
+    elif o["type"] == OP_ADD:
+        y = x + vals[o["src1"]]
+    elif o["type"] == OP_SUMPOOL:
+        K = ip[0]
+        Ho, Wo = x.shape[2] // K, x.shape[3] // K
+        y = x[:, :, :Ho * K, :Wo * K].reshape(B, x.shape[1], Ho, K, Wo, K).sum(axis=(3, 5), dtype=np.uint64)
+    elif o["type"] == OP_LUT:
+        p, r, w, shift, _, _, ntab = ip[:7]
+        tables = np.frombuffer(o["payload"], np.int64).reshape(ntab, 1 << w).view(np.uint64)
+        v = (x << np.uint64(shift)) + np.uint64(o["lp"][0] % (1 << 64))
+        if r > 0:
+            v = v + (np.uint64(1) << np.uint64(63 - p + r - 1))
+        overflow |= bool((v >> np.uint64(63)).any())
+        idx = ((v >> np.uint64(63 - w)) & np.uint64((1 << w) - 1)).astype(np.int64)
+        ch = np.arange(x.shape[1]).reshape(1, -1, 1, 1) if ntab > 1 else np.zeros((1, 1, 1, 1), np.int64)
+        y = tables[np.broadcast_to(ch, idx.shape), idx]
+    elif o["type"] == OP_MAXPOOL:
+        y = max_pool_words(x, ip[0], ip[1], ip[2])
+    else:
+        raise ValueError("unknown op")
+    return y, overflow
+
+
+def run_clear(blob, phases_in, all_tensors=False):
+    """phases_in: uint64 [B, n_in] -> (uint64 [B, n_out], overflow flag); all_tensors: the phases of every tensor, by id, instead"""
     c = parse_blob(blob)
     T = c["tensors"]
     B = phases_in.shape[0]
     vals = {c["input"]: np.ascontiguousarray(phases_in, np.uint64).reshape(B, *T[c["input"]])}
     overflow = False
     for o in c["ops"]:
-        x = vals[o["src0"]]
-        ip = o["ip"]
-        if o["type"] == OP_CONV:
-            Cout, KH, KW, stride, pad = ip[:5]
-            w = np.frombuffer(o["payload"], np.int8).reshape(Cout, x.shape[1], KH, KW)
-            y = _conv_u64(x, w, stride, pad)
-        elif o["type"] == OP_ADD:
-            y = x + vals[o["src1"]]
-        elif o["type"] == OP_SUMPOOL:
-            K = ip[0]
-            Ho, Wo = x.shape[2] // K, x.shape[3] // K
-            y = x[:, :, :Ho * K, :Wo * K].reshape(B, x.shape[1], Ho, K, Wo, K).sum(axis=(3, 5), dtype=np.uint64)
-        elif o["type"] == OP_LUT:
-            p, r, w, shift, _, _, ntab = ip[:7]
-            tables = np.frombuffer(o["payload"], np.int64).reshape(ntab, 1 << w).view(np.uint64)
-            v = (x << np.uint64(shift)) + np.uint64(o["lp"][0] % (1 << 64))
-            if r > 0:
-                v = v + (np.uint64(1) << np.uint64(63 - p + r - 1))
-            overflow |= bool((v >> np.uint64(63)).any())
-            idx = ((v >> np.uint64(63 - w)) & np.uint64((1 << w) - 1)).astype(np.int64)
-            ch = np.arange(x.shape[1]).reshape(1, -1, 1, 1) if ntab > 1 else np.zeros((1, 1, 1, 1), np.int64)
-            y = tables[np.broadcast_to(ch, idx.shape), idx]
-        else:
-            raise ValueError("unknown op")
-        vals[o["dst"]] = y
+        vals[o["dst"]], over = eval_op(o, vals[o["src0"]], vals)
+        overflow |= over
+    if all_tensors:
+        return vals, overflow
     return vals[c["output"]].reshape(B, -1), overflow

@@ -15,7 +15,7 @@ COUNTS = (1, 3, 4, 5, 257, 4099)      # a partial block, one block, two, several
 
 
 def _oracle_out(qm, q):
-    import maxpool_circuit_ref as circuit_ref      # the frozen interpreter plus the max pool
+    from oracle import circuit_ref
     out, ov = circuit_ref.run_clear(qm.compiled.blob, qm.encode_input(q))
     assert not ov
     return qm.decode_output(out)

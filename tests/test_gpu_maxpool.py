@@ -1,5 +1,5 @@
 """The stem MaxPool2d (circuit op 5) on the GPU: the difference key switch, the pooling tree on encrypted rows and in clear mode,
-pooled circuits against the numpy interpreter (tests/maxpool_circuit_ref.py), statistics, simulate, the CLI."""
+pooled circuits against the numpy interpreter (oracle/circuit_ref.py), statistics, simulate, the CLI."""
 import os
 import subprocess
 import sys
@@ -7,7 +7,7 @@ import sys
 import numpy as np
 import pytest
 
-import maxpool_circuit_ref as mref
+from oracle import circuit_ref as mref
 
 pytestmark = pytest.mark.gpu
 

@@ -115,30 +115,8 @@ def _split_eval(blob, phases_in):
             vals[o["dst"]] = first + np.where(idx & 1, np.uint64(0) - second, second)
             n_split += 1
         else:
-            vals[o["dst"]] = _run_one(R, o, x, vals, B)
+            vals[o["dst"]] = R.eval_op(o, x, vals)[0]
     return vals[c["output"]].reshape(B, -1), n_split
-
-
-def _run_one(R, o, x, vals, B):
-    ip = o["ip"]
-    if o["type"] == R.OP_CONV:
-        Cout, KH, KW, stride, pad = ip[:5]
-        return R._conv_u64(x, np.frombuffer(o["payload"], np.int8).reshape(Cout, x.shape[1], KH, KW), stride, pad)
-    if o["type"] == R.OP_ADD:
-        return x + vals[o["src1"]]
-    if o["type"] == R.OP_SUMPOOL:
-        K = ip[0]
-        Ho, Wo = x.shape[2] // K, x.shape[3] // K
-        return x[:, :, :Ho * K, :Wo * K].reshape(B, x.shape[1], Ho, K, Wo, K).sum(axis=(3, 5), dtype=np.uint64)
-    assert o["type"] == R.OP_LUT
-    p, r, w, shift, _, _, ntab = ip[:7]
-    tables = np.frombuffer(o["payload"], np.int64).reshape(ntab, 1 << w).view(np.uint64)
-    v = (x << np.uint64(shift)) + np.uint64(o["lp"][0] % (1 << 64))
-    if r > 0:
-        v = v + (np.uint64(1) << np.uint64(63 - p + r - 1))
-    idx = ((v >> np.uint64(63 - w)) & np.uint64((1 << w) - 1)).astype(np.int64)
-    ch = np.arange(x.shape[1]).reshape(1, -1, 1, 1) if ntab > 1 else np.zeros((1, 1, 1, 1), np.int64)
-    return tables[np.broadcast_to(ch, idx.shape), idx]
 
 
 @pytest.mark.parametrize("bit_width", [4, 5])

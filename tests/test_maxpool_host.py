@@ -1,5 +1,5 @@
 """The stem MaxPool2d of the RGB ResNet-18 trunks (reference models/backbone.py:252-259) on the host: model rows, import rules,
-checkpoint mapping, the compiled op against a numpy interpreter (tests/maxpool_circuit_ref.py), blob validation, noise budget and
+checkpoint mapping, the compiled op against the numpy interpreter (oracle/circuit_ref.py), blob validation, noise budget and
 bootstrap counts (no GPU)."""
 import hashlib
 import struct
@@ -119,7 +119,7 @@ def _pooled(pool, img, bits=4):
 @pytest.mark.parametrize("pool,img", GEOMS)
 def test_compiled_pool_matches_numpy(pool, img):
     from dctfhe import compile as cc
-    import maxpool_circuit_ref as mref
+    from oracle import circuit_ref as mref
     c, calib = _pooled(pool, img)
     ops = [o for o in c.ops if o.type == cc.OP_MAXPOOL]
     assert len(ops) == 1

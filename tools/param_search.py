@@ -1,7 +1,7 @@
 """Noise-model search for the small-key lengths of the exact-evaluation catalogue (dctfhe/params.py::default_params): per group of
 tiers that share a key-switch key, the smallest n (steps of 8) that keeps the worst look-up site of the benchmark circuits at the
 budget.  The circuits are compiled once (calibration is the slow part); each candidate only re-runs the encoding / tier assignment
-and the noise pricing (dctfhe/compile.py::_assign_encodings, _estimate_noise).  CPU only.
+and the noise pricing (dctfhe/compile.py::_price).  CPU only.
 usage: python tools/param_search.py [--configs r20_24_16,r20_3_32,r18_3_32]   -> the table profiles/r03_param_search.log holds
        python tools/param_search.py --bit-width 5 --configs r20_24_16,r20_3_32,r18_3_32,r18_48_112
            -> the 5-bit catalogue (params.default_params_5bit: its new tiers only), profiles/bw5_param_search.log"""
@@ -50,17 +50,9 @@ def price(circs, ps):
     for name, c in circs.items():
         c2 = copy.copy(c)
         c2.tensors = [copy.copy(t) for t in c.tensors]
-        c2.ops = [copy.copy(o) for o in c.ops]
-        for o in c2.ops:
-            o.ip, o.lp = list(o.ip), list(o.lp)
+        c2.ops = [dataclasses.replace(o, lut=copy.copy(o.lut), pool=copy.copy(o.pool)) for o in c.ops]     # the sites pricing writes to
         c2.param_set = copy.deepcopy(ps)
-        cc._assign_encodings(c2)
-        cc._estimate_noise(c2)
-        if getattr(c2.param_set, "table_tier_fallback_for_w", None) and c2.worst_site_failure > c2.param_set.p_budget:
-            c2.param_set.table_tier_for_w = {**c2.param_set.table_tier_for_w, **c2.param_set.table_tier_fallback_for_w}
-            c2.param_set.table_tier_fallback_for_w = None
-            cc._assign_encodings(c2)
-            cc._estimate_noise(c2)
+        cc._price(c2)
         worst = max(worst, c2.worst_site_failure)
         fails[name] = c2.expected_failures_per_image
         counts[name] = c2.pbs_counts()

@@ -1531,6 +1531,160 @@ extern "C" int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int t
   return dev_keyswitch_pack(K, tier, d_in.as<uint64_t>(), L, deff ? deff : dim, count, sc, rows);
 }
 
+// ---- ring-packed results (kernels.h k_ring_*): the packing key and the pack on small ciphertexts -------------
+// Wire form of the key (seeded only): PackBlobHeader, the client's 32-byte public generator key, then the n_max * l * N body words.
+static constexpr uint32_t PACK_BLOB_MAGIC = 0x4b505244u /* 'DRPK' */, PACK_BLOB_VERSION = 1;
+struct PackBlobHeader { uint32_t magic, version; int32_t logN, l, beta, n_max; double sigma; uint64_t total_bytes; };
+// the generator stream of a spec's masks (noise: + 1): a stream of its own per (logN, l, beta, sigma) -- sigma included, because the
+// Gaussian draw scales with it: two exports of one client key at different sigma on ONE stream would differ by E (1 - sigma2 / sigma1)
+// and give E away.  Bit 63 is set (every other stream id of these generator keys is below 2^17), bit 0 clear (the noise stream is + 1); the 62 bits between are
+// the IEEE-754 bits of sigma times an odd constant (a bijection mod 2^64) xor the gadget: distinct specs meet with probability 2^-61.
+static uint64_t ring_stream(int logN, int l, int beta, double sigma) {
+  uint64_t sb;
+  memcpy(&sb, &sigma, 8);
+  const uint64_t mix = (sb * 0x9E3779B97F4A7C15ULL) ^ (((uint64_t)logN << 24) | ((uint64_t)l << 16) | ((uint64_t)beta << 8));
+  return (1ULL << 63) | (mix & 0x7FFFFFFFFFFFFFFEULL);
+}
+static int check_pack_spec(const char* who, int logN, int l, int beta, int n_max, double sigma, int D) {
+  if (logN < 5 || logN > 12) return fail("%s: ring 2^%d outside 2^5 .. 2^12", who, logN);
+  if (D > 0 && (1 << logN) > D) return fail("%s: the ring key is a prefix of the big key: N_p = %d > D = %d", who, 1 << logN, D);
+  if (l < 1 || beta < 1 || beta > 32) return fail("%s: %d levels of %d bits (levels >= 1, 1 <= bits <= 32)", who, l, beta);
+  if (l * beta > 63) return fail("%s: gadget of %d x %d bits exceeds 63", who, l, beta);
+  if (n_max < 1) return fail("%s: a small key of %d bits", who, n_max);
+  if (!(sigma >= 0.0) || sigma >= 1.0) return fail("%s: noise std %g outside [0, 1)", who, sigma);
+  return 0;
+}
+static size_t pack_blob_size(int logN, int l, int n_max) { return sizeof(PackBlobHeader) + 32 + ((size_t)n_max * l << logN) * 8; }
+
+struct dctfhe_pack_key {
+  dctfhe_ctx* ctx = nullptr;
+  int logN = 0, l = 0, beta = 0, n_max = 0;
+  double sigma = 0;
+  DevBuf key;                    // u64 [n_max][l][2][N]
+  ~dctfhe_pack_key() { if (ctx) hipSetDevice(ctx->device); }
+};
+
+extern "C" int dctfhe_pack_key_export(dctfhe_client_key* C, int logN, int l, int beta, double sigma, void* buf, size_t capacity, size_t* size) {
+  if (!C || !size) return fail("dctfhe_pack_key_export: null argument");
+  CHK(check_pack_spec("dctfhe_pack_key_export", logN, l, beta, C->p.n_max, sigma, C->p.D));
+  const size_t need = pack_blob_size(logN, l, C->p.n_max);
+  *size = need;
+  if (!buf) return 0;                       // size query
+  if (capacity < need) return fail("dctfhe_pack_key_export: buffer of %zu bytes, %zu needed", capacity, need);
+  HIPCHK(hipSetDevice(C->ctx->device));
+  const int N = 1 << logN, rows = C->p.n_max * l;
+  PackBlobHeader h{};
+  h.magic = PACK_BLOB_MAGIC; h.version = PACK_BLOB_VERSION; h.logN = logN; h.l = l; h.beta = beta; h.n_max = C->p.n_max; h.sigma = sigma;
+  h.total_bytes = need;
+  char* q = (char*)buf;
+  memcpy(q, &h, sizeof h); q += sizeof h;
+  key_to_bytes(C->pub, (uint8_t*)q); q += 32;
+  DevBuf d_b;
+  HIPCHK(d_b.alloc((size_t)rows * N * 8));
+  hipLaunchKernelGGL(k_ring_key_gen, dim3((unsigned)rows), dim3(256), (size_t)N * 8, C->ctx->stream, C->s(), C->S(), N, l, beta, sigma, C->pub, C->sec,
+                     ring_stream(logN, l, beta, sigma), d_b.as<uint64_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(d_b.download(q, (size_t)rows * N * 8, C->ctx->stream));
+  return 0;
+}
+extern "C" int dctfhe_pack_key_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_pack_key** out) {
+  if (!ctx || !buf || !out) return fail("dctfhe_pack_key_import: null argument");
+  if (size < sizeof(PackBlobHeader) + 32) return fail("dctfhe_pack_key_import: packing-key blob too short (%zu bytes)", size);
+  PackBlobHeader h;
+  memcpy(&h, buf, sizeof h);
+  if (h.magic != PACK_BLOB_MAGIC) return fail("dctfhe_pack_key_import: not a packing-key blob (magic)");
+  if (h.version != PACK_BLOB_VERSION) return fail("dctfhe_pack_key_import: packing-key blob version %u, this library reads %u", h.version, PACK_BLOB_VERSION);
+  CHK(check_pack_spec("dctfhe_pack_key_import", h.logN, h.l, h.beta, h.n_max, h.sigma, 0));
+  if (h.total_bytes != size || pack_blob_size(h.logN, h.l, h.n_max) != size)
+    return fail("dctfhe_pack_key_import: packing-key blob of %zu bytes, its header needs %zu (length)", size, pack_blob_size(h.logN, h.l, h.n_max));
+  HIPCHK(hipSetDevice(ctx->device));
+  std::unique_ptr<dctfhe_pack_key> K(new dctfhe_pack_key);
+  K->ctx = ctx; K->logN = h.logN; K->l = h.l; K->beta = h.beta; K->n_max = h.n_max; K->sigma = h.sigma;
+  const size_t N = (size_t)1 << h.logN, rows = (size_t)h.n_max * h.l;
+  const rng_key pub = key_from_bytes((const uint8_t*)buf + sizeof h);
+  DevBuf d_b;
+  HIPCHK(d_b.upload((const char*)buf + sizeof h + 32, rows * N * 8));
+  HIPCHK(K->key.alloc(rows * 2 * N * 8));
+  CHK(launch_expand(pub, ring_stream(h.logN, h.l, h.beta, h.sigma), 0, N, (int)N, ~0ULL, d_b.as<uint64_t>(), (int)N, rows, 2 * N, K->key.as<uint64_t>(), ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *out = K.release();
+  return 0;
+}
+extern "C" int dctfhe_pack_key_destroy(dctfhe_pack_key* K) { delete K; return 0; }
+extern "C" int dctfhe_pack_key_info(dctfhe_pack_key* K, int* logN, int* l, int* beta, int* n_max, double* sigma) {
+  if (!K) return fail("dctfhe_pack_key_info: null argument");
+  if (logN) *logN = K->logN;
+  if (l) *l = K->l;
+  if (beta) *beta = K->beta;
+  if (n_max) *n_max = K->n_max;
+  if (sigma) *sigma = K->sigma;
+  return 0;
+}
+// test view: the expanded key [n_max][l][2][N]
+extern "C" int dctfhe_pack_key_export_rows(dctfhe_pack_key* K, uint64_t* out) {
+  if (!K || !out) return fail("dctfhe_pack_key_export_rows: null argument");
+  HIPCHK(hipSetDevice(K->ctx->device));
+  HIPCHK(K->key.download(out, K->key.bytes, K->ctx->stream));
+  return 0;
+}
+extern "C" size_t dctfhe_ring_words(int logN, size_t count) {
+  if (logN < 0 || logN > 30) return 0;
+  return (((count + ((size_t)1 << logN) - 1) >> logN) << logN) + count;
+}
+
+// `count` device small ciphertexts (rows of n + 1 words) -> their ring-packed wire words in HOST memory, as many whole groups at a time
+// as 64 MB of transposed digits hold
+static int dev_ring_pack(dctfhe_pack_key* K, const uint64_t* d_small, size_t count, int n, uint16_t* out) {
+  hipStream_t st = K->ctx->stream;
+  const size_t N = (size_t)1 << K->logN, groups = (count + N - 1) / N, dig_per_group = (size_t)n * K->l * N;
+  const size_t G = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(groups, 4096), ((size_t)64 << 20) / (dig_per_group * 4)));
+  DevBuf d_dig, d_out;
+  HIPCHK(d_dig.alloc(G * dig_per_group * 4));
+  HIPCHK(d_out.alloc(G * 2 * N * sizeof(uint16_t)));
+  const size_t lds = N * 8 + N * 4;
+  for (size_t g0 = 0; g0 < groups; g0 += G) {
+    const size_t gn = std::min(G, groups - g0), cn = std::min(count - g0 * N, gn * N);
+    const uint64_t* src = d_small + g0 * N * (size_t)(n + 1);
+    hipLaunchKernelGGL(k_ring_digits, dim3(ew_grid(gn * (size_t)n * N)), dim3(256), 0, st, src, cn, n, K->logN, K->l, K->beta, d_dig.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_ring_pack, dim3((unsigned)(gn * 2 * (N / RING_TILE))), dim3(256), lds, st, d_dig.as<int32_t>(), src, cn, n, K->logN, K->l,
+                       K->key.as<uint64_t>(), d_out.as<uint16_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out + g0 * 2 * N, d_out.p, dctfhe_ring_words(K->logN, cn) * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+extern "C" int dctfhe_ring_pack(dctfhe_ctx* ctx, dctfhe_pack_key* K, const uint64_t* cts_small, size_t count, int n, uint16_t* out) {
+  if (!ctx || !K || (count && (!cts_small || !out))) return fail("dctfhe_ring_pack: null argument");
+  if (K->ctx != ctx) return fail("dctfhe_ring_pack: the packing key was imported on another context");
+  if (n < 1 || n > K->n_max) return fail("dctfhe_ring_pack: small ciphertexts of %d mask words, the packing key covers n_max = %d", n, K->n_max);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  DevBuf d_small;
+  HIPCHK(d_small.upload(cts_small, count * (size_t)(n + 1) * 8));
+  return dev_ring_pack(K, d_small.as<uint64_t>(), count, n, out);
+}
+// CLIENT: phases of ring-packed results under the first 2^logN bits of the big key
+extern "C" int dctfhe_decrypt_ring(dctfhe_ctx* ctx, dctfhe_client_key* C, int logN, const uint16_t* words, size_t count, uint64_t* phases) {
+  if (!ctx || !C || (count && (!words || !phases))) return fail("dctfhe_decrypt_ring: null argument");
+  if (logN < 5 || logN > 12) return fail("dctfhe_decrypt_ring: ring 2^%d outside 2^5 .. 2^12", logN);
+  if ((1 << logN) > C->p.D) return fail("dctfhe_decrypt_ring: the ring key is a prefix of the big key: N_p = %d > D = %d", 1 << logN, C->p.D);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t N = (size_t)1 << logN, groups = (count + N - 1) / N, bytes = dctfhe_ring_words(logN, count) * sizeof(uint16_t);
+  DevBuf d_w, d_ph;
+  HIPCHK(d_w.alloc(bytes));
+  HIPCHK(d_ph.alloc(count * 8));
+  HIPCHK(hipMemcpyAsync(d_w.p, words, bytes, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_ring_phase16, dim3((unsigned)(groups * ((N + 255) / 256))), dim3(256), N * 3, ctx->stream, C->S(), logN, d_w.as<uint16_t>(), count,
+                     d_ph.as<uint64_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(phases, d_ph.p, count * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 // the centred mod switch on host buffers (the scheduler applies it between every key switch and its bootstrap)
 extern "C" int dctfhe_modswitch_center(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, uint64_t* cts_small, size_t count) {
   if (!ctx || !K || (count && !cts_small)) return fail("dctfhe_modswitch_center: null argument");
@@ -2171,6 +2325,31 @@ extern "C" int dctfhe_session_download_packed(dctfhe_session* s, int tier, uint1
   const int t = s->circ->output_tensor;
   const size_t Ls = s->t_L[t];
   return dev_keyswitch_pack(s->keys, tier, s->d_tensor[t], Ls, (int)s->t_deff[t], s->tensor_words[t] / Ls, s->lut, rows);
+}
+// the outputs ring-packed: key-switched to `tier` chunk by chunk like the packed rows above, collected as small ciphertexts on the device,
+// then packed group by group with the client's packing key -- at download time, outside dctfhe_session_run and its timing
+extern "C" int dctfhe_session_download_ring(dctfhe_session* s, int tier, dctfhe_pack_key* K, uint16_t* out) {
+  if (!s || !K || !out) return fail("dctfhe_session_download_ring: null argument");
+  if (!s->keys) return fail("dctfhe_session_download_ring: a clear-mode session holds phases, not ciphertexts (dctfhe_session_download)");
+  if (K->ctx != s->ctx || s->keys->ctx != s->ctx) return fail("dctfhe_session_download_ring: session, evaluation keys and packing key must share one context");
+  if (tier < 0 || tier >= s->keys->p.n_tiers) return fail("dctfhe_session_download_ring: tier %d out of range (%d tiers)", tier, s->keys->p.n_tiers);
+  const int n = s->keys->p.tiers[tier].n;
+  if (n > K->n_max) return fail("dctfhe_session_download_ring: tier %d has n = %d, the packing key covers n_max = %d", tier, n, K->n_max);
+  if ((1 << K->logN) > s->keys->p.D) return fail("dctfhe_session_download_ring: the ring key is a prefix of the big key: N_p = %d > D = %d", 1 << K->logN, s->keys->p.D);
+  HIPCHK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  const int t = s->circ->output_tensor;
+  const size_t Ls = s->t_L[t], count = s->tensor_words[t] / Ls, n1 = (size_t)n + 1;
+  DevBuf d_small;
+  HIPCHK(d_small.alloc(count * n1 * 8));
+  for (size_t c0 = 0; c0 < count; c0 += s->lut.chunk) {
+    const size_t cn = std::min(s->lut.chunk, count - c0);
+    KsInput in;
+    in.rows = s->d_tensor[t] + c0 * Ls; in.L = Ls; in.deff = (int)s->t_deff[t];
+    CHK(dev_keyswitch(s->keys, tier, in, cn, s->lut, nullptr));
+    HIPCHK(hipMemcpyAsync(d_small.as<uint64_t>() + c0 * n1, s->lut.small(), cn * n1 * 8, hipMemcpyDeviceToDevice, st));
+  }
+  return dev_ring_pack(K, d_small.as<uint64_t>(), count, n, out);
 }
 
 // ---- margin audit (include/dctfhe.h): the slots are those of for_each_bootstrap, the kernel k_margin_probe

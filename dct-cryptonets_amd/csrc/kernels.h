@@ -651,6 +651,120 @@ __global__ void __launch_bounds__(256) k_margin_probe(const uint8_t* __restrict_
   }
 }
 
+// ---- ring-packed results: a batch's small ciphertexts in ONE GLWE ciphertext per N results ---------------
+// Ring key Z(X) = sum_c S[c] X^c, the first N bits of the big key (k = 1, the nested-prefix rule of every tier).  The packing key has one
+// GLWE row (A, B = A Z + E + s_j g_lev X^0) per small-key bit j and level lev, g_lev = 2^(64 - beta (lev + 1)); the server holds it
+// expanded, [n_max][l][2][N].  A group of m <= N small ciphertexts (a_i, b_i) packs to
+//     acc = (0, sum_i b_i X^i) - sum_i sum_j sum_lev dig_lev(a_ij) X^i PK[j][lev]            (negacyclic, mod 2^64)
+// whose phase has result i's phase at coefficient i: the message of a key row is a constant polynomial, so nothing else lands there.
+
+// the packing key's bodies [n_max * l][N]: row r = j l + lev is the p = k row of a k = 1 bootstrap key (bsk_row_zero: noise draw, mask
+// draw into LDS, B += A Z) with the gadget term on coefficient 0.  Mask word c of row r is rnd64(pub, stream, r N + c), its noise
+// gauss_torus(sec, stream + 1, r N + c): k_seeded_expand rebuilds the masks (stride N, N mask words, N body words).  One block per row.
+__global__ void k_ring_key_gen(const uint8_t* __restrict__ s_small, const uint8_t* __restrict__ S_big, int N, int l, int beta, double sigma,
+                               rng_key pub, rng_key sec, uint64_t stream, uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int j = (int)(blockIdx.x / l), lev = (int)(blockIdx.x % l);
+  uint64_t* B = out + (size_t)blockIdx.x * N;
+  bsk_row_zero(S_big, (uint64_t)blockIdx.x, 1, N, sigma, pub, sec, stream, reinterpret_cast<uint64_t*>(smem_raw), B, nullptr);
+  if (threadIdx.x == 0 && s_small[j]) B[0] += 1ULL << (64 - beta * (lev + 1));      // thread 0 owns coefficient 0 in the loops above
+}
+
+// digits of the mask words of `count` small ciphertexts (rows of n + 1 words; groups of N = 2^logN in order), TRANSPOSED:
+// dig[((g n + j) l + lev) N + i] is level lev of mask word j of result i of group g, so k_ring_pack reads a key row's digits contiguously.
+// The closest-representable signed decomposition of oracle/tfhe_ref.c ref_decompose: digits in [-B/2, B/2), the top carry dropped.
+// Slots of a partial last group beyond its results are left unwritten (k_ring_pack never reads them).
+__global__ void k_ring_digits(const uint64_t* __restrict__ small, size_t count, int n, int logN, int l, int beta, int32_t* __restrict__ dig) {
+  const size_t N = (size_t)1 << logN, groups = (count + N - 1) >> logN, total = groups * (size_t)n * N;
+  const int tot = l * beta;
+  const uint64_t B = 1ULL << beta, half = B >> 1, mask = B - 1;
+  for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t)gridDim.x * blockDim.x) {
+    const size_t i = x & (N - 1), gj = x >> logN, g = gj / n, j = gj % n, c = g * N + i;
+    if (c >= count) continue;
+    const uint64_t v = small[c * (size_t)(n + 1) + j];
+    uint64_t q = (v + (1ULL << (63 - tot))) >> (64 - tot), carry = 0;
+    for (int lev = l - 1; lev >= 0; lev--) {
+      const uint64_t d = (q & mask) + carry;
+      q >>= beta;
+      carry = d >= half;
+      dig[(gj * l + lev) * N + i] = (int32_t)(carry ? (int64_t)d - (int64_t)B : (int64_t)d);
+    }
+  }
+}
+
+// One workgroup per (group g, component: 0 mask / 1 body, tile of RING_TILE output coefficients).  Per key row r < n l the row's
+// polynomial (the window of it the tile reads, all N u64 in a full group) and the group's digits of that row (m i32) are staged in LDS; thread (c = tile coefficient, part = slot residue)
+// accumulates acc[c] -= d[i] (+-K[(c - i) mod N]) in u64 over its slots i = part, part + PARTS, ..., the sign flipped where c < i (X^N = -1).
+// A half-wave reads 32 consecutive key words (conflict-free 8-byte LDS reads) and one digit (a broadcast).  Epilogue: the parts are summed
+// through LDS, the body term b_c joins component 1, and the word goes out rounded as k_pack16 does: the N mask words of the group, then
+// its first m body words.  Groups before the last are full, so group g starts at u16 index 2 g N.
+constexpr int RING_TILE = 32, RING_PARTS = 256 / RING_TILE;
+__global__ void __launch_bounds__(256) k_ring_pack(const int32_t* __restrict__ dig, const uint64_t* __restrict__ small, size_t count, int n,
+                                                   int logN, int l, const uint64_t* __restrict__ key, uint16_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ uint64_t red[256];
+  const int N = 1 << logN, tiles = N / RING_TILE;
+  uint64_t* K = reinterpret_cast<uint64_t*>(smem_raw);
+  int32_t* d = reinterpret_cast<int32_t*>(K + N);
+  const int tile = (int)(blockIdx.x % tiles), comp = (int)((blockIdx.x / tiles) & 1);
+  const size_t g = blockIdx.x / (2 * (size_t)tiles);
+  const size_t left = count - g * N;
+  const int m = left < (size_t)N ? (int)left : N;
+  const int c = tile * RING_TILE + (threadIdx.x % RING_TILE), part = threadIdx.x / RING_TILE;
+  const int rows = n * l;
+  // the tile's coefficients meet key words (c - i) mod N, i < m: a window of m + RING_TILE - 1 words ending at the tile's last
+  // coefficient -- all a partial group has to stage (one ResNet-20 image: 95 of 2048 words per row)
+  const int span = m + RING_TILE - 1 < N ? m + RING_TILE - 1 : N;
+  const int first = span < N ? (tile * RING_TILE - (m - 1)) & (N - 1) : 0;
+  uint64_t acc = 0;
+  for (int r = 0; r < rows; r++) {
+    __syncthreads();
+    const uint64_t* krow = key + ((size_t)r * 2 + comp) * N;
+    const int32_t* drow = dig + (g * rows + r) * (size_t)N;
+    for (int x = threadIdx.x; x < span; x += 256) { const int idx = (first + x) & (N - 1); K[idx] = krow[idx]; }
+    for (int x = threadIdx.x; x < m; x += 256) d[x] = drow[x];
+    __syncthreads();
+#pragma unroll 4
+    for (int i = part; i < m; i += RING_PARTS) {
+      const int64_t dd = d[i];
+      acc += (uint64_t)(c >= i ? -dd : dd) * K[(c - i) & (N - 1)];
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  if (part != 0) return;
+  for (int p = 1; p < RING_PARTS; p++) acc += red[p * RING_TILE + c % RING_TILE];
+  uint16_t* grp = out + g * 2 * (size_t)N;
+  if (comp == 0) grp[c] = (uint16_t)round16(acc);
+  else if (c < m) grp[N + c] = (uint16_t)round16(acc + small[(g * N + c) * (size_t)(n + 1) + n]);
+}
+
+// client: phases of ring-packed results on the 16-bit torus, phase16_i = (B16[i] - (A16 Z)[i]) mod 2^16 (negacyclic), returned as
+// phase16 << 48.  One workgroup per (group, 256 slots); the group's mask and the ring key's bits sit in LDS, each thread walks the key
+// bits (a broadcast read) for its slot with 32-bit partial sums, whose low 16 bits stay exact as in k_phase16.
+__global__ void __launch_bounds__(256) k_ring_phase16(const uint8_t* __restrict__ S, int logN, const uint16_t* __restrict__ words, size_t count,
+                                                      uint64_t* __restrict__ phases) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int N = 1 << logN, tiles = (N + 255) / 256;
+  uint16_t* A = reinterpret_cast<uint16_t*>(smem_raw);
+  uint8_t* Z = reinterpret_cast<uint8_t*>(A + N);
+  const size_t g = blockIdx.x / tiles;
+  const size_t left = count - g * N;
+  const int m = left < (size_t)N ? (int)left : N;
+  const uint16_t* grp = words + g * 2 * (size_t)N;
+  for (int x = threadIdx.x; x < N; x += 256) { A[x] = grp[x]; Z[x] = S[x]; }
+  __syncthreads();
+  const int i = (int)(blockIdx.x % tiles) * 256 + threadIdx.x;
+  if (i >= m) return;
+  uint32_t part = 0;
+  for (int c = 0; c < N; c++) {
+    if (!Z[c]) continue;  // uniform branch
+    const uint32_t a = A[(i - c) & (N - 1)];
+    part += c <= i ? a : 0u - a;
+  }
+  phases[g * N + i] = (uint64_t)(((uint32_t)grp[N + i] - part) & 0xFFFFu) << 48;
+}
+
 // ------------------------------------------------------------------------------------------ K4-K6 bootstrap
 struct pbs_launch {
   const uint64_t* cts_small;  // count x (n+1)

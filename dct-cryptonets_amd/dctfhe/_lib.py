@@ -61,6 +61,8 @@ EXPORTS = [
     "dctfhe_session_download_packed", "dctfhe_keyswitch_pack", "dctfhe_decrypt_packed",
     "dctfhe_margin_probe_host", "dctfhe_margin_probe", "dctfhe_session_set_audit", "dctfhe_session_audit",
     "dctfhe_device_bytes_live",
+    "dctfhe_pack_key_export", "dctfhe_pack_key_import", "dctfhe_pack_key_destroy", "dctfhe_pack_key_info", "dctfhe_pack_key_export_rows",
+    "dctfhe_ring_words", "dctfhe_ring_pack", "dctfhe_session_download_ring", "dctfhe_decrypt_ring",
 ]
 
 _lib = None
@@ -148,6 +150,17 @@ def load():
     L.dctfhe_session_audit.argtypes = [vp, C.POINTER(MarginStats), i32, C.POINTER(C.c_int)]
     L.dctfhe_device_bytes_live.argtypes = []
     L.dctfhe_device_bytes_live.restype = sz
+    pi, pd = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    L.dctfhe_pack_key_export.argtypes = [vp, i32, i32, i32, C.c_double, vp, sz, C.POINTER(sz)]
+    L.dctfhe_pack_key_import.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    L.dctfhe_pack_key_destroy.argtypes = [vp]
+    L.dctfhe_pack_key_info.argtypes = [vp, pi, pi, pi, pi, pd]
+    L.dctfhe_pack_key_export_rows.argtypes = [vp, vp]
+    L.dctfhe_ring_words.argtypes = [i32, sz]
+    L.dctfhe_ring_words.restype = sz
+    L.dctfhe_ring_pack.argtypes = [vp, vp, vp, sz, i32, vp]
+    L.dctfhe_session_download_ring.argtypes = [vp, i32, vp, vp]
+    L.dctfhe_decrypt_ring.argtypes = [vp, vp, i32, vp, sz, vp]
     _lib = L
     return L
 

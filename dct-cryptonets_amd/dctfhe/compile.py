@@ -381,9 +381,49 @@ class OutputCompaction:
     pfail: float                   # per result, against the decode margin 2^-(out_bits + 3)
 
 
-def output_compaction(circ):
+@dataclass
+class RingCompaction:
+    """how a circuit's results travel ring-packed (include/dctfhe.h dctfhe_session_download_ring): key-switched to `tier`, then up to
+    spec.N of them in one GLWE ciphertext of 16-bit words"""
+    tier: int
+    name: str
+    n: int
+    spec: object                   # params.PackSpec
+    var: float                     # what the key switch and the ring pack (full group) add (torus^2)
+    pfail: float                   # per result, against the decode margin 2^-(out_bits + 3)
+    results_per_image: int
+
+    def bytes_per_batch(self, batch=1):
+        return 2 * self.spec.words(batch * self.results_per_image)
+
+
+def _ring_compaction(circ, spec):
+    ps, out = circ.param_set, circ.tensors[circ.output_tensor]
+    spec = spec if spec is not None else P.default_pack_spec(ps)
+    if spec.N > ps.D:
+        raise ValueError(f"ring packing: the ring key is a prefix of the big key, N_p = {spec.N} > D = {ps.D}")
+    deff = out.deff or ps.D
+    var, ti = min((P.var_keyswitch(deff, t) + P.var_ring_pack(t.n, spec), i) for i, t in enumerate(ps.tiers) if t.ksk_share < 0)
+    t = ps.tiers[ti]
+    margin = 2.0 ** -(circ.out_bits + 3)
+    pfail = P.p_fail(margin, out.var + var)
+    budget = getattr(ps, "p_budget", 1e-12)
+    if pfail > budget:
+        raise ValueError(f"ring-packed results leave the budget: best tier {t.name} (n = {t.n}) adds sigma 2^{0.5 * math.log2(var):.1f} (ring pack alone "
+                         f"2^{0.5 * math.log2(P.var_ring_pack(t.n, spec)):.1f}) to an output of sigma 2^{0.5 * math.log2(max(out.var, 2.0 ** -128)):.1f} at "
+                         f"effective dimension {deff}; margin 2^-{circ.out_bits + 3}, p_fail {pfail:.1e} per result > {budget:.1e}")
+    return RingCompaction(tier=ti, name=t.name, n=t.n, spec=spec, var=var, pfail=pfail, results_per_image=circ.n_out())
+
+
+def output_compaction(circ, form="rows", spec=None):
     """The tier whose key-switch key packs this circuit's results: among the tiers that own one (ksk_share < 0), the least
-    var_keyswitch(deff_out, t) + var_round16(t.n).  Raises ValueError when a packed result would leave the catalogue's failure budget."""
+    var_keyswitch(deff_out, t) + var_round16(t.n).  Raises ValueError when a packed result would leave the catalogue's failure budget.
+    form="ring": the same choice with var_ring_pack(t.n, spec) in place of the row rounding (spec: a params.PackSpec, default
+    params.default_pack_spec) -> RingCompaction."""
+    if form == "ring":
+        return _ring_compaction(circ, spec)
+    if form != "rows":
+        raise ValueError(f"output compaction form {form!r} (rows or ring)")
     ps, out = circ.param_set, circ.tensors[circ.output_tensor]
     deff = out.deff or ps.D
     var, ti = min((P.var_keyswitch(deff, t) + P.var_round16(t.n), i) for i, t in enumerate(ps.tiers) if t.ksk_share < 0)

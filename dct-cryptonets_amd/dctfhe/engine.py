@@ -249,6 +249,86 @@ class PackedCiphertexts:
         return cls(n, np.frombuffer(blob, "<u2", count * (n + 1), H).astype(np.uint16))
 
 
+class PackedRing:
+    """Result ciphertexts in RING-PACKED form (include/dctfhe.h dctfhe_session_download_ring): groups of up to N_p = 2^logN results, each
+    group one GLWE ciphertext of 16-bit words -- its N_p mask words, then one body word per result.  words: flat uint16, groups
+    contiguous.  Wire form: to_bytes / from_bytes (little-endian)."""
+
+    MAGIC, VERSION = b"DRCT", 1
+    _HDR = struct.Struct("<4sIiQ")            # magic, version, logN, count; then groups * N_p + count u16
+
+    def __init__(self, logN, count, words):
+        logN, count = int(logN), int(count)
+        if not 5 <= logN <= 12:
+            raise ValueError(f"ring-packed ciphertexts need 5 <= logN <= 12 (got {logN})")
+        if count < 0:
+            raise ValueError(f"ring-packed ciphertexts: count {count}")
+        words = np.ascontiguousarray(words, np.uint16).reshape(-1)
+        if words.size != self.n_words(logN, count):
+            raise ValueError(f"{words.size} words are not {count} results in rings of {1 << logN} ({self.n_words(logN, count)} words)")
+        self.logN, self.count, self.words = logN, count, words
+
+    @staticmethod
+    def n_words(logN, count):
+        N = 1 << logN
+        return -(-count // N) * N + count
+
+    def __len__(self):
+        return self.count
+
+    @property
+    def nbytes(self):
+        return self._HDR.size + self.words.nbytes
+
+    def to_bytes(self):
+        return self._HDR.pack(self.MAGIC, self.VERSION, self.logN, self.count) + self.words.astype("<u2", copy=False).tobytes()
+
+    @classmethod
+    def from_bytes(cls, blob):
+        blob = bytes(blob)
+        H = cls._HDR.size
+        if len(blob) < H:
+            raise ValueError("ring-packed-ciphertext blob too short")
+        magic, version, logN, count = cls._HDR.unpack_from(blob)
+        if magic != cls.MAGIC or version != cls.VERSION:
+            raise ValueError("not a ring-packed-ciphertext blob (magic / version)")
+        if not 5 <= logN <= 12 or len(blob) != H + 2 * cls.n_words(logN, count):
+            raise ValueError(f"ring-packed-ciphertext blob of {len(blob)} bytes, its header says logN = {logN}, {count} results")
+        return cls(logN, count, np.frombuffer(blob, "<u2", cls.n_words(logN, count), H).astype(np.uint16))
+
+
+class PackKey:
+    """Server side of ring packing (dctfhe_pack_key): the client's packing key, expanded on the GPU from its seeded blob."""
+
+    def __init__(self, ctx, blob):
+        self.ctx, self.L = ctx, ctx.L
+        blob = _as_u8(blob)
+        self.h = C.c_void_p()
+        check(self.L.dctfhe_pack_key_import(ctx.h, ptr(blob), blob.size, C.byref(self.h)))
+        a, b, c, d, e = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        check(self.L.dctfhe_pack_key_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
+        self.logN, self.l, self.beta, self.n_max, self.sigma = a.value, b.value, c.value, d.value, e.value
+
+    def export_rows(self):
+        """test view: the expanded key [n_max, l, 2, N_p] (mask, body)"""
+        out = np.empty((self.n_max, self.l, 2, 1 << self.logN), np.uint64)
+        check(self.L.dctfhe_pack_key_export_rows(self.h, ptr(out)))
+        return out
+
+    def ring_pack(self, cts_small):
+        """small ciphertexts [count, n + 1] -> PackedRing (dctfhe_ring_pack)"""
+        cts = np.ascontiguousarray(cts_small, np.uint64)
+        count, n = cts.shape[0], cts.shape[1] - 1
+        out = np.empty(PackedRing.n_words(self.logN, count), np.uint16)
+        check(self.L.dctfhe_ring_pack(self.ctx.h, self.h, ptr(cts), count, n, ptr(out)))
+        return PackedRing(self.logN, count, out)
+
+    def close(self):
+        if self.h:
+            self.L.dctfhe_pack_key_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class ClientKey:
     """Secret side (include/dctfhe.h dctfhe_client_key): encrypts, decrypts, generates evaluation keys."""
 
@@ -334,6 +414,21 @@ class ClientKey:
         """PackedCiphertexts -> phases (phase16 << 48: QuantizedModule.decode_output reads them like decrypt's)"""
         out = np.empty(len(packed), np.uint64)
         check(self.L.dctfhe_decrypt_packed(self.ctx.h, self.h, packed.n, ptr(packed.rows), len(packed), ptr(out)))
+        return out
+
+    def export_pack_key(self, spec):
+        """the packing key for ring-packed results as its seeded blob (dctfhe_pack_key_export); spec: params.PackSpec"""
+        n = C.c_size_t()
+        args = (self.h, int(spec.logN), int(spec.l), int(spec.beta), float(spec.sigma))
+        check(self.L.dctfhe_pack_key_export(*args, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        check(self.L.dctfhe_pack_key_export(*args, ptr(out), out.size, C.byref(n)))
+        return out
+
+    def decrypt_ring(self, ring):
+        """PackedRing -> phases (phase16 << 48), one per result"""
+        out = np.empty(len(ring), np.uint64)
+        check(self.L.dctfhe_decrypt_ring(self.ctx.h, self.h, ring.logN, ptr(ring.words), len(ring), ptr(out)))
         return out
 
     def margin_probe(self, tier, cts_small, table_bits, want_err=True, want_stats=True):
@@ -480,7 +575,7 @@ class Keys:
 
     def __getattr__(self, name):
         if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter",
-                    "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed", "margin_probe"):
+                    "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed", "margin_probe", "export_pack_key", "decrypt_ring"):
             return getattr(self.client, name)
         if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
@@ -599,6 +694,14 @@ class Session:
         out = np.empty((self.batch * self.circuit.n_out, n + 1), np.uint16)
         check(self.L.dctfhe_session_download_packed(self.h, int(tier), ptr(out)))
         return PackedCiphertexts(n, out)
+
+    def download_ring(self, tier, pack_key):
+        """the outputs key-switched to `tier` and ring-packed with the client's packing key (dctfhe_session_download_ring): a PackedRing
+        of batch x n_out results; encrypted sessions only"""
+        count = self.batch * self.circuit.n_out
+        out = np.empty(PackedRing.n_words(pack_key.logN, count), np.uint16)
+        check(self.L.dctfhe_session_download_ring(self.h, int(tier), pack_key.h, ptr(out)))
+        return PackedRing(pack_key.logN, count, out)
 
     def close(self):
         if self.h:

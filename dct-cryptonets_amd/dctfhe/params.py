@@ -125,6 +125,55 @@ def var_round16(n):
     return (n / 2.0 + 1.0) * 2.0 ** -32 / 12.0
 
 
+@dataclass
+class PackSpec:
+    """ring packing of result ciphertexts (include/dctfhe.h dctfhe_pack_key_export): ring N_p = 2^logN whose key is the first N_p bits of the
+    big key, l gadget levels of beta bits, key-row noise sigma.  Stands alone: no ParamSet field, nothing of it is serialised into a circuit."""
+    logN: int = 11
+    l: int = 1
+    beta: int = 16
+    sigma: float = None            # None: sigma_min(N_p); 0.0 is a noise-free key (tests only)
+
+    def __post_init__(self):
+        if self.sigma is None:
+            self.sigma = sigma_min(1 << self.logN)
+
+    @property
+    def N(self):
+        return 1 << self.logN
+
+    def groups(self, count):
+        return -(-int(count) // self.N)
+
+    def words(self, count):
+        """16-bit words of `count` ring-packed results: per group N mask words, then one body word per result"""
+        return self.groups(count) * self.N + int(count)
+
+
+def default_pack_spec(ps=None):
+    """N_p = 2048, one level of 16 bits: with results rounded to 16 bits anyway a second level buys nothing, and the key stays 13 MB.
+    ps given: raises ValueError where its big key is shorter than the ring (the ring key is a prefix of it)"""
+    spec = PackSpec(logN=11, l=1, beta=16)
+    if ps is not None and spec.N > ps.D:
+        raise ValueError(f"ring packing: the ring key is a prefix of the big key, N_p = {spec.N} > D = {ps.D}; pass a PackSpec with a smaller ring")
+    return spec
+
+
+def test_pack_spec():
+    """for test_params() (D = 1024): a ring of 256, noise far below every margin (NOT secure, like the catalogue it goes with)"""
+    return PackSpec(logN=8, l=1, beta=16, sigma=2.0 ** -48)
+
+
+def var_ring_pack(n, spec, m=None):
+    """what ring packing adds to a small ciphertext of n mask words in a group of m results (default: a full ring): the key rows' noise
+    through m n l digits, the decomposition's rounding of the n mask words against a binary key, and the 16-bit rounding of the N_p mask
+    coefficients and the body against the ring key (half its bits set)"""
+    m = spec.N if m is None else m
+    B = 2.0 ** spec.beta
+    return (m * n * spec.l * ((B * B + 2) / 12.0) * spec.sigma ** 2 + (n / 2.0) * 2.0 ** (-2 * spec.beta * spec.l) / 12.0
+            + (spec.N / 2.0 + 1.0) * 2.0 ** -32 / 12.0)
+
+
 def p_fail(margin, var):
     """two-sided Gaussian tail beyond `margin`"""
     if var <= 0:

@@ -5,7 +5,8 @@
     compile_torch_model(...)         homomorphic_eval.py:287    compile_torch_model (same circuit builder)
     Configuration(...)               homomorphic_eval.py:266    Configuration (progress flags kept, inert; compress_input_ciphertexts,
                                                                 compress_evaluation_keys: seeded inputs / compressed evaluation keys;
-                                                                compress_output_ciphertexts: packed 16-bit results)
+                                                                compress_output_ciphertexts: packed 16-bit results, as rows
+                                                                or, with "ring", up to N_p of them in one GLWE ciphertext)
     q.fhe_circuit.graph.maximum_integer_bit_width()    :301     FHECircuit.graph.maximum_integer_bit_width()
     q.fhe_circuit.mlir                                 :311     FHECircuit.mlir  (text dump of the compiled circuit)
     q.fhe_circuit.keygen()                             :315     FHECircuit.keygen()  (keys generated on the GPU)
@@ -22,14 +23,14 @@ import numpy as np
 
 from . import compile as cc
 from . import params as P
-from .engine import Circuit, Context, Keys, PackedCiphertexts, SeededCiphertexts, Session
+from .engine import Circuit, Context, Keys, PackedCiphertexts, PackedRing, PackKey, SeededCiphertexts, Session
 
 
 class Configuration:
     """Stand-in for concrete.fhe.Configuration (reference homomorphic_eval.py:266-273)."""
 
     def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
-                 compress_evaluation_keys=False, compress_output_ciphertexts=False, **kwargs):
+                 compress_evaluation_keys=False, compress_output_ciphertexts=False, result_packing_spec=None, **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
         # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
         # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
@@ -37,8 +38,21 @@ class Configuration:
         self.compress_evaluation_keys = bool(compress_evaluation_keys)
         # dctfhe addition (like tier_policy): results come back key-switched to a small key and rounded to 16 bits per word
         # (include/dctfhe.h dctfhe_session_download_packed; the tier is dctfhe.compile.output_compaction's).  Off by default.
-        self.compress_output_ciphertexts = bool(compress_output_ciphertexts)
+        # "ring": up to N_p results in one GLWE ciphertext instead (dctfhe_session_download_ring), with the packing key the client exports
+        # (FHECircuit.export_result_packing_key) and the server loads; result_packing_spec: its params.PackSpec (None: the default one).
+        # True (or "rows") keeps meaning the rows form; "none" is False; any other string raises ValueError (it used to count as True).
+        self.compress_output_ciphertexts = _output_form(compress_output_ciphertexts)
+        self.result_packing_spec = result_packing_spec
         self.extra = kwargs
+
+
+def _output_form(v):
+    """a compress_output_ciphertexts / packed value -> False, True (16-bit rows) or the string ring"""
+    if isinstance(v, str):
+        if v not in ("none", "rows", "ring"):
+            raise ValueError(f"compress_output_ciphertexts {v!r} (False, True / 'rows', or 'ring')")
+        return {"none": False, "rows": True, "ring": "ring"}[v]
+    return bool(v)
 
 
 class MarginReport:
@@ -118,6 +132,12 @@ class FHECircuit:
     def evaluate_encrypted(self, cts, batch, dim=None, packed=None):
         return self._o.evaluate_encrypted(cts, batch, dim, packed)
 
+    def export_result_packing_key(self):
+        return self._o.export_result_packing_key()
+
+    def load_result_packing_key(self, blob):
+        return self._o.load_result_packing_key(blob)
+
     @property
     def statistics(self):
         """Concrete's `fhe_circuit.statistics` is a property; here the engine's dctfhe_stats of the compiled circuit"""
@@ -139,6 +159,8 @@ class QuantizedModule:
         self.last_io = None
         self.sim_seed = 977
         self._compaction = None
+        self._ring_compaction = None
+        self._pack_key = None
 
     # -- lazy device objects -------------------------------------------------------------
     def _context(self):
@@ -166,12 +188,47 @@ class QuantizedModule:
             self._sessions[key] = Session(ctx, self._circuit, self._keys if mode == "execute" else None, batch)
         return self._sessions[key]
 
-    def output_compaction(self):
-        """the tier packed results are key-switched to (dctfhe.compile.output_compaction); raises ValueError where packing would leave
-        the catalogue's failure budget"""
+    def output_compaction(self, form="rows"):
+        """the tier packed results are key-switched to (dctfhe.compile.output_compaction; form "rows" or "ring"); raises ValueError where
+        packing would leave the catalogue's failure budget"""
+        if form == "ring":
+            if self._ring_compaction is None:
+                self._ring_compaction = cc.output_compaction(self.compiled, form="ring", spec=self.configuration.result_packing_spec)
+            return self._ring_compaction
         if self._compaction is None:
             self._compaction = cc.output_compaction(self.compiled)
         return self._compaction
+
+    def export_result_packing_key(self):
+        """client side: the packing key of ring-packed results as a blob to ship to the server once (no secret inside; 13 MB at the default
+        spec).  The spec is the one output_compaction("ring") priced"""
+        if self._keys is None:
+            self._keygen(None)
+        if not isinstance(self._keys, Keys):
+            raise RuntimeError("the result packing key is made by the client (its secret key); this module holds evaluation keys only")
+        return self._keys.client.export_pack_key(self.output_compaction("ring").spec)
+
+    def load_result_packing_key(self, blob):
+        """server side (or a single process, with its own export): the packing key `compress_output_ciphertexts="ring"` packs with"""
+        ctx = self._context()
+        if self._pack_key is not None:
+            self._pack_key.close()
+        self._pack_key = PackKey(ctx, blob)
+
+    def _ring_plan(self):
+        """(tier, packing key) of a ring-packed download; refuses before anything runs"""
+        oc = self.output_compaction("ring")
+        pk = self._pack_key
+        if pk is None:
+            raise RuntimeError('compress_output_ciphertexts="ring" needs the client\'s result packing key: '
+                               "fhe_circuit.load_result_packing_key(fhe_circuit.export_result_packing_key())")
+        if (pk.logN, pk.l, pk.beta) != (oc.spec.logN, oc.spec.l, oc.spec.beta) or pk.n_max < oc.n:
+            raise RuntimeError(f"the loaded result packing key (logN {pk.logN}, {pk.l} x {pk.beta} bits, n_max {pk.n_max}) is not the one this "
+                               f"configuration prices (logN {oc.spec.logN}, {oc.spec.l} x {oc.spec.beta} bits, n {oc.n})")
+        if pk.sigma > oc.spec.sigma:
+            raise RuntimeError(f"the loaded result packing key is noisier (sigma {pk.sigma:.3g}) than the spec this configuration priced "
+                               f"({oc.spec.sigma:.3g}): its p_fail is not covered")
+        return oc.tier, pk
 
     # -- client / server split (reference homomorphic_eval.py:313-317 keeps both halves in one process) ------------
     def export_evaluation_keys(self, compressed=None):
@@ -202,18 +259,23 @@ class QuantizedModule:
         """server side: input ciphertexts [batch * n_in, D+1] -> output ciphertexts [batch * n_out, D+1]; dim: the compact wire
         form instead -- input rows of dim mask words + body, output rows of Session.dims()[1] mask words + body.  cts may also be
         SeededCiphertexts (or their to_bytes() form): the masks are regenerated on the GPU; dim then only selects the output form.
-        packed (default: Configuration.compress_output_ciphertexts): the outputs as PackedCiphertexts instead, whatever dim says"""
+        packed (default: Configuration.compress_output_ciphertexts): True / "rows": the outputs as PackedCiphertexts instead, "ring": as
+        a PackedRing (needs load_result_packing_key), whatever dim says"""
         if isinstance(cts, (bytes, bytearray, memoryview)):
             cts = SeededCiphertexts.from_bytes(cts)
-        if packed is None:
-            packed = self.configuration.compress_output_ciphertexts
-        tier = self.output_compaction().tier if packed else None
+        packed = self.configuration.compress_output_ciphertexts if packed is None else _output_form(packed)
+        if packed == "ring":
+            tier, pack_key = self._ring_plan()
+        else:
+            tier = self.output_compaction().tier if packed else None
         sess = self._session("execute", batch)
         if isinstance(cts, SeededCiphertexts):
             sess.upload_seeded(cts)
         else:
             sess.upload(cts, dim)
         sess.run()
+        if packed == "ring":
+            return sess.download_ring(tier, pack_key)
         if packed:
             return sess.download_packed(tier)
         if dim is None:
@@ -239,13 +301,15 @@ class QuantizedModule:
         return v
 
     def decrypt_result(self, x):
-        """client side: what evaluate_encrypted returned -> decoded integers [B, F].  x: PackedCiphertexts or their to_bytes() form, or
-        rows [B * F, dim + 1] of uint64 (full width or the compact wire form)"""
+        """client side: what evaluate_encrypted returned -> decoded integers [B, F].  x: PackedCiphertexts or a PackedRing, or the
+        to_bytes() form of either, or rows [B * F, dim + 1] of uint64 (full width or the compact wire form)"""
         if self._keys is None or not hasattr(self._keys, "decrypt"):
             raise RuntimeError("decrypting needs the client key (fhe_circuit.keygen); this module holds evaluation keys only")
         if isinstance(x, (bytes, bytearray, memoryview)):
-            x = PackedCiphertexts.from_bytes(x)
-        if isinstance(x, PackedCiphertexts):
+            x = PackedRing.from_bytes(x) if bytes(x[:4]) == PackedRing.MAGIC else PackedCiphertexts.from_bytes(x)
+        if isinstance(x, PackedRing):
+            ph = self._keys.decrypt_ring(x)
+        elif isinstance(x, PackedCiphertexts):
             ph = self._keys.decrypt_packed(x)
         else:
             x = np.asarray(x)
@@ -288,7 +352,11 @@ class QuantizedModule:
             seeded = self.configuration.compress_input_ciphertexts
             # Configuration(compress_output_ciphertexts=True): results come back packed (refused here, before anything is encrypted,
             # where the compiler's price for it leaves the budget)
-            pack_tier = self.output_compaction().tier if self.configuration.compress_output_ciphertexts else None
+            form = self.configuration.compress_output_ciphertexts
+            if form == "ring":
+                pack_tier, pack_key = self._ring_plan()
+            else:
+                pack_tier = self.output_compaction().tier if form else None
             t1 = time.time()
             cts = self._keys.encrypt_seeded(phases.reshape(-1)) if seeded else self._keys.encrypt(phases.reshape(-1), in_dim)
             t2 = time.time()
@@ -303,6 +371,11 @@ class QuantizedModule:
                 out = sess.download(out_dim).reshape(-1, out_dim + 1)
                 t5 = time.time()
                 out_ph = self._keys.decrypt(out, out_dim).reshape(B, -1)
+            elif form == "ring":
+                pr = sess.download_ring(pack_tier, pack_key)
+                out = pr.words
+                t5 = time.time()
+                out_ph = self._keys.decrypt_ring(pr).reshape(B, -1)
             else:
                 pk = sess.download_packed(pack_tier)
                 out = pk.rows
@@ -352,6 +425,9 @@ class QuantizedModule:
         if self._keys is not None:
             self._keys.close()
             self._keys = None
+        if self._pack_key is not None:
+            self._pack_key.close()
+            self._pack_key = None
         if self._circuit is not None:
             self._circuit.close()
             self._circuit = None

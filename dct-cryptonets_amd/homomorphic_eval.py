@@ -58,6 +58,9 @@ def parse_args():
                    help="exact = the reference's call (int rounding_threshold_bits); approximate = its README's suggested speed-up")
     e.add_argument("--tier_policy", default="exact", choices=["exact", "p_error"],
                    help="exact: outputs equal the integer circuit whatever --p_error; p_error: cheaper tiers failing with probability <= --p_error per look-up")
+    e.add_argument("--compress_outputs", default="none", choices=["none", "rows", "ring"],
+                   help="results on the way back: full rows; rows: key-switched 16-bit rows; ring: up to 2048 results in one GLWE "
+                        "ciphertext (the client's packing key is made after keygen and loaded)")
     return parser.parse_args()
 
 
@@ -120,7 +123,8 @@ def main():
 
     calib_data, _ = make(params.calib_batch_size, params.seed + 100)
     print("\nCompiling FHE Model (this can take up to 10 minutes for larger networks)...")
-    configuration = Configuration(show_progress=False, progress_tag=True, progress_title="Evaluation: ")
+    configuration = Configuration(show_progress=False, progress_tag=True, progress_title="Evaluation: ",
+                                  compress_output_ciphertexts=params.compress_outputs)
     t = time.time()
     compile_fn = compile_brevitas_qat_model if quantization_type == "QAT" else compile_torch_model
     rtb = params.rounding_threshold_bits if params.rounding_method == "exact" else {"n_bits": params.rounding_threshold_bits, "method": "approximate"}
@@ -135,6 +139,11 @@ def main():
     t = time.time()
     q_module.fhe_circuit.keygen()
     print(f"Keygen time: {time.time() - t:.2f}s")
+    if params.compress_outputs == "ring" and params.fhe_mode == "execute":
+        t = time.time()
+        blob = q_module.fhe_circuit.export_result_packing_key()
+        q_module.fhe_circuit.load_result_packing_key(blob)
+        print(f"Result packing key: {blob.nbytes} bytes, {time.time() - t:.2f}s")
 
     x, y = make(params.test_subset, params.seed)
     bs = params.test_batch_size

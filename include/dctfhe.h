@@ -302,6 +302,51 @@ int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, con
  * so that whatever decodes dctfhe_decrypt's phases decodes these. */
 int dctfhe_decrypt_packed(dctfhe_ctx* ctx, dctfhe_client_key* client, int n, const uint16_t* rows, size_t count, uint64_t* phases);
 
+/* RING-PACKED result ciphertexts: up to N_p = 2^logN results travel in ONE GLWE ciphertext, 2 (N_p + m) bytes
+ * for m results instead of 2 m (n + 1).  Opt-in; it needs key material of its own, the PACKING KEY, which the client makes once.
+ *
+ * Spec: ring size N_p = 2^logN (5 <= logN <= 12, N_p <= D), l_p gadget levels of beta_p bits (l_p >= 1, 1 <= beta_p <= 32: digits are
+ * kept in 32 bits; l_p beta_p <= 63), noise std sigma_p (fraction of the torus).  dctfhe.params default_pack_spec: logN 11, one level of
+ * 16 bits -- the 16-bit rounding below already costs more than the second level would save.
+ * Ring key: Z(X) = sum_{c < N_p} S[c] X^c, the first N_p bits of the big key as ONE polynomial (k = 1; the nested-prefix rule of every
+ * tier's GLWE key).
+ * Packing key: for every small-key bit j < n_max and level lev < l_p one GLWE row (A, B), B = A Z + E + s_j 2^(64 - beta_p (lev + 1)) X^0,
+ * negacyclic, mod 2^64.  With row r = j l_p + lev and the spec's generator stream
+ *     R = 1 << 63 | ((bits(sigma_p) * 0x9E3779B97F4A7C15 mod 2^64) ^ (logN << 24 | l_p << 16 | beta_p << 8)) & 0x7FFFFFFFFFFFFFFE
+ * (bits: the IEEE-754 double as a u64; nothing else draws from R or R + 1: every other stream id of the key-material generator keys is below 2^17, and encryptions use the per-handle keys)
+ * mask word A[c] is generator word (pub, R, r N_p + c) of the client's PUBLIC generator key and E[c] the Gaussian draw
+ * (sec, R + 1, r N_p + c) of the secret one, as for the bootstrap keys.  sigma_p is part of R because the Gaussian draw scales with it:
+ * exports of one client key at two sigma_p never share a draw.
+ * Blob (seeded form only, little-endian): u32 magic 'DRPK', u32 version 1, i32 logN, l_p, beta_p, n_max, f64 sigma_p, u64 total bytes;
+ * the 32-byte public generator key; n_max l_p N_p body words B (u64).  Import regenerates every A on the GPU.  Small keys are prefixes of
+ * one small key, so one packing key serves every tier: tier t uses its first n_t l_p rows.  13 MB at the default spec and n_max = 800.
+ *
+ * Pack (server): results are key-switched to the small key of `tier` exactly as dctfhe_keyswitch_prefix(tier, shift 0, deff) does, taken in
+ * order in groups of N_p (result i of a group in slot i; the last group may hold m < N_p), and per group
+ *     acc = (0, sum_i b_i X^i) - sum_i sum_{j<n} sum_lev dig_lev(a_ij) X^i PK[j][lev]
+ * with dig the closest-representable signed decomposition (digits in [-B/2, B/2), the top carry dropped) and X^i the negacyclic shift.
+ * A key row's message is a constant polynomial, so coefficient i of acc's phase is result i's phase and nothing else.
+ * Wire form: per group the N_p mask words, then the first m body words, each (uint16_t)((w + 2^47) >> 48) as in the packed rows above;
+ * groups contiguous, little-endian: dctfhe_ring_words(logN, count) = groups N_p + count words.
+ * Decrypt (client): phase16_i = (B16[i] - (A16 Z)[i]) mod 2^16, negacyclic, returned as (uint64_t)phase16 << 48.
+ *
+ * pack_key_export: CLIENT; buf == NULL: size query.  Refused: N_p > D, l_p beta_p > 63, a spec outside the ranges above.
+ * pack_key_import: SERVER; refused: a blob of the wrong magic, version or length.  pack_key_export_rows: test view of the expanded key,
+ * [n_max][l_p][2][N_p] (A then B).  ring_pack: the primitive on host small ciphertexts count x (n + 1), 1 <= n <= n_max of the key.
+ * session_download_ring: the session's outputs in that form; key-switched in chunks like dctfhe_session_download_packed, packed at download
+ * time -- dctfhe_session_run and dctfhe_timing do not see it.  Refused: a clear-mode session, a tier whose n exceeds the key's n_max, a packing key imported on another context. */
+typedef struct dctfhe_pack_key dctfhe_pack_key;       /* SERVER: the expanded packing key (public material) */
+int dctfhe_pack_key_export(dctfhe_client_key* client, int logN, int l_p, int beta_p, double sigma_p, void* buf, size_t capacity, size_t* size);
+int dctfhe_pack_key_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_pack_key** out);
+int dctfhe_pack_key_destroy(dctfhe_pack_key* key);
+int dctfhe_pack_key_info(dctfhe_pack_key* key, int* logN, int* l_p, int* beta_p, int* n_max, double* sigma_p /* each may be NULL */);
+int dctfhe_pack_key_export_rows(dctfhe_pack_key* key, uint64_t* out /* n_max x l_p x 2 x N_p */);
+size_t dctfhe_ring_words(int logN, size_t count);
+int dctfhe_ring_pack(dctfhe_ctx* ctx, dctfhe_pack_key* key, const uint64_t* cts_small /* count x (n+1) */, size_t count, int n,
+                     uint16_t* out /* dctfhe_ring_words */);
+int dctfhe_session_download_ring(dctfhe_session* s, int tier, dctfhe_pack_key* key, uint16_t* out /* dctfhe_ring_words of batch x n_out */);
+int dctfhe_decrypt_ring(dctfhe_ctx* ctx, dctfhe_client_key* client, int logN, const uint16_t* words, size_t count, uint64_t* phases);
+
 /* MARGIN AUDIT: the decision noise of every bootstrap that has a key switch of its own, measured in a real run.
  * A development and assurance tool: it needs the client's SECRET key, so it is never a server path.
  *

@@ -1685,6 +1685,188 @@ extern "C" int dctfhe_decrypt_ring(dctfhe_ctx* ctx, dctfhe_client_key* C, int lo
   return 0;
 }
 
+// ---- public-key inputs (kernels.h k_pk_*): the key, the encryptor without a secret, the extraction
+// Wire form of the key (seeded only): PubBlobHeader, the client's 32-byte public generator key, then the N_e body words.
+static constexpr uint32_t PUB_BLOB_MAGIC = 0x4b425044u /* 'DPBK' */, PUB_BLOB_VERSION = 1;
+struct PubBlobHeader { uint32_t magic, version; int32_t logN, reserved; double sigma; uint64_t total_bytes; };
+// the generator stream of the key's mask (noise: + 1), a stream of its own per (logN, sigma) for the reason given at ring_stream.  Bit 62
+// is set and bit 63 clear: the packing-key streams have bit 63 set and every other id of these generator keys is below 2^17.
+static uint64_t public_key_stream(int logN, double sigma) {
+  uint64_t sb;
+  memcpy(&sb, &sigma, 8);
+  const uint64_t mix = (sb * 0x9E3779B97F4A7C15ULL) ^ ((uint64_t)logN << 24);
+  return (1ULL << 62) | (mix & 0x3FFFFFFFFFFFFFFEULL);
+}
+static int check_public_spec(const char* who, int logN, double sigma, int dim) {
+  if (logN < 5 || logN > 12) return fail("%s: ring 2^%d outside 2^5 .. 2^12", who, logN);
+  if (dim > 0 && (1 << logN) > dim) return fail("%s: the ring key is a prefix of what an input masks: N_e = %d > %d", who, 1 << logN, dim);
+  if (!(sigma >= 0.0) || sigma >= 1.0) return fail("%s: noise std %g outside [0, 1)", who, sigma);
+  return 0;
+}
+static size_t pub_blob_size(int logN) { return sizeof(PubBlobHeader) + 32 + ((size_t)8 << logN); }
+
+struct dctfhe_public_key {
+  dctfhe_ctx* ctx = nullptr;
+  int logN = 0;
+  double sigma = 0;
+  DevBuf key;                    // u64 [2][N_e]: A, B
+  rng_key enc{};                 // the encryptor's own generator key (32 bytes from the OS at import)
+  uint64_t calls = 0;            // call c draws from streams 3 c (u), 3 c + 1 (e1), 3 c + 2 (e2)
+  ~dctfhe_public_key() { if (ctx) hipSetDevice(ctx->device); }
+};
+static constexpr uint64_t PUB_MAX_CALLS = 1ULL << 62;      // 3 c + 2 stays inside 64 bits
+
+extern "C" int dctfhe_public_key_export(dctfhe_client_key* C, int logN, double sigma, void* buf, size_t capacity, size_t* size) {
+  if (!C || !size) return fail("dctfhe_public_key_export: null argument");
+  CHK(check_public_spec("dctfhe_public_key_export", logN, sigma, C->p.input_dim > 0 ? C->p.input_dim : C->p.D));
+  const size_t need = pub_blob_size(logN);
+  *size = need;
+  if (!buf) return 0;                       // size query
+  if (capacity < need) return fail("dctfhe_public_key_export: buffer of %zu bytes, %zu needed", capacity, need);
+  HIPCHK(hipSetDevice(C->ctx->device));
+  const int N = 1 << logN;
+  PubBlobHeader h{};
+  h.magic = PUB_BLOB_MAGIC; h.version = PUB_BLOB_VERSION; h.logN = logN; h.sigma = sigma; h.total_bytes = need;
+  char* q = (char*)buf;
+  memcpy(q, &h, sizeof h); q += sizeof h;
+  key_to_bytes(C->pub, (uint8_t*)q); q += 32;
+  DevBuf d_b;
+  HIPCHK(d_b.alloc((size_t)N * 8));
+  hipLaunchKernelGGL(k_pk_gen, dim3(1), dim3(256), (size_t)N * 8, C->ctx->stream, C->S(), N, sigma, C->pub, C->sec, public_key_stream(logN, sigma), d_b.as<uint64_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(d_b.download(q, (size_t)N * 8, C->ctx->stream));
+  return 0;
+}
+extern "C" int dctfhe_public_key_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_public_key** out) {
+  if (!ctx || !buf || !out) return fail("dctfhe_public_key_import: null argument");
+  if (size < sizeof(PubBlobHeader) + 32) return fail("dctfhe_public_key_import: public-key blob too short (%zu bytes)", size);
+  PubBlobHeader h;
+  memcpy(&h, buf, sizeof h);
+  if (h.magic != PUB_BLOB_MAGIC) return fail("dctfhe_public_key_import: not a public-key blob (magic)");
+  if (h.version != PUB_BLOB_VERSION) return fail("dctfhe_public_key_import: public-key blob version %u, this library reads %u", h.version, PUB_BLOB_VERSION);
+  CHK(check_public_spec("dctfhe_public_key_import", h.logN, h.sigma, 0));
+  if (h.total_bytes != size || pub_blob_size(h.logN) != size)
+    return fail("dctfhe_public_key_import: public-key blob of %zu bytes, its header needs %zu (length)", size, pub_blob_size(h.logN));
+  HIPCHK(hipSetDevice(ctx->device));
+  std::unique_ptr<dctfhe_public_key> K(new dctfhe_public_key);
+  K->ctx = ctx; K->logN = h.logN; K->sigma = h.sigma;
+  {  // the encryptor's generator key from the OS: two handles, even of one blob, never share a draw
+    uint8_t raw[32];
+    size_t got = 0;
+    while (got < sizeof raw) {
+      const ssize_t r = getrandom(raw + got, sizeof raw - got, 0);
+      if (r <= 0) return fail("dctfhe_public_key_import: the OS gave no random bytes for the encryption key (getrandom)");
+      got += (size_t)r;
+    }
+    K->enc = key_from_bytes(raw);
+  }
+  const size_t N = (size_t)1 << h.logN;
+  DevBuf d_b;
+  HIPCHK(d_b.upload((const char*)buf + sizeof h + 32, N * 8));
+  HIPCHK(K->key.alloc(2 * N * 8));
+  CHK(launch_expand(key_from_bytes((const uint8_t*)buf + sizeof h), public_key_stream(h.logN, h.sigma), 0, N, (int)N, ~0ULL, d_b.as<uint64_t>(), (int)N, 1, 2 * N,
+                    K->key.as<uint64_t>(), ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *out = K.release();
+  return 0;
+}
+extern "C" int dctfhe_public_key_destroy(dctfhe_public_key* K) { delete K; return 0; }
+extern "C" int dctfhe_public_key_info(dctfhe_public_key* K, int* logN, double* sigma) {
+  if (!K) return fail("dctfhe_public_key_info: null argument");
+  if (logN) *logN = K->logN;
+  if (sigma) *sigma = K->sigma;
+  return 0;
+}
+// test view: the expanded key [2][N_e] (A then B)
+extern "C" int dctfhe_public_key_export_rows(dctfhe_public_key* K, uint64_t* out) {
+  if (!K || !out) return fail("dctfhe_public_key_export_rows: null argument");
+  HIPCHK(hipSetDevice(K->ctx->device));
+  HIPCHK(K->key.download(out, K->key.bytes, K->ctx->stream));
+  return 0;
+}
+// reproducible tests only: fix the encryptor's generator key and restart its call counter
+extern "C" int dctfhe_public_key_set_encrypt_seed(dctfhe_public_key* K, const uint8_t* seed32) {
+  if (!K || !seed32) return fail("dctfhe_public_key_set_encrypt_seed: null argument");
+  K->enc = key_from_bytes(seed32);
+  K->calls = 0;
+  return 0;
+}
+extern "C" size_t dctfhe_public_words(int logN, size_t count) { return dctfhe_ring_words(logN, count); }
+
+// the draws of call `call` for `count` phases, on the device: u i32 [groups N_e], e1 i64 [groups N_e], e2 i64 [count]
+static int dev_public_draws(dctfhe_public_key* K, uint64_t call, size_t count, DevBuf* u, DevBuf* e1, DevBuf* e2) {
+  const size_t N = (size_t)1 << K->logN, nmask = (count + N - 1) / N * N;
+  HIPCHK(u->alloc(nmask * 4));
+  HIPCHK(e1->alloc(nmask * 8));
+  HIPCHK(e2->alloc(count * 8));
+  hipLaunchKernelGGL(k_pk_draws, dim3(ew_grid(nmask)), dim3(256), 0, K->ctx->stream, K->enc, 3 * call, nmask, count, K->sigma, u->as<int32_t>(), e1->as<int64_t>(),
+                     e2->as<int64_t>());
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// test view: what call `call` of dctfhe_encrypt_public draws for `count` phases -- u one byte per bit [groups N_e], e1 [groups N_e], e2 [count]
+extern "C" int dctfhe_public_key_draws(dctfhe_public_key* K, uint64_t call, size_t count, uint8_t* u, int64_t* e1, int64_t* e2) {
+  if (!K || !u || !e1 || !e2) return fail("dctfhe_public_key_draws: null argument");
+  if (count == 0) return fail("dctfhe_public_key_draws: no phases (count == 0)");
+  if (call >= PUB_MAX_CALLS) return fail("dctfhe_public_key_draws: call counter out of range");
+  HIPCHK(hipSetDevice(K->ctx->device));
+  const size_t N = (size_t)1 << K->logN, nmask = (count + N - 1) / N * N;
+  DevBuf d_u, d_e1, d_e2;
+  CHK(dev_public_draws(K, call, count, &d_u, &d_e1, &d_e2));
+  std::vector<int32_t> u32(nmask);
+  HIPCHK(d_u.download(u32.data(), nmask * 4, K->ctx->stream));
+  for (size_t x = 0; x < nmask; x++) u[x] = (uint8_t)u32[x];
+  HIPCHK(d_e1.download(e1, nmask * 8, K->ctx->stream));
+  HIPCHK(d_e2.download(e2, count * 8, K->ctx->stream));
+  return 0;
+}
+// ENCRYPTOR: `count` phases -> dctfhe_public_words(logN, count) wire words; one step of the handle's call counter
+extern "C" int dctfhe_encrypt_public(dctfhe_ctx* ctx, dctfhe_public_key* K, const uint64_t* phases, size_t count, uint64_t* words_out) {
+  if (!ctx || !K || !phases || !words_out) return fail("dctfhe_encrypt_public: null argument");
+  if (K->ctx != ctx) return fail("dctfhe_encrypt_public: the public key was imported on another context");
+  if (count == 0) return fail("dctfhe_encrypt_public: no phases (count == 0)");
+  if (K->calls >= PUB_MAX_CALLS) return fail("dctfhe_encrypt_public: this handle's call counter is exhausted");
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t N = (size_t)1 << K->logN, groups = (count + N - 1) / N, nwords = dctfhe_ring_words(K->logN, count);
+  DevBuf d_ph, d_u, d_e1, d_e2, d_out;
+  HIPCHK(d_ph.alloc(count * 8));
+  HIPCHK(d_out.alloc(nwords * 8));
+  HIPCHK(hipMemcpyAsync(d_ph.p, phases, count * 8, hipMemcpyHostToDevice, st));
+  CHK(dev_public_draws(K, K->calls++, count, &d_u, &d_e1, &d_e2));      // the counter moves even if a later step fails: a draw is never reused
+  hipLaunchKernelGGL(k_pk_encrypt, dim3((unsigned)(groups * 2 * (N / RING_TILE))), dim3(256), N * 8 + N * 4, st, d_u.as<int32_t>(), d_e1.as<int64_t>(),
+                     d_e2.as<int64_t>(), d_ph.as<uint64_t>(), count, K->logN, K->key.as<uint64_t>(), d_out.as<uint64_t>());
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(words_out, d_out.p, nwords * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+// device wire words -> rows at stride L (body at word L - 1) starting at d_rows
+static int launch_ring_extract(int logN, const uint64_t* d_words, size_t count, size_t L, uint64_t* d_rows, hipStream_t st) {
+  const size_t N = (size_t)1 << logN, groups = (count + N - 1) / N;
+  hipLaunchKernelGGL(k_pk_extract, dim3((unsigned)(groups * (N / EXTRACT_TILE))), dim3(256), N * 8, st, d_words, count, logN, L, d_rows);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static constexpr size_t PUB_MAX_COUNT = (size_t)1 << 30;      // keeps groups x tiles inside a 32-bit grid
+// SERVER, the primitive on host buffers: wire words of `count` public-key inputs -> LWE rows of dim mask words + body
+extern "C" int dctfhe_ring_extract(dctfhe_ctx* ctx, int logN, const uint64_t* words, size_t count, int dim, uint64_t* rows_out) {
+  if (!ctx || !words || !rows_out) return fail("dctfhe_ring_extract: null argument");
+  if (logN < 5 || logN > 12) return fail("dctfhe_ring_extract: ring 2^%d outside 2^5 .. 2^12", logN);
+  if (count == 0 || count > PUB_MAX_COUNT) return fail("dctfhe_ring_extract: %zu inputs (1 .. 2^30)", count);
+  if (dim < (1 << logN) || dim > (1 << 20)) return fail("dctfhe_ring_extract: rows of %d mask words, a slot of this ring fills N_e = %d (N_e <= dim <= 2^20)", dim, 1 << logN);
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t L = (size_t)dim + 1, nwords = dctfhe_ring_words(logN, count);
+  DevBuf d_w, d_r;
+  HIPCHK(d_w.alloc(nwords * 8));
+  HIPCHK(d_r.alloc(count * L * 8));
+  HIPCHK(hipMemcpyAsync(d_w.p, words, nwords * 8, hipMemcpyHostToDevice, ctx->stream));
+  CHK(launch_ring_extract(logN, d_w.as<uint64_t>(), count, L, d_r.as<uint64_t>(), ctx->stream));
+  HIPCHK(hipMemcpyAsync(rows_out, d_r.p, count * L * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 // the centred mod switch on host buffers (the scheduler applies it between every key switch and its bootstrap)
 extern "C" int dctfhe_modswitch_center(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, uint64_t* cts_small, size_t count) {
   if (!ctx || !K || (count && !cts_small)) return fail("dctfhe_modswitch_center: null argument");
@@ -2259,6 +2441,27 @@ extern "C" int dctfhe_session_upload_seeded(dctfhe_session* s, const uint8_t* ma
   HIPCHK(d_b.alloc(count * 8));
   HIPCHK(hipMemcpyAsync(d_b.p, bodies, count * 8, hipMemcpyHostToDevice, st));
   CHK(launch_expand(key_from_bytes(mask_key), stream, 0, (uint64_t)s->D + 1, dim_eff, ~0ULL, d_b.as<uint64_t>(), 1, count, Ls, s->d_tensor[t], st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+// public-key inputs: the wire words cross PCIe (16 bytes per input in full groups), k_pk_extract writes the rows straight into the input tensor
+extern "C" int dctfhe_session_upload_public(dctfhe_session* s, int logN, const uint64_t* words, size_t count) {
+  if (!s || !words) return fail("dctfhe_session_upload_public: null argument");
+  if (!s->keys) return fail("dctfhe_session_upload_public: a clear-mode session takes phases (dctfhe_session_upload), not ciphertexts");
+  if (logN < 5 || logN > 12) return fail("dctfhe_session_upload_public: ring 2^%d outside 2^5 .. 2^12", logN);
+  const int t = s->circ->input_tensor;
+  const size_t Ls = s->t_L[t], deff = s->t_deff[t], n = s->tensor_words[t] / Ls;
+  if (count == 0) return fail("dctfhe_session_upload_public: no inputs (count == 0)");
+  if (count != n) return fail("dctfhe_session_upload_public: %zu inputs, the session takes batch x n_in = %zu", count, n);
+  // the rule of upload_seeded: the circuit reads only the first deff mask words (and Ls > deff holds them and the body)
+  if (((size_t)1 << logN) > deff) return fail("dctfhe_session_upload_public: a slot fills N_e = %d mask words; this circuit's input keeps %zu", 1 << logN, deff);
+  HIPCHK(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->ctx->stream;
+  const size_t nwords = dctfhe_ring_words(logN, count);
+  DevBuf d_w;
+  HIPCHK(d_w.alloc(nwords * 8));
+  HIPCHK(hipMemcpyAsync(d_w.p, words, nwords * 8, hipMemcpyHostToDevice, st));
+  CHK(launch_ring_extract(logN, d_w.as<uint64_t>(), count, Ls, s->d_tensor[t], st));
   HIPCHK(hipStreamSynchronize(st));
   return 0;
 }

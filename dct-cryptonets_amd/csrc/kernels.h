@@ -699,6 +699,30 @@ __global__ void k_ring_digits(const uint64_t* __restrict__ small, size_t count, 
 // through LDS, the body term b_c joins component 1, and the word goes out rounded as k_pack16 does: the N mask words of the group, then
 // its first m body words.  Groups before the last are full, so group g starts at u16 index 2 g N.
 constexpr int RING_TILE = 32, RING_PARTS = 256 / RING_TILE;
+// One key row's share of a tile (k_ring_pack, k_pk_encrypt): the window [first, first + span) of the row's polynomial and the row's m
+// multipliers go to LDS, then the thread (coefficient c, slot residue part) takes acc -= mul[i] (+-K[(c - i) mod N]) over its slots.
+// Every thread of the workgroup calls it: two barriers.
+__device__ __forceinline__ uint64_t ring_tile_row(const uint64_t* __restrict__ krow, const int32_t* __restrict__ mrow, int N, int m, int first, int span,
+                                                  int c, int part, uint64_t* __restrict__ K, int32_t* __restrict__ d, uint64_t acc) {
+  __syncthreads();
+  for (int x = threadIdx.x; x < span; x += 256) { const int idx = (first + x) & (N - 1); K[idx] = krow[idx]; }
+  for (int x = threadIdx.x; x < m; x += 256) d[x] = mrow[x];
+  __syncthreads();
+#pragma unroll 4
+  for (int i = part; i < m; i += RING_PARTS) {
+    const int64_t dd = d[i];
+    acc += (uint64_t)(c >= i ? -dd : dd) * K[(c - i) & (N - 1)];
+  }
+  return acc;
+}
+// the RING_PARTS partial sums of a coefficient meet through LDS; the sum is valid in the threads of part 0
+__device__ __forceinline__ uint64_t ring_tile_sum(uint64_t acc, uint64_t* __restrict__ red, int part) {
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  if (part == 0)
+    for (int p = 1; p < RING_PARTS; p++) acc += red[p * RING_TILE + threadIdx.x % RING_TILE];
+  return acc;
+}
 __global__ void __launch_bounds__(256) k_ring_pack(const int32_t* __restrict__ dig, const uint64_t* __restrict__ small, size_t count, int n,
                                                    int logN, int l, const uint64_t* __restrict__ key, uint16_t* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -717,23 +741,10 @@ __global__ void __launch_bounds__(256) k_ring_pack(const int32_t* __restrict__ d
   const int span = m + RING_TILE - 1 < N ? m + RING_TILE - 1 : N;
   const int first = span < N ? (tile * RING_TILE - (m - 1)) & (N - 1) : 0;
   uint64_t acc = 0;
-  for (int r = 0; r < rows; r++) {
-    __syncthreads();
-    const uint64_t* krow = key + ((size_t)r * 2 + comp) * N;
-    const int32_t* drow = dig + (g * rows + r) * (size_t)N;
-    for (int x = threadIdx.x; x < span; x += 256) { const int idx = (first + x) & (N - 1); K[idx] = krow[idx]; }
-    for (int x = threadIdx.x; x < m; x += 256) d[x] = drow[x];
-    __syncthreads();
-#pragma unroll 4
-    for (int i = part; i < m; i += RING_PARTS) {
-      const int64_t dd = d[i];
-      acc += (uint64_t)(c >= i ? -dd : dd) * K[(c - i) & (N - 1)];
-    }
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
+  for (int r = 0; r < rows; r++)
+    acc = ring_tile_row(key + ((size_t)r * 2 + comp) * N, dig + (g * rows + r) * (size_t)N, N, m, first, span, c, part, K, d, acc);
+  acc = ring_tile_sum(acc, red, part);
   if (part != 0) return;
-  for (int p = 1; p < RING_PARTS; p++) acc += red[p * RING_TILE + c % RING_TILE];
   uint16_t* grp = out + g * 2 * (size_t)N;
   if (comp == 0) grp[c] = (uint16_t)round16(acc);
   else if (c < m) grp[N + c] = (uint16_t)round16(acc + small[(g * N + c) * (size_t)(n + 1) + n]);
@@ -763,6 +774,84 @@ __global__ void __launch_bounds__(256) k_ring_phase16(const uint8_t* __restrict_
     part += c <= i ? a : 0u - a;
   }
   phases[g * N + i] = (uint64_t)(((uint32_t)grp[N + i] - part) & 0xFFFFu) << 48;
+}
+
+// ---- public-key inputs: up to N phases in ONE GLWE ciphertext made without the secret key -----------------
+// Public key: one GLWE zero row (A, B = A Z + E) under the ring key Z of the ring-packed results above, N = 2^logN <= input_dim.  A group
+// of m <= N phases encrypts to C_a = A u + e1, C_b[i] = (B u)[i] + e2[i] + phase_i (i < m) with u binary: coefficient i of C_b - C_a Z is
+// phase_i + (E u + e2 - e1 Z)[i].  The server extracts slot i as an LWE row under the first N bits of the big key.
+
+// the key's body [N]: row 0 of a k = 1 bootstrap key without a message (bsk_row_zero): mask word c is rnd64(pub, stream, c), its noise
+// gauss_torus(sec, stream + 1, c); k_seeded_expand rebuilds the mask.  One block.
+__global__ void k_pk_gen(const uint8_t* __restrict__ S_big, int N, double sigma, rng_key pub, rng_key sec, uint64_t stream, uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  bsk_row_zero(S_big, 0, 1, N, sigma, pub, sec, stream, reinterpret_cast<uint64_t*>(smem_raw), out, nullptr);
+}
+
+// the draws of one encryption call, all from the encryptor's own generator key: u[x] the top bit of word (stream, x), e1[x] the Gaussian
+// draw (stream + 1, x) for x < nmask = groups N, e2[x] the draw (stream + 2, x) for x < count <= nmask
+__global__ void k_pk_draws(rng_key key, uint64_t stream, size_t nmask, size_t count, double sigma, int32_t* __restrict__ u, int64_t* __restrict__ e1,
+                           int64_t* __restrict__ e2) {
+  for (size_t x = (size_t)blockIdx.x * blockDim.x + threadIdx.x; x < nmask; x += (size_t)gridDim.x * blockDim.x) {
+    u[x] = (int32_t)(rnd64(key, stream, x) >> 63);
+    e1[x] = gauss_torus(key, stream + 1, x, sigma);
+    if (x < count) e2[x] = gauss_torus(key, stream + 2, x, sigma);
+  }
+}
+
+// One workgroup per (group g, component: 0 mask / 1 body, tile of RING_TILE output coefficients), the tile loop of k_ring_pack with ONE
+// key row (component comp of the public key, all N words) and the group's N bits u as multipliers: ring_tile_row leaves
+// -sum_{i: u_i = 1} +-K[(c - i) mod N], the sign flipped where c < i.  Epilogue: the mask takes e1, the first m body coefficients e2 and
+// the phase; body tiles beyond m leave at once.  N = 32 is one tile: c < N always, and the staging loops stop at N.
+// Wire words (u64): per group its N mask words, then its first m body words; groups before the last are full.
+__global__ void __launch_bounds__(256) k_pk_encrypt(const int32_t* __restrict__ u, const int64_t* __restrict__ e1, const int64_t* __restrict__ e2,
+                                                    const uint64_t* __restrict__ phases, size_t count, int logN, const uint64_t* __restrict__ key,
+                                                    uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __shared__ uint64_t red[256];
+  const int N = 1 << logN, tiles = N / RING_TILE;
+  uint64_t* K = reinterpret_cast<uint64_t*>(smem_raw);
+  int32_t* d = reinterpret_cast<int32_t*>(K + N);
+  const int tile = (int)(blockIdx.x % tiles), comp = (int)((blockIdx.x / tiles) & 1);
+  const size_t g = blockIdx.x / (2 * (size_t)tiles);
+  const size_t left = count - g * N;
+  const int m = left < (size_t)N ? (int)left : N;
+  if (comp == 1 && tile * RING_TILE >= m) return;      // the whole workgroup: no body word of this tile travels
+  const int c = tile * RING_TILE + (threadIdx.x % RING_TILE), part = threadIdx.x / RING_TILE;
+  uint64_t acc = ring_tile_row(key + (size_t)comp * N, u + g * N, N, N, 0, N, c, part, K, d, 0);
+  acc = ring_tile_sum(acc, red, part);
+  if (part != 0) return;
+  const size_t x = g * N + c;
+  uint64_t* grp = out + g * 2 * (size_t)N;
+  if (comp == 0) grp[c] = (uint64_t)e1[x] - acc;
+  else if (c < m) grp[N + c] = (uint64_t)e2[x] + phases[x] - acc;
+}
+
+// server: slot i of a group -> the LWE row a_j = C_a[i - j] (j <= i), -C_a[N + i - j] (i < j < N), zeros up to the row's body, body
+// C_b[i], written at row stride L (body at word L - 1) -- straight into a session's input tensor, or into rows of dim + 1 words.
+// One workgroup per (group, tile of EXTRACT_TILE slots); the group's N mask words sit in LDS (<= 32 KB); each wave writes whole rows, its
+// lanes on consecutive mask words (reads run DOWN the LDS array, conflict-free; stores are 512 contiguous bytes per wave), the body last.
+constexpr int EXTRACT_TILE = 32;
+__global__ void __launch_bounds__(256) k_pk_extract(const uint64_t* __restrict__ words, size_t count, int logN, size_t L, uint64_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int N = 1 << logN, tiles = N / EXTRACT_TILE;
+  uint64_t* A = reinterpret_cast<uint64_t*>(smem_raw);
+  const int tile = (int)(blockIdx.x % tiles);
+  const size_t g = blockIdx.x / tiles;
+  const size_t left = count - g * N;
+  const int m = left < (size_t)N ? (int)left : N;
+  if (tile * EXTRACT_TILE >= m) return;                // the whole workgroup: no slot of this tile is filled
+  const uint64_t* grp = words + g * 2 * (size_t)N;
+  for (int x = threadIdx.x; x < N; x += 256) A[x] = grp[x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int end = (tile + 1) * EXTRACT_TILE < m ? (tile + 1) * EXTRACT_TILE : m;
+  for (int i = tile * EXTRACT_TILE + wv; i < end; i += 4) {
+    uint64_t* row = out + (g * N + i) * L;
+    for (size_t j = lane; j + 1 < L; j += 64)
+      row[j] = j < (size_t)N ? ((int)j <= i ? A[i - (int)j] : (uint64_t)0 - A[N + i - (int)j]) : 0;
+    if (lane == 0) row[L - 1] = grp[N + i];
+  }
 }
 
 // ------------------------------------------------------------------------------------------ K4-K6 bootstrap

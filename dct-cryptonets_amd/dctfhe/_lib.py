@@ -63,6 +63,9 @@ EXPORTS = [
     "dctfhe_device_bytes_live",
     "dctfhe_pack_key_export", "dctfhe_pack_key_import", "dctfhe_pack_key_destroy", "dctfhe_pack_key_info", "dctfhe_pack_key_export_rows",
     "dctfhe_ring_words", "dctfhe_ring_pack", "dctfhe_session_download_ring", "dctfhe_decrypt_ring",
+    "dctfhe_public_key_export", "dctfhe_public_key_import", "dctfhe_public_key_destroy", "dctfhe_public_key_info", "dctfhe_public_key_export_rows",
+    "dctfhe_public_key_set_encrypt_seed", "dctfhe_public_key_draws", "dctfhe_public_words", "dctfhe_encrypt_public", "dctfhe_ring_extract",
+    "dctfhe_session_upload_public",
 ]
 
 _lib = None
@@ -161,6 +164,18 @@ def load():
     L.dctfhe_ring_pack.argtypes = [vp, vp, vp, sz, i32, vp]
     L.dctfhe_session_download_ring.argtypes = [vp, i32, vp, vp]
     L.dctfhe_decrypt_ring.argtypes = [vp, vp, i32, vp, sz, vp]
+    L.dctfhe_public_key_export.argtypes = [vp, i32, C.c_double, vp, sz, C.POINTER(sz)]
+    L.dctfhe_public_key_import.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    L.dctfhe_public_key_destroy.argtypes = [vp]
+    L.dctfhe_public_key_info.argtypes = [vp, pi, pd]
+    L.dctfhe_public_key_export_rows.argtypes = [vp, vp]
+    L.dctfhe_public_key_set_encrypt_seed.argtypes = [vp, C.c_char_p]
+    L.dctfhe_public_key_draws.argtypes = [vp, C.c_uint64, sz, vp, vp, vp]
+    L.dctfhe_public_words.argtypes = [i32, sz]
+    L.dctfhe_public_words.restype = sz
+    L.dctfhe_encrypt_public.argtypes = [vp, vp, vp, sz, vp]
+    L.dctfhe_ring_extract.argtypes = [vp, i32, vp, sz, i32, vp]
+    L.dctfhe_session_upload_public.argtypes = [vp, i32, vp, sz]
     _lib = L
     return L
 

@@ -25,6 +25,7 @@ Dt = T[2j] - S  (split_tables).  The blob keeps one LUT record with w = 7 and th
 Every op carries the typed site of its kind (ConvSite, LutSite, PoolSite: the names and rules of csrc/circuit.h, which decodes what
 this module writes).  Which slot of a blob record holds which field is known to _encode_record alone.
 """
+import copy
 import math
 import struct
 from dataclasses import dataclass, replace
@@ -439,6 +440,51 @@ def output_compaction(circ, form="rows", spec=None):
 
 
 # the site's own rules, for callers that hold a look-up op
+@dataclass
+class PublicInputPlan:
+    """what public-key inputs (include/dctfhe.h dctfhe_encrypt_public) cost a circuit: the variance an extracted input carries in place
+    of a fresh encryption's, and the circuit priced again with it -- hand-over steps and tiers as compiled"""
+    spec: object                   # params.PublicInputSpec
+    var: float                     # params.var_public_input(spec) (torus^2)
+    worst_site: int                # op index of the look-up site with the largest p_fail per element (-1: the circuit has none)
+    worst_note: str
+    worst_pfail: float
+    worst_pfail_fresh: float       # the same site with fresh secret-key inputs
+    expected_failures_per_image: float
+    inputs_per_image: int
+    bytes_per_image: int           # wire words of ONE image's inputs, 8 bytes each (a batch shares groups: bytes_per_batch)
+
+    def bytes_per_batch(self, batch=1):
+        return 8 * self.spec.words(batch * self.inputs_per_image)
+
+
+def public_input_plan(circ, spec=None):
+    """Prices `circ` with its input tensor's variance replaced by params.var_public_input(spec) (spec: a params.PublicInputSpec, default
+    params.default_public_input_spec) on a COPY: circ, its blob and report() stay as they are.  Raises ValueError, with the numbers, when
+    the ring does not fit the circuit's inputs or when a site that met p_budget with fresh inputs no longer does."""
+    ps = circ.param_set
+    spec = spec if spec is not None else P.default_public_input_spec(ps)
+    spec.check(ps)
+    var = P.var_public_input(spec)
+    c = copy.copy(circ)
+    c.tensors = [copy.copy(t) for t in circ.tensors]
+    c.ops = [copy.copy(o) for o in circ.ops]
+    _estimate_noise(c, input_var=var, settle=False)
+    budget = getattr(ps, "p_budget", 1e-12)
+    sites = [(o.pfail, i) for i, o in enumerate(c.ops) if o.type in (OP_LUT, OP_MAXPOOL)]
+    lost = [(pf, i) for pf, i in sites if pf > budget and circ.ops[i].pfail <= budget]
+    if lost:
+        pf, i = max(lost)
+        raise ValueError(f"public-key inputs leave the budget: an extracted input has sigma 2^{0.5 * math.log2(var):.1f} (N_e = {spec.N}, key and "
+                         f"encryptor noise 2^{math.log2(spec.sigma):.1f}) against 2^{math.log2(ps.input_sigma):.1f} fresh; {len(lost)} site(s) "
+                         f"leave p_budget, the worst op {i} ({circ.ops[i].note}): p_fail {pf:.1e} per element > {budget:.1e} "
+                         f"(fresh inputs: {circ.ops[i].pfail:.1e})")
+    pf, i = max(sites) if sites else (0.0, -1)
+    return PublicInputPlan(spec=spec, var=var, worst_site=i, worst_note=circ.ops[i].note if i >= 0 else "", worst_pfail=pf,
+                           worst_pfail_fresh=circ.ops[i].pfail if i >= 0 else 0.0, expected_failures_per_image=c.expected_failures_per_image,
+                           inputs_per_image=circ.n_in(), bytes_per_image=8 * spec.words(circ.n_in()))
+
+
 def step_tier(o, i): return o.lut.step_tier(i)
 def is_split(o): return o.lut.split()
 def chain_steps(o): return o.lut.n_steps()
@@ -819,9 +865,11 @@ def _assign_encodings(circ):
 
 
 # ------------------------------------------------------------------------------------------ noise budget
-def _estimate_noise(circ):
+def _estimate_noise(circ, input_var=None, settle=True):
+    """input_var: the input tensor's variance (default: a fresh secret-key encryption's).  settle=False prices the hand-over steps the
+    sites already have instead of choosing them again (public_input_plan: the blob is what it is)"""
     ps, T = circ.param_set, circ.tensors
-    T[circ.input_tensor].var = ps.input_sigma ** 2
+    T[circ.input_tensor].var = ps.input_sigma ** 2 if input_var is None else input_var
     total, flips = 0.0, 0.0
     for o in circ.ops:
         s = T[o.src0]
@@ -835,7 +883,7 @@ def _estimate_noise(circ):
             for fail in _price_max_pool(ps, o, s, T[o.dst]):       # one by one: the sum keeps its order
                 total += fail
         else:
-            fail, flip = _price_lut(ps, o, s, T[o.dst])
+            fail, flip = _price_lut(ps, o, s, T[o.dst], settle)
             total += fail
             flips += flip
     circ.expected_failures_per_image = total
@@ -865,9 +913,9 @@ def _price_max_pool(ps, o, s, d):
     return fails
 
 
-def _price_lut(ps, o, s, d):
+def _price_lut(ps, o, s, d, settle=True):
     """-> (expected failures, expected boundary flips) per image; settles the site's hand-over steps (LutSite.coarse_from, coarse2,
-    coarse2_from)"""
+    coarse2_from) unless settle is False: then the site is priced as it stands"""
     L = o.lut
     n_elt = s.C * s.H * s.W
     tt = ps.tiers[L.tab_tier]
@@ -904,9 +952,9 @@ def _price_lut(ps, o, s, d):
         second = P.p_fail(2.0 ** -(W_ + 2), v_second) if split else 0.0
         return pf_ + P.p_fail(2.0 ** -(W_ + 2), v_ + v_tab_in) + second, var + ([v_second] if split else []) + [v_ + v_tab_in]
 
-    chosen = handed_over(R_)
+    chosen = handed_over(R_) if settle else L
     pf = site_pfail(chosen)[0]
-    if R_ > 0 and L.coarse >= 0:
+    if settle and R_ > 0 and L.coarse >= 0:
         # earliest step from which the one-level bit tier keeps the site within 2x of its all-precise failure rate
         budget = max(2.0 * pf, getattr(ps, "p_budget", 1e-12))
         cf = R_

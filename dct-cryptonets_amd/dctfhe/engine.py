@@ -126,6 +126,20 @@ class Context:
         check(self.L.dctfhe_expand_seeded(self.h, sc.key, C.c_uint64(sc.stream), sc.D, sc.input_dim, ptr(sc.bodies), sc.bodies.size, dim, ptr(out)))
         return out
 
+    def ring_extract(self, logN, words=None, count=None, dim=None):
+        """server primitive (dctfhe_ring_extract): wire words of `count` public-key inputs (or a PublicInputs: ring_extract(pi, dim=...))
+        -> LWE rows [count, dim + 1] under the first 2^logN bits of the big key; dim None: 2^logN, the tightest row"""
+        if isinstance(logN, PublicInputs):
+            logN, words, count = logN.logN, logN.words, len(logN)
+        words = np.ascontiguousarray(words, np.uint64).reshape(-1)
+        count = int(count)
+        dim = (1 << int(logN)) if dim is None else int(dim)
+        if 5 <= int(logN) <= 12 and words.size != PublicInputs.n_words(logN, count):
+            raise ValueError(f"{words.size} words are not {count} public-key inputs in rings of {1 << logN}")
+        out = np.empty((count, max(dim, 0) + 1), np.uint64)
+        check(self.L.dctfhe_ring_extract(self.h, int(logN), ptr(words), count, dim, ptr(out)))
+        return out
+
     def decompress_bsk(self, blob, tier):
         """test view: the standard-domain bootstrap key of `tier` as importing a compressed blob rebuilds it"""
         blob = _as_u8(blob)
@@ -329,6 +343,105 @@ class PackKey:
             self.h = C.c_void_p()
 
 
+class PublicInputs:
+    """Input ciphertexts made with a PUBLIC key (include/dctfhe.h dctfhe_encrypt_public): groups of up to N_e = 2^logN inputs, each group
+    one GLWE ciphertext of 64-bit words -- its N_e mask words, then one body word per input.  words: flat uint64, groups contiguous.
+    Wire form: to_bytes / from_bytes (little-endian)."""
+
+    MAGIC, VERSION = b"DPIN", 1
+    _HDR = struct.Struct("<4sIiQ")            # magic, version, logN, count; then groups * N_e + count u64
+
+    def __init__(self, logN, count, words):
+        logN, count = int(logN), int(count)
+        if not 5 <= logN <= 12:
+            raise ValueError(f"public-key inputs need 5 <= logN <= 12 (got {logN})")
+        if count < 0:
+            raise ValueError(f"public-key inputs: count {count}")
+        words = np.ascontiguousarray(words, np.uint64).reshape(-1)
+        if words.size != self.n_words(logN, count):
+            raise ValueError(f"{words.size} words are not {count} inputs in rings of {1 << logN} ({self.n_words(logN, count)} words)")
+        self.logN, self.count, self.words = logN, count, words
+
+    @staticmethod
+    def n_words(logN, count):
+        N = 1 << logN
+        return -(-count // N) * N + count
+
+    def __len__(self):
+        return self.count
+
+    @property
+    def nbytes(self):
+        return self._HDR.size + self.words.nbytes
+
+    def to_bytes(self):
+        return self._HDR.pack(self.MAGIC, self.VERSION, self.logN, self.count) + self.words.astype("<u8", copy=False).tobytes()
+
+    @classmethod
+    def from_bytes(cls, blob):
+        blob = bytes(blob)
+        H = cls._HDR.size
+        if len(blob) < H:
+            raise ValueError("public-key-input blob too short")
+        magic, version, logN, count = cls._HDR.unpack_from(blob)
+        if magic != cls.MAGIC or version != cls.VERSION:
+            raise ValueError("not a public-key-input blob (magic / version)")
+        if not 5 <= logN <= 12 or len(blob) != H + 8 * cls.n_words(logN, count):
+            raise ValueError(f"public-key-input blob of {len(blob)} bytes, its header says logN = {logN}, {count} inputs")
+        return cls(logN, count, np.frombuffer(blob, "<u8", cls.n_words(logN, count), H).astype(np.uint64))
+
+
+class PublicKey:
+    """Data-owner side of public-key inputs (dctfhe_public_key): the client's public key, expanded on the GPU from its seeded blob, and
+    the handle's own generator key (32 bytes from the OS).  Encrypts; can decrypt nothing."""
+
+    def __init__(self, ctx, blob):
+        self.ctx, self.L = ctx, ctx.L
+        blob = _as_u8(blob)
+        self.h = C.c_void_p()
+        check(self.L.dctfhe_public_key_import(ctx.h, ptr(blob), blob.size, C.byref(self.h)))
+        a, b = C.c_int(), C.c_double()
+        check(self.L.dctfhe_public_key_info(self.h, C.byref(a), C.byref(b)))
+        self.logN, self.sigma = a.value, b.value
+
+    @property
+    def N(self):
+        return 1 << self.logN
+
+    def export_rows(self):
+        """test view: the expanded key [2, N_e] (A, B)"""
+        out = np.empty((2, self.N), np.uint64)
+        check(self.L.dctfhe_public_key_export_rows(self.h, ptr(out)))
+        return out
+
+    def set_encrypt_seed(self, seed32):
+        """FIX the generator key the handle drew from the OS and restart its call counter -- reproducible tests only"""
+        seed32 = bytes(seed32)
+        if len(seed32) != 32:
+            raise ValueError("an encryption seed is exactly 32 bytes")
+        check(self.L.dctfhe_public_key_set_encrypt_seed(self.h, seed32))
+
+    def draws(self, call, count):
+        """test view: what call `call` draws for `count` phases -> (u uint8 [groups N_e], e1 int64 [groups N_e], e2 int64 [count])"""
+        count = int(count)
+        nmask = -(-count // self.N) * self.N
+        u, e1, e2 = np.empty(nmask, np.uint8), np.empty(nmask, np.int64), np.empty(max(count, 0), np.int64)
+        check(self.L.dctfhe_public_key_draws(self.h, int(call), count, ptr(u), ptr(e1), ptr(e2)))
+        return u, e1, e2
+
+    def encrypt(self, phases):
+        """phases (uint64, any shape, taken flat) -> PublicInputs; one step of the handle's call counter"""
+        phases = np.ascontiguousarray(phases, np.uint64).reshape(-1)
+        out = np.empty(PublicInputs.n_words(self.logN, phases.size), np.uint64)
+        check(self.L.dctfhe_encrypt_public(self.ctx.h, self.h, ptr(phases), phases.size, ptr(out)))
+        return PublicInputs(self.logN, phases.size, out)
+
+    def close(self):
+        if self.h:
+            self.L.dctfhe_public_key_destroy(self.h)
+            self.h = C.c_void_p()
+
+
 class ClientKey:
     """Secret side (include/dctfhe.h dctfhe_client_key): encrypts, decrypts, generates evaluation keys."""
 
@@ -423,6 +536,15 @@ class ClientKey:
         check(self.L.dctfhe_pack_key_export(*args, None, 0, C.byref(n)))
         out = np.empty(n.value, np.uint8)
         check(self.L.dctfhe_pack_key_export(*args, ptr(out), out.size, C.byref(n)))
+        return out
+
+    def export_public_key(self, spec):
+        """the public key of public-key inputs as its seeded blob (dctfhe_public_key_export); spec: params.PublicInputSpec"""
+        n = C.c_size_t()
+        args = (self.h, int(spec.logN), float(spec.sigma))
+        check(self.L.dctfhe_public_key_export(*args, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        check(self.L.dctfhe_public_key_export(*args, ptr(out), out.size, C.byref(n)))
         return out
 
     def decrypt_ring(self, ring):
@@ -575,7 +697,8 @@ class Keys:
 
     def __getattr__(self, name):
         if name in ("export_secret", "export_bsk", "encrypt", "decrypt", "seed", "input_dim", "set_encrypt_nonce", "set_encrypt_counter",
-                    "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed", "margin_probe", "export_pack_key", "decrypt_ring"):
+                    "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed", "margin_probe", "export_pack_key", "decrypt_ring",
+                    "export_public_key"):
             return getattr(self.client, name)
         if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
@@ -639,6 +762,10 @@ class Session:
         if self.keys is not None and sc.D != self.keys.D:
             raise ValueError(f"seeded ciphertexts under D = {sc.D}, the session's keys have D = {self.keys.D}")
         check(self.L.dctfhe_session_upload_seeded(self.h, sc.key, C.c_uint64(sc.stream), sc.input_dim, ptr(sc.bodies), sc.bodies.size))
+
+    def upload_public(self, pi):
+        """PublicInputs of batch x n_in inputs: the wire words go to the device, k_pk_extract writes the rows into the input tensor"""
+        check(self.L.dctfhe_session_upload_public(self.h, pi.logN, ptr(pi.words), len(pi)))
 
     def set_noise(self, seed, sigma_per_op):
         """clear-mode sessions: `simulate` with the noise model (sigma per op, fraction of the torus); None switches it off"""

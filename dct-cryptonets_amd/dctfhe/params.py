@@ -174,6 +174,59 @@ def var_ring_pack(n, spec, m=None):
             + (spec.N / 2.0 + 1.0) * 2.0 ** -32 / 12.0)
 
 
+@dataclass
+class PublicInputSpec:
+    """public-key inputs (include/dctfhe.h dctfhe_public_key_export): ring N_e = 2^logN whose key is the first N_e bits of the big key, noise
+    sigma of the key row and of the encryptor's own draws.  Stands alone: no ParamSet field, nothing of it is serialised into a circuit."""
+    logN: int = 11
+    sigma: float = None            # None: sigma_min(N_e) (below 1 from N_e = 128 on); 0.0 is noise-free (tests only)
+
+    def __post_init__(self):
+        if not 5 <= int(self.logN) <= 12:
+            raise ValueError(f"public-key inputs need 5 <= logN <= 12 (got {self.logN})")
+        if self.sigma is None:
+            self.sigma = sigma_min(1 << self.logN)
+        if not 0.0 <= self.sigma < 1.0:
+            raise ValueError(f"public-key inputs: noise std {self.sigma} outside [0, 1)")
+
+    @property
+    def N(self):
+        return 1 << self.logN
+
+    def groups(self, count):
+        return -(-int(count) // self.N)
+
+    def words(self, count):
+        """64-bit words of `count` public-key inputs: per group N mask words, then one body word per input"""
+        return self.groups(count) * self.N + int(count)
+
+    def check(self, ps):
+        """raises ValueError where the ring does not fit what an input of `ps` masks (input_dim, or D)"""
+        dim = ps.input_dim or ps.D
+        if self.N > dim:
+            raise ValueError(f"public-key inputs: the ring key is a prefix of what an input masks, N_e = {self.N} > {dim}; "
+                             f"pass a PublicInputSpec with a smaller ring")
+        return self
+
+
+def default_public_input_spec(ps=None):
+    """N_e = 2048 at sigma_min(2048): a full group costs 16 bytes per input.  ps given: raises ValueError where its inputs mask fewer
+    than 2048 words (input_dim, or D)"""
+    spec = PublicInputSpec(logN=11)
+    return spec.check(ps) if ps is not None else spec
+
+
+def test_public_input_spec():
+    """for test_params() (D = 1024): a ring of 256, noise far below every margin (NOT secure, like the catalogue it goes with)"""
+    return PublicInputSpec(logN=8, sigma=2.0 ** -48)
+
+
+def var_public_input(spec):
+    """the noise of an extracted public-key input: E u (N_e/2 units of sigma^2: u uniform binary), e1 Z (N_e/2: binary key, half the bits
+    set) and e2 (one unit)"""
+    return (spec.N + 1) * spec.sigma ** 2
+
+
 def p_fail(margin, var):
     """two-sided Gaussian tail beyond `margin`"""
     if var <= 0:

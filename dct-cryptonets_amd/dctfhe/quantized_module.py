@@ -6,7 +6,8 @@
     Configuration(...)               homomorphic_eval.py:266    Configuration (progress flags kept, inert; compress_input_ciphertexts,
                                                                 compress_evaluation_keys: seeded inputs / compressed evaluation keys;
                                                                 compress_output_ciphertexts: packed 16-bit results, as rows
-                                                                or, with "ring", up to N_p of them in one GLWE ciphertext)
+                                                                or, with "ring", up to N_p of them in one GLWE ciphertext;
+                                                                public_key_inputs: inputs encrypted with a public key)
     q.fhe_circuit.graph.maximum_integer_bit_width()    :301     FHECircuit.graph.maximum_integer_bit_width()
     q.fhe_circuit.mlir                                 :311     FHECircuit.mlir  (text dump of the compiled circuit)
     q.fhe_circuit.keygen()                             :315     FHECircuit.keygen()  (keys generated on the GPU)
@@ -23,14 +24,15 @@ import numpy as np
 
 from . import compile as cc
 from . import params as P
-from .engine import Circuit, Context, Keys, PackedCiphertexts, PackedRing, PackKey, SeededCiphertexts, Session
+from .engine import Circuit, Context, Keys, PackedCiphertexts, PackedRing, PackKey, PublicInputs, PublicKey, SeededCiphertexts, Session
 
 
 class Configuration:
     """Stand-in for concrete.fhe.Configuration (reference homomorphic_eval.py:266-273)."""
 
     def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
-                 compress_evaluation_keys=False, compress_output_ciphertexts=False, result_packing_spec=None, **kwargs):
+                 compress_evaluation_keys=False, compress_output_ciphertexts=False, result_packing_spec=None, public_key_inputs=False,
+                 public_input_spec=None, **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
         # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
         # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
@@ -43,6 +45,14 @@ class Configuration:
         # True (or "rows") keeps meaning the rows form; "none" is False; any other string raises ValueError (it used to count as True).
         self.compress_output_ciphertexts = _output_form(compress_output_ciphertexts)
         self.result_packing_spec = result_packing_spec
+        # dctfhe addition: fhe="execute" encrypts its inputs WITHOUT the secret key, through a public key the client exports once
+        # (include/dctfhe.h dctfhe_encrypt_public; FHECircuit.export_public_key / load_public_key / encrypt_public split the parties);
+        # public_input_spec: its params.PublicInputSpec (None: the default one).  Off by default.  The seeded form is made with the
+        # secret key, so the two switches exclude each other.
+        self.public_key_inputs = bool(public_key_inputs)
+        self.public_input_spec = public_input_spec
+        if self.public_key_inputs and self.compress_input_ciphertexts:
+            raise ValueError("public_key_inputs and compress_input_ciphertexts exclude each other: a seeded input is made with the secret key")
         self.extra = kwargs
 
 
@@ -138,6 +148,15 @@ class FHECircuit:
     def load_result_packing_key(self, blob):
         return self._o.load_result_packing_key(blob)
 
+    def export_public_key(self):
+        return self._o.export_public_key()
+
+    def load_public_key(self, blob):
+        return self._o.load_public_key(blob)
+
+    def encrypt_public(self, x):
+        return self._o.encrypt_public(x)
+
     @property
     def statistics(self):
         """Concrete's `fhe_circuit.statistics` is a property; here the engine's dctfhe_stats of the compiled circuit"""
@@ -161,6 +180,9 @@ class QuantizedModule:
         self._compaction = None
         self._ring_compaction = None
         self._pack_key = None
+        self._public_plan = None
+        self._public_key = None
+        self._public_key_of = None         # the key set forward(fhe="execute") made its own public key for
 
     # -- lazy device objects -------------------------------------------------------------
     def _context(self):
@@ -215,6 +237,54 @@ class QuantizedModule:
             self._pack_key.close()
         self._pack_key = PackKey(ctx, blob)
 
+    def public_input_plan(self):
+        """what public-key inputs cost this circuit (dctfhe.compile.public_input_plan with Configuration.public_input_spec); raises
+        ValueError where a site would leave the catalogue's failure budget"""
+        if self._public_plan is None:
+            self._public_plan = cc.public_input_plan(self.compiled, self.configuration.public_input_spec)
+        return self._public_plan
+
+    def export_public_key(self):
+        """client side: the public key of public-key inputs as a blob to hand to data owners (no secret inside; 16 KB at the default
+        spec).  The spec is the one public_input_plan() priced"""
+        spec = self.public_input_plan().spec
+        if self._keys is None:
+            if self._public_key is not None:      # a data owner's module: a fresh key set here would be an unrelated one
+                raise RuntimeError("the public key is made by the client (its secret key); this module holds a loaded public key only")
+            self._keygen(None)
+        if not isinstance(self._keys, Keys):
+            raise RuntimeError("the public key is made by the client (its secret key); this module holds evaluation keys only")
+        return self._keys.client.export_public_key(spec)
+
+    def load_public_key(self, blob):
+        """data-owner side: the client's public key; this module can then run `encrypt_public` and needs neither the client key nor
+        evaluation keys for it"""
+        plan = self.public_input_plan()
+        ctx = self._context()
+        pk = PublicKey(ctx, blob)
+        if pk.logN != plan.spec.logN or pk.sigma > plan.spec.sigma:
+            got = (pk.logN, pk.sigma)
+            pk.close()
+            raise RuntimeError(f"the public key (logN {got[0]}, sigma {got[1]:.3g}) is not covered by the spec this configuration priced "
+                               f"(logN {plan.spec.logN}, sigma {plan.spec.sigma:.3g})")
+        if self._public_key is not None:
+            self._public_key.close()
+        self._public_key, self._public_key_of = pk, None
+
+    def encrypt_public(self, x):
+        """data-owner side: float inputs [B, C, H, W] -> PublicInputs (quantise, encode, encrypt with the loaded public key)"""
+        if self._public_key is None:
+            raise RuntimeError("encrypt_public needs the client's public key: fhe_circuit.load_public_key(blob)")
+        q = self.quantize_input(np.asarray(x))
+        return self._public_key.encrypt(self.encode_input(q).reshape(-1))
+
+    def _own_public_key(self):
+        """forward(fhe="execute") under Configuration(public_key_inputs=True): this module's own public key, made once per key set"""
+        if self._public_key is None or self._public_key_of is not self._keys:
+            self.load_public_key(self.export_public_key())
+            self._public_key_of = self._keys
+        return self._public_key
+
     def _ring_plan(self):
         """(tier, packing key) of a ring-packed download; refuses before anything runs"""
         oc = self.output_compaction("ring")
@@ -259,10 +329,13 @@ class QuantizedModule:
         """server side: input ciphertexts [batch * n_in, D+1] -> output ciphertexts [batch * n_out, D+1]; dim: the compact wire
         form instead -- input rows of dim mask words + body, output rows of Session.dims()[1] mask words + body.  cts may also be
         SeededCiphertexts (or their to_bytes() form): the masks are regenerated on the GPU; dim then only selects the output form.
+        PublicInputs (or their to_bytes() form, told from seeded bytes by the magic): the rows are extracted on the GPU, likewise.
         packed (default: Configuration.compress_output_ciphertexts): True / "rows": the outputs as PackedCiphertexts instead, "ring": as
         a PackedRing (needs load_result_packing_key), whatever dim says"""
         if isinstance(cts, (bytes, bytearray, memoryview)):
-            cts = SeededCiphertexts.from_bytes(cts)
+            cts = PublicInputs.from_bytes(cts) if bytes(cts[:4]) == PublicInputs.MAGIC else SeededCiphertexts.from_bytes(cts)
+        if isinstance(cts, PublicInputs):
+            self.public_input_plan()          # refuses before anything runs
         packed = self.configuration.compress_output_ciphertexts if packed is None else _output_form(packed)
         if packed == "ring":
             tier, pack_key = self._ring_plan()
@@ -271,6 +344,8 @@ class QuantizedModule:
         sess = self._session("execute", batch)
         if isinstance(cts, SeededCiphertexts):
             sess.upload_seeded(cts)
+        elif isinstance(cts, PublicInputs):
+            sess.upload_public(cts)
         else:
             sess.upload(cts, dim)
         sess.run()
@@ -357,10 +432,17 @@ class QuantizedModule:
                 pack_tier, pack_key = self._ring_plan()
             else:
                 pack_tier = self.output_compaction().tier if form else None
+            # Configuration(public_key_inputs=True): encrypted without the secret key, extracted on the GPU (priced first, like the above)
+            public = self._own_public_key() if self.configuration.public_key_inputs else None
             t1 = time.time()
-            cts = self._keys.encrypt_seeded(phases.reshape(-1)) if seeded else self._keys.encrypt(phases.reshape(-1), in_dim)
+            if public is not None:
+                cts = public.encrypt(phases.reshape(-1))
+            else:
+                cts = self._keys.encrypt_seeded(phases.reshape(-1)) if seeded else self._keys.encrypt(phases.reshape(-1), in_dim)
             t2 = time.time()
-            if seeded:
+            if public is not None:
+                sess.upload_public(cts)
+            elif seeded:
                 sess.upload_seeded(cts)
             else:
                 sess.upload(cts, in_dim)
@@ -382,8 +464,8 @@ class QuantizedModule:
                 t5 = time.time()
                 out_ph = self._keys.decrypt_packed(pk).reshape(B, -1)
             self.last_io = dict(encrypt_s=t2 - t1, upload_s=t3 - t2, run_s=t4 - t3, download_s=t5 - t4, decrypt_s=time.time() - t5,
-                                input_bytes=int(cts.nbytes), output_bytes=int(out.nbytes),
-                                upload_bytes=int(cts.bodies.nbytes if seeded else cts.nbytes))
+                                input_bytes=int(cts.words.nbytes if public is not None else cts.nbytes), output_bytes=int(out.nbytes),
+                                upload_bytes=int(cts.words.nbytes if public is not None else cts.bodies.nbytes if seeded else cts.nbytes))
         else:
             sess.upload(phases)
             timing = sess.run(timing=True)
@@ -428,6 +510,9 @@ class QuantizedModule:
         if self._pack_key is not None:
             self._pack_key.close()
             self._pack_key = None
+        if self._public_key is not None:
+            self._public_key.close()
+            self._public_key = None
         if self._circuit is not None:
             self._circuit.close()
             self._circuit = None

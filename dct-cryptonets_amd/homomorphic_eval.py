@@ -61,6 +61,8 @@ def parse_args():
     e.add_argument("--compress_outputs", default="none", choices=["none", "rows", "ring"],
                    help="results on the way back: full rows; rows: key-switched 16-bit rows; ring: up to 2048 results in one GLWE "
                         "ciphertext (the client's packing key is made after keygen and loaded)")
+    e.add_argument("--public_key_inputs", action="store_true",
+                   help="encrypt the inputs without the secret key, through a public key made after keygen; the GPU extracts the rows")
     return parser.parse_args()
 
 
@@ -124,7 +126,7 @@ def main():
     calib_data, _ = make(params.calib_batch_size, params.seed + 100)
     print("\nCompiling FHE Model (this can take up to 10 minutes for larger networks)...")
     configuration = Configuration(show_progress=False, progress_tag=True, progress_title="Evaluation: ",
-                                  compress_output_ciphertexts=params.compress_outputs)
+                                  compress_output_ciphertexts=params.compress_outputs, public_key_inputs=params.public_key_inputs)
     t = time.time()
     compile_fn = compile_brevitas_qat_model if quantization_type == "QAT" else compile_torch_model
     rtb = params.rounding_threshold_bits if params.rounding_method == "exact" else {"n_bits": params.rounding_threshold_bits, "method": "approximate"}

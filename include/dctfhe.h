@@ -347,6 +347,53 @@ int dctfhe_ring_pack(dctfhe_ctx* ctx, dctfhe_pack_key* key, const uint64_t* cts_
 int dctfhe_session_download_ring(dctfhe_session* s, int tier, dctfhe_pack_key* key, uint16_t* out /* dctfhe_ring_words of batch x n_out */);
 int dctfhe_decrypt_ring(dctfhe_ctx* ctx, dctfhe_client_key* client, int logN, const uint16_t* words, size_t count, uint64_t* phases);
 
+/* PUBLIC-KEY INPUTS: a party that holds no secret encrypts up to N_e = 2^logN input phases into ONE GLWE
+ * ciphertext with a compact public key; the server extracts them as LWE rows.  16 bytes per input in full groups.  Opt-in.
+ *
+ * Spec: ring N_e = 2^logN, 5 <= logN <= 12, N_e <= input_dim (D where input_dim is 0): the ring key Z(X) = sum_{c < N_e} S[c] X^c is
+ * the first N_e bits of the big key (the ring key of the ring-packed results above), and a circuit's input tensor keeps only input_dim
+ * mask words.  Noise std sigma (fraction of the torus) for the key row and for the encryptor's e1, e2.  dctfhe.params
+ * default_public_input_spec: logN 11, sigma_min(2048).
+ * Public key: ONE GLWE zero row (A, B), B = A Z + E, negacyclic, mod 2^64.  With the spec's generator stream
+ *     P = 1 << 62 | ((bits(sigma) * 0x9E3779B97F4A7C15 mod 2^64) ^ (logN << 24)) & 0x3FFFFFFFFFFFFFFE
+ * (bits: the IEEE-754 double as a u64) A[c] is generator word (pub, P, c) of the client's PUBLIC generator key and E[c] the Gaussian draw
+ * (sec, P + 1, c) of the secret one.  Bit 62 set and bit 63 clear: P and P + 1 meet no packing-key stream R, R + 1 (bit 63 set) and no
+ * other id of these generator keys (all below 2^17); sigma and logN are part of P for the reason given at R.
+ * Blob (seeded form only, little-endian): u32 magic 'DPBK', u32 version 1, i32 logN, i32 0, f64 sigma, u64 total bytes; the 32-byte public
+ * generator key; N_e body words B (u64): 16 448 bytes at logN 11.  Import regenerates A on the GPU.
+ *
+ * Encryption, per group of m <= N_e phases (phase i of a call: group i / N_e, slot i mod N_e): u uniform in {0,1}^N_e, e1 Gaussian(sigma)
+ * on N_e coefficients, e2 on m;  C_a = A u + e1;  C_b[i] = (B u)[i] + e2[i] + phase_i, i < m.  Coefficient i of C_b - C_a Z is
+ * phase_i + (E u + e2 - e1 Z)[i].
+ * Wire form: per group its N_e mask words, then its first m body words, u64 little-endian, groups contiguous:
+ * dctfhe_public_words(logN, count) = groups N_e + count words (the layout of the ring-packed results at full width).
+ * Randomness: the encryptor holds NO client key.  public_key_import draws a 32-byte generator key from the OS (getrandom) and keeps a call
+ * counter; call c = 0, 1, ... draws u[x] = the top bit of generator word (key, 3 c, x), e1[x] = the Gaussian draw (key, 3 c + 1, x) for
+ * x < groups N_e (x = group N_e + coefficient) and e2[x] = the draw (key, 3 c + 2, x) for x < count: no two calls and no two handles share
+ * a draw.  public_key_set_encrypt_seed fixes the key and restarts the counter -- reproducible tests only; public_key_draws regenerates
+ * the draws of one call (u one byte per bit, e1, e2 signed torus words), so a reference can rebuild the ciphertext bit for bit.
+ * Extraction (server): slot i of a group is the LWE row a_j = C_a[i - j] (j <= i), a_j = -C_a[N_e + i - j] (i < j < N_e), a_j = 0
+ * (N_e <= j), body C_b[i], under the first N_e bits of the big key.
+ *
+ * public_key_export: CLIENT; buf == NULL: size query.  Refused: logN outside [5, 12], N_e > input_dim (or D), sigma outside [0, 1).
+ * public_key_import: ENCRYPTOR; refused: a blob of the wrong magic, version or length.  public_key_export_rows: test view, [2][N_e].
+ * encrypt_public / ring_extract / public_key_draws refuse count == 0; ring_extract needs dim >= N_e and writes count rows of dim + 1
+ * words; session_upload_public writes the rows straight into the session's input tensor and refuses a clear-mode session,
+ * count != batch x n_in and N_e beyond the mask words the circuit's input keeps. */
+typedef struct dctfhe_public_key dctfhe_public_key;   /* ENCRYPTOR: the expanded public key and the handle's own generator key */
+int dctfhe_public_key_export(dctfhe_client_key* client, int logN, double sigma, void* buf, size_t capacity, size_t* size);
+int dctfhe_public_key_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_public_key** out);
+int dctfhe_public_key_destroy(dctfhe_public_key* key);
+int dctfhe_public_key_info(dctfhe_public_key* key, int* logN, double* sigma /* each may be NULL */);
+int dctfhe_public_key_export_rows(dctfhe_public_key* key, uint64_t* out /* 2 x N_e */);
+int dctfhe_public_key_set_encrypt_seed(dctfhe_public_key* key, const uint8_t* seed32);
+int dctfhe_public_key_draws(dctfhe_public_key* key, uint64_t call, size_t count, uint8_t* u /* groups x N_e */, int64_t* e1 /* groups x N_e */,
+                            int64_t* e2 /* count */);
+size_t dctfhe_public_words(int logN, size_t count);
+int dctfhe_encrypt_public(dctfhe_ctx* ctx, dctfhe_public_key* key, const uint64_t* phases, size_t count, uint64_t* words_out /* dctfhe_public_words */);
+int dctfhe_ring_extract(dctfhe_ctx* ctx, int logN, const uint64_t* words, size_t count, int dim, uint64_t* rows_out /* count x (dim+1) */);
+int dctfhe_session_upload_public(dctfhe_session* s, int logN, const uint64_t* words, size_t count);
+
 /* MARGIN AUDIT: the decision noise of every bootstrap that has a key switch of its own, measured in a real run.
  * A development and assurance tool: it needs the client's SECRET key, so it is never a server path.
  *

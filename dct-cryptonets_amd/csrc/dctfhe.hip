@@ -348,6 +348,11 @@ struct dctfhe_session {
   DevBuf d_audit_key, d_audit;      // bytes of the small key; margin_slot per slot
   std::vector<dctfhe_margin_stats> audit_slots, audit_last;
   std::vector<int> audit_first;
+  // sharded look-up sites (dctfhe_session_set_shard): this session is part `part` of `parts`; whole[t] = 0: only this part's rows of
+  // tensor t are valid.  (0, 1), the default: every tensor is whole at all times
+  int part = 0, parts = 1;
+  bool has_run = false;
+  std::vector<char> whole;
   void wipe_audit_key() { if (d_audit_key.p) hipMemset(d_audit_key.p, 0, d_audit_key.bytes); }      // the secret does not outlive the audit
   void audit_off() {
     wipe_audit_key();
@@ -1354,8 +1359,10 @@ struct LutRows {
 };
 static size_t ring_of(const dctfhe_keys* K, int tier) { return (size_t)K->p.tiers[tier].k << K->p.tiers[tier].logN; }
 // probe: the margin audit's slots of this site in for_each_bootstrap order -- steps, a split's second look-up, the table
+// e0: the rows are a slice that starts at element e0 of the tensor (a sharded session): the per-channel tables go by e0 + c.  Everything
+// else under a site is indexed by the launch: the scratch, and the parity rows `par`, which hold one chunk at a time
 static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, size_t count, int hw, const LutScratch& sc, Timers* tm, int deff,
-                         const MarginProbe* probe = nullptr) {
+                         const MarginProbe* probe = nullptr, size_t e0 = 0) {
   const bool split = L.split();
   const int p = L.p, steps = L.n_steps(), nchan = L.ntab, tab_tier = L.tab_tier, tier2 = L.tier2(K->p);
   const size_t Lw = b.Lw, ring2 = split ? ring_of(K, tier2) : 0;
@@ -1369,7 +1376,7 @@ static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, siz
     KsInput work;            // the working rows as they stand
     work.rows = w0; work.L = Lw; work.deff = deff;
     PbsLut tab;              // the site's table look-up
-    tab.tables = split ? b.tab_s : b.tables; tab.w = L.table_bits(); tab.idx = b.idx ? b.idx + c0 : nullptr; tab.hw = hw; tab.nchan = nchan; tab.e_offset = c0;
+    tab.tables = split ? b.tab_s : b.tables; tab.w = L.table_bits(); tab.idx = b.idx ? b.idx + c0 : nullptr; tab.hw = hw; tab.nchan = nchan; tab.e_offset = e0 + c0;
     for (int i = 0; i < steps; i++) {
       const int vlog = 62 - p + i;
       KsInput in = work; in.shift = p - i;
@@ -2380,6 +2387,7 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   if (keys) CHK(session_lut_scratch(s.get()));
   HIPCHK(s->d_overflow.alloc(sizeof(int)));
   HIPCHK(hipMemset(s->d_overflow.p, 0, sizeof(int)));
+  s->whole.assign(circ->tensors.size(), 1);
   if (keys) {
     dctfhe_stats stt;
     circuit_stats(*circ, keys->p, &stt);
@@ -2400,6 +2408,7 @@ extern "C" int dctfhe_session_upload_rows(dctfhe_session* s, const uint64_t* cts
   if (!s->keys) {      // clear mode: one word per element, stored as given
     HIPCHK(hipMemcpyAsync(s->d_tensor[t], cts_in, s->tensor_words[t] * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
+    s->whole[t] = 1;
     return 0;
   }
   if (dim < 1 || dim > s->D) return fail("dctfhe_session_upload: rows of %d mask words, the key has %d", dim, s->D);
@@ -2423,6 +2432,7 @@ extern "C" int dctfhe_session_upload_rows(dctfhe_session* s, const uint64_t* cts
   hipLaunchKernelGGL(k_restride, dim3(ew_grid(count * Ls)), dim3(256), 0, st, tmp.as<uint64_t>(), Lh, s->d_tensor[t], Ls, count, std::min(deff, (size_t)dim));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
+  s->whole[t] = 1;
   return 0;
 }
 // seeded inputs: only the bodies cross PCIe (8 bytes per ciphertext); the masks are written straight into the input tensor
@@ -2442,6 +2452,7 @@ extern "C" int dctfhe_session_upload_seeded(dctfhe_session* s, const uint8_t* ma
   HIPCHK(hipMemcpyAsync(d_b.p, bodies, count * 8, hipMemcpyHostToDevice, st));
   CHK(launch_expand(key_from_bytes(mask_key), stream, 0, (uint64_t)s->D + 1, dim_eff, ~0ULL, d_b.as<uint64_t>(), 1, count, Ls, s->d_tensor[t], st));
   HIPCHK(hipStreamSynchronize(st));
+  s->whole[t] = 1;
   return 0;
 }
 // public-key inputs: the wire words cross PCIe (16 bytes per input in full groups), k_pk_extract writes the rows straight into the input tensor
@@ -2463,6 +2474,7 @@ extern "C" int dctfhe_session_upload_public(dctfhe_session* s, int logN, const u
   HIPCHK(hipMemcpyAsync(d_w.p, words, nwords * 8, hipMemcpyHostToDevice, st));
   CHK(launch_ring_extract(logN, d_w.as<uint64_t>(), count, Ls, s->d_tensor[t], st));
   HIPCHK(hipStreamSynchronize(st));
+  s->whole[t] = 1;
   return 0;
 }
 extern "C" int dctfhe_session_upload(dctfhe_session* s, const uint64_t* cts_in) {
@@ -2493,8 +2505,17 @@ extern "C" int dctfhe_session_set_noise_split(dctfhe_session* s, const double* s
   return 0;
 }
 
+// a sharded session: every download reads the whole output tensor
+static int output_whole(const dctfhe_session* s, const char* who) {
+  const int t = s->circ->output_tensor;
+  if (!s->whole[t])
+    return fail("%s: output tensor %d holds only the rows of part %d of %d: exchange the other parts' rows and call dctfhe_session_mark_whole first", who, t, s->part,
+                s->parts);
+  return 0;
+}
 extern "C" int dctfhe_session_download_rows(dctfhe_session* s, uint64_t* cts_out, int dim) {
   if (!s || !cts_out) return fail("dctfhe_session_download: null argument");
+  CHK(output_whole(s, "dctfhe_session_download"));
   HIPCHK(hipSetDevice(s->ctx->device));
   const int t = s->circ->output_tensor;
   hipStream_t st = s->ctx->stream;
@@ -2524,6 +2545,7 @@ extern "C" int dctfhe_session_download_packed(dctfhe_session* s, int tier, uint1
   if (!s || !rows) return fail("dctfhe_session_download_packed: null argument");
   if (!s->keys) return fail("dctfhe_session_download_packed: a clear-mode session holds phases, not ciphertexts (dctfhe_session_download)");
   if (tier < 0 || tier >= s->keys->p.n_tiers) return fail("dctfhe_session_download_packed: tier %d out of range (%d tiers)", tier, s->keys->p.n_tiers);
+  CHK(output_whole(s, "dctfhe_session_download_packed"));
   HIPCHK(hipSetDevice(s->ctx->device));
   const int t = s->circ->output_tensor;
   const size_t Ls = s->t_L[t];
@@ -2539,6 +2561,7 @@ extern "C" int dctfhe_session_download_ring(dctfhe_session* s, int tier, dctfhe_
   const int n = s->keys->p.tiers[tier].n;
   if (n > K->n_max) return fail("dctfhe_session_download_ring: tier %d has n = %d, the packing key covers n_max = %d", tier, n, K->n_max);
   if ((1 << K->logN) > s->keys->p.D) return fail("dctfhe_session_download_ring: the ring key is a prefix of the big key: N_p = %d > D = %d", 1 << K->logN, s->keys->p.D);
+  CHK(output_whole(s, "dctfhe_session_download_ring"));
   HIPCHK(hipSetDevice(s->ctx->device));
   hipStream_t st = s->ctx->stream;
   const int t = s->circ->output_tensor;
@@ -2583,6 +2606,7 @@ extern "C" int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* C)
   HIPCHK(hipSetDevice(s->ctx->device));
   if (!C) { s->audit_off(); return 0; }
   if (!s->keys) return fail("dctfhe_session_set_audit: a clear-mode session holds phases, not ciphertexts: there is no decision noise to measure");
+  if (s->parts > 1) return fail("dctfhe_session_set_audit: this session is part %d of %d; the margin audit stays unsharded", s->part, s->parts);
   const dctfhe_params &P = s->keys->p, &Q = C->p;
   if (C->ctx->device != s->ctx->device) return fail("dctfhe_session_set_audit: the client key lives on device %d, the session on %d", C->ctx->device, s->ctx->device);
   if (P.D != Q.D || P.n_max != Q.n_max || P.n_tiers != Q.n_tiers)
@@ -2633,22 +2657,124 @@ extern "C" int dctfhe_session_audit(dctfhe_session* s, dctfhe_margin_stats* out,
   return 0;
 }
 
-extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
+// ---- sharded look-up sites (include/dctfhe.h): the partition rule, the exchange plan, and what moves rows between the parts
+extern "C" int dctfhe_shard_rows(size_t rows, int parts, int part, size_t* first, size_t* count) {
+  if (!first || !count) return fail("dctfhe_shard_rows: null argument");
+  if (parts < 1 || parts > 64) return fail("dctfhe_shard_rows: %d parts (1 .. 64)", parts);
+  if (part < 0 || part >= parts) return fail("dctfhe_shard_rows: part %d of %d", part, parts);
+  const size_t q = rows / (size_t)parts, r = rows % (size_t)parts, p = (size_t)part;
+  *first = p * q + std::min(p, r);
+  *count = q + (p < r ? 1 : 0);
+  return 0;
+}
+static bool op_runs_sliced(const SiteOp& o) { return o.type == OP_LUT || o.type == OP_ADD; }
+extern "C" int dctfhe_session_set_shard(dctfhe_session* s, int part, int parts) {
+  if (!s) return fail("dctfhe_session_set_shard: null session");
+  size_t f, n;
+  CHK(dctfhe_shard_rows(0, parts, part, &f, &n));
+  if (s->has_run) return fail("dctfhe_session_set_shard: the session has run; shard it before its first run");
+  if (s->d_audit_key.p && parts > 1) return fail("dctfhe_session_set_shard: the margin audit is on, and it stays unsharded: turn it off first");
+  s->part = part; s->parts = parts;
+  return 0;
+}
+// the exchange points of a circuit: (op after which, tensor) per sliced tensor that a whole-needing op or the download reads
+static void shard_plan_of(const CircuitPlan& c, std::vector<std::pair<int, int>>* plan) {
+  std::vector<char> whole(c.tensors.size(), 1);
+  std::vector<int> writer(c.tensors.size(), -1);
+  auto need = [&](int t) { if (!whole[t]) { plan->push_back({writer[t], t}); whole[t] = 1; } };
+  for (int i = 0; i < (int)c.ops.size(); i++) {
+    const SiteOp& o = c.ops[i];
+    if (op_runs_sliced(o)) { whole[o.dst] = 0; writer[o.dst] = i; continue; }
+    need(o.src0);
+    whole[o.dst] = 1;
+  }
+  need(c.output_tensor);
+  std::sort(plan->begin(), plan->end());
+}
+extern "C" int dctfhe_session_shard_plan(dctfhe_session* s, int32_t* after_op, int32_t* tensor, int capacity, int* n) {
+  if (!s || !n) return fail("dctfhe_session_shard_plan: null argument");
+  std::vector<std::pair<int, int>> plan;
+  shard_plan_of(*s->circ, &plan);
+  *n = (int)plan.size();
+  if (!after_op || !tensor) return 0;
+  if (capacity < *n) return fail("dctfhe_session_shard_plan: room for %d entries, the circuit has %d", capacity, *n);
+  for (int i = 0; i < *n; i++) { after_op[i] = plan[i].first; tensor[i] = plan[i].second; }
+  return 0;
+}
+static int tensor_ok(const dctfhe_session* s, int t, const char* who) {
+  if (t < 0 || t >= (int)s->circ->tensors.size()) return fail("%s: tensor %d out of range (%zu tensors)", who, t, s->circ->tensors.size());
+  if (!s->d_tensor[t]) return fail("%s: tensor %d has no storage (no op of the circuit touches it)", who, t);
+  return 0;
+}
+extern "C" int dctfhe_session_tensor(dctfhe_session* s, int tensor, void** dev, size_t* row_words, size_t* rows) {
+  if (!s || !dev || !row_words || !rows) return fail("dctfhe_session_tensor: null argument");
+  CHK(tensor_ok(s, tensor, "dctfhe_session_tensor"));
+  *dev = s->d_tensor[tensor]; *row_words = s->t_L[tensor]; *rows = s->tensor_words[tensor] / s->t_L[tensor];
+  return 0;
+}
+extern "C" int dctfhe_session_mark_whole(dctfhe_session* s, int tensor) {
+  if (!s) return fail("dctfhe_session_mark_whole: null session");
+  CHK(tensor_ok(s, tensor, "dctfhe_session_mark_whole"));
+  s->whole[tensor] = 1;
+  return 0;
+}
+extern "C" int dctfhe_session_copy_rows(dctfhe_session* dst, dctfhe_session* src, int tensor, size_t first, size_t count) {
+  if (!dst || !src) return fail("dctfhe_session_copy_rows: null session");
+  if (dst->circ != src->circ) return fail("dctfhe_session_copy_rows: the sessions run different circuits");
+  if (dst->batch != src->batch) return fail("dctfhe_session_copy_rows: the sessions differ in batch (%d and %d)", dst->batch, src->batch);
+  CHK(tensor_ok(dst, tensor, "dctfhe_session_copy_rows"));
+  CHK(tensor_ok(src, tensor, "dctfhe_session_copy_rows"));
+  const size_t L = dst->t_L[tensor], rows = dst->tensor_words[tensor] / L;
+  if ((dst->keys == nullptr) != (src->keys == nullptr) || src->t_L[tensor] != L)
+    return fail("dctfhe_session_copy_rows: the sessions store tensor %d differently (rows of %zu and %zu words)", tensor, L, src->t_L[tensor]);
+  if (dst->ctx->device != src->ctx->device) return fail("dctfhe_session_copy_rows: the sessions live on devices %d and %d", dst->ctx->device, src->ctx->device);
+  if (first > rows || count > rows - first) return fail("dctfhe_session_copy_rows: rows %zu .. %zu of a tensor of %zu", first, first + count, rows);
+  if (count == 0 || dst == src) return 0;
+  HIPCHK(hipSetDevice(dst->ctx->device));
+  if (src->ctx->stream != dst->ctx->stream) {      // after src's work: its runs are synchronous, an event covers whatever else its stream holds
+    DevEvent e;
+    HIPCHK(e.create());
+    HIPCHK(hipEventRecord(e.e, src->ctx->stream));
+    HIPCHK(hipStreamWaitEvent(dst->ctx->stream, e.e, 0));
+    HIPCHK(hipMemcpyAsync(dst->d_tensor[tensor] + first * L, src->d_tensor[tensor] + first * L, count * L * 8, hipMemcpyDeviceToDevice, dst->ctx->stream));
+    HIPCHK(hipStreamSynchronize(dst->ctx->stream));      // the event dies with this scope
+    return 0;
+  }
+  HIPCHK(hipMemcpyAsync(dst->d_tensor[tensor] + first * L, src->d_tensor[tensor] + first * L, count * L * 8, hipMemcpyDeviceToDevice, dst->ctx->stream));
+  return 0;
+}
+
+// ops [first_op, end_op) of the circuit on the session's part: look-ups and adds on its rows, everything else in full
+static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_timing* timing) {
   HIPCHK(hipSetDevice(s->ctx->device));
   hipStream_t st = s->ctx->stream;
   dctfhe_circuit* c = s->circ;
   dctfhe_keys* K = s->keys;
   const int B = s->batch;
+  const bool sharded = s->parts > 1;
+  s->has_run = true;
   Timers tm{st, timing != nullptr, &s->ev_pool, {}};
   const hipEvent_t e0 = tm.take(), e1 = tm.take();
   HIPCHK(hipEventRecord(e0, st));
   if (timing) memset(timing, 0, sizeof *timing);
   const LutScratch& sc = s->lut;
   const bool audit = s->d_audit_key.p != nullptr;
-  if (audit && !s->audit_slots.empty())      // every run starts from zeroed slots
+  if (audit && first_op == 0 && !s->audit_slots.empty())      // every run starts from zeroed slots
     HIPCHK(hipMemsetAsync(s->d_audit.p, 0, s->audit_slots.size() * sizeof(margin_slot), st));
-  for (size_t i = 0; i < c->ops.size(); i++) {
+  for (size_t i = (size_t)first_op; i < (size_t)end_op; i++) {
     const SiteOp& o = c->ops[i];
+    // this part's rows of an element-wise op (all of them in an unsharded session); any other op reads whole tensors
+    size_t r0 = 0, rn = (size_t)B * c->tensors[o.dst].elems();
+    if (op_runs_sliced(o)) {
+      CHK(dctfhe_shard_rows(rn, s->parts, s->part, &r0, &rn));
+      s->whole[o.dst] = !sharded;
+    } else {
+      if (!s->whole[o.src0])
+        return fail("op %zu needs tensor %d whole, and it holds only the rows of part %d of %d: exchange the other parts' rows and call dctfhe_session_mark_whole first",
+                    i, o.src0, s->part, s->parts);
+      s->whole[o.dst] = 1;
+    }
+    if (rn == 0) continue;      // an empty part of a small tensor
     const MarginProbe probe_i = audit ? MarginProbe{s->d_audit_key.as<uint8_t>(), s->d_audit.as<margin_slot>() + s->audit_first[i]} : MarginProbe{};
     const MarginProbe* probe = audit ? &probe_i : nullptr;
     const TensorShape& a = c->tensors[o.src0];
@@ -2666,9 +2792,9 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
       }
       case OP_ADD: {
         const int h = tm.begin(CAT_LINEAR);
-        const size_t count = s->tensor_words[o.dst] / Ld;
-        hipLaunchKernelGGL(k_add, dim3(ew_grid(s->tensor_words[o.dst])), dim3(256), 0, st, src, Ls, ds, s->d_tensor[o.src1], s->t_L[o.src1], s->t_deff[o.src1], dst, Ld,
-                           count);
+        const size_t Lb = s->t_L[o.src1];
+        hipLaunchKernelGGL(k_add, dim3(ew_grid(rn * Ld)), dim3(256), 0, st, src + r0 * Ls, Ls, ds, s->d_tensor[o.src1] + r0 * Lb, Lb, s->t_deff[o.src1], dst + r0 * Ld, Ld,
+                           rn);
         HIPCHK(hipGetLastError());
         tm.end(h);
         break;
@@ -2683,15 +2809,16 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
       }
       case OP_LUT: {
         const LutSite& L = o.lut;
-        const size_t E = (size_t)B * a.elems();
+        const size_t E = rn;
         const int hw = a.H * a.W;
+        src += r0 * Ls; dst += r0 * Ld;      // the slice; r0 goes along wherever the element's number in the tensor is meant
         const int64_t* halves = c->d_split[i].as<int64_t>();      // [S | Dt] of a parity split, else nullptr
         const int64_t* half_d = halves ? halves + ((size_t)L.ntab << (L.w - 1)) : nullptr;
         if (!K) {
           const double sg2 = (i < s->sim_sigma2.size() && s->sim_sigma2[i] > 0) ? s->sim_sigma2[i] : sg;
           hipLaunchKernelGGL(k_lut_clear, dim3(ew_grid(E)), dim3(256), 0, st, src, dst, E, L.shift, L.body_add, L.p, L.r, L.w, c->d_payload[i].as<int64_t>(),
                              hw, L.ntab, s->d_overflow.as<int>(), sg, rng_key{{(uint32_t)s->sim_seed, (uint32_t)(s->sim_seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}},
-                             (uint64_t)(0x51D0000 + (s->sim_run << 12) + i), (int)L.approx(), (int)L.split(), sg2, halves, half_d);
+                             (uint64_t)(0x51D0000 + (s->sim_run << 12) + i), (int)L.approx(), (int)L.split(), sg2, halves, half_d, r0);
           HIPCHK(hipGetLastError());
         } else {
           // the one-bit steps clear the low bits in place on a shifted copy of the input (+ LutSite::round_add).  Approximate rounding (the
@@ -2714,7 +2841,7 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
           LutRows rows;
           rows.src = src; rows.Ls = Ls; rows.work = dst; rows.Lw = Ld; rows.par = s->pool_buf[i][0]; rows.Lp = Ld;
           rows.tables = c->d_payload[i].as<int64_t>(); rows.tab_s = halves; rows.tab_d = half_d;
-          CHK(dev_round_lut(K, L, rows, E, hw, sc, &tm, deff, probe));
+          CHK(dev_round_lut(K, L, rows, E, hw, sc, &tm, deff, probe, r0));
         }
         break;
       }
@@ -2734,7 +2861,7 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
       default: return fail("op %zu: unknown type %d", i, o.type);
     }
   }
-  s->sim_run++;
+  if (end_op == (int)c->ops.size() && first_op < end_op) s->sim_run++;      // `simulate` draws afresh in every pass over the circuit (its last op ends one)
   HIPCHK(hipEventRecord(e1, st));
   HIPCHK(hipEventSynchronize(e1));
   if (timing) {
@@ -2758,6 +2885,13 @@ extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) {
   }
   return 0;
 }
+extern "C" int dctfhe_session_run_span(dctfhe_session* s, int first_op, int end_op, dctfhe_timing* timing) {
+  if (!s) return fail("dctfhe_session_run_span: null session");
+  const int n = (int)s->circ->ops.size();
+  if (first_op < 0 || end_op < first_op || end_op > n) return fail("dctfhe_session_run_span: ops [%d, %d) of a circuit of %d", first_op, end_op, n);
+  return session_run_ops(s, first_op, end_op, timing);
+}
+extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) { return session_run_ops(s, 0, (int)s->circ->ops.size(), timing); }
 
 // ------------------------------------------------------------------------------------------ probes
 // ---- margin audit, the primitives (include/dctfhe.h): the definition on the host, and the session's kernel on host rows

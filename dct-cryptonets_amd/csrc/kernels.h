@@ -1174,30 +1174,32 @@ __device__ __forceinline__ uint64_t noisy_lookup(uint64_t centre, int w, const i
 // (RNG indices 2e and 2e + 1; sigma at the first, sigma2 at the second, whose input also carries the parity bootstrap's output) on the
 // half tables S / Dt [ntab][2^(w-1)], the second with b0 in the padding bit, so that the negacyclic wrap returns (-1)^b0 Dt[t'];
 // with sigma == 0 it is the plain 2^w-entry read.
+// in / out point at the first of `count` elements of a slice that starts at element e0 of the tensor (a sharded session; 0: the whole tensor).
 __global__ void k_lut_clear(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, size_t count, int shift, uint64_t body_add,
                             int p, int r, int w, const int64_t* __restrict__ tables, int hw, int nchan, int* __restrict__ overflow,
                             double sigma, rng_key seed, uint64_t stream, int approx, int split, double sigma2,
-                            const int64_t* __restrict__ tab_s, const int64_t* __restrict__ tab_d) {
+                            const int64_t* __restrict__ tab_s, const int64_t* __restrict__ tab_d, size_t e0) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t g = e0 + e;      // the element's number in the whole tensor: its channel's table and its noise draws go by it
     uint64_t v = (in[e] << shift) + body_add;
     if (r > 0 && !(approx && sigma > 0)) v += 1ULL << (63 - p + r - 1);
     if (v >> 63) atomicOr(overflow, 1);  // message left the padded range: an FHE run would wrap
     uint64_t idx = (v >> (63 - w)) & ((1ULL << w) - 1);
     if (sigma > 0 && split) {
-      const size_t ti = nchan > 1 ? (e / (size_t)hw) % (size_t)nchan : 0;
+      const size_t ti = nchan > 1 ? (g / (size_t)hw) % (size_t)nchan : 0;
       const uint64_t centre = (idx >> 1) << (64 - w);              // t' as a (w-1)-bit message under a clear padding bit
-      out[e] = noisy_lookup(centre, w - 1, tab_s + (ti << (w - 1)), seed, stream, 2 * e, sigma) +
-               noisy_lookup(centre + ((idx & 1) << 63), w - 1, tab_d + (ti << (w - 1)), seed, stream, 2 * e + 1, sigma2);
+      out[e] = noisy_lookup(centre, w - 1, tab_s + (ti << (w - 1)), seed, stream, 2 * g, sigma) +
+               noisy_lookup(centre + ((idx & 1) << 63), w - 1, tab_d + (ti << (w - 1)), seed, stream, 2 * g + 1, sigma2);
       continue;
     }
     if (sigma > 0) {
       // exact rounding: the value sits at the centre of its box; approximate: where its low bits put it (+ half an input unit)
       const uint64_t centre = approx && r > 0 ? v + (1ULL << (62 - p)) : (idx << (63 - w));
-      const size_t ti = nchan > 1 ? (e / (size_t)hw) % (size_t)nchan : 0;
-      out[e] = noisy_lookup(centre, w, tables + (ti << w), seed, stream, e, sigma);
+      const size_t ti = nchan > 1 ? (g / (size_t)hw) % (size_t)nchan : 0;
+      out[e] = noisy_lookup(centre, w, tables + (ti << w), seed, stream, g, sigma);
       continue;
     }
-    const size_t ti = nchan > 1 ? (e / (size_t)hw) % (size_t)nchan : 0;
+    const size_t ti = nchan > 1 ? (g / (size_t)hw) % (size_t)nchan : 0;
     out[e] = (uint64_t)tables[(ti << w) + idx];
   }
 }

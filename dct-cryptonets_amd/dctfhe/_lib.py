@@ -66,6 +66,8 @@ EXPORTS = [
     "dctfhe_public_key_export", "dctfhe_public_key_import", "dctfhe_public_key_destroy", "dctfhe_public_key_info", "dctfhe_public_key_export_rows",
     "dctfhe_public_key_set_encrypt_seed", "dctfhe_public_key_draws", "dctfhe_public_words", "dctfhe_encrypt_public", "dctfhe_ring_extract",
     "dctfhe_session_upload_public",
+    "dctfhe_shard_rows", "dctfhe_session_set_shard", "dctfhe_session_run_span", "dctfhe_session_shard_plan", "dctfhe_session_tensor",
+    "dctfhe_session_mark_whole", "dctfhe_session_copy_rows",
 ]
 
 _lib = None
@@ -176,6 +178,13 @@ def load():
     L.dctfhe_encrypt_public.argtypes = [vp, vp, vp, sz, vp]
     L.dctfhe_ring_extract.argtypes = [vp, i32, vp, sz, i32, vp]
     L.dctfhe_session_upload_public.argtypes = [vp, i32, vp, sz]
+    L.dctfhe_shard_rows.argtypes = [sz, i32, i32, C.POINTER(sz), C.POINTER(sz)]
+    L.dctfhe_session_set_shard.argtypes = [vp, i32, i32]
+    L.dctfhe_session_run_span.argtypes = [vp, i32, i32, C.POINTER(Timing)]
+    L.dctfhe_session_shard_plan.argtypes = [vp, vp, vp, i32, pi]
+    L.dctfhe_session_tensor.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
+    L.dctfhe_session_mark_whole.argtypes = [vp, i32]
+    L.dctfhe_session_copy_rows.argtypes = [vp, vp, i32, sz, sz]
     _lib = L
     return L
 

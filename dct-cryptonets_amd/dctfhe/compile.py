@@ -336,6 +336,26 @@ class CompiledCircuit:
                 out[nm] = out.get(nm, 0) + self._decisions(o)
         return out
 
+    def shard_plan(self):
+        """The exchange points of a run whose look-up sites are sharded over several GPUs (include/dctfhe.h dctfhe_session_shard_plan, the
+        same list): [(after_op, tensor)] in op order.  Look-ups and adds run on a part's rows and leave their output sliced; convolutions,
+        pools and the download read whole tensors -- so every sliced tensor one of them reads is exchanged once, right after the op that
+        writes it.  A tensor read by adds and look-ups only never travels.  The plan depends on the circuit alone."""
+        whole, writer, plan = [True] * len(self.tensors), {}, []
+
+        def need(t):
+            if not whole[t]:
+                plan.append((writer[t], t))
+                whole[t] = True
+        for i, o in enumerate(self.ops):
+            if o.type in (OP_LUT, OP_ADD):
+                whole[o.dst], writer[o.dst] = False, i
+            else:
+                need(o.src0)
+                whole[o.dst] = True
+        need(self.output_tensor)
+        return sorted(plan)
+
     def report(self):
         """Text dump standing in for `fhe_circuit.mlir` (reference homomorphic_eval.py:309-311)."""
         names = {OP_CONV: "conv2d", OP_ADD: "add", OP_SUMPOOL: "sum_pool", OP_LUT: "round_lut", OP_MAXPOOL: "max_pool2d"}
@@ -369,6 +389,16 @@ class CompiledCircuit:
         if self.rounding_method == "approximate":
             lines.append(f"// approximate rounding: expected boundary flips per image: {self.expected_boundary_flips_per_image:.2e}")
         return "\n".join(lines)
+
+
+def shard_rows(rows, parts, part):
+    """(first, count) of the rows part `part` of `parts` owns in a tensor of `rows` rows (include/dctfhe.h dctfhe_shard_rows, the same
+    rule): q = rows // parts, r = rows % parts; part p owns q + (p < r) consecutive rows from p q + min(p, r).  Empty parts are legal."""
+    rows, parts, part = int(rows), int(parts), int(part)
+    if rows < 0 or not 1 <= parts <= 64 or not 0 <= part < parts:
+        raise ValueError(f"shard_rows: part {part} of {parts} (1 .. 64 parts) of {rows} rows")
+    q, r = divmod(rows, parts)
+    return part * q + min(part, r), q + (1 if part < r else 0)
 
 
 @dataclass

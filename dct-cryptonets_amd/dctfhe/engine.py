@@ -709,6 +709,13 @@ class Keys:
         self.client.close()
 
 
+def shard_rows(rows, parts, part):
+    """(first, count) of part `part`'s rows of a tensor of `rows` rows: the library's partition rule (dctfhe_shard_rows; host-only)"""
+    f, n = C.c_size_t(), C.c_size_t()
+    check(_lib.load().dctfhe_shard_rows(int(rows), int(parts), int(part), C.byref(f), C.byref(n)))
+    return f.value, n.value
+
+
 class Circuit:
     def __init__(self, ctx, blob):
         self.ctx, self.L = ctx, ctx.L
@@ -787,6 +794,40 @@ class Session:
         t = Timing() if timing else None
         check(self.L.dctfhe_session_run(self.h, C.byref(t) if timing else None))
         return t
+
+    # -- sharded look-up sites (include/dctfhe.h dctfhe_session_set_shard): one image over several sessions, one per GPU ----------
+    def set_shard(self, part, parts):
+        """this session evaluates part `part` of `parts` of every look-up and add; (0, 1) is the plain run.  Before the first run only"""
+        check(self.L.dctfhe_session_set_shard(self.h, int(part), int(parts)))
+
+    def run_span(self, first_op, end_op, timing=False):
+        """ops [first_op, end_op) in order (dctfhe_session_run_span); refused at an op that needs a whole tensor which is still sliced"""
+        t = Timing() if timing else None
+        check(self.L.dctfhe_session_run_span(self.h, int(first_op), int(end_op), C.byref(t) if timing else None))
+        return t
+
+    def shard_plan(self):
+        """the exchange points [(after_op, tensor)] in op order (dctfhe_session_shard_plan; CompiledCircuit.shard_plan is the same list)"""
+        n = C.c_int()
+        check(self.L.dctfhe_session_shard_plan(self.h, None, None, 0, C.byref(n)))
+        a, t = np.empty(n.value, np.int32), np.empty(n.value, np.int32)
+        check(self.L.dctfhe_session_shard_plan(self.h, ptr(a), ptr(t), n.value, C.byref(n)))
+        return [(int(x), int(y)) for x, y in zip(a, t)]
+
+    def tensor(self, tensor):
+        """(device pointer, stored row stride in 64-bit words, rows) of a tensor of the circuit (dctfhe_session_tensor)"""
+        dev, L, rows = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        check(self.L.dctfhe_session_tensor(self.h, int(tensor), C.byref(dev), C.byref(L), C.byref(rows)))
+        return dev.value, L.value, rows.value
+
+    def mark_whole(self, tensor):
+        """every part's rows of `tensor` are in place in this session (dctfhe_session_mark_whole)"""
+        check(self.L.dctfhe_session_mark_whole(self.h, int(tensor)))
+
+    def copy_rows_from(self, src, tensor, first, count):
+        """rows [first, first + count) of `tensor` from session `src` (same circuit, batch and mode), device to device: the loopback
+        exchange of parts that share a process (dctfhe_session_copy_rows)"""
+        check(self.L.dctfhe_session_copy_rows(self.h, src.h, int(tensor), int(first), int(count)))
 
     def download(self, dim=None):
         if dim is None or self.keys is None:

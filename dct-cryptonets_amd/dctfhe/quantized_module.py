@@ -32,7 +32,7 @@ class Configuration:
 
     def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
                  compress_evaluation_keys=False, compress_output_ciphertexts=False, result_packing_spec=None, public_key_inputs=False,
-                 public_input_spec=None, **kwargs):
+                 public_input_spec=None, shard_image=False, **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
         # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
         # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
@@ -53,6 +53,11 @@ class Configuration:
         self.public_input_spec = public_input_spec
         if self.public_key_inputs and self.compress_input_ciphertexts:
             raise ValueError("public_key_inputs and compress_input_ciphertexts exclude each other: a seeded input is made with the secret key")
+        # dctfhe addition: under an initialised torch.distributed group of more than one rank, fhe="execute" spreads every image over the
+        # ranks' GPUs -- each evaluates its rows of the look-up sites, rows are exchanged where a convolution, a pool or the download
+        # reads a whole tensor (include/dctfhe.h dctfhe_session_set_shard).  Every rank calls forward with the same
+        # x and holds the same keys (keygen(seed=...) or load_evaluation_keys).  Off by default; one rank, or no group: the plain path.
+        self.shard_image = bool(shard_image)
         self.extra = kwargs
 
 
@@ -208,6 +213,26 @@ class QuantizedModule:
             if mode == "execute" and self._keys is None:
                 self._keygen(None)
             self._sessions[key] = Session(ctx, self._circuit, self._keys if mode == "execute" else None, batch)
+        return self._sessions[key]
+
+    def _shard_group(self):
+        """(rank, world) when Configuration(shard_image=True) meets an initialised torch.distributed group of more than one rank"""
+        if not self.configuration.shard_image:
+            return None
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() < 2:
+            return None
+        return dist.get_rank(), dist.get_world_size()
+
+    def _shard_session(self, batch, rank, world):
+        """this rank's part of an image-sharded encrypted run: a session of its own, sharded before its first run"""
+        if self._keys is None or not hasattr(self._keys, "decrypt"):
+            raise RuntimeError("shard_image: every rank needs the same client key before forward(): fhe_circuit.keygen(seed=...) with one seed on all ranks")
+        key = ("execute", ("shard", batch, rank, world))
+        if key not in self._sessions:
+            sess = Session(self._context(), self._circuit, self._keys, batch)
+            sess.set_shard(rank, world)
+            self._sessions[key] = sess
         return self._sessions[key]
 
     def output_compaction(self, form="rows"):
@@ -408,7 +433,8 @@ class QuantizedModule:
         phases = self.encode_input(q)
         B = q.shape[0]
         mode = "execute" if fhe == "execute" else "clear"
-        sess = self._session(mode, B)
+        shard = self._shard_group() if mode == "execute" else None
+        sess = self._session(mode, B) if shard is None else self._shard_session(B, *shard)
         if mode == "clear":
             # "simulate" = the integer circuit with the compiler's noise model sampled at every look-up (reference: Concrete's
             # simulation, homomorphic_eval.py:333-347); "disable" = noise-free.  At the exact tiers the two coincide.
@@ -435,7 +461,18 @@ class QuantizedModule:
             # Configuration(public_key_inputs=True): encrypted without the secret key, extracted on the GPU (priced first, like the above)
             public = self._own_public_key() if self.configuration.public_key_inputs else None
             t1 = time.time()
-            if public is not None:
+            if shard is not None:
+                # an image over the ranks' GPUs: rank 0 encrypts -- in the seeded form, or with the public key -- and its blob travels
+                # (kilobytes; a handle's encryption randomness is its own, so the ranks must not each encrypt); every rank expands it whole
+                import torch
+                from . import sharding
+                dev, seeded = torch.device("cuda", self.device), public is None
+                blob = b""
+                if shard[0] == 0:
+                    blob = (public.encrypt(phases.reshape(-1)) if public is not None else self._keys.encrypt_seeded(phases.reshape(-1))).to_bytes()
+                blob = sharding.broadcast_bytes(blob, shard[1], dev)
+                cts = PublicInputs.from_bytes(blob) if public is not None else SeededCiphertexts.from_bytes(blob)
+            elif public is not None:
                 cts = public.encrypt(phases.reshape(-1))
             else:
                 cts = self._keys.encrypt_seeded(phases.reshape(-1)) if seeded else self._keys.encrypt(phases.reshape(-1), in_dim)
@@ -447,7 +484,13 @@ class QuantizedModule:
             else:
                 sess.upload(cts, in_dim)
             t3 = time.time()
-            timing = sess.run(timing=True)
+            if shard is not None:
+                # run_span to each exchange point of the compiler's plan, the rows of that tensor between the ranks, mark_whole; the
+                # output is whole on every rank at the end, so each downloads and decrypts its own copy
+                spans, moved = sharding.run_sharded(sess, self.compiled.shard_plan(), len(self.compiled.ops), cc.shard_rows, shard[1], dev, timing=True)
+                timing = _sum_timings(spans)
+            else:
+                timing = sess.run(timing=True)
             t4 = time.time()
             if pack_tier is None:
                 out = sess.download(out_dim).reshape(-1, out_dim + 1)
@@ -466,6 +509,8 @@ class QuantizedModule:
             self.last_io = dict(encrypt_s=t2 - t1, upload_s=t3 - t2, run_s=t4 - t3, download_s=t5 - t4, decrypt_s=time.time() - t5,
                                 input_bytes=int(cts.words.nbytes if public is not None else cts.nbytes), output_bytes=int(out.nbytes),
                                 upload_bytes=int(cts.words.nbytes if public is not None else cts.bodies.nbytes if seeded else cts.nbytes))
+            if shard is not None:
+                self.last_io.update(shard=shard, exchanged_bytes=int(moved))
         else:
             sess.upload(phases)
             timing = sess.run(timing=True)
@@ -478,6 +523,8 @@ class QuantizedModule:
     def audit_quantized(self, q):
         """An encrypted pass over integer inputs q [B, C, H, W] with the margin audit on: (decoded outputs [B, F], MarginReport).  Every
         bootstrap decision of the run is measured with the client's secret key, so it runs where the client key is."""
+        if self.configuration.shard_image:
+            raise RuntimeError("the margin audit stays unsharded: audit() is refused under Configuration(shard_image=True)")
         if self._keys is not None and not hasattr(self._keys, "decrypt"):
             raise RuntimeError("the margin audit needs the client key (fhe_circuit.keygen); this module holds evaluation keys only")
         phases = self.encode_input(q)
@@ -519,6 +566,21 @@ class QuantizedModule:
         if self._ctx is not None:
             self._ctx.close()
             self._ctx = None
+
+
+def _sum_timings(spans):
+    """the spans of a sharded pass as one Timing: every field summed"""
+    from ._lib import MAX_TIERS, Timing
+    out = Timing()
+    for t in spans:
+        out.total_ms += t.total_ms
+        out.ks_ms += t.ks_ms
+        out.linear_ms += t.linear_ms
+        for i in range(MAX_TIERS):
+            out.pbs_ms[i] += t.pbs_ms[i]
+            out.pbs_launches[i] += t.pbs_launches[i]
+            out.pbs_cts[i] = t.pbs_cts[i]
+    return out
 
 
 def _as_numpy(t):

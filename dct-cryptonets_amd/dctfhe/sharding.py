@@ -5,6 +5,10 @@ time inside forward(), homomorphic_eval.py:70), so a batch shards by image: rank
 r, r+G, r+2G, ...  Keys and circuit are regenerated per rank from the seed; the only exchange on the data
 path is one all_gather of the decrypted-side logits (RCCL on GPUs, gloo in the CPU tests).
 
+Sharding ONE image: the look-up sites of an image are element-wise, so `parts` sessions each evaluate their rows of
+every look-up and add (dctfhe.engine.Session.set_shard) and exchange rows only where a convolution, a pool or the download reads a whole
+tensor (CompiledCircuit.shard_plan).  exchange_rows is that exchange, broadcast_bytes ships rank 0's input blob, run_sharded walks the plan.
+
 Every collective bench.py issues lives here, so that the CPU tests (gloo, world size 2) and the one-rank RCCL smoke test
 (tests/test_gpu_rccl_smoke.py: `nccl` backend on cuda:0) run the very calls the 8-GPU job makes."""
 import torch
@@ -67,3 +71,81 @@ def all_true(flag, world, dev):
 def barrier(world):
     if _live(world):
         dist.barrier()
+
+
+def _collective_device(dev):
+    """where a collective's tensors live: the GPU under RCCL, host memory under gloo"""
+    return torch.device("cpu") if dist.get_backend() == "gloo" else dev
+
+
+def broadcast_bytes(data, world, dev, src=0):
+    """rank `src`'s bytes to every rank (the seeded or public-key input blob of a sharded image: kilobytes, never the rows)"""
+    if not _live(world):
+        return bytes(data)
+    cdev = _collective_device(dev)
+    mine = dist.get_rank() == src
+    n = torch.tensor([len(data) if mine else 0], dtype=torch.int64, device=cdev)
+    dist.broadcast(n, src)
+    if mine:
+        t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(cdev)
+    else:
+        t = torch.empty(int(n.item()), dtype=torch.uint8, device=cdev)
+    dist.broadcast(t, src)
+    return bytes(t.cpu().numpy().tobytes())
+
+
+class _DeviceRows:
+    """rows of 64-bit words in device memory, as torch.as_tensor reads them without a copy"""
+
+    def __init__(self, dev_ptr, rows, row_words):
+        self.__cuda_array_interface__ = dict(shape=(int(rows), int(row_words)), typestr="<i8", data=(int(dev_ptr), False), version=2, strides=None)
+
+
+def tensor_view(session, tensor, dev):
+    """a session's tensor [rows, row_words] as an int64 torch tensor on `dev` over the session's own memory (Session.tensor)"""
+    dev_ptr, row_words, rows = session.tensor(tensor)
+    return torch.as_tensor(_DeviceRows(dev_ptr, rows, row_words), device=dev)
+
+
+def exchange_rows(tensor_view, ranges, world):
+    """Every part's rows of one tensor into every rank's copy: one broadcast per part of that part's row range ranges[p] = (first, count),
+    straight from and into `tensor_view` (rows are contiguous).  Uneven ranges need no padding and an empty one no call; under gloo the
+    rows are staged through host memory.  Returns the bytes this rank sent or received.  The engine's run is synchronous, so the rows are
+    there when this is called; it returns once they are in place."""
+    if len(ranges) != world:
+        raise ValueError(f"exchange_rows: {len(ranges)} row ranges for {world} ranks")
+    if not _live(world):
+        return 0
+    rank, staged, moved = dist.get_rank(), dist.get_backend() == "gloo", 0
+    for p, (first, count) in enumerate(ranges):
+        if count == 0:
+            continue
+        rows = tensor_view[first:first + count]
+        if staged:
+            buf = rows.cpu() if rank == p else torch.empty(rows.shape, dtype=rows.dtype)
+            dist.broadcast(buf, p)
+            if rank != p:
+                rows.copy_(buf)
+        else:
+            dist.broadcast(rows, p)
+        if world > 1:
+            moved += rows.numel() * 8
+    if tensor_view.is_cuda:
+        torch.cuda.synchronize(tensor_view.device)
+    return moved
+
+
+def run_sharded(session, plan, n_ops, shard_rows, world, dev, timing=False):
+    """A sharded session's pass over the circuit: run_span up to each exchange point of `plan` [(after_op, tensor)], exchange_rows,
+    mark_whole; then the rest.  -> (timings of the spans, bytes exchanged)"""
+    timings, moved, first = [], 0, 0
+    for after_op, tensor in plan:
+        if after_op + 1 > first:
+            timings.append(session.run_span(first, after_op + 1, timing))
+            first = after_op + 1
+        view = tensor_view(session, tensor, dev)
+        moved += exchange_rows(view, [shard_rows(view.shape[0], world, p) for p in range(world)], world)
+        session.mark_whole(tensor)
+    if first < n_ops:
+        timings.append(session.run_span(first, n_ops, timing))
+    return timings, moved

@@ -63,6 +63,9 @@ def parse_args():
                         "ciphertext (the client's packing key is made after keygen and loaded)")
     e.add_argument("--public_key_inputs", action="store_true",
                    help="encrypt the inputs without the secret key, through a public key made after keygen; the GPU extracts the rows")
+    e.add_argument("--shard_image", action="store_true",
+                   help="under torch.distributed.run: spread every encrypted image over the ranks' GPUs (each evaluates its rows of the "
+                        "look-up sites); one key seed is broadcast from rank 0.  Off, or a single process: the plain path")
     return parser.parse_args()
 
 
@@ -126,7 +129,17 @@ def main():
     calib_data, _ = make(params.calib_batch_size, params.seed + 100)
     print("\nCompiling FHE Model (this can take up to 10 minutes for larger networks)...")
     configuration = Configuration(show_progress=False, progress_tag=True, progress_title="Evaluation: ",
-                                  compress_output_ciphertexts=params.compress_outputs, public_key_inputs=params.public_key_inputs)
+                                  compress_output_ciphertexts=params.compress_outputs, public_key_inputs=params.public_key_inputs,
+                                  shard_image=params.shard_image)
+    key_seed = None
+    if params.shard_image and "RANK" in os.environ:      # one rank per GPU; every rank needs the same keys: rank 0's seed travels
+        import torch.distributed as dist
+        from dctfhe import sharding
+        params.device = int(os.environ.get("LOCAL_RANK", 0))
+        torch.cuda.set_device(params.device)
+        dist.init_process_group("nccl")
+        key_seed = sharding.broadcast_seed(os.urandom(32), dist.get_world_size(), torch.device("cuda", params.device))
+        params.verbose = params.verbose and dist.get_rank() == 0
     t = time.time()
     compile_fn = compile_brevitas_qat_model if quantization_type == "QAT" else compile_torch_model
     rtb = params.rounding_threshold_bits if params.rounding_method == "exact" else {"n_bits": params.rounding_threshold_bits, "method": "approximate"}
@@ -139,7 +152,7 @@ def main():
         with open("mlir.txt", "a") as f:
             print(q_module.fhe_circuit.mlir, file=f)
     t = time.time()
-    q_module.fhe_circuit.keygen()
+    q_module.fhe_circuit.keygen(seed=key_seed)
     print(f"Keygen time: {time.time() - t:.2f}s")
     if params.compress_outputs == "ring" and params.fhe_mode == "execute":
         t = time.time()

@@ -438,6 +438,36 @@ int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* client);
  * *n_slots = 0.  capacity < *n_slots is refused. */
 int dctfhe_session_audit(dctfhe_session* s, dctfhe_margin_stats* out, int capacity, int* n_slots);
 
+/* SHARDED LOOK-UP SITES: one image over `parts` sessions, one per GPU.  Opt-in; the default (0, 1) is the plain run.
+ *
+ * Partition rule (every element-wise tensor; a "row" is one ciphertext of the flat [B][C][H][W] order): with q = rows / parts and
+ * r = rows % parts, part p owns the q + (p < r) consecutive rows from p q + min(p, r).  Empty parts are legal (rows < parts).
+ * shard_rows is host-only (no GPU); refused: parts < 1, parts > 64, part outside [0, parts).
+ *
+ * Every tensor of a session is WHOLE or SLICED (only this part's rows are valid).  The input is whole after an upload.  Look-ups and adds
+ * run on this part's rows only, read the same rows of their sources (a whole source may feed them) and leave their destination sliced.
+ * Convolutions, sum pools, max pools and every download need whole sources; they are computed in full on every part (a max pool's own
+ * bootstraps included) and leave whole destinations.  Nothing on the server side is random, so a row does not depend on the launch it
+ * was computed in: a sharded run reproduces the unsharded output ciphertexts word for word.
+ *
+ * set_shard: refused once the session has run, and while the margin audit is on (the audit stays unsharded; set_audit likewise refuses
+ * a sharded session).
+ * run_span: ops [first_op, end_op) in order, synchronous like dctfhe_session_run; an op that needs a whole tensor which is sliced is
+ * refused with its number and the tensor's.  dctfhe_session_run is run_span over the whole circuit, for every (part, parts).
+ * shard_plan: the exchange points, in op order: one entry per sliced tensor that a whole-needing op or the download reads, placed after
+ * the op that writes the tensor.  It depends on the circuit only.  after_op / tensor == NULL: only *n is written; capacity < *n is refused.
+ * At an entry the caller brings every part's rows of `tensor` into every session (session_tensor: the device pointer, the stored row
+ * stride in words and the row count; between processes a broadcast per part) and then calls mark_whole.
+ * copy_rows: rows [first, first + count) of `tensor` from src to dst, device to device, on dst's stream after src's work -- the loopback
+ * that lets one process and one GPU run all parts.  Refused: sessions of different circuits, batches or modes, rows out of range. */
+int dctfhe_shard_rows(size_t rows, int parts, int part, size_t* first, size_t* count);
+int dctfhe_session_set_shard(dctfhe_session* s, int part, int parts);
+int dctfhe_session_run_span(dctfhe_session* s, int first_op, int end_op, dctfhe_timing* timing /* may be NULL */);
+int dctfhe_session_shard_plan(dctfhe_session* s, int32_t* after_op, int32_t* tensor, int capacity, int* n);
+int dctfhe_session_tensor(dctfhe_session* s, int tensor, void** dev, size_t* row_words, size_t* rows);
+int dctfhe_session_mark_whole(dctfhe_session* s, int tensor);
+int dctfhe_session_copy_rows(dctfhe_session* dst, dctfhe_session* src, int tensor, size_t first, size_t count);
+
 /* f64 FMA peak micro-benchmark (TFLOP/s) used to price the blind-rotate kernel in bench.py. */
 int dctfhe_fp64_peak(dctfhe_ctx* ctx, double* tflops);
 /* stand-alone timing of the blind-rotate kernel: count ciphertexts of tier `tier`, average ms per launch */

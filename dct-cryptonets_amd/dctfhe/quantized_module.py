@@ -24,7 +24,8 @@ import numpy as np
 
 from . import compile as cc
 from . import params as P
-from .engine import Circuit, Context, Keys, PackedCiphertexts, PackedRing, PackKey, PublicInputs, PublicKey, SeededCiphertexts, Session
+from . import roles
+from .engine import Circuit, Context, Keys, PackKey, PublicInputs, PublicKey, SeededCiphertexts, Session
 
 
 class Configuration:
@@ -61,13 +62,7 @@ class Configuration:
         self.extra = kwargs
 
 
-def _output_form(v):
-    """a compress_output_ciphertexts / packed value -> False, True (16-bit rows) or the string ring"""
-    if isinstance(v, str):
-        if v not in ("none", "rows", "ring"):
-            raise ValueError(f"compress_output_ciphertexts {v!r} (False, True / 'rows', or 'ring')")
-        return {"none": False, "rows": True, "ring": "ring"}[v]
-    return bool(v)
+_output_form = roles.output_form
 
 
 class MarginReport:
@@ -287,11 +282,11 @@ class QuantizedModule:
         plan = self.public_input_plan()
         ctx = self._context()
         pk = PublicKey(ctx, blob)
-        if pk.logN != plan.spec.logN or pk.sigma > plan.spec.sigma:
-            got = (pk.logN, pk.sigma)
+        try:
+            roles.check_public_key(plan, pk)
+        except RuntimeError:
             pk.close()
-            raise RuntimeError(f"the public key (logN {got[0]}, sigma {got[1]:.3g}) is not covered by the spec this configuration priced "
-                               f"(logN {plan.spec.logN}, sigma {plan.spec.sigma:.3g})")
+            raise
         if self._public_key is not None:
             self._public_key.close()
         self._public_key, self._public_key_of = pk, None
@@ -300,8 +295,7 @@ class QuantizedModule:
         """data-owner side: float inputs [B, C, H, W] -> PublicInputs (quantise, encode, encrypt with the loaded public key)"""
         if self._public_key is None:
             raise RuntimeError("encrypt_public needs the client's public key: fhe_circuit.load_public_key(blob)")
-        q = self.quantize_input(np.asarray(x))
-        return self._public_key.encrypt(self.encode_input(q).reshape(-1))
+        return roles.encrypt_public(self.compiled, self._public_key, x)
 
     def _own_public_key(self):
         """forward(fhe="execute") under Configuration(public_key_inputs=True): this module's own public key, made once per key set"""
@@ -312,18 +306,7 @@ class QuantizedModule:
 
     def _ring_plan(self):
         """(tier, packing key) of a ring-packed download; refuses before anything runs"""
-        oc = self.output_compaction("ring")
-        pk = self._pack_key
-        if pk is None:
-            raise RuntimeError('compress_output_ciphertexts="ring" needs the client\'s result packing key: '
-                               "fhe_circuit.load_result_packing_key(fhe_circuit.export_result_packing_key())")
-        if (pk.logN, pk.l, pk.beta) != (oc.spec.logN, oc.spec.l, oc.spec.beta) or pk.n_max < oc.n:
-            raise RuntimeError(f"the loaded result packing key (logN {pk.logN}, {pk.l} x {pk.beta} bits, n_max {pk.n_max}) is not the one this "
-                               f"configuration prices (logN {oc.spec.logN}, {oc.spec.l} x {oc.spec.beta} bits, n {oc.n})")
-        if pk.sigma > oc.spec.sigma:
-            raise RuntimeError(f"the loaded result packing key is noisier (sigma {pk.sigma:.3g}) than the spec this configuration priced "
-                               f"({oc.spec.sigma:.3g}): its p_fail is not covered")
-        return oc.tier, pk
+        return roles.ring_plan(self.output_compaction("ring"), self._pack_key)
 
     # -- client / server split (reference homomorphic_eval.py:313-317 keeps both halves in one process) ------------
     def export_evaluation_keys(self, compressed=None):
@@ -357,31 +340,16 @@ class QuantizedModule:
         PublicInputs (or their to_bytes() form, told from seeded bytes by the magic): the rows are extracted on the GPU, likewise.
         packed (default: Configuration.compress_output_ciphertexts): True / "rows": the outputs as PackedCiphertexts instead, "ring": as
         a PackedRing (needs load_result_packing_key), whatever dim says"""
-        if isinstance(cts, (bytes, bytearray, memoryview)):
-            cts = PublicInputs.from_bytes(cts) if bytes(cts[:4]) == PublicInputs.MAGIC else SeededCiphertexts.from_bytes(cts)
+        cts = roles.parse_inputs(cts)
         if isinstance(cts, PublicInputs):
             self.public_input_plan()          # refuses before anything runs
         packed = self.configuration.compress_output_ciphertexts if packed is None else _output_form(packed)
+        pack_key = None
         if packed == "ring":
             tier, pack_key = self._ring_plan()
         else:
             tier = self.output_compaction().tier if packed else None
-        sess = self._session("execute", batch)
-        if isinstance(cts, SeededCiphertexts):
-            sess.upload_seeded(cts)
-        elif isinstance(cts, PublicInputs):
-            sess.upload_public(cts)
-        else:
-            sess.upload(cts, dim)
-        sess.run()
-        if packed == "ring":
-            return sess.download_ring(tier, pack_key)
-        if packed:
-            return sess.download_packed(tier)
-        if dim is None:
-            return sess.download().reshape(-1, self._keys.D + 1)
-        out_dim = sess.dims()[1]
-        return sess.download(out_dim).reshape(-1, out_dim + 1)
+        return roles.evaluate_encrypted(self._session("execute", batch), self._keys, cts, dim, packed, tier, pack_key)
 
     def statistics(self):
         self._context()
@@ -389,35 +357,23 @@ class QuantizedModule:
 
     # -- quantisation at the boundary ----------------------------------------------------
     def quantize_input(self, x):
-        c = self.compiled
-        return cc.act_quant(np.asarray(x, np.float64), c.in_scale, True, c.in_bits)
+        return roles.quantize_input(self.compiled, x)
 
     def encode_input(self, q):
-        return (q.astype(np.int64).astype(np.uint64) << np.uint64(self.compiled.e_in)).reshape(q.shape[0], -1)
+        return roles.encode_input(self.compiled, q)
 
     def decode_output(self, phases):
-        e = self.compiled.e_out
-        v = (phases + (np.uint64(1) << np.uint64(e - 1))).view(np.int64) >> np.int64(e)     # signed, rounded
-        return v
+        return roles.decode_output(self.compiled, phases)
 
     def decrypt_result(self, x):
         """client side: what evaluate_encrypted returned -> decoded integers [B, F].  x: PackedCiphertexts or a PackedRing, or the
         to_bytes() form of either, or rows [B * F, dim + 1] of uint64 (full width or the compact wire form)"""
         if self._keys is None or not hasattr(self._keys, "decrypt"):
             raise RuntimeError("decrypting needs the client key (fhe_circuit.keygen); this module holds evaluation keys only")
-        if isinstance(x, (bytes, bytearray, memoryview)):
-            x = PackedRing.from_bytes(x) if bytes(x[:4]) == PackedRing.MAGIC else PackedCiphertexts.from_bytes(x)
-        if isinstance(x, PackedRing):
-            ph = self._keys.decrypt_ring(x)
-        elif isinstance(x, PackedCiphertexts):
-            ph = self._keys.decrypt_packed(x)
-        else:
-            x = np.asarray(x)
-            ph = self._keys.decrypt(x, x.shape[-1] - 1)
-        return self.decode_output(ph.reshape(-1, self.compiled.n_out()))
+        return roles.decrypt_result(self.compiled, self._keys, x)
 
     def dequantize_output(self, q):
-        return q.astype(np.float64) * self.compiled.out_scale
+        return roles.dequantize_output(self.compiled, q)
 
     # -- the reference's entry point -----------------------------------------------------
     def forward(self, x, fhe="disable"):

@@ -54,6 +54,7 @@ struct dctfhe_ctx {
   int device = 0;
   hipStream_t stream = nullptr, own = nullptr;
   hipDeviceProp_t prop;
+  int max_grid_y = 0, max_grid_z = 0;      // hipDeviceAttributeMaxGridDimY / Z: what a launch grid may hold (dev_conv2d)
   ~dctfhe_ctx() { if (own) hipStreamDestroy(own); }
 };
 
@@ -484,6 +485,8 @@ extern "C" int dctfhe_ctx_create(int device_id, dctfhe_ctx** out) {
   std::unique_ptr<dctfhe_ctx> c(new dctfhe_ctx);
   c->device = device_id;
   HIPCHK(hipGetDeviceProperties(&c->prop, device_id));
+  HIPCHK(hipDeviceGetAttribute(&c->max_grid_y, hipDeviceAttributeMaxGridDimY, device_id));
+  HIPCHK(hipDeviceGetAttribute(&c->max_grid_z, hipDeviceAttributeMaxGridDimZ, device_id));
   HIPCHK(hipStreamCreate(&c->own));
   c->stream = c->own;
   *out = c.release();
@@ -1323,12 +1326,24 @@ static int dev_ks_pbs(dctfhe_keys* K, int tier, const KsInput& in, size_t count,
   return dev_pbs(K, tier, sc.small(), count, lut, out, tm);
 }
 
-static int dev_conv2d(hipStream_t st, const uint64_t* in, int batch, int Cin, int H, int W, size_t Lin, size_t deff, const int8_t* d_w, const ConvPack* pk, int Cout,
+// Both kernels put one output pixel per block of gridDim.y and one block of output channels per block of gridDim.z: a launch beyond what
+// the device reports for either is refused here, by its numbers, instead of surfacing as a launch error
+static int conv_grid_ok(const dctfhe_ctx* cx, size_t pixels, size_t blocks) {
+  if (pixels > (size_t)cx->max_grid_y)
+    return fail("convolution: %zu output pixels (batch x Ho x Wo) exceed the device's launch-grid limit of %d: run it in smaller batches", pixels, cx->max_grid_y);
+  if (blocks > (size_t)cx->max_grid_z)
+    return fail("convolution: %zu blocks of output channels exceed the device's launch-grid limit of %d", blocks, cx->max_grid_z);
+  return 0;
+}
+static int dev_conv2d(const dctfhe_ctx* cx, const uint64_t* in, int batch, int Cin, int H, int W, size_t Lin, size_t deff, const int8_t* d_w, const ConvPack* pk, int Cout,
                       int KH, int KW, int stride, int pad, uint64_t* out, size_t Lout) {
+  hipStream_t st = cx->stream;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+  const size_t pixels = (size_t)batch * Ho * Wo;
   if (pk && pk->d_w && Lout >= 32) {
+    CHK(conv_grid_ok(cx, pixels, (size_t)(Cout + 63) / 64));
     // ciphertext rows: the contraction over (ci, ky, kx) on the matrix cores, input words split into signed byte limbs on the fly
-    dim3 grid((unsigned)((Lout + 31) / 32), (unsigned)(batch * Ho * Wo), (unsigned)((Cout + 63) / 64));
+    dim3 grid((unsigned)((Lout + 31) / 32), (unsigned)pixels, (unsigned)((Cout + 63) / 64));
     hipLaunchKernelGGL(k_conv2d_mfma, grid, dim3(256), 0, st, in, H, W, Lin, deff, pk->d_w, pk->d_taps, pk->kpad, Cin * H * W, Cout, stride, Ho, Wo, Lout, out);
     HIPCHK(hipGetLastError());
     return 0;
@@ -1337,7 +1352,8 @@ static int dev_conv2d(hipStream_t st, const uint64_t* in, int batch, int Cin, in
   // 16 output channels per thread: 32 / 64 (fewer re-reads of the input) measured 1.45x / 3.5x SLOWER -- their per-tap weights no
   // longer fit the scalar registers (profiles/r02_exp_ablations.log)
   constexpr int COT = 16;
-  dim3 grid((unsigned)((Lout + 255) / 256), (unsigned)(batch * Ho * Wo), (unsigned)((Cout + COT - 1) / COT));
+  CHK(conv_grid_ok(cx, pixels, (size_t)(Cout + COT - 1) / COT));
+  dim3 grid((unsigned)((Lout + 255) / 256), (unsigned)pixels, (unsigned)((Cout + COT - 1) / COT));
   hipLaunchKernelGGL(k_conv2d<COT>, grid, dim3(256), 0, st, in, Cin, H, W, Lin, deff, d_w, Cout, KH, KW, stride, pad, Ho, Wo, Lout, out);
   HIPCHK(hipGetLastError());
   return 0;
@@ -1970,15 +1986,24 @@ extern "C" int dctfhe_round_lut(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int bit_ti
   return dctfhe_round_lut_split(ctx, K, bit_tier, tab_tier, w == 7 ? tab_tier : -1, cts, count, p, r, tables, ntab, w, table_idx, cts_out);
 }
 
-extern "C" int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int batch, int Cin, int H, int W, const int8_t* weight, int Cout,
-                             int KH, int KW, int stride, int pad, uint64_t* out) {
-  if (!ctx) return fail("dctfhe_conv2d: null context");
-  if (D < 0 || batch < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0) return fail("dctfhe_conv2d: bad geometry");
-  if (H + 2 * pad < KH || W + 2 * pad < KW) return fail("dctfhe_conv2d: kernel larger than the padded input");
+// K1 one kernel at a time on host buffers, on rows at an effective dimension (the storage form of a session's tensors; see the K2 entry
+// points below): the same dev_conv2d and the same ConvPack as the session, so the matrix-core kernel runs exactly when it would there
+static int rows_ok(const char* what, int dim, int deff) {
+  if (dim < 0 || deff < 0 || deff > dim || dim > (1 << 16)) return fail("%s: rows of %d mask words with effective dimension %d", what, dim, deff);
+  return 0;
+}
+static int conv2d_rows(const char* what, dctfhe_ctx* ctx, const uint64_t* in, int dim_in, int deff_in, int batch, int Cin, int H, int W, const int8_t* weight,
+                       int Cout, int KH, int KW, int stride, int pad, int dim_o, uint64_t* out) {
+  if (!ctx) return fail("%s: null context", what);
+  if (!in || !weight || !out) return fail("%s: null argument", what);
+  if (dim_in < 0 || dim_o < 0 || batch < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0) return fail("%s: bad geometry", what);
+  if (H + 2 * pad < KH || W + 2 * pad < KW) return fail("%s: kernel larger than the padded input", what);
+  CHK(rows_ok(what, dim_in, deff_in));
+  if (dim_o < deff_in || dim_o > (1 << 16)) return fail("%s: output rows of %d mask words cannot hold the result (%d needed)", what, dim_o, deff_in);
   HIPCHK(hipSetDevice(ctx->device));
-  const size_t L = (size_t)D + 1;
+  const size_t Li = (size_t)dim_in + 1, Lo = (size_t)dim_o + 1;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-  const size_t nin = (size_t)batch * Cin * H * W * L, nout = (size_t)batch * Cout * Ho * Wo * L, nw = (size_t)Cout * Cin * KH * KW;
+  const size_t nin = (size_t)batch * Cin * H * W * Li, nout = (size_t)batch * Cout * Ho * Wo * Lo, nw = (size_t)Cout * Cin * KH * KW;
   DevBuf d_in, d_out, d_w;
   HIPCHK(d_in.upload(in, nin * 8));
   HIPCHK(d_out.alloc(nout * 8));
@@ -1986,18 +2011,23 @@ extern "C" int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int bat
   DevBuf slab;
   std::vector<ConvPack> pk;
   CHK(build_conv_packs({weight}, {ConvSite{Cout, Cin, H, W, KH, KW, stride, pad}}, &slab, &pk));
-  CHK(dev_conv2d(ctx->stream, d_in.as<uint64_t>(), batch, Cin, H, W, L, L - 1, d_w.as<int8_t>(), &pk[0], Cout, KH, KW, stride, pad, d_out.as<uint64_t>(), L));
+  CHK(dev_conv2d(ctx, d_in.as<uint64_t>(), batch, Cin, H, W, Li, (size_t)deff_in, d_w.as<int8_t>(), &pk[0], Cout, KH, KW, stride, pad, d_out.as<uint64_t>(), Lo));
   HIPCHK(d_out.download(out, nout * 8, ctx->stream));
   return 0;
+}
+extern "C" int dctfhe_conv2d_rows(dctfhe_ctx* ctx, const uint64_t* in, int dim_in, int deff_in, int batch, int Cin, int H, int W, const int8_t* weight, int Cout,
+                                  int KH, int KW, int stride, int pad, int dim_o, uint64_t* out) {
+  return conv2d_rows("dctfhe_conv2d_rows", ctx, in, dim_in, deff_in, batch, Cin, H, W, weight, Cout, KH, KW, stride, pad, dim_o, out);
+}
+// full-width rows: dim_in = deff_in = dim_o = D (under its own name, so that its messages read as they always did)
+extern "C" int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int batch, int Cin, int H, int W, const int8_t* weight, int Cout,
+                             int KH, int KW, int stride, int pad, uint64_t* out) {
+  return conv2d_rows("dctfhe_conv2d", ctx, in, D, D, batch, Cin, H, W, weight, Cout, KH, KW, stride, pad, D, out);
 }
 
 // ---- K2 (residual add, rounding offset / shift, window-sum pooling) one kernel at a time on host buffers.  Rows of `dim` mask words +
 // body of which the first `deff` may be non-zero -- the storage form of the session's tensors, so that the kernels are checked at mixed
 // effective dimensions outside a circuit (reference backbone.py:102 torch.add, :276 AvgPool2d).
-static int rows_ok(const char* what, int dim, int deff) {
-  if (dim < 0 || deff < 0 || deff > dim || dim > (1 << 16)) return fail("%s: rows of %d mask words with effective dimension %d", what, dim, deff);
-  return 0;
-}
 extern "C" int dctfhe_add_rows(dctfhe_ctx* ctx, const uint64_t* a, int dim_a, int deff_a, const uint64_t* b, int dim_b, int deff_b, size_t count, int dim_o,
                                uint64_t* out) {
   if (!ctx || !a || !b || !out) return fail("dctfhe_add_rows: null argument");
@@ -2786,7 +2816,7 @@ static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_t
     switch (o.type) {
       case OP_CONV: {
         const int h = tm.begin(CAT_LINEAR);
-        CHK(dev_conv2d(st, src, B, a.C, a.H, a.W, Ls, ds, c->d_payload[i].as<int8_t>(), &c->conv[i], o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride, o.conv.pad, dst, Ld));
+        CHK(dev_conv2d(s->ctx, src, B, a.C, a.H, a.W, Ls, ds, c->d_payload[i].as<int8_t>(), &c->conv[i], o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride, o.conv.pad, dst, Ld));
         tm.end(h);
         break;
       }

@@ -119,6 +119,17 @@ class Context:
         check(self.L.dctfhe_conv2d(self.h, D, ptr(cts), batch, Cin, H, W, ptr(weight), Cout, KH, KW, stride, pad, ptr(out)))
         return out
 
+    def conv2d_rows(self, x, deff, weight, stride, pad, dim_o):
+        """x [batch, Cin, H, W, dim + 1] rows at effective dimension deff, weight int8 [Cout, Cin, KH, KW] -> [batch, Cout, Ho, Wo, dim_o + 1]
+        (include/dctfhe.h dctfhe_conv2d_rows: the session's convolution, matrix cores when dim_o + 1 >= 32)"""
+        x, weight = np.ascontiguousarray(x, np.uint64), np.ascontiguousarray(weight, np.int8)
+        B, Cin, H, W, L = x.shape
+        Cout, _, KH, KW = weight.shape
+        Ho, Wo = (max(H + 2 * pad - KH, 0) // max(stride, 1) + 1, max(W + 2 * pad - KW, 0) // max(stride, 1) + 1)   # the library checks the geometry
+        out = np.empty((B, Cout, Ho, Wo, max(dim_o, 0) + 1), np.uint64)
+        check(self.L.dctfhe_conv2d_rows(self.h, ptr(x), L - 1, deff, B, Cin, H, W, ptr(weight), Cout, KH, KW, stride, pad, dim_o, ptr(out)))
+        return out
+
     def expand_seeded(self, sc, dim=None):
         """SeededCiphertexts -> rows of dim mask words + body (None: sc.input_dim, the compact wire form of ClientKey.encrypt)"""
         dim = sc.input_dim if dim is None else int(dim)

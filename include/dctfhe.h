@@ -214,6 +214,14 @@ int dctfhe_affine_rows(dctfhe_ctx* ctx, const uint64_t* a, int dim_a, int deff_a
                        int dim_o, uint64_t* inout);
 int dctfhe_sum_pool_rows(dctfhe_ctx* ctx, const uint64_t* in /* [batch][C][H][W] rows */, int dim_in, int deff_in, int batch, int C, int H,
                          int W, int K, int dim_o, uint64_t* out /* [batch][C][H/K][W/K] rows */);
+/* K1 on rows: dctfhe_conv2d as the session runs it, on input rows of dim_in mask words + body whose mask words from deff_in on count as
+ * zero (and are not read) into output rows of dim_o >= deff_in mask words: words [deff_in, dim_o) are zero, the body is last.  The
+ * matrix-core kernel is taken exactly when the session takes it (dim_o + 1 >= 32), the integer-VALU kernel otherwise.  dctfhe_conv2d is
+ * this call with dim_in = deff_in = dim_o = D.  A launch whose batch x Ho x Wo output pixels (or whose output-channel blocks) exceed the
+ * device's launch-grid limit is refused with a message that names both numbers. */
+int dctfhe_conv2d_rows(dctfhe_ctx* ctx, const uint64_t* in /* [batch][Cin][H][W] rows of dim_in+1 */, int dim_in, int deff_in, int batch,
+                       int Cin, int H, int W, const int8_t* weight /* [Cout][Cin][KH][KW] */, int Cout, int KH, int KW, int stride,
+                       int pad, int dim_o, uint64_t* out /* [batch][Cout][Ho][Wo] rows of dim_o+1 */);
 
 /* max pool (circuit op 5), one piece at a time on host buffers.
  * keyswitch_diff: key switch of cts[ia[c]] - cts[ib[c]] (count rows of D + 1 words and count index pairs, indices < count), shifted

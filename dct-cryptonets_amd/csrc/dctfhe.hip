@@ -228,28 +228,46 @@ struct PoolPlan {
   std::vector<PoolLevel> lv;
   size_t rows_buf[2] = {0, 0};  // rows of level buffers A and B
   size_t pairs_per_batch = 0;
+  // the output rows the plan computes (all of them unless the pool is divided), the smallest range of source rows that holds every tap
+  // it reads, and the range of row-pass results [B*C*H][Wo] that holds its intermediates (the clear-mode `mid` buffer)
+  size_t out_first = 0, out_count = 0, in_first = 0, in_count = 0, mid_first = 0, mid_count = 0;
   DevBuf maps;
 };
-static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, PoolPlan* P) {
+// range == nullptr: the whole op, every row-pass result computed.  range = {first, count}: a divided pool's part (dctfhe_shard_pool) -- the
+// output rows [first, first + count) of [B][C][Ho][Wo], and of the row pass only the results (b, c, y, xo) that the column pass of one of
+// these outputs reads.  An output (and an intermediate) has the candidates and the level count of the whole op, so it goes through the very
+// pairings of the undivided tree.  Map entries into the op's input are global rows; level buffers are numbered from 0 for the part; the last
+// level (or the extra gather) writes output row out_first + i.  Host only: `maps` is what PoolPlan::maps holds on the device.
+static int pool_plan_host(int batch, int C, int H, int W, int k, int s, int p, const size_t* range, PoolPlan* P, std::vector<int32_t>* maps_out) {
   const int Ho = pool_out_size(H, k, s, p), Wo = pool_out_size(W, k, s, p);
   if ((double)batch * C * H * W >= 2147483647.0) return fail("max pool: %d x %d x %d x %d rows exceed the int32 index maps", batch, C, H, W);
-  std::vector<int32_t> maps;
+  const size_t n_out = (size_t)batch * C * Ho * Wo, n_mid = (size_t)batch * C * H * Wo;
+  const size_t o0 = range ? range[0] : 0, on = range ? range[1] : n_out;
+  if (o0 > n_out || on > n_out - o0) return fail("max pool: output rows %zu .. %zu of %zu", o0, o0 + on, n_out);
+  P->out_first = o0; P->out_count = on;
+  std::vector<int32_t>& maps = *maps_out;
   std::vector<std::vector<int32_t>> cand;      // per output of the current pass: its candidates' rows in the current source buffer
   int cur = 0;                                 // buffer the candidates live in
   int next_buf = 1;
-  auto run_pass = [&](size_t outer, int n_in, int inner, int n_out, const std::vector<int32_t>& row_of) {
-    // row_of[(ou * n_in + x) * inner + i]: row of input element (ou, x, i) in buffer `cur`
-    const size_t nout = outer * (size_t)n_out * inner;
+  // one 1-D pass [outer][n_in][inner] -> [outer][n_out][inner] for the outputs `ids` (ascending numbers in the whole pass output);
+  // row_of(element of the pass input) -> its row in buffer `cur`
+  auto run_pass = [&](const std::vector<size_t>& ids, int n_in, int inner, int n_out1, auto&& row_of) {
+    const size_t nout = ids.size();
     cand.assign(nout, {});
-    int mmax = 1;
-    for (size_t e = 0; e < nout; e++) {
-      const int i = (int)(e % inner), o = (int)((e / inner) % n_out);
-      const size_t ou = e / ((size_t)inner * n_out);
+    int mmax = 1;                              // over the whole pass, not the part: the level count is the undivided tree's
+    for (int o = 0; o < n_out1; o++) {
+      int m = 0;
+      for (int j = 0; j < k; j++) m += (o * s - p + j >= 0 && o * s - p + j < n_in) ? 1 : 0;
+      mmax = std::max(mmax, m);
+    }
+    for (size_t q = 0; q < nout; q++) {
+      const size_t e = ids[q];
+      const int i = (int)(e % inner), o = (int)((e / inner) % n_out1);
+      const size_t ou = e / ((size_t)inner * n_out1);
       for (int j = 0; j < k; j++) {
         const int x = o * s - p + j;
-        if (x >= 0 && x < n_in) cand[e].push_back(row_of[(ou * n_in + x) * inner + i]);
+        if (x >= 0 && x < n_in) cand[q].push_back(row_of((ou * n_in + x) * inner + i));
       }
-      mmax = std::max(mmax, (int)cand[e].size());
     }
     int L = 0;
     while ((1 << L) < mmax) L++;
@@ -275,22 +293,42 @@ static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, PoolPl
       maps.insert(maps.end(), g.begin(), g.end());
       pl.a_off = maps.size(); maps.insert(maps.end(), ia.begin(), ia.end());
       pl.b_off = maps.size(); maps.insert(maps.end(), ib.begin(), ib.end());
-      P->rows_buf[next_buf - 1] = std::max(P->rows_buf[next_buf - 1], pl.n_dst);
       P->lv.push_back(pl);
       cand.swap(nc);
       cur = next_buf;
       next_buf = 3 - next_buf;
     }
   };
-  // row pass: [B*C*H][W] -> [B*C*H][Wo]
-  std::vector<int32_t> rows((size_t)batch * C * H * W);
-  for (size_t r = 0; r < rows.size(); r++) rows[r] = (int32_t)r;
-  run_pass((size_t)batch * C * H, W, 1, Wo, rows);
-  std::vector<int32_t> mid(cand.size());
-  for (size_t e = 0; e < cand.size(); e++) mid[e] = cand[e][0];
+  // the row-pass results to compute: all of them, or those under the windows of the part's outputs
+  auto col_taps = [&](size_t e, auto&& f) {
+    const size_t xo = e % Wo, yo = (e / Wo) % Ho, bc = e / ((size_t)Wo * Ho);
+    for (int j = 0; j < k; j++) {
+      const int y = (int)yo * s - p + j;
+      if (y >= 0 && y < H) f((bc * H + (size_t)y) * Wo + xo);
+    }
+  };
+  std::vector<size_t> mids, outs(on);
+  for (size_t q = 0; q < on; q++) outs[q] = o0 + q;
+  if (!range) {
+    mids.resize(n_mid);
+    for (size_t m = 0; m < n_mid; m++) mids[m] = m;
+  } else if (on) {
+    size_t lo = n_mid, hi = 0;
+    for (size_t e : outs) col_taps(e, [&](size_t m) { lo = std::min(lo, m); hi = std::max(hi, m); });
+    std::vector<char> read(hi - lo + 1, 0);
+    for (size_t e : outs) col_taps(e, [&](size_t m) { read[m - lo] = 1; });
+    for (size_t m = lo; m <= hi; m++) if (read[m - lo]) mids.push_back(m);
+  }
+  if (!mids.empty()) { P->mid_first = mids.front(); P->mid_count = mids.back() - mids.front() + 1; }
+  // row pass: [B*C*H][W] -> [B*C*H][Wo], on the op's input in place
+  size_t in_lo = (size_t)-1, in_hi = 0;
+  run_pass(mids, W, 1, Wo, [&](size_t r) { in_lo = std::min(in_lo, r); in_hi = std::max(in_hi, r); return (int32_t)r; });
+  if (!mids.empty()) { P->in_first = in_lo; P->in_count = in_hi - in_lo + 1; }
+  std::vector<int32_t> mid_row(P->mid_count, -1);      // row-pass result -> its row in buffer `cur`
+  for (size_t q = 0; q < mids.size(); q++) mid_row[mids[q] - P->mid_first] = cand[q][0];
   // column pass on the row pass's output: [B*C][H][Wo] -> [B*C][Ho][Wo]
-  run_pass((size_t)batch * C, H, Wo, Ho, mid);
-  // the op's output is in output order: the last level already wrote it so when every output ended on row e; else one more gather
+  run_pass(outs, H, Wo, Ho, [&](size_t m) { return mid_row[m - P->mid_first]; });
+  // the op's output is in output order: the last level already wrote it so when every output ended on its own row; else one more gather
   bool identity = !P->lv.empty();
   for (size_t e = 0; e < cand.size() && identity; e++) identity = cand[e][0] == (int32_t)e;
   if (identity) {
@@ -305,6 +343,22 @@ static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, PoolPl
   for (const PoolLevel& l : P->lv)
     if (l.dst == 1 || l.dst == 2) P->rows_buf[l.dst - 1] = std::max(P->rows_buf[l.dst - 1], l.n_dst);
   for (const PoolLevel& l : P->lv) P->pairs_per_batch += l.pairs;
+  // the gather and the key switch read through the maps unchecked: every entry is a row of the op's input, or a row the level before wrote
+  size_t written[3] = {(size_t)batch * C * H * W, 0, 0};
+  for (const PoolLevel& l : P->lv) {
+    auto outside = [&](size_t off, size_t n) {
+      for (size_t q = 0; q < n; q++)
+        if (maps[off + q] < 0 || (size_t)maps[off + q] >= written[l.src]) return true;
+      return false;
+    };
+    if (outside(l.g_off, l.n_dst) || outside(l.a_off, l.pairs) || outside(l.b_off, l.pairs)) return fail("max pool: an index map entry outside its source buffer");
+    if (l.dst < 3) written[l.dst] = l.n_dst;
+  }
+  return 0;
+}
+static int pool_plan(int batch, int C, int H, int W, int k, int s, int p, const size_t* range, PoolPlan* P) {
+  std::vector<int32_t> maps;
+  CHK(pool_plan_host(batch, C, H, W, k, s, p, range, P, &maps));
   HIPCHK(P->maps.alloc(maps.size() * 4));
   if (!maps.empty()) HIPCHK(hipMemcpy(P->maps.p, maps.data(), maps.size() * 4, hipMemcpyHostToDevice));
   return 0;
@@ -354,6 +408,11 @@ struct dctfhe_session {
   int part = 0, parts = 1;
   bool has_run = false;
   std::vector<char> whole;
+  // divided max pools (dctfhe_session_set_shard_pool): a pool computes the part's output rows and reads only its need range of the source,
+  // so a sliced tensor may hold more valid rows than the part's own: marked[t], the ranges (first, end) dctfhe_session_mark_rows declared
+  bool shard_set = false, shard_pool = false;
+  std::vector<std::vector<std::pair<size_t, size_t>>> marked;
+  std::vector<size_t> pool_pairs_run;   // per op: pairwise maxima its last run sent to the bootstrap (max pools; 0 elsewhere)
   void wipe_audit_key() { if (d_audit_key.p) hipMemset(d_audit_key.p, 0, d_audit_key.bytes); }      // the secret does not outlive the audit
   void audit_off() {
     wipe_audit_key();
@@ -1453,16 +1512,18 @@ static int alloc_lut_scratch(dctfhe_keys* K, size_t chunk, LutScratch* sc) {
 // the levels of a max-pool plan on device rows.  Input rows of stride Ls (first ds mask words meaningful); level buffers and output rows of
 // stride Lo, of which the first `dout` = max(ds, ring of the tier) mask words may be non-zero.  Each level: the gather, then per chunk the
 // key switch of the differences (KS_DIFF), the centred mod switch and the relu bootstrap accumulated into the gathered b rows.
+// d_out is the op's whole output tensor: the plan writes its rows from P.out_first on.  launched: the pairwise maxima sent to the bootstrap.
 static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, const uint64_t* d_in, size_t Ls, size_t ds, uint64_t* const bufs[2],
                         uint64_t* d_out, size_t Lo, size_t dout, const int64_t* d_table, const LutScratch& sc, Timers* tm,
-                        const MarginProbe* probe = nullptr) {
+                        const MarginProbe* probe = nullptr, size_t* launched = nullptr) {
   hipStream_t st = K->ctx->stream;
   const int tier = S.tier;
+  if (launched) *launched = 0;
   const int32_t* maps = P.maps.as<int32_t>();
   for (const PoolLevel& l : P.lv) {
     const uint64_t* src = l.src == 0 ? d_in : bufs[l.src - 1];
     const size_t L_src = l.src == 0 ? Ls : Lo, d_src = l.src == 0 ? ds : dout;
-    uint64_t* dst = l.dst == 3 ? d_out : bufs[l.dst - 1];
+    uint64_t* dst = l.dst == 3 ? d_out + P.out_first * Lo : bufs[l.dst - 1];
     const int h = tm ? tm->begin(CAT_LINEAR) : -1;
     hipLaunchKernelGGL(k_pool_gather, dim3(ew_grid(l.n_dst * Lo)), dim3(256), 0, st, src, L_src, d_src, maps + l.g_off, dst, Lo, l.n_dst);
     HIPCHK(hipGetLastError());
@@ -1474,21 +1535,28 @@ static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, co
       diff.source = KS_DIFF; diff.ia = maps + l.a_off + c0; diff.ib = maps + l.b_off + c0;
       PbsOut acc{dst + c0 * Lo, Lo}; acc.accumulate = true;
       CHK(dev_ks_pbs(K, tier, diff, cn, PbsLut{d_table, S.p_d}, acc, sc, tm, probe));
+      if (launched) *launched += cn;
     }
   }
   return 0;
 }
-// clear mode: row pass into `mid` ([B*C*H][Wo] words), column pass into out
+// clear mode: row pass into `mid`, column pass into out.  `mid` holds the row-pass results [mid_first, mid_first + mid_count) of
+// [B*C*H][Wo] and the column pass computes the outputs [out_first, out_first + out_count) of [B*C][Ho][Wo]: everything for the whole op, a
+// part's intermediates and outputs for a divided pool.  The caller guarantees that the range of intermediates covers every tap of these
+// outputs (PoolPlan), so the column pass never indexes outside `mid`; the row pass reads `in` within the tensor, in bounds for any range.
 static int clear_max_pool(hipStream_t st, const uint64_t* in, uint64_t* mid, uint64_t* out, int batch, int C, int H, int W, int k, int s, int p,
-                          int shift, uint64_t body_add, int p_d, const int64_t* d_table, double sigma, uint64_t seed, uint64_t stream) {
+                          int shift, uint64_t body_add, int p_d, const int64_t* d_table, double sigma, uint64_t seed, uint64_t stream,
+                          size_t mid_first, size_t mid_count, size_t out_first, size_t out_count) {
   const int Ho = pool_out_size(H, k, s, p), Wo = pool_out_size(W, k, s, p);
   const rng_key key{{(uint32_t)seed, (uint32_t)(seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}};
-  const size_t n1 = (size_t)batch * C * H * Wo, n2 = (size_t)batch * C * Ho * Wo;
-  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(n1)), dim3(256), 0, st, in, mid, (size_t)batch * C * H, W, 1, Wo, k, s, p, shift, body_add, p_d,
-                     d_table, sigma, key, stream);
+  if (mid_first + mid_count > (size_t)batch * C * H * Wo || out_first + out_count > (size_t)batch * C * Ho * Wo)
+    return fail("max pool (clear): intermediates %zu .. %zu or outputs %zu .. %zu outside the op", mid_first, mid_first + mid_count, out_first, out_first + out_count);
+  if (out_count == 0) return 0;
+  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(mid_count)), dim3(256), 0, st, in, mid, mid_first, mid_count, (size_t)0, mid_first, W, 1, Wo, k, s, p, shift,
+                     body_add, p_d, d_table, sigma, key, stream);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(n2)), dim3(256), 0, st, mid, out, (size_t)batch * C, H, Wo, Ho, k, s, p, shift, body_add, p_d,
-                     d_table, sigma, key, stream + 1);
+  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(out_count)), dim3(256), 0, st, mid, out, out_first, out_count, mid_first, (size_t)0, H, Wo, Ho, k, s, p, shift,
+                     body_add, p_d, d_table, sigma, key, stream + 1);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2126,7 +2194,8 @@ extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   if (!K) {
     DevBuf di, dm, d_o;
     HIPCHK(di.upload(in, nin * 8)); HIPCHK(dm.alloc((size_t)batch * C * H * Wo * 8)); HIPCHK(d_o.alloc(nout * 8));
-    CHK(clear_max_pool(st, di.as<uint64_t>(), dm.as<uint64_t>(), d_o.as<uint64_t>(), batch, C, H, W, k, s, p, 0, 1ULL << 62, p_d, nullptr, 0.0, 0, 0));
+    CHK(clear_max_pool(st, di.as<uint64_t>(), dm.as<uint64_t>(), d_o.as<uint64_t>(), batch, C, H, W, k, s, p, 0, 1ULL << 62, p_d, nullptr, 0.0, 0, 0, 0,
+                          (size_t)batch * C * H * Wo, 0, nout));
     HIPCHK(d_o.download(out, nout * 8, st));
     return 0;
   }
@@ -2143,7 +2212,7 @@ extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   }
   const size_t Li = (size_t)dim_in + 1, Lo = (size_t)dim_o + 1;
   PoolPlan P;
-  CHK(pool_plan(batch, C, H, W, k, s, p, &P));
+  CHK(pool_plan(batch, C, H, W, k, s, p, nullptr, &P));
   DevBuf di, d_o, ba, bb, d_tab;
   HIPCHK(di.upload(in, nin * Li * 8)); HIPCHK(d_o.alloc(nout * Lo * 8));
   HIPCHK(ba.alloc(P.rows_buf[0] * Lo * 8)); HIPCHK(bb.alloc(P.rows_buf[1] * Lo * 8));
@@ -2327,7 +2396,11 @@ static int session_plan_buffers(dctfhe_session* s) {
   last_use[circ->output_tensor] = 1 << 30;
   // the input stays resident too: dctfhe_session_run may be called again without a fresh upload (bench.py does)
   last_use[circ->input_tensor] = 1 << 30;
+  // a second plan (dctfhe_session_set_shard_pool, before the first run) keeps the input's buffer, the first allocation: it may be uploaded already
+  uint64_t* const input_kept = s->owned.empty() ? nullptr : s->owned[0].as<uint64_t>();
+  if (input_kept) s->owned.erase(s->owned.begin() + 1, s->owned.end());
   s->d_tensor.assign(nt, nullptr);
+  s->d_tensor[circ->input_tensor] = input_kept;
   s->tensor_words.assign(nt, 0);
   for (int t = 0; t < nt; t++) s->tensor_words[t] = (size_t)batch * circ->tensors[t].elems() * s->t_L[t];
   std::vector<size_t> freelist;      // indices into s->owned
@@ -2356,15 +2429,18 @@ static int session_plan_buffers(dctfhe_session* s) {
     const TensorShape& a = circ->tensors[o.src0];
     CHK(alloc_t(o.dst));
     if (o.type == OP_MAXPOOL) {
-      // the tree's level buffers (encrypted) or the row pass's output (clear)
+      // the tree's level buffers (encrypted) or the row pass's output (clear); of a divided pool, this part's
       const PoolSite& S = o.pool;
-      size_t words[2] = {0, 0};
+      size_t words[2] = {0, 0}, range[2] = {0, 0};
+      if (s->shard_pool) CHK(dctfhe_shard_rows((size_t)batch * circ->tensors[o.dst].elems(), s->parts, s->part, &range[0], &range[1]));
+      s->pool[i].reset(new PoolPlan);
       if (keys) {
-        s->pool[i].reset(new PoolPlan);
-        CHK(pool_plan(batch, a.C, a.H, a.W, S.k, S.stride, S.pad, s->pool[i].get()));
+        CHK(pool_plan(batch, a.C, a.H, a.W, S.k, S.stride, S.pad, s->shard_pool ? range : nullptr, s->pool[i].get()));
         for (int b = 0; b < 2; b++) words[b] = s->pool[i]->rows_buf[b] * s->t_L[o.dst];
       } else {
-        words[0] = (size_t)batch * a.C * a.H * pool_out_size(a.W, S.k, S.stride, S.pad);
+        std::vector<int32_t> unused;
+        CHK(pool_plan_host(batch, a.C, a.H, a.W, S.k, S.stride, S.pad, s->shard_pool ? range : nullptr, s->pool[i].get(), &unused));
+        words[0] = s->pool[i]->mid_count;
       }
       for (int b = 0; b < 2; b++) {
         if (!words[b]) continue;
@@ -2418,6 +2494,8 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   HIPCHK(s->d_overflow.alloc(sizeof(int)));
   HIPCHK(hipMemset(s->d_overflow.p, 0, sizeof(int)));
   s->whole.assign(circ->tensors.size(), 1);
+  s->marked.assign(circ->tensors.size(), {});
+  s->pool_pairs_run.assign(circ->ops.size(), 0);
   if (keys) {
     dctfhe_stats stt;
     circuit_stats(*circ, keys->p, &stt);
@@ -2704,31 +2782,114 @@ extern "C" int dctfhe_session_set_shard(dctfhe_session* s, int part, int parts) 
   CHK(dctfhe_shard_rows(0, parts, part, &f, &n));
   if (s->has_run) return fail("dctfhe_session_set_shard: the session has run; shard it before its first run");
   if (s->d_audit_key.p && parts > 1) return fail("dctfhe_session_set_shard: the margin audit is on, and it stays unsharded: turn it off first");
-  s->part = part; s->parts = parts;
+  if (s->shard_pool) return fail("dctfhe_session_set_shard: the max pools are divided for part %d of %d: turn that off first (dctfhe_session_set_shard_pool)", s->part, s->parts);
+  s->part = part; s->parts = parts; s->shard_set = true;
   return 0;
 }
-// the exchange points of a circuit: (op after which, tensor) per sliced tensor that a whole-needing op or the download reads
-static void shard_plan_of(const CircuitPlan& c, std::vector<std::pair<int, int>>* plan) {
-  std::vector<char> whole(c.tensors.size(), 1);
+// ---- divided max pools: the partition rule of one pool, the switch, the rows a part holds, the plan with row ranges
+static bool pool_geometry_ok(int batch, int C, int H, int W, int k, int s, int p) {
+  return batch >= 1 && C >= 1 && H >= 1 && W >= 1 && k >= 1 && k <= 32 && s >= 1 && p >= 0 && 2 * p <= k && H + 2 * p >= k && W + 2 * p >= k;
+}
+extern "C" int dctfhe_shard_pool(int batch, int C, int H, int W, int k, int s, int pad, int parts, int part, size_t* out_first, size_t* out_count,
+                                 size_t* in_first, size_t* in_count, size_t* pairs) {
+  if (!out_first || !out_count || !in_first || !in_count || !pairs) return fail("dctfhe_shard_pool: null argument");
+  if (!pool_geometry_ok(batch, C, H, W, k, s, pad))
+    return fail("dctfhe_shard_pool: bad geometry (1 <= k <= 32, s >= 1, 0 <= p <= k/2, window inside the padded input)");
+  const size_t n_out = (size_t)batch * C * pool_out_size(H, k, s, pad) * pool_out_size(W, k, s, pad);
+  size_t range[2];
+  CHK(dctfhe_shard_rows(n_out, parts, part, &range[0], &range[1]));
+  PoolPlan P;
+  std::vector<int32_t> maps;
+  CHK(pool_plan_host(batch, C, H, W, k, s, pad, parts > 1 ? range : nullptr, &P, &maps));      // one part: the undivided op as it runs today
+  *out_first = range[0]; *out_count = range[1];
+  *in_first = parts > 1 ? P.in_first : 0; *in_count = parts > 1 ? P.in_count : (size_t)batch * C * H * W;
+  *pairs = P.pairs_per_batch;
+  return 0;
+}
+extern "C" int dctfhe_session_set_shard_pool(dctfhe_session* s, int on) {
+  if (!s) return fail("dctfhe_session_set_shard_pool: null session");
+  if (s->has_run) return fail("dctfhe_session_set_shard_pool: the session has run; divide its max pools before its first run");
+  if (s->d_audit_key.p) return fail("dctfhe_session_set_shard_pool: the margin audit is on, and it stays unsharded: turn it off first");
+  if (!s->shard_set) return fail("dctfhe_session_set_shard_pool: the session is not sharded: call dctfhe_session_set_shard first");
+  const bool want = on != 0 && s->parts > 1;      // one part of one: the undivided op
+  if (want == s->shard_pool) return 0;
+  HIPCHK(hipSetDevice(s->ctx->device));
+  s->shard_pool = want;
+  return session_plan_buffers(s);      // the pools' trees and level buffers for this part (or the whole op again); the input's buffer stays
+}
+// the first rows of [first, first + count) of tensor t that this session does not hold: neither its own part's nor marked.  false: none
+static bool rows_missing(const dctfhe_session* s, int t, size_t first, size_t count, size_t* g0, size_t* g1) {
+  if (s->whole[t] || count == 0) return false;
+  std::vector<std::pair<size_t, size_t>> have = s->marked[t];
+  size_t f = 0, n = 0;
+  dctfhe_shard_rows((size_t)s->batch * s->circ->tensors[t].elems(), s->parts, s->part, &f, &n);
+  have.push_back({f, f + n});
+  std::sort(have.begin(), have.end());
+  size_t pos = first;
+  const size_t end = first + count;
+  for (const auto& iv : have) {
+    if (pos >= end) break;
+    if (iv.first > pos) { *g0 = pos; *g1 = std::min(iv.first, end); return true; }
+    pos = std::max(pos, iv.second);
+  }
+  if (pos < end) { *g0 = pos; *g1 = end; return true; }
+  return false;
+}
+extern "C" int dctfhe_session_pool_pairs(dctfhe_session* s, int op, size_t* pairs) {
+  if (!s || !pairs) return fail("dctfhe_session_pool_pairs: null argument");
+  if (op < 0 || op >= (int)s->circ->ops.size() || s->circ->ops[op].type != OP_MAXPOOL) return fail("dctfhe_session_pool_pairs: op %d is not a max pool", op);
+  *pairs = s->pool_pairs_run[op];
+  return 0;
+}
+// the exchange points of a circuit: (op after which, tensor) per sliced tensor that a whole-needing op or the download reads.  divided:
+// a max pool runs on its part's outputs, leaves its destination sliced and needs only a range of its source: reader = that pool's op
+// (-1: the whole tensor is needed).  A tensor that a pool and later a whole-needing op read travels whole, once.
+struct ShardEntry { int after_op, tensor, reader; };
+static void shard_plan_of(const CircuitPlan& c, bool divided, std::vector<ShardEntry>* plan) {
+  std::vector<char> state(c.tensors.size(), 2);      // 0: sliced, 1: a pool's need range is there, 2: whole
   std::vector<int> writer(c.tensors.size(), -1);
-  auto need = [&](int t) { if (!whole[t]) { plan->push_back({writer[t], t}); whole[t] = 1; } };
+  auto need = [&](int t, int reader) {
+    if (state[t] == 0) plan->push_back({writer[t], t, reader});
+    else if (state[t] == 1) {      // a second reader of a ranged tensor: it travels whole
+      for (ShardEntry& e : *plan) if (e.tensor == t && e.after_op == writer[t]) e.reader = -1;
+      reader = -1;
+    }
+    state[t] = std::max<char>(state[t], reader < 0 ? 2 : 1);
+  };
   for (int i = 0; i < (int)c.ops.size(); i++) {
     const SiteOp& o = c.ops[i];
-    if (op_runs_sliced(o)) { whole[o.dst] = 0; writer[o.dst] = i; continue; }
-    need(o.src0);
-    whole[o.dst] = 1;
+    if (op_runs_sliced(o)) { state[o.dst] = 0; writer[o.dst] = i; continue; }
+    const bool part_only = divided && o.type == OP_MAXPOOL;
+    need(o.src0, part_only ? i : -1);
+    state[o.dst] = part_only ? 0 : 2;
+    writer[o.dst] = i;
   }
-  need(c.output_tensor);
-  std::sort(plan->begin(), plan->end());
+  need(c.output_tensor, -1);
+  std::sort(plan->begin(), plan->end(), [](const ShardEntry& a, const ShardEntry& b) { return std::make_pair(a.after_op, a.tensor) < std::make_pair(b.after_op, b.tensor); });
 }
 extern "C" int dctfhe_session_shard_plan(dctfhe_session* s, int32_t* after_op, int32_t* tensor, int capacity, int* n) {
   if (!s || !n) return fail("dctfhe_session_shard_plan: null argument");
-  std::vector<std::pair<int, int>> plan;
-  shard_plan_of(*s->circ, &plan);
+  std::vector<ShardEntry> plan;
+  shard_plan_of(*s->circ, s->shard_pool, &plan);
   *n = (int)plan.size();
   if (!after_op || !tensor) return 0;
   if (capacity < *n) return fail("dctfhe_session_shard_plan: room for %d entries, the circuit has %d", capacity, *n);
-  for (int i = 0; i < *n; i++) { after_op[i] = plan[i].first; tensor[i] = plan[i].second; }
+  for (int i = 0; i < *n; i++) { after_op[i] = plan[i].after_op; tensor[i] = plan[i].tensor; }
+  return 0;
+}
+extern "C" int dctfhe_session_shard_plan_rows(dctfhe_session* s, int32_t* after_op, int32_t* tensor, size_t* first, size_t* count, int capacity, int* n) {
+  if (!s || !n) return fail("dctfhe_session_shard_plan_rows: null argument");
+  std::vector<ShardEntry> plan;
+  shard_plan_of(*s->circ, s->shard_pool, &plan);
+  *n = (int)plan.size();
+  if (!after_op || !tensor || !first || !count) return 0;
+  if (capacity < *n) return fail("dctfhe_session_shard_plan_rows: room for %d entries, the circuit has %d", capacity, *n);
+  for (int i = 0; i < *n; i++) {
+    const ShardEntry& e = plan[i];
+    after_op[i] = e.after_op; tensor[i] = e.tensor;
+    first[i] = e.reader < 0 ? 0 : s->pool[e.reader]->in_first;
+    count[i] = e.reader < 0 ? (size_t)s->batch * s->circ->tensors[e.tensor].elems() : s->pool[e.reader]->in_count;
+  }
   return 0;
 }
 static int tensor_ok(const dctfhe_session* s, int t, const char* who) {
@@ -2746,6 +2907,17 @@ extern "C" int dctfhe_session_mark_whole(dctfhe_session* s, int tensor) {
   if (!s) return fail("dctfhe_session_mark_whole: null session");
   CHK(tensor_ok(s, tensor, "dctfhe_session_mark_whole"));
   s->whole[tensor] = 1;
+  return 0;
+}
+extern "C" int dctfhe_session_mark_rows(dctfhe_session* s, int tensor, size_t first, size_t count) {
+  if (!s) return fail("dctfhe_session_mark_rows: null session");
+  CHK(tensor_ok(s, tensor, "dctfhe_session_mark_rows"));
+  const size_t rows = s->tensor_words[tensor] / s->t_L[tensor];
+  if (first > rows || count > rows - first) return fail("dctfhe_session_mark_rows: rows %zu .. %zu of a tensor of %zu", first, first + count, rows);
+  if (s->whole[tensor] || count == 0) return 0;
+  s->marked[tensor].push_back({first, first + count});
+  size_t g0, g1;
+  if (!rows_missing(s, tensor, 0, rows, &g0, &g1)) { s->whole[tensor] = 1; s->marked[tensor].clear(); }
   return 0;
 }
 extern "C" int dctfhe_session_copy_rows(dctfhe_session* dst, dctfhe_session* src, int tensor, size_t first, size_t count) {
@@ -2798,12 +2970,24 @@ static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_t
     if (op_runs_sliced(o)) {
       CHK(dctfhe_shard_rows(rn, s->parts, s->part, &r0, &rn));
       s->whole[o.dst] = !sharded;
+      s->marked[o.dst].clear();
+    } else if (o.type == OP_MAXPOOL && s->shard_pool) {      // a divided pool: the part's outputs, from the need range of its source
+      const PoolPlan& pp = *s->pool[i];
+      size_t g0 = 0, g1 = 0;
+      if (rows_missing(s, o.src0, pp.in_first, pp.in_count, &g0, &g1))
+        return fail("op %zu (max pool) reads rows %zu .. %zu of tensor %d, and part %d of %d lacks rows %zu .. %zu: bring them in and call dctfhe_session_mark_rows first",
+                    i, pp.in_first, pp.in_first + pp.in_count, o.src0, s->part, s->parts, g0, g1);
+      r0 = pp.out_first; rn = pp.out_count;
+      s->whole[o.dst] = 0;
+      s->marked[o.dst].clear();
     } else {
       if (!s->whole[o.src0])
         return fail("op %zu needs tensor %d whole, and it holds only the rows of part %d of %d: exchange the other parts' rows and call dctfhe_session_mark_whole first",
                     i, o.src0, s->part, s->parts);
       s->whole[o.dst] = 1;
+      s->marked[o.dst].clear();
     }
+    s->pool_pairs_run[i] = 0;
     if (rn == 0) continue;      // an empty part of a small tensor
     const MarginProbe probe_i = audit ? MarginProbe{s->d_audit_key.as<uint8_t>(), s->d_audit.as<margin_slot>() + s->audit_first[i]} : MarginProbe{};
     const MarginProbe* probe = audit ? &probe_i : nullptr;
@@ -2879,12 +3063,13 @@ static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_t
         const PoolSite& S = o.pool;
         if (!K) {
           const int h = tm.begin(CAT_LINEAR);
+          const PoolPlan& pp = *s->pool[i];
           CHK(clear_max_pool(st, src, s->pool_buf[i][0], dst, B, a.C, a.H, a.W, S.k, S.stride, S.pad, S.shift, S.body_add, S.p_d, c->d_payload[i].as<int64_t>(), sg,
-                             s->sim_seed, (1ULL << 40) | ((uint64_t)(0x51D0000 + (s->sim_run << 12) + i) << 1)));
+                             s->sim_seed, (1ULL << 40) | ((uint64_t)(0x51D0000 + (s->sim_run << 12) + i) << 1), pp.mid_first, pp.mid_count, pp.out_first, pp.out_count));
           tm.end(h);
         } else {
           uint64_t* const bufs[2] = {s->pool_buf[i][0], s->pool_buf[i][1]};
-          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], c->d_payload[i].as<int64_t>(), sc, &tm, probe));
+          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], c->d_payload[i].as<int64_t>(), sc, &tm, probe, &s->pool_pairs_run[i]));
         }
         break;
       }

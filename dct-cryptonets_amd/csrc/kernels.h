@@ -1208,11 +1208,14 @@ __global__ void k_lut_clear(const uint64_t* __restrict__ in, uint64_t* __restric
 // in-range taps.  sigma == 0: the maximum of the words read as signed int64.  sigma > 0 (`simulate`): the taps are folded as
 // m = m + relu(x - m) with the noise sampled on every difference before the relu table (`table`: 2^p_d entries, index
 // ((x - m) << shift) + body_add) -- one noisy look-up per pairwise maximum, as many as the encrypted tree runs.
-__global__ void k_maxpool_clear(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, size_t outer, int n_in, int inner, int n_out, int k,
-                                int s, int p, int shift, uint64_t body_add, int p_d, const int64_t* __restrict__ table, double sigma,
-                                rng_key seed, uint64_t stream) {
-  const size_t total = outer * (size_t)n_out * inner;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+// The launch computes outputs [e0, e0 + count) of the pass (all of them, or a divided pool's part; consecutive lanes on consecutive
+// outputs).  in points at element in0 of the pass input and out at element out0 of the pass output, so a part's `mid` buffer holds its
+// intermediates only; the noise of an output is drawn by its number e in the whole pass, whichever part computes it.
+__global__ void k_maxpool_clear(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, size_t e0, size_t count, size_t in0, size_t out0,
+                                int n_in, int inner, int n_out, int k, int s, int p, int shift, uint64_t body_add, int p_d,
+                                const int64_t* __restrict__ table, double sigma, rng_key seed, uint64_t stream) {
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = e0 + t;
     const int i = (int)(e % inner);
     const int o = (int)((e / inner) % n_out);
     const size_t ou = e / ((size_t)inner * n_out);
@@ -1221,7 +1224,7 @@ __global__ void k_maxpool_clear(const uint64_t* __restrict__ in, uint64_t* __res
     for (int j = 0; j < k; j++) {
       const int x = o * s - p + j;
       if (x < 0 || x >= n_in) continue;
-      const uint64_t v = in[(ou * n_in + x) * inner + i];
+      const uint64_t v = in[(ou * n_in + x) * inner + i - in0];
       if (taken == 0) {
         m = v;
       } else if (sigma > 0) {
@@ -1233,7 +1236,7 @@ __global__ void k_maxpool_clear(const uint64_t* __restrict__ in, uint64_t* __res
       }
       taken++;
     }
-    out[e] = m;
+    out[e - out0] = m;
   }
 }
 

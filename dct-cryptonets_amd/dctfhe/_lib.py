@@ -68,6 +68,7 @@ EXPORTS = [
     "dctfhe_session_upload_public",
     "dctfhe_shard_rows", "dctfhe_session_set_shard", "dctfhe_session_run_span", "dctfhe_session_shard_plan", "dctfhe_session_tensor",
     "dctfhe_session_mark_whole", "dctfhe_session_copy_rows",
+    "dctfhe_shard_pool", "dctfhe_session_set_shard_pool", "dctfhe_session_mark_rows", "dctfhe_session_shard_plan_rows", "dctfhe_session_pool_pairs",
 ]
 
 _lib = None
@@ -186,6 +187,11 @@ def load():
     L.dctfhe_session_tensor.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
     L.dctfhe_session_mark_whole.argtypes = [vp, i32]
     L.dctfhe_session_copy_rows.argtypes = [vp, vp, i32, sz, sz]
+    L.dctfhe_shard_pool.argtypes = [i32] * 9 + [C.POINTER(sz)] * 5
+    L.dctfhe_session_set_shard_pool.argtypes = [vp, i32]
+    L.dctfhe_session_mark_rows.argtypes = [vp, i32, sz, sz]
+    L.dctfhe_session_shard_plan_rows.argtypes = [vp, vp, vp, vp, vp, i32, pi]
+    L.dctfhe_session_pool_pairs.argtypes = [vp, i32, C.POINTER(sz)]
     _lib = L
     return L
 

@@ -334,25 +334,47 @@ class CompiledCircuit:
                 out[nm] = out.get(nm, 0) + self._decisions(o)
         return out
 
-    def shard_plan(self):
+    def shard_plan(self, rows=False, part=0, parts=1, batch=1):
         """The exchange points of a run whose look-up sites are sharded over several GPUs (include/dctfhe.h dctfhe_session_shard_plan, the
         same list): [(after_op, tensor)] in op order.  Look-ups and adds run on a part's rows and leave their output sliced; convolutions,
         pools and the download read whole tensors -- so every sliced tensor one of them reads is exchanged once, right after the op that
-        writes it.  A tensor read by adds and look-ups only never travels.  The plan depends on the circuit alone."""
-        whole, writer, plan = [True] * len(self.tensors), {}, []
+        writes it.  A tensor read by adds and look-ups only never travels.  The plan depends on the circuit alone.
 
-        def need(t):
-            if not whole[t]:
-                plan.append((writer[t], t))
-                whole[t] = True
+        rows=True: the plan of a run whose max pools are divided too (Configuration(shard_pool=True); dctfhe_session_shard_plan_rows of
+        a session with dctfhe_session_set_shard_pool on), for part `part` of `parts` and `batch` images: [(after_op, tensor, first,
+        count)].  A divided pool leaves its destination sliced and needs only its need range of the source (shard_pool); every other
+        entry carries (0, rows of the tensor).  A tensor that a pool and another whole-needing op read travels whole."""
+        state, writer, plan = [2] * len(self.tensors), {}, []      # 0: sliced, 1: a pool's need range is there, 2: whole
+
+        def need(t, reader):
+            if state[t] == 0:
+                plan.append([writer[t], t, reader])
+            elif state[t] == 1:
+                for e in plan:
+                    if e[0] == writer[t] and e[1] == t:
+                        e[2] = -1
+                reader = -1
+            state[t] = max(state[t], 2 if reader < 0 else 1)
         for i, o in enumerate(self.ops):
             if o.type in (OP_LUT, OP_ADD):
-                whole[o.dst], writer[o.dst] = False, i
+                state[o.dst], writer[o.dst] = 0, i
+                continue
+            part_only = rows and parts > 1 and o.type == OP_MAXPOOL
+            need(o.src0, i if part_only else -1)
+            state[o.dst], writer[o.dst] = (0 if part_only else 2), i
+        need(self.output_tensor, -1)
+        plan.sort(key=lambda e: (e[0], e[1]))
+        if not rows:
+            return [(a, t) for a, t, _ in plan]
+        out = []
+        for a, t, reader in plan:
+            T = self.tensors[t]
+            if reader < 0:
+                out.append((a, t, 0, batch * T.C * T.H * T.W))
             else:
-                need(o.src0)
-                whole[o.dst] = True
-        need(self.output_tensor)
-        return sorted(plan)
+                S = self.ops[reader].pool
+                out.append((a, t) + shard_pool(batch, T.C, T.H, T.W, S.k, S.stride, S.pad, parts, part)[2:4])
+        return out
 
     def report(self):
         """Text dump standing in for `fhe_circuit.mlir` (reference homomorphic_eval.py:309-311)."""
@@ -397,6 +419,31 @@ def shard_rows(rows, parts, part):
         raise ValueError(f"shard_rows: part {part} of {parts} (1 .. 64 parts) of {rows} rows")
     q, r = divmod(rows, parts)
     return part * q + min(part, r), q + (1 if part < r else 0)
+
+
+def shard_pool(batch, C, H, W, k, s, pad, parts, part):
+    """Part `part` of `parts` of a divided max pool over [batch][C][H][W] (include/dctfhe.h dctfhe_shard_pool, the same rule) ->
+    (out_first, out_count, in_first, in_count, pairs).  The part owns the output rows shard_rows gives it over the flat [B][C][Ho][Wo]
+    order.  Its intermediates are the row-pass results (b, c, y, xo) under the column windows of these outputs; the need range is the
+    smallest contiguous range of source rows holding every tap of theirs; pairs counts a pairwise maximum per tap but the first of every
+    intermediate and every output -- late pairing (pool_level_pairs) spends exactly taps - 1 on a window however it pairs.  An empty part
+    needs nothing; parts = 1 is the undivided op, which computes every row-pass result, read by a window or not."""
+    Ho, Wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
+    n_out = batch * C * Ho * Wo
+    o0, on = shard_rows(n_out, parts, part)
+    tw, th = np.array(pool_taps(W, k, s, pad), np.int64), np.array(pool_taps(H, k, s, pad), np.int64)
+    if parts == 1:
+        return 0, n_out, 0, batch * C * H * W, int(batch * C * (H * (tw - 1).sum() + Wo * (th - 1).sum()))
+    if on == 0:
+        return o0, 0, 0, 0, 0
+    e = np.arange(o0, o0 + on, dtype=np.int64)
+    xo, yo, bc = e % Wo, (e // Wo) % Ho, e // (Wo * Ho)
+    y = yo[:, None] * s - pad + np.arange(k)[None, :]
+    mids = np.unique(((bc[:, None] * H + y) * Wo + xo[:, None])[(y >= 0) & (y < H)])
+    pairs = int((th[yo] - 1).sum() + (tw[mids % Wo] - 1).sum())
+    first = (mids[0] // Wo) * W + max(0, (mids[0] % Wo) * s - pad)
+    last = (mids[-1] // Wo) * W + min(W - 1, (mids[-1] % Wo) * s - pad + k - 1)
+    return o0, on, int(first), int(last - first + 1), pairs
 
 
 @dataclass

@@ -727,6 +727,14 @@ def shard_rows(rows, parts, part):
     return f.value, n.value
 
 
+def shard_pool(batch, C_, H, W, k, s, pad, parts, part):
+    """(out_first, out_count, in_first, in_count, pairs) of part `part` of a divided max pool: its output rows, the source rows it needs
+    and the pairwise maxima it runs (dctfhe_shard_pool; host-only; dctfhe.compile.shard_pool is the same rule)"""
+    v = [C.c_size_t() for _ in range(5)]
+    check(_lib.load().dctfhe_shard_pool(*(int(x) for x in (batch, C_, H, W, k, s, pad, parts, part)), *(C.byref(x) for x in v)))
+    return tuple(x.value for x in v)
+
+
 class Circuit:
     def __init__(self, ctx, blob):
         self.ctx, self.L = ctx, ctx.L
@@ -824,6 +832,31 @@ class Session:
         a, t = np.empty(n.value, np.int32), np.empty(n.value, np.int32)
         check(self.L.dctfhe_session_shard_plan(self.h, ptr(a), ptr(t), n.value, C.byref(n)))
         return [(int(x), int(y)) for x, y in zip(a, t)]
+
+    def set_shard_pool(self, on=True):
+        """divide the max pools too: each computes this part's outputs from its need range of the source and leaves its destination
+        sliced (dctfhe_session_set_shard_pool).  After set_shard, before the first run, never with the margin audit"""
+        check(self.L.dctfhe_session_set_shard_pool(self.h, 1 if on else 0))
+
+    def shard_plan_rows(self):
+        """the exchange points with the rows this part needs of each [(after_op, tensor, first, count)]: a divided pool's need range, else
+        the whole tensor (dctfhe_session_shard_plan_rows; CompiledCircuit.shard_plan(rows=True, ...) is the same list)"""
+        n = C.c_int()
+        check(self.L.dctfhe_session_shard_plan_rows(self.h, None, None, None, None, 0, C.byref(n)))
+        a, t = np.empty(n.value, np.int32), np.empty(n.value, np.int32)
+        f, c = np.empty(n.value, np.uintp), np.empty(n.value, np.uintp)
+        check(self.L.dctfhe_session_shard_plan_rows(self.h, ptr(a), ptr(t), ptr(f), ptr(c), n.value, C.byref(n)))
+        return [tuple(int(x) for x in e) for e in zip(a, t, f, c)]
+
+    def mark_rows(self, tensor, first, count):
+        """rows [first, first + count) of `tensor` have been brought into this session (dctfhe_session_mark_rows)"""
+        check(self.L.dctfhe_session_mark_rows(self.h, int(tensor), int(first), int(count)))
+
+    def pool_pairs(self, op):
+        """pairwise maxima the last run of max-pool op `op` sent to the bootstrap (dctfhe_session_pool_pairs)"""
+        n = C.c_size_t()
+        check(self.L.dctfhe_session_pool_pairs(self.h, int(op), C.byref(n)))
+        return n.value
 
     def tensor(self, tensor):
         """(device pointer, stored row stride in 64-bit words, rows) of a tensor of the circuit (dctfhe_session_tensor)"""

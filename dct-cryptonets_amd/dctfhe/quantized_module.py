@@ -33,7 +33,7 @@ class Configuration:
 
     def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
                  compress_evaluation_keys=False, compress_output_ciphertexts=False, result_packing_spec=None, public_key_inputs=False,
-                 public_input_spec=None, shard_image=False, **kwargs):
+                 public_input_spec=None, shard_image=False, shard_pool=False, **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
         # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
         # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
@@ -59,6 +59,11 @@ class Configuration:
         # reads a whole tensor (include/dctfhe.h dctfhe_session_set_shard).  Every rank calls forward with the same
         # x and holds the same keys (keygen(seed=...) or load_evaluation_keys).  Off by default; one rank, or no group: the plain path.
         self.shard_image = bool(shard_image)
+        # ... and with shard_pool the max pools are divided too: a rank computes its own pool outputs and receives only the rows of the
+        # pool's source under its windows (dctfhe_session_set_shard_pool).  It refines shard_image and needs it.
+        self.shard_pool = bool(shard_pool)
+        if self.shard_pool and not self.shard_image:
+            raise ValueError("shard_pool divides the max pools of a sharded image: it needs shard_image=True")
         self.extra = kwargs
 
 
@@ -227,6 +232,8 @@ class QuantizedModule:
         if key not in self._sessions:
             sess = Session(self._context(), self._circuit, self._keys, batch)
             sess.set_shard(rank, world)
+            if self.configuration.shard_pool:
+                sess.set_shard_pool(True)
             self._sessions[key] = sess
         return self._sessions[key]
 
@@ -443,7 +450,12 @@ class QuantizedModule:
             if shard is not None:
                 # run_span to each exchange point of the compiler's plan, the rows of that tensor between the ranks, mark_whole; the
                 # output is whole on every rank at the end, so each downloads and decrypts its own copy
-                spans, moved = sharding.run_sharded(sess, self.compiled.shard_plan(), len(self.compiled.ops), cc.shard_rows, shard[1], dev, timing=True)
+                # (shard_pool: the plan with row ranges -- a rank receives its need range of a divided pool's source, then mark_rows)
+                if self.configuration.shard_pool:
+                    plans = [self.compiled.shard_plan(rows=True, part=p, parts=shard[1], batch=B) for p in range(shard[1])]
+                    spans, moved = sharding.run_sharded_rows(sess, plans, len(self.compiled.ops), cc.shard_rows, shard[0], shard[1], dev, timing=True)
+                else:
+                    spans, moved = sharding.run_sharded(sess, self.compiled.shard_plan(), len(self.compiled.ops), cc.shard_rows, shard[1], dev, timing=True)
                 timing = _sum_timings(spans)
             else:
                 timing = sess.run(timing=True)

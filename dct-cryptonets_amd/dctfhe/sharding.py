@@ -8,6 +8,8 @@ path is one all_gather of the decrypted-side logits (RCCL on GPUs, gloo in the C
 Sharding ONE image: the look-up sites of an image are element-wise, so `parts` sessions each evaluate their rows of
 every look-up and add (dctfhe.engine.Session.set_shard) and exchange rows only where a convolution, a pool or the download reads a whole
 tensor (CompiledCircuit.shard_plan).  exchange_rows is that exchange, broadcast_bytes ships rank 0's input blob, run_sharded walks the plan.
+With the max pools divided too (Configuration(shard_pool=True)) run_sharded_rows walks the plan with row ranges:
+exchange_need_rows sends a rank only the rows of its need range that other ranks own.
 
 Every collective bench.py issues lives here, so that the CPU tests (gloo, world size 2) and the one-rank RCCL smoke test
 (tests/test_gpu_rccl_smoke.py: `nccl` backend on cuda:0) run the very calls the 8-GPU job makes."""
@@ -146,6 +148,74 @@ def run_sharded(session, plan, n_ops, shard_rows, world, dev, timing=False):
         view = tensor_view(session, tensor, dev)
         moved += exchange_rows(view, [shard_rows(view.shape[0], world, p) for p in range(world)], world)
         session.mark_whole(tensor)
+    if first < n_ops:
+        timings.append(session.run_span(first, n_ops, timing))
+    return timings, moved
+
+
+def _overlap(a, b):
+    """(first, count) of the rows two ranges (first, count) share"""
+    lo, hi = max(a[0], b[0]), min(a[0] + a[1], b[0] + b[1])
+    return (lo, hi - lo) if hi > lo else (lo, 0)
+
+
+def needed_from(own, need, rank):
+    """what `rank` receives at a ranged exchange point: [(source rank, first, count)], the rows of its need range that other ranks own.
+    own[p], need[p]: the (first, count) part p wrote and part p needs.  Host-only."""
+    return [(p, *_overlap(own[p], need[rank])) for p in range(len(own)) if p != rank and _overlap(own[p], need[rank])[1]]
+
+
+def exchange_need_rows(tensor_view, own, need, world):
+    """A ranged exchange point: every rank receives, from each rank that owns some, the rows of its need range -- point to point, one
+    transfer per (owner, reader) pair with rows in common, straight from and into `tensor_view`.  Uneven and empty ranges need no padding;
+    under gloo the rows are staged through host memory.  Returns the bytes this rank received."""
+    if len(own) != world or len(need) != world:
+        raise ValueError(f"exchange_need_rows: {len(own)} own and {len(need)} need ranges for {world} ranks")
+    if not _live(world):
+        return 0
+    rank, staged = dist.get_rank(), dist.get_backend() == "gloo"
+    ops, landing, received = [], [], 0
+    for q in range(world):
+        for p, first, count in needed_from(own, need, q):
+            rows = tensor_view[first:first + count]
+            if rank == p:
+                ops.append(dist.P2POp(dist.isend, rows.cpu() if staged else rows, q))
+            elif rank == q:
+                buf = torch.empty(rows.shape, dtype=rows.dtype) if staged else rows
+                ops.append(dist.P2POp(dist.irecv, buf, p))
+                landing.append((rows, buf))
+                received += rows.numel() * 8
+    if ops:
+        for req in dist.batch_isend_irecv(ops):
+            req.wait()
+    for rows, buf in landing:
+        if staged:
+            rows.copy_(buf)
+    if tensor_view.is_cuda:
+        torch.cuda.synchronize(tensor_view.device)
+    return received
+
+
+def run_sharded_rows(session, plans, n_ops, shard_rows, rank, world, dev, timing=False):
+    """run_sharded with the max pools divided: plans[p] is part p's plan with row ranges [(after_op, tensor, first, count)]
+    (CompiledCircuit.shard_plan(rows=True, part=p, ...); the entries agree between the parts, the ranges differ).  An entry whose range is
+    the whole tensor for every part is the broadcast exchange and mark_whole; any other sends each rank its need range and ends in
+    mark_rows.  -> (timings of the spans, bytes exchanged)"""
+    timings, moved, first = [], 0, 0
+    for i, (after_op, tensor, _, _) in enumerate(plans[rank]):
+        if after_op + 1 > first:
+            timings.append(session.run_span(first, after_op + 1, timing))
+            first = after_op + 1
+        view = tensor_view(session, tensor, dev)
+        rows = view.shape[0]
+        own = [shard_rows(rows, world, p) for p in range(world)]
+        need = [tuple(plans[p][i][2:4]) for p in range(world)]
+        if all(n == (0, rows) for n in need):
+            moved += exchange_rows(view, own, world)
+            session.mark_whole(tensor)
+        else:
+            moved += exchange_need_rows(view, own, need, world)
+            session.mark_rows(tensor, *need[rank])
     if first < n_ops:
         timings.append(session.run_span(first, n_ops, timing))
     return timings, moved

@@ -66,6 +66,9 @@ def parse_args():
     e.add_argument("--shard_image", action="store_true",
                    help="under torch.distributed.run: spread every encrypted image over the ranks' GPUs (each evaluates its rows of the "
                         "look-up sites); one key seed is broadcast from rank 0.  Off, or a single process: the plain path")
+    e.add_argument("--shard_pool", action="store_true",
+                   help="with --shard_image: divide the max pools too -- a rank computes its own pool outputs and receives only the rows "
+                        "under its windows")
     return parser.parse_args()
 
 
@@ -130,7 +133,7 @@ def main():
     print("\nCompiling FHE Model (this can take up to 10 minutes for larger networks)...")
     configuration = Configuration(show_progress=False, progress_tag=True, progress_title="Evaluation: ",
                                   compress_output_ciphertexts=params.compress_outputs, public_key_inputs=params.public_key_inputs,
-                                  shard_image=params.shard_image)
+                                  shard_image=params.shard_image, shard_pool=params.shard_pool)
     key_seed = None
     if params.shard_image and "RANK" in os.environ:      # one rank per GPU; every rank needs the same keys: rank 0's seed travels
         import torch.distributed as dist

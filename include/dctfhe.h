@@ -476,6 +476,33 @@ int dctfhe_session_tensor(dctfhe_session* s, int tensor, void** dev, size_t* row
 int dctfhe_session_mark_whole(dctfhe_session* s, int tensor);
 int dctfhe_session_copy_rows(dctfhe_session* dst, dctfhe_session* src, int tensor, size_t first, size_t count);
 
+/* Divided max pools: opt-in on top of set_shard.  A pool's outputs read small windows and its tree of pairwise
+ * maxima is driven by host-built index maps, so part p computes only its own outputs -- the rows dctfhe_shard_rows gives it over the flat
+ * [B][C][Ho][Wo] order, the rows the look-up behind the pool then reads -- and produces the words of the undivided run.
+ * shard_pool (host-only, no GPU): the partition of one pool.  (out_first, out_count): the part's output rows.  Its intermediates are the
+ * row-pass results (b, c, y, xo) under the column windows of these outputs; the row pass computes only those, and a part recomputes the
+ * halo it shares with a neighbour instead of receiving it.  (in_first, in_count): the smallest contiguous range of source rows [B][C][H][W]
+ * that holds every tap of every owned window (a superset of the taps).  pairs: the pairwise maxima (bootstraps) the part runs; every
+ * output and intermediate goes through the pairings of the undivided tree (late pairing, level count of the whole pass).  An empty part
+ * has in_count = 0 and pairs = 0.  parts = 1 is the undivided op as dctfhe_session_run executes it: the whole source, every row-pass result.
+ * set_shard_pool: on != 0 -> OP_MAXPOOL runs on the part's outputs and leaves its destination sliced; the pools' trees, level buffers and
+ * clear-mode intermediates are planned again for the part (an uploaded input stays).  Refused without a prior set_shard, once the session
+ * has run, and while the margin audit is on; set_shard is refused while it is on.  Off (the default): nothing changes.
+ * mark_rows: the caller has brought rows [first, first + count) of `tensor` in.  A sliced tensor holds its own part's rows and what was
+ * marked since it was written; once that is every row it is whole.  A divided pool runs when its need range is held, and run_span names
+ * op, tensor and the first missing rows otherwise.  mark_whole stays as it is.
+ * shard_plan_rows: the entries of shard_plan with a row range each: the need range of this session's part for a tensor that one divided
+ * pool reads, (0, rows) for every other entry.  With the pools divided the entries are those of a circuit whose pools leave their
+ * destination sliced (shard_plan answers likewise); without, shard_plan's with (0, rows).
+ * pool_pairs: the pairwise maxima the last run of max-pool op `op` sent to the bootstrap (0 before a run, for an empty part and in clear
+ * mode, which runs no bootstraps). */
+int dctfhe_shard_pool(int batch, int C, int H, int W, int k, int s, int pad, int parts, int part, size_t* out_first, size_t* out_count,
+                      size_t* in_first, size_t* in_count, size_t* pairs);
+int dctfhe_session_set_shard_pool(dctfhe_session* s, int on);
+int dctfhe_session_mark_rows(dctfhe_session* s, int tensor, size_t first, size_t count);
+int dctfhe_session_shard_plan_rows(dctfhe_session* s, int32_t* after_op, int32_t* tensor, size_t* first, size_t* count, int capacity, int* n);
+int dctfhe_session_pool_pairs(dctfhe_session* s, int op, size_t* pairs);
+
 /* f64 FMA peak micro-benchmark (TFLOP/s) used to price the blind-rotate kernel in bench.py. */
 int dctfhe_fp64_peak(dctfhe_ctx* ctx, double* tflops);
 /* stand-alone timing of the blind-rotate kernel: count ciphertexts of tier `tier`, average ms per launch */

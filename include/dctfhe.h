@@ -110,7 +110,16 @@ int dctfhe_keygen(dctfhe_ctx* ctx, const dctfhe_params* params, const uint8_t se
                   dctfhe_eval_keys** eval);
 int dctfhe_eval_keys_destroy(dctfhe_eval_keys* eval);
 /* evaluation-key persistence / shipping to the server: a flat blob (header + parameters, then per tier its key-switch key
- * and its Fourier bootstrap key).  buf == NULL: only *size is written (size query). */
+ * and its Fourier bootstrap key).  buf == NULL: only *size is written (size query).
+ * Blob ('DEVK', little-endian): u32 magic, u32 version, u64 total bytes, the dctfhe_params; then per tier its own key-switch key
+ * [D][lk][n+1] u64 (absent where ksk_share >= 0) and its Fourier bootstrap key: exactly blocks (k+1) l (k+1) polynomials in the order of
+ * dctfhe_client_key_export_bsk (blocks = n, or 3n/2 for unroll 2; no padding), each M = N/2 complex doubles (re, im).
+ * Fourier-key layout of one polynomial: the forward transform runs in place in mixed radix M = R_0 ... R_{s-1} with P = 8 or 16 points
+ * per thread (16 for logN 9, l 2; 8 for every other shape), every pass of radix P and the last of radix M / P^(s-1), T = M / P threads.
+ * Entry j T + t (j < P, t < T) holds in-place position p = P t + j.  Its value is the polynomial, coefficients read as SIGNED 64-bit
+ * integers, evaluated at e^{i pi (1 - 4k) / N} and multiplied by 2^-64 / M, where k = spectrum_freq(p) (csrc/fft_core.h): with
+ * W_i = prod_{j > i} R_j, digit (p / W_i) mod R_i of the position is frequency digit k_i of weight R_0 ... R_{i-1}.
+ * tests/key_material_ref.py restates the rule; tests/test_gpu_key_material.py holds every shape's key to a long-double transform. */
 int dctfhe_eval_keys_export(dctfhe_eval_keys* eval, void* buf, size_t capacity, size_t* size);
 /* import accepts both blob forms: the one above and the compressed one below (told apart by the magic). */
 int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_eval_keys** out);
@@ -130,7 +139,21 @@ int dctfhe_client_key_export_secret(dctfhe_client_key* client, uint8_t* big_key 
 /* standard-domain keys: ksk [D][lk][n+1] (public, from the evaluation keys); bsk [n][(k+1)l][k+1][N], regenerated from the
  * client's streams -- exactly what dctfhe_eval_keys_generate transformed to the Fourier domain.
  * Key-switch-key words live on the torus grid 2^-(8 limbs), limbs = 2 / 4 / 8 for lk*betak + 6 <= 16 / <= 32 / more (their low
- * 64 - 8 limbs bits are zero: masks drawn on the grid, bodies rounded to it); dctfhe_eval_keys_import refuses a key off that grid. */
+ * 64 - 8 limbs bits are zero: masks drawn on the grid, bodies rounded to it); dctfhe_eval_keys_import refuses a key off that grid.
+ *
+ * Generator streams of the key material (pub: the client's PUBLIC generator key, the 32 bytes a compressed blob carries after its
+ * parameters; sec: the secret one, the seed).  A mask word is a generator word (dctfhe_rng_*); a noise term is the Gaussian draw of its
+ * index: generator words 2 idx and 2 idx + 1 through Box-Muller, times sigma 2^64, rounded to the nearest integer (variance
+ * (sigma 2^64)^2 + 1/12 in units of 2^-64; 0 where sigma = 0).
+ *   key-switch key of tier t, row = i lk + lev (i < D): mask word j < n is (pub, 16 + 2t, row (n + 1) + j) with the low 64 - 8 limbs bits
+ *     cleared; noise (sec, 16 + 2t + 1, row); body = <a, s> + noise + S_i 2^(64 - betak (lev + 1)), rounded to the grid (a tie goes up).
+ *   bootstrap key of tier t, global row grow = block (k + 1) l + r, r = p l + lev (p <= k, lev < l): coefficient c of mask polynomial
+ *     j < k is (pub, 64 + 2t, (grow k + j) N + c); noise coefficient c is (sec, 64 + 2t + 1, grow N + c).  The row is
+ *     GLWE_S(0) + bit_block 2^(64 - beta (lev + 1)) at coefficient 0 of polynomial p (a mask polynomial for p < k, the body for p = k),
+ *     S_j = bits [j N, (j + 1) N) of the big key; bit = the small key's, or for unroll 2 the pair secret's: per pair (a, b) the blocks
+ *     a (1 - b), (1 - a) b, a b.  The indices are global: they do not depend on how a key is generated in pieces.
+ * The tier index is part of every stream id, so two tiers of one shape share no draw.  The compressed blob ships the same rows with pure
+ * draws as masks (BODY FORM, see dctfhe_eval_keys_export_compressed): same noise terms, word for word. */
 int dctfhe_eval_keys_export_ksk(dctfhe_eval_keys* eval, int tier, uint64_t* out);
 int dctfhe_client_key_export_bsk(dctfhe_client_key* client, int tier, uint64_t* out);
 /* the generator itself: `count` 64-bit outputs (key, stream, idx0 + i).  _host runs on the CPU (known-answer tests need no GPU) */

@@ -70,7 +70,36 @@ struct SiteOp {
   LutSite lut;
   std::vector<int64_t> halves;   // split look-up: [S | Dt] of split_tables_host, until dctfhe_circuit_load has uploaded them
 };
-struct CircuitPlan { std::vector<TensorShape> tensors; std::vector<SiteOp> ops; int input_tensor = 0, output_tensor = 0, max_bit_width = 0; };
+// A slab group: an OP_CONV at `first` and the maximal run of OP_LUT / OP_MAXPOOL behind it, ops [first, end), in
+// which every op reads exactly the destination of the op before it and nothing else reads that destination.  The destinations of ops
+// [first, end - 1) are TRANSIENT: a session under a memory budget holds S channels of one image of them at a time; the last destination
+// is written whole.  Only groups with a transient tensor (end - first >= 2) are listed.
+struct SlabGroup { int first = 0, end = 0, channels = 0; };
+struct CircuitPlan {
+  std::vector<TensorShape> tensors; std::vector<SiteOp> ops; int input_tensor = 0, output_tensor = 0, max_bit_width = 0;
+  std::vector<SlabGroup> groups;
+};
+static void decode_slab_groups(CircuitPlan* c) {
+  const int n = (int)c->ops.size();
+  std::vector<int> readers(c->tensors.size(), 0), writers(c->tensors.size(), 0);
+  for (const SiteOp& o : c->ops) {
+    readers[o.src0]++;
+    if (o.type == OP_ADD) readers[o.src1]++;
+    writers[o.dst]++;
+  }
+  readers[c->output_tensor]++;      // the download reads it
+  readers[c->input_tensor]++;       // ... and the input stays resident
+  c->groups.clear();
+  for (int i = 0; i < n; i++) {
+    if (c->ops[i].type != OP_CONV) continue;
+    int j = i + 1;
+    while (j < n && (c->ops[j].type == OP_LUT || c->ops[j].type == OP_MAXPOOL) && c->ops[j].src0 == c->ops[j - 1].dst && readers[c->ops[j - 1].dst] == 1 &&
+           writers[c->ops[j - 1].dst] == 1 && c->ops[j].dst != c->ops[j].src0)
+      j++;
+    if (j - i >= 2) c->groups.push_back(SlabGroup{i, j, c->ops[i].conv.Cout});
+    i = j - 1;
+  }
+}
 
 // The bootstraps one element of a site takes, in execution order: f(tier, table_bits, has_own_keyswitch).  The only place that knows them.
 // Look-up: the one-bit steps; for a split the parity bootstrap (on the last step's small ciphertext) and the second look-up; the table.
@@ -200,6 +229,7 @@ static int parse_circuit(const void* blob, size_t size, CircuitPlan* c) {
       }
     }
   }
+  decode_slab_groups(c);
   return 0;
 }
 

@@ -413,6 +413,12 @@ struct dctfhe_session {
   bool shard_set = false, shard_pool = false;
   std::vector<std::vector<std::pair<size_t, size_t>>> marked;
   std::vector<size_t> pool_pairs_run;   // per op: pairwise maxima its last run sent to the bootstrap (max pools; 0 elsewhere)
+  // memory budget (dctfhe_session_set_memory_budget): slab[g] = channels of slab group g that exist at a time; divided_group[op] = the op's
+  // group when it is divided, else -1; pool_last[op]: the tree of the shorter last slab of a max pool in a divided group
+  std::vector<int> slab, divided_group;
+  std::vector<std::unique_ptr<PoolPlan>> pool_last;
+  size_t budget_bytes = 0, planned_bytes = 0, undivided_bytes = 0;
+  std::vector<int> circ_heights() const { std::vector<int> h; for (const SlabGroup& G : circ->groups) h.push_back(G.channels); return h; }      // the undivided heights
   void wipe_audit_key() { if (d_audit_key.p) hipMemset(d_audit_key.p, 0, d_audit_key.bytes); }      // the secret does not outlive the audit
   void audit_off() {
     wipe_audit_key();
@@ -1394,27 +1400,40 @@ static int conv_grid_ok(const dctfhe_ctx* cx, size_t pixels, size_t blocks) {
     return fail("convolution: %zu blocks of output channels exceed the device's launch-grid limit of %d", blocks, cx->max_grid_z);
   return 0;
 }
+// The output window: channels [c0, c1) of the Cout the weights hold, into a buffer laid out [batch][c1 - c0][Ho][Wo] (kernels.h).  The whole
+// output (window == nullptr) goes out in one launch and is refused past the grid limit, as it always was; a window is launched in chunks
+// of at most max_grid_y pixels, with the first pixel of each passed to the kernel, and is never refused for its pixel count.
+struct ConvWindow { int c0, c1; };
 static int dev_conv2d(const dctfhe_ctx* cx, const uint64_t* in, int batch, int Cin, int H, int W, size_t Lin, size_t deff, const int8_t* d_w, const ConvPack* pk, int Cout,
-                      int KH, int KW, int stride, int pad, uint64_t* out, size_t Lout) {
+                      int KH, int KW, int stride, int pad, uint64_t* out, size_t Lout, const ConvWindow* window = nullptr) {
   hipStream_t st = cx->stream;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
   const size_t pixels = (size_t)batch * Ho * Wo;
-  if (pk && pk->d_w && Lout >= 32) {
-    CHK(conv_grid_ok(cx, pixels, (size_t)(Cout + 63) / 64));
-    // ciphertext rows: the contraction over (ci, ky, kx) on the matrix cores, input words split into signed byte limbs on the fly
-    dim3 grid((unsigned)((Lout + 31) / 32), (unsigned)pixels, (unsigned)((Cout + 63) / 64));
-    hipLaunchKernelGGL(k_conv2d_mfma, grid, dim3(256), 0, st, in, H, W, Lin, deff, pk->d_w, pk->d_taps, pk->kpad, Cin * H * W, Cout, stride, Ho, Wo, Lout, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
+  const int c0 = window ? window->c0 : 0, c1 = window ? window->c1 : Cout;
+  if (c0 < 0 || c0 >= c1 || c1 > Cout) return fail("convolution: output window of channels [%d, %d) of %d", c0, c1, Cout);
+  const bool mfma = pk && pk->d_w && Lout >= 32;
   // clear mode (one word per element): u64 wrap MACs on the vector ALU.
   // 16 output channels per thread: 32 / 64 (fewer re-reads of the input) measured 1.45x / 3.5x SLOWER -- their per-tap weights no
   // longer fit the scalar registers (profiles/r02_exp_ablations.log)
   constexpr int COT = 16;
-  CHK(conv_grid_ok(cx, pixels, (size_t)(Cout + COT - 1) / COT));
-  dim3 grid((unsigned)((Lout + 255) / 256), (unsigned)pixels, (unsigned)((Cout + COT - 1) / COT));
-  hipLaunchKernelGGL(k_conv2d<COT>, grid, dim3(256), 0, st, in, Cin, H, W, Lin, deff, d_w, Cout, KH, KW, stride, pad, Ho, Wo, Lout, out);
-  HIPCHK(hipGetLastError());
+  const size_t blocks = (size_t)(c1 - c0 + (mfma ? 63 : COT - 1)) / (mfma ? 64 : COT);
+  // a window's chunk: what the device's grid holds, and no more than the 65 535 every device takes (so that the chunked path is the same
+  // code on a device that reports more)
+  const size_t chunk = window ? std::min<size_t>((size_t)std::max(cx->max_grid_y, 1), 65535) : std::max<size_t>(pixels, 1);
+  CHK(conv_grid_ok(cx, std::min(pixels, chunk), blocks));
+  if (pixels > (size_t)INT32_MAX) return fail("convolution: %zu output pixels (batch x Ho x Wo) do not fit a 32-bit pixel number", pixels);
+  for (size_t pix0 = 0; pix0 < pixels; pix0 += chunk) {
+    const size_t np = std::min(pixels - pix0, chunk);
+    if (mfma) {
+      // ciphertext rows: the contraction over (ci, ky, kx) on the matrix cores, input words split into signed byte limbs on the fly
+      dim3 grid((unsigned)((Lout + 31) / 32), (unsigned)np, (unsigned)blocks);
+      hipLaunchKernelGGL(k_conv2d_mfma, grid, dim3(256), 0, st, in, H, W, Lin, deff, pk->d_w, pk->d_taps, pk->kpad, Cin * H * W, c0, c1, (int)pix0, stride, Ho, Wo, Lout, out);
+    } else {
+      dim3 grid((unsigned)((Lout + 255) / 256), (unsigned)np, (unsigned)blocks);
+      hipLaunchKernelGGL(k_conv2d<COT>, grid, dim3(256), 0, st, in, Cin, H, W, Lin, deff, d_w, c0, c1, (int)pix0, KH, KW, stride, pad, Ho, Wo, Lout, out);
+    }
+    HIPCHK(hipGetLastError());
+  }
   return 0;
 }
 
@@ -1432,7 +1451,8 @@ struct LutRows {
   const int64_t *tables = nullptr, *tab_s = nullptr, *tab_d = nullptr;
   const int32_t* idx = nullptr;
 };
-static size_t ring_of(const dctfhe_keys* K, int tier) { return (size_t)K->p.tiers[tier].k << K->p.tiers[tier].logN; }
+static size_t ring_of(const dctfhe_params& P, int tier);
+static size_t ring_of(const dctfhe_keys* K, int tier) { return ring_of(K->p, tier); }
 // probe: the margin audit's slots of this site in for_each_bootstrap order -- steps, a split's second look-up, the table
 // e0: the rows are a slice that starts at element e0 of the tensor (a sharded session): the per-channel tables go by e0 + c.  Everything
 // else under a site is indexed by the launch: the scratch, and the parity rows `par`, which hold one chunk at a time
@@ -1484,11 +1504,8 @@ static int dev_round_lut(dctfhe_keys* K, const LutSite& L, const LutRows& b, siz
   return 0;
 }
 // the mask words a rounding chain touches: its input's, and the rings of the bit tiers whose outputs it accumulates (the step entries)
-static int round_chain_deff(const dctfhe_keys* K, int src_deff, const LutSite& L) {
-  int d = src_deff, left = L.n_steps();
-  for_each_bootstrap(L, K->p, [&](int tier, int, bool) { if (left-- > 0 && tier >= 0) d = std::max(d, (int)ring_of(K, tier)); });
-  return d;
-}
+static int round_chain_deff(const dctfhe_params& P, int src_deff, const LutSite& L);
+static int round_chain_deff(const dctfhe_keys* K, int src_deff, const LutSite& L) { return round_chain_deff(K->p, src_deff, L); }
 
 // can the key switch of `tier` run on the first deff rows of its key only?  (matrix-core path, whole 64-row steps; otherwise it walks the
 // whole stored row and every word of it has to be meaningful)
@@ -1546,16 +1563,18 @@ static int dev_max_pool(dctfhe_keys* K, const PoolSite& S, const PoolPlan& P, co
 // outputs (PoolPlan), so the column pass never indexes outside `mid`; the row pass reads `in` within the tensor, in bounds for any range.
 static int clear_max_pool(hipStream_t st, const uint64_t* in, uint64_t* mid, uint64_t* out, int batch, int C, int H, int W, int k, int s, int p,
                           int shift, uint64_t body_add, int p_d, const int64_t* d_table, double sigma, uint64_t seed, uint64_t stream,
-                          size_t mid_first, size_t mid_count, size_t out_first, size_t out_count) {
+                          size_t mid_first, size_t mid_count, size_t out_first, size_t out_count, size_t in_base = 0, size_t out_base = 0) {
+  // in_base / out_base: the elements of the op's input / output that `in` / `out` point at (0: the whole tensors; a slab of a divided
+  // group: the slab's first element, so that every output keeps its number in the whole op, and with it its noise)
   const int Ho = pool_out_size(H, k, s, p), Wo = pool_out_size(W, k, s, p);
   const rng_key key{{(uint32_t)seed, (uint32_t)(seed >> 32), 0x73696d75u, 0, 0, 0, 0, 0}};
   if (mid_first + mid_count > (size_t)batch * C * H * Wo || out_first + out_count > (size_t)batch * C * Ho * Wo)
     return fail("max pool (clear): intermediates %zu .. %zu or outputs %zu .. %zu outside the op", mid_first, mid_first + mid_count, out_first, out_first + out_count);
   if (out_count == 0) return 0;
-  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(mid_count)), dim3(256), 0, st, in, mid, mid_first, mid_count, (size_t)0, mid_first, W, 1, Wo, k, s, p, shift,
+  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(mid_count)), dim3(256), 0, st, in, mid, mid_first, mid_count, in_base, mid_first, W, 1, Wo, k, s, p, shift,
                      body_add, p_d, d_table, sigma, key, stream);
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(out_count)), dim3(256), 0, st, mid, out, out_first, out_count, mid_first, (size_t)0, H, Wo, Ho, k, s, p, shift,
+  hipLaunchKernelGGL(k_maxpool_clear, dim3(ew_grid(out_count)), dim3(256), 0, st, mid, out, out_first, out_count, mid_first, out_base, H, Wo, Ho, k, s, p, shift,
                      body_add, p_d, d_table, sigma, key, stream + 1);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2061,17 +2080,20 @@ static int rows_ok(const char* what, int dim, int deff) {
   return 0;
 }
 static int conv2d_rows(const char* what, dctfhe_ctx* ctx, const uint64_t* in, int dim_in, int deff_in, int batch, int Cin, int H, int W, const int8_t* weight,
-                       int Cout, int KH, int KW, int stride, int pad, int dim_o, uint64_t* out) {
+                       int Cout, int KH, int KW, int stride, int pad, int dim_o, uint64_t* out, const ConvWindow* window = nullptr) {
   if (!ctx) return fail("%s: null context", what);
   if (!in || !weight || !out) return fail("%s: null argument", what);
   if (dim_in < 0 || dim_o < 0 || batch < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0) return fail("%s: bad geometry", what);
   if (H + 2 * pad < KH || W + 2 * pad < KW) return fail("%s: kernel larger than the padded input", what);
   CHK(rows_ok(what, dim_in, deff_in));
   if (dim_o < deff_in || dim_o > (1 << 16)) return fail("%s: output rows of %d mask words cannot hold the result (%d needed)", what, dim_o, deff_in);
+  if (window && window->c0 >= window->c1) return fail("%s: empty output window: channels [%d, %d)", what, window->c0, window->c1);
+  if (window && (window->c0 < 0 || window->c1 > Cout)) return fail("%s: output window of channels [%d, %d) outside the %d the weights hold", what, window->c0, window->c1, Cout);
+  const int Cwin = window ? window->c1 - window->c0 : Cout;
   HIPCHK(hipSetDevice(ctx->device));
   const size_t Li = (size_t)dim_in + 1, Lo = (size_t)dim_o + 1;
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-  const size_t nin = (size_t)batch * Cin * H * W * Li, nout = (size_t)batch * Cout * Ho * Wo * Lo, nw = (size_t)Cout * Cin * KH * KW;
+  const size_t nin = (size_t)batch * Cin * H * W * Li, nout = (size_t)batch * Cwin * Ho * Wo * Lo, nw = (size_t)Cout * Cin * KH * KW;
   DevBuf d_in, d_out, d_w;
   HIPCHK(d_in.upload(in, nin * 8));
   HIPCHK(d_out.alloc(nout * 8));
@@ -2079,13 +2101,20 @@ static int conv2d_rows(const char* what, dctfhe_ctx* ctx, const uint64_t* in, in
   DevBuf slab;
   std::vector<ConvPack> pk;
   CHK(build_conv_packs({weight}, {ConvSite{Cout, Cin, H, W, KH, KW, stride, pad}}, &slab, &pk));
-  CHK(dev_conv2d(ctx, d_in.as<uint64_t>(), batch, Cin, H, W, Li, (size_t)deff_in, d_w.as<int8_t>(), &pk[0], Cout, KH, KW, stride, pad, d_out.as<uint64_t>(), Lo));
+  CHK(dev_conv2d(ctx, d_in.as<uint64_t>(), batch, Cin, H, W, Li, (size_t)deff_in, d_w.as<int8_t>(), &pk[0], Cout, KH, KW, stride, pad, d_out.as<uint64_t>(), Lo,
+                 window));
   HIPCHK(d_out.download(out, nout * 8, ctx->stream));
   return 0;
 }
 extern "C" int dctfhe_conv2d_rows(dctfhe_ctx* ctx, const uint64_t* in, int dim_in, int deff_in, int batch, int Cin, int H, int W, const int8_t* weight, int Cout,
                                   int KH, int KW, int stride, int pad, int dim_o, uint64_t* out) {
   return conv2d_rows("dctfhe_conv2d_rows", ctx, in, dim_in, deff_in, batch, Cin, H, W, weight, Cout, KH, KW, stride, pad, dim_o, out);
+}
+// output channels [c0, c1) only: out is [batch][c1 - c0][Ho][Wo] rows, launched in pixel chunks (dev_conv2d), so no pixel count is refused
+extern "C" int dctfhe_conv2d_rows_window(dctfhe_ctx* ctx, const uint64_t* in, int dim_in, int deff_in, int batch, int Cin, int H, int W, const int8_t* weight,
+                                         int Cout, int KH, int KW, int stride, int pad, int dim_o, int c0, int c1, uint64_t* out) {
+  const ConvWindow window{c0, c1};
+  return conv2d_rows("dctfhe_conv2d_rows_window", ctx, in, dim_in, deff_in, batch, Cin, H, W, weight, Cout, KH, KW, stride, pad, dim_o, out, &window);
 }
 // full-width rows: dim_in = deff_in = dim_o = D (under its own name, so that its messages read as they always did)
 extern "C" int dctfhe_conv2d(dctfhe_ctx* ctx, int D, const uint64_t* in, int batch, int Cin, int H, int W, const int8_t* weight, int Cout,
@@ -2303,11 +2332,10 @@ extern "C" int dctfhe_circuit_stats(dctfhe_circuit* c, const dctfhe_params* P, d
 
 // ------------------------------------------------------------------------------------------ session
 // 1. every tier the circuit bootstraps on exists in the keys, and its tables fit that tier's ring
-static int session_check_keys(dctfhe_session* s) {
-  const dctfhe_params& P = s->keys->p;
+static int circuit_check_tiers(const CircuitPlan& circ, const dctfhe_params& P) {
   auto lacks = [&](int t) { return t < 0 || t >= P.n_tiers; };
-  for (size_t i = 0; i < s->circ->ops.size(); i++) {
-    const SiteOp& o = s->circ->ops[i];
+  for (size_t i = 0; i < circ.ops.size(); i++) {
+    const SiteOp& o = circ.ops[i];
     const LutSite& L = o.lut;
     const bool pool = o.type == OP_MAXPOOL;
     if (o.type == OP_LUT) {
@@ -2341,143 +2369,404 @@ static int session_conv_packs(dctfhe_session* s) {
 // 3. row layout per tensor.  Encrypted: a tensor is stored at its effective dimension -- the compiler's `deff_in` of the consuming op
 // (mask words beyond it are zero in every ciphertext of the tensor); the output of a look-up is as wide as its table tier's ring, or as
 // the rounding chain that works in place on it.  75 % of a ResNet tensor used to be stored, written and streamed zeros.
-static int session_row_layout(dctfhe_session* s) {
-  const dctfhe_circuit* circ = s->circ;
-  const dctfhe_keys* keys = s->keys;
-  const int nt = (int)circ->tensors.size();
-  s->t_L.assign(nt, 1);
-  s->t_deff.assign(nt, 0);
-  if (!keys) return 0;
-  const size_t D = (size_t)s->D;
+// From the parameters alone (P == nullptr: clear mode, one word per element), so that dctfhe_memory_plan needs no keys.
+static size_t ring_of(const dctfhe_params& P, int tier) { return (size_t)P.tiers[tier].k << P.tiers[tier].logN; }
+static int round_chain_deff(const dctfhe_params& P, int src_deff, const LutSite& L) {
+  int d = src_deff, left = L.n_steps();
+  for_each_bootstrap(L, P, [&](int tier, int, bool) { if (left-- > 0 && tier >= 0) d = std::max(d, (int)ring_of(P, tier)); });
+  return d;
+}
+// does the key switch of `tier` run on the matrix cores?  The rule dctfhe_eval_keys follows when it builds a key's byte-limb form
+static bool tier_ks_mfma(const dctfhe_params& P, int tier) {
+  const dctfhe_tier& t = P.tiers[tier];
+  const size_t rows = (size_t)P.D * t.lk;
+  return rows % 64 == 0 && rows <= (1u << 17) && t.betak <= 7;
+}
+static int plan_row_layout(const CircuitPlan& circ, const dctfhe_params* P, std::vector<size_t>* t_L, std::vector<size_t>* t_deff) {
+  const int nt = (int)circ.tensors.size();
+  t_L->assign(nt, 1);
+  t_deff->assign(nt, 0);
+  if (!P) return 0;
+  const size_t D = (size_t)P->D;
   // (the matrix-core key switch walks the key in steps of 64 rows: an effective dimension it cannot take is kept at full width)
   // ... and the integer-VALU key switch (betak = 8, or a key the matrix-core tiling does not cover) walks whole rows of D words: a
   // circuit that uses such a tier keeps every tensor at full width
   bool all_mfma = true;
-  for (const SiteOp& o : circ->ops)
-    for_each_bootstrap(o, keys->p, [&](int t, int, bool) { all_mfma = all_mfma && keys->tiers[t].mfma(); });
+  for (const SiteOp& o : circ.ops)
+    for_each_bootstrap(o, *P, [&](int t, int, bool) { all_mfma = all_mfma && t >= 0 && t < P->n_tiers && tier_ks_mfma(*P, t); });
   auto clampd = [&](int d) { return (size_t)((all_mfma && d > 0 && (size_t)d < D && d % 64 == 0) ? d : D); };
   std::vector<char> known(nt, 0);
-  auto set = [&](int t, size_t deff, size_t width) { s->t_deff[t] = deff; s->t_L[t] = (all_mfma ? std::max(deff, width) : D) + 1; known[t] = 1; };
-  for (const SiteOp& o : circ->ops)
-    if (o.src0 == circ->input_tensor) { set(circ->input_tensor, clampd(o.deff_in), 0); break; }
-  if (!known[circ->input_tensor]) set(circ->input_tensor, D, 0);
-  for (size_t i = 0; i < circ->ops.size(); i++) {
-    const SiteOp& o = circ->ops[i];
+  auto set = [&](int t, size_t deff, size_t width) { (*t_deff)[t] = deff; (*t_L)[t] = (all_mfma ? std::max(deff, width) : D) + 1; known[t] = 1; };
+  for (const SiteOp& o : circ.ops)
+    if (o.src0 == circ.input_tensor) { set(circ.input_tensor, clampd(o.deff_in), 0); break; }
+  if (!known[circ.input_tensor]) set(circ.input_tensor, D, 0);
+  for (size_t i = 0; i < circ.ops.size(); i++) {
+    const SiteOp& o = circ.ops[i];
     if (!known[o.src0] || (o.type == OP_ADD && !known[o.src1])) return fail("op %zu reads a tensor no earlier op wrote", i);
     if (o.type == OP_LUT) {
       const LutSite& L = o.lut;
-      size_t ring = ring_of(keys, L.tab_tier);
-      if (L.split()) ring = std::max(ring, ring_of(keys, L.tier2(keys->p)));      // the sum of both look-ups: as wide as the wider ring
-      if (clampd(L.deff_in) < s->t_deff[o.src0]) return fail("op %zu: look-up compiled for effective dimension %d, its input has %zu", i, L.deff_in, s->t_deff[o.src0]);
-      const size_t chain = L.n_steps() > 0 ? (size_t)round_chain_deff(keys, (int)clampd(L.deff_in), L) : 0;
+      size_t ring = ring_of(*P, L.tab_tier);
+      if (L.split()) ring = std::max(ring, ring_of(*P, L.tier2(*P)));      // the sum of both look-ups: as wide as the wider ring
+      if (clampd(L.deff_in) < (*t_deff)[o.src0]) return fail("op %zu: look-up compiled for effective dimension %d, its input has %zu", i, L.deff_in, (*t_deff)[o.src0]);
+      const size_t chain = L.n_steps() > 0 ? (size_t)round_chain_deff(*P, (int)clampd(L.deff_in), L) : 0;
       set(o.dst, ring, chain);
     } else if (o.type == OP_MAXPOOL) {      // the relu bootstraps accumulate into the first kN words of copies of the input
-      set(o.dst, std::max(s->t_deff[o.src0], ring_of(keys, o.pool.tier)), 0);
+      set(o.dst, std::max((*t_deff)[o.src0], ring_of(*P, o.pool.tier)), 0);
     } else if (o.type == OP_ADD) {
-      set(o.dst, std::max(s->t_deff[o.src0], s->t_deff[o.src1]), 0);
+      set(o.dst, std::max((*t_deff)[o.src0], (*t_deff)[o.src1]), 0);
     } else {
-      set(o.dst, s->t_deff[o.src0], 0);
+      set(o.dst, (*t_deff)[o.src0], 0);
     }
   }
   return 0;
 }
 
-// 4. device buffers.  Tensor liveness: free a buffer after its last reader; reuse freed buffers of sufficient size
-static int session_plan_buffers(dctfhe_session* s) {
-  const dctfhe_circuit* circ = s->circ;
-  const bool keys = s->keys != nullptr;
-  const int nt = (int)circ->tensors.size(), batch = s->batch;
+// 4. device buffers, in two passes.  The SIZING pass (plan_session, host only: no allocation, no device) walks the ops once: tensor
+// liveness -- a buffer goes back to the free list after its last reader, and a freed buffer of sufficient size is reused -- plus, per op,
+// a max pool's level buffers and index maps and a parity split's second work buffer, and the look-up scratch.  It lists the allocations
+// in the order they are made.  The ALLOCATION pass (session_allocate) makes exactly those.
+// Memory budget: slab[g] channels of ONE image of every transient tensor of slab group g exist at a time, so a
+// transient tensor, the level buffers, the maps and the parity buffer of an op inside a divided group are sized for the tallest slab.
+// slab[g] = the group's channel count: the undivided group, byte for byte what runs without a budget.
+struct PoolCut { size_t parts = 1, part = 0; bool on = false; };      // a divided max pool of a sharded session (dctfhe_session_set_shard_pool)
+struct SlabPool { int channels = 0; std::unique_ptr<PoolPlan> plan; std::vector<int32_t> maps; };
+// What a max pool's tree costs: rows of level buffers A / B, int32 map entries, the largest batch of pairwise maxima of a level, and the
+// clear mode's row-pass results.  Every channel of every image goes through the same tree, and a level lists its rows output by output,
+// so each figure is that of ONE channel times the channels: a divided group is sized from the one-channel tree, whatever its slab
+// height, and its real trees are built once, for the heights in force (plan_session with trees = true checks them against this).
+struct PoolSize {
+  size_t rows_buf[2] = {0, 0}, maps = 0, max_pairs = 0, mid_count = 0;
+  PoolSize times(size_t c) const { PoolSize r; r.rows_buf[0] = rows_buf[0] * c; r.rows_buf[1] = rows_buf[1] * c; r.maps = maps * c; r.max_pairs = max_pairs * c; r.mid_count = mid_count * c; return r; }
+  bool operator==(const PoolSize& o) const { return rows_buf[0] == o.rows_buf[0] && rows_buf[1] == o.rows_buf[1] && maps == o.maps && max_pairs == o.max_pairs && mid_count == o.mid_count; }
+};
+static PoolSize pool_size_of(const PoolPlan& P, size_t maps) {
+  PoolSize r;
+  r.rows_buf[0] = P.rows_buf[0]; r.rows_buf[1] = P.rows_buf[1]; r.maps = maps; r.mid_count = P.mid_count;
+  for (const PoolLevel& l : P.lv) r.max_pairs = std::max(r.max_pairs, l.pairs);
+  return r;
+}
+// what one descent of the planner keeps between its steps: per max pool the one-channel figures and the tree of the undivided op
+struct PoolCache { std::map<int, PoolSize> unit; std::map<int, std::shared_ptr<SlabPool>> whole; };
+struct SessionPlan {
+  std::vector<size_t> t_L, t_deff, tensor_words;      // tensor_words: what the tensor's buffer holds (a slab of it if transient)
+  std::vector<size_t> alloc_bytes;                    // the allocations, in order; [0] is the input tensor's
+  std::vector<int> alloc_pool_op;                     // the max pool whose level buffer made the allocation (-1: anything else)
+  std::vector<int> tensor_alloc;                      // per tensor: its allocation (-1: no op touches it)
+  std::vector<std::array<int, 2>> op_alloc;           // per op: level buffers A / B of a max pool, or [0] the parity work buffer
+  std::vector<std::array<std::shared_ptr<SlabPool>, 2>> pool;   // per max pool: the op's tree, or in a divided group (trees = true) a full slab's and the last, shorter slab's
+  std::vector<int> slab;                              // per slab group: S
+  std::vector<int> divided_group;                     // per op: its group when that group is divided, else -1
+  size_t scratch_chunk = 0, bytes_buffers = 0, bytes_maps = 0, bytes_scratch = 0, bytes_flag = sizeof(int);
+  size_t largest_transient = 0;                       // bytes, over the transient tensors of groups that can still be lowered
+  int largest_transient_group = -1;
+  size_t total() const { return bytes_buffers + bytes_maps + bytes_scratch + bytes_flag; }
+};
+static size_t lut_scratch_bytes(const dctfhe_params& P, size_t chunk) {
+  int lkmax = 1, nmax = 1;
+  for (int i = 0; i < P.n_tiers; i++) { lkmax = std::max(lkmax, P.tiers[i].lk); nmax = std::max(nmax, P.tiers[i].n); }
+  return chunk * (size_t)P.D * lkmax + chunk * 8 + chunk * (size_t)(nmax + 1) * 8 + 64 * sizeof(int64_t);
+}
+static int plan_session(const CircuitPlan& circ, const dctfhe_params* P, int batch, const PoolCut& cut, const std::vector<int>& slab, SessionPlan* out,
+                        PoolCache* cache, bool trees) {
+  SessionPlan& sp = *out;
+  const bool keys = P != nullptr;
+  const int nt = (int)circ.tensors.size(), nops = (int)circ.ops.size();
+  if (slab.size() != circ.groups.size()) return fail("memory plan: %zu slab heights for %zu slab groups", slab.size(), circ.groups.size());
+  CHK(plan_row_layout(circ, P, &sp.t_L, &sp.t_deff));
+  sp.slab = slab;
+  sp.divided_group.assign(nops, -1);
+  std::vector<int> transient(nt, 0);      // per tensor: channels of it that exist at a time (0: all, of every image)
+  for (size_t g = 0; g < circ.groups.size(); g++) {
+    const SlabGroup& G = circ.groups[g];
+    if (slab[g] < 1 || slab[g] > G.channels) return fail("memory plan: slab height %d of a group of %d channels (ops %d .. %d)", slab[g], G.channels, G.first, G.end);
+    if (slab[g] == G.channels) continue;
+    for (int i = G.first; i < G.end; i++) sp.divided_group[i] = (int)g;
+    for (int i = G.first; i < G.end - 1; i++) transient[circ.ops[i].dst] = slab[g];
+  }
   std::vector<int> last_use(nt, -1);
-  for (int i = 0; i < (int)circ->ops.size(); i++) {
-    const SiteOp& o = circ->ops[i];
+  for (int i = 0; i < nops; i++) {
+    const SiteOp& o = circ.ops[i];
     last_use[o.src0] = i;
     if (o.type == OP_ADD) last_use[o.src1] = i;
   }
-  last_use[circ->output_tensor] = 1 << 30;
+  for (size_t g = 0; g < circ.groups.size(); g++)      // every slab of a divided group reads the convolution's source
+    if (slab[g] < circ.groups[g].channels) {
+      int& lu = last_use[circ.ops[circ.groups[g].first].src0];
+      lu = std::max(lu, circ.groups[g].end - 1);
+    }
+  last_use[circ.output_tensor] = 1 << 30;
   // the input stays resident too: dctfhe_session_run may be called again without a fresh upload (bench.py does)
-  last_use[circ->input_tensor] = 1 << 30;
-  // a second plan (dctfhe_session_set_shard_pool, before the first run) keeps the input's buffer, the first allocation: it may be uploaded already
-  uint64_t* const input_kept = s->owned.empty() ? nullptr : s->owned[0].as<uint64_t>();
-  if (input_kept) s->owned.erase(s->owned.begin() + 1, s->owned.end());
-  s->d_tensor.assign(nt, nullptr);
-  s->d_tensor[circ->input_tensor] = input_kept;
-  s->tensor_words.assign(nt, 0);
-  for (int t = 0; t < nt; t++) s->tensor_words[t] = (size_t)batch * circ->tensors[t].elems() * s->t_L[t];
-  std::vector<size_t> freelist;      // indices into s->owned
-  auto size_of = [&](size_t f) { return s->owned[freelist[f]].bytes; };
-  auto get = [&](size_t words, uint64_t** p) -> int {
+  last_use[circ.input_tensor] = 1 << 30;
+  sp.tensor_words.assign(nt, 0);
+  for (int t = 0; t < nt; t++) {
+    const TensorShape& T = circ.tensors[t];
+    sp.tensor_words[t] = (transient[t] ? (size_t)transient[t] * T.H * T.W : (size_t)batch * T.elems()) * sp.t_L[t];
+  }
+  sp.alloc_bytes.clear(); sp.alloc_pool_op.clear();
+  sp.tensor_alloc.assign(nt, -1);
+  sp.op_alloc.assign(nops, {-1, -1});
+  sp.pool.clear(); sp.pool.resize(nops);
+  std::vector<int> freelist;      // allocations
+  auto get = [&](size_t words, int pool_op) {
     int best = -1;
     for (int i = 0; i < (int)freelist.size(); i++)
-      if (size_of(i) >= words * 8 && (best < 0 || size_of(i) < size_of(best))) best = i;
-    if (best >= 0) { *p = s->owned[freelist[best]].as<uint64_t>(); freelist.erase(freelist.begin() + best); return 0; }
-    DevBuf b;
-    HIPCHK(b.alloc(words * 8));
-    *p = b.as<uint64_t>();
-    s->owned.push_back(std::move(b));
-    return 0;
+      if (sp.alloc_bytes[freelist[i]] >= words * 8 && (best < 0 || sp.alloc_bytes[freelist[i]] < sp.alloc_bytes[freelist[best]])) best = i;
+    if (best >= 0) { const int a = freelist[best]; freelist.erase(freelist.begin() + best); return a; }
+    sp.alloc_bytes.push_back(words * 8);
+    sp.alloc_pool_op.push_back(pool_op);
+    return (int)sp.alloc_bytes.size() - 1;
   };
-  auto alloc_t = [&](int t) -> int { return s->d_tensor[t] ? 0 : get(s->tensor_words[t], &s->d_tensor[t]); };
-  auto give_back = [&](uint64_t* p) {
-    for (size_t i = 0; p && i < s->owned.size(); i++)
-      if (s->owned[i].p == p) freelist.push_back(i);
-  };
-  CHK(alloc_t(circ->input_tensor));
-  s->pool.resize(circ->ops.size());
-  s->pool_buf.assign(circ->ops.size(), {nullptr, nullptr});
-  for (int i = 0; i < (int)circ->ops.size(); i++) {
-    const SiteOp& o = circ->ops[i];
-    const TensorShape& a = circ->tensors[o.src0];
-    CHK(alloc_t(o.dst));
+  auto alloc_t = [&](int t) { if (sp.tensor_alloc[t] < 0) sp.tensor_alloc[t] = get(sp.tensor_words[t], -1); };
+  alloc_t(circ.input_tensor);
+  size_t maxe = 1;      // the largest batch of bootstraps: the look-up scratch's chunk
+  sp.bytes_maps = 0;
+  for (int i = 0; i < nops; i++) {
+    const SiteOp& o = circ.ops[i];
+    const TensorShape& a = circ.tensors[o.src0];
+    const int g = sp.divided_group[i];
+    // elements of the op's input per launch: every image's, or one slab's
+    const size_t elems_in = g >= 0 ? (size_t)slab[g] * a.H * a.W : (size_t)batch * a.elems();
+    // A divided group runs once per slab, so what outlives a slab must not share a buffer with what a slab rewrites: the group's last
+    // destination is allocated before any of its transient tensors and level buffers exist (it cannot take one they free), and the
+    // convolution's source is held to the end of the group (below).  Within a slab the ops run in circuit order, as undivided.
+    if (g >= 0 && i == circ.groups[g].first) alloc_t(circ.ops[circ.groups[g].end - 1].dst);
+    alloc_t(o.dst);
     if (o.type == OP_MAXPOOL) {
-      // the tree's level buffers (encrypted) or the row pass's output (clear); of a divided pool, this part's
+      // the tree's level buffers (encrypted) or the row pass's output (clear); of a divided pool, this part's; of a divided group, a slab's
       const PoolSite& S = o.pool;
       size_t words[2] = {0, 0}, range[2] = {0, 0};
-      if (s->shard_pool) CHK(dctfhe_shard_rows((size_t)batch * circ->tensors[o.dst].elems(), s->parts, s->part, &range[0], &range[1]));
-      s->pool[i].reset(new PoolPlan);
-      if (keys) {
-        CHK(pool_plan(batch, a.C, a.H, a.W, S.k, S.stride, S.pad, s->shard_pool ? range : nullptr, s->pool[i].get()));
-        for (int b = 0; b < 2; b++) words[b] = s->pool[i]->rows_buf[b] * s->t_L[o.dst];
+      if (cut.on) CHK(dctfhe_shard_rows((size_t)batch * circ.tensors[o.dst].elems(), (int)cut.parts, (int)cut.part, &range[0], &range[1]));
+      const int heights[2] = {g >= 0 ? slab[g] : a.C, g >= 0 ? a.C % slab[g] : 0};
+      PoolSize size;      // of the tallest tree
+      if (g < 0) {        // the whole op: its tree, built once per descent
+        std::shared_ptr<SlabPool>& sl = cache->whole[i];
+        if (!sl) {
+          sl.reset(new SlabPool);
+          sl->channels = a.C;
+          sl->plan.reset(new PoolPlan);
+          CHK(pool_plan_host(batch, a.C, a.H, a.W, S.k, S.stride, S.pad, cut.on ? range : nullptr, sl->plan.get(), &sl->maps));
+        }
+        sp.pool[i][0] = sl;
+        size = pool_size_of(*sl->plan, sl->maps.size());
       } else {
-        std::vector<int32_t> unused;
-        CHK(pool_plan_host(batch, a.C, a.H, a.W, S.k, S.stride, S.pad, s->shard_pool ? range : nullptr, s->pool[i].get(), &unused));
-        words[0] = s->pool[i]->mid_count;
+        if (!cache->unit.count(i)) {
+          PoolPlan one;
+          std::vector<int32_t> maps;
+          CHK(pool_plan_host(1, 1, a.H, a.W, S.k, S.stride, S.pad, nullptr, &one, &maps));
+          cache->unit[i] = pool_size_of(one, maps.size());
+        }
+        size = cache->unit[i].times((size_t)heights[0]);
+        if (keys) sp.bytes_maps += cache->unit[i].maps * (size_t)heights[1] * 4;      // the shorter last slab's maps (counted again below: the full slab's)
+        for (int v = 0; v < 2 && trees && keys; v++) {      // (clear mode runs a slab from its element numbers: no tree)
+          if (!heights[v]) continue;
+          std::shared_ptr<SlabPool> sl(new SlabPool);
+          sl->channels = heights[v];
+          sl->plan.reset(new PoolPlan);
+          CHK(pool_plan_host(1, heights[v], a.H, a.W, S.k, S.stride, S.pad, nullptr, sl->plan.get(), &sl->maps));
+          if (!(pool_size_of(*sl->plan, sl->maps.size()) == cache->unit[i].times((size_t)heights[v])))
+            return fail("op %d: the max-pool tree of %d channels is not %d times the one-channel tree", i, heights[v], heights[v]);
+          sp.pool[i][v] = sl;
+        }
       }
-      for (int b = 0; b < 2; b++) {
-        if (!words[b]) continue;
-        size_t fr = 0, tot = 0;
-        hipMemGetInfo(&fr, &tot);
-        bool reuse = false;
-        for (size_t f = 0; f < freelist.size(); f++) reuse = reuse || size_of(f) >= words[b] * 8;
-        if (!reuse && words[b] * 8 > fr)
-          return fail("op %d: the max pool's level buffer needs %.1f GB, %.1f GB of device memory are free (batch %d too large for one device)", i,
-                      words[b] * 8e-9, fr * 1e-9, batch);
-        CHK(get(words[b], &s->pool_buf[i][b]));
+      if (keys) {
+        sp.bytes_maps += size.maps * 4;
+        for (int b = 0; b < 2; b++) words[b] = size.rows_buf[b] * sp.t_L[o.dst];
+        maxe = std::max(maxe, size.max_pairs);
+      } else {
+        words[0] = size.mid_count;
       }
+      for (int b = 0; b < 2; b++)
+        if (words[b]) sp.op_alloc[i][b] = get(words[b], i);
     }
+    if (o.type == OP_LUT) maxe = std::max(maxe, elems_in);
     if (o.type == OP_LUT && keys && o.lut.split()) {
       // the second work buffer of a parity-split site: the parity bootstrap's output, then the second look-up's; chunk-sized (the
       // look-up scratch's chunk is at most 16384)
-      const size_t rows = std::min<size_t>((size_t)batch * a.elems(), 16384);
-      CHK(get(rows * s->t_L[o.dst], &s->pool_buf[i][0]));
+      sp.op_alloc[i][0] = get(std::min<size_t>(elems_in, 16384) * sp.t_L[o.dst], -1);
     }
-    for (uint64_t* p : s->pool_buf[i]) give_back(p);      // held for this op only: back to the free list after it
-    auto release = [&](int t) { if (last_use[t] == i && t != o.dst) give_back(s->d_tensor[t]); };
+    for (int b : sp.op_alloc[i]) if (b >= 0) freelist.push_back(b);      // held for this op only: back to the free list after it
+    auto release = [&](int t) { if (last_use[t] == i && t != o.dst && sp.tensor_alloc[t] >= 0) freelist.push_back(sp.tensor_alloc[t]); };
     release(o.src0);
     if (o.type == OP_ADD && o.src1 != o.src0) release(o.src1);
+    if (g >= 0 && i == circ.groups[g].end - 1) release(circ.ops[circ.groups[g].first].src0);
+  }
+  sp.bytes_buffers = 0;
+  for (size_t b : sp.alloc_bytes) sp.bytes_buffers += b;
+  sp.scratch_chunk = std::min<size_t>(maxe, 16384);
+  sp.bytes_scratch = keys ? lut_scratch_bytes(*P, sp.scratch_chunk) : 0;
+  // where the next cut goes: the group with the largest transient tensor among those that can still be lowered
+  sp.largest_transient = 0; sp.largest_transient_group = -1;
+  for (size_t g = 0; g < circ.groups.size(); g++) {
+    if (slab[g] <= 1) continue;
+    for (int i = circ.groups[g].first; i < circ.groups[g].end - 1; i++) {
+      const TensorShape& T = circ.tensors[circ.ops[i].dst];
+      const size_t bytes = (slab[g] == circ.groups[g].channels ? (size_t)batch * T.elems() : (size_t)slab[g] * T.H * T.W) * sp.t_L[circ.ops[i].dst] * 8;
+      if (bytes > sp.largest_transient) { sp.largest_transient = bytes; sp.largest_transient_group = (int)g; }
+    }
+  }
+  return 0;
+}
+// The planner's choice: start undivided; while the plan exceeds the budget, lower by one channel the slab height of the group that holds the
+// largest transient tensor.  budget 0: no budget, the undivided plan.  Refused when height 1 everywhere still does not fit.
+static int plan_under_budget(const CircuitPlan& circ, const dctfhe_params* P, int batch, size_t budget, SessionPlan* out, size_t* undivided_bytes) {
+  std::vector<int> slab;
+  for (const SlabGroup& G : circ.groups) slab.push_back(G.channels);
+  PoolCache cache;      // a step of the descent builds no tree: the undivided ops keep theirs, a divided group is sized from one channel
+  CHK(plan_session(circ, P, batch, PoolCut{}, slab, out, &cache, false));
+  if (undivided_bytes) *undivided_bytes = out->total();
+  size_t smallest = out->total();
+  while (budget && out->total() > budget) {
+    const int g = out->largest_transient_group;
+    if (g < 0) {
+      int worst = 0;      // the op whose destination is the largest tensor left
+      size_t big = 0;
+      for (int i = 0; i < (int)circ.ops.size(); i++)
+        if (out->tensor_words[circ.ops[i].dst] * 8 >= big) { big = out->tensor_words[circ.ops[i].dst] * 8; worst = i; }
+      return fail("memory budget of %zu bytes: the smallest plan (down to one channel of every slab group at a time) needs %zu bytes; the largest tensor left, %zu bytes, is the destination of op %d",
+                  budget, smallest, big, worst);
+    }
+    slab[g]--;
+    CHK(plan_session(circ, P, batch, PoolCut{}, slab, out, &cache, false));
+    smallest = std::min(smallest, out->total());
   }
   return 0;
 }
 
-// 5. the look-up scratch: one chunk as large as the largest batch of bootstraps, at most 16384
-static int session_lut_scratch(dctfhe_session* s) {
+// the allocation pass: what the plan lists, in its order.  A second plan (dctfhe_session_set_shard_pool, dctfhe_session_set_memory_budget,
+// before the first run) keeps the input's buffer, the first allocation: it may be uploaded already
+static int session_allocate(dctfhe_session* s, SessionPlan&& sp, bool keep_scratch) {
   const dctfhe_circuit* circ = s->circ;
-  size_t maxe = 1;
-  for (size_t i = 0; i < circ->ops.size(); i++) {
-    const SiteOp& o = circ->ops[i];
-    if (o.type == OP_LUT) maxe = std::max(maxe, (size_t)s->batch * circ->tensors[o.src0].elems());
-    if (o.type == OP_MAXPOOL) for (const PoolLevel& l : s->pool[i]->lv) maxe = std::max(maxe, l.pairs);
+  const bool keys = s->keys != nullptr;
+  const int nt = (int)circ->tensors.size(), nops = (int)circ->ops.size();
+  if (!s->owned.empty()) {
+    if (s->owned[0].bytes != sp.alloc_bytes[0]) return fail("session plan: the input's buffer changed its size");
+    s->owned.erase(s->owned.begin() + 1, s->owned.end());
   }
-  return alloc_lut_scratch(s->keys, std::min<size_t>(maxe, 16384), &s->lut);
+  s->pool.clear(); s->pool.resize(nops);
+  s->pool_last.clear(); s->pool_last.resize(nops);
+  keep_scratch = keep_scratch && s->lut.chunk > 0;
+  if (!keep_scratch) s->lut = LutScratch{};
+  for (size_t a = s->owned.size(); a < sp.alloc_bytes.size(); a++) {
+    if (sp.alloc_pool_op[a] >= 0) {
+      size_t fr = 0, tot = 0;
+      hipMemGetInfo(&fr, &tot);
+      if (sp.alloc_bytes[a] > fr)
+        return fail("op %d: the max pool's level buffer needs %.1f GB, %.1f GB of device memory are free (batch %d too large for one device)", sp.alloc_pool_op[a],
+                    sp.alloc_bytes[a] * 1e-9, fr * 1e-9, s->batch);
+    }
+    DevBuf b;
+    HIPCHK(b.alloc(sp.alloc_bytes[a]));
+    s->owned.push_back(std::move(b));
+  }
+  s->t_L = sp.t_L; s->t_deff = sp.t_deff; s->tensor_words = sp.tensor_words;
+  s->d_tensor.assign(nt, nullptr);
+  for (int t = 0; t < nt; t++) if (sp.tensor_alloc[t] >= 0) s->d_tensor[t] = s->owned[sp.tensor_alloc[t]].as<uint64_t>();
+  s->pool_buf.assign(nops, {nullptr, nullptr});
+  for (int i = 0; i < nops; i++) {
+    for (int b = 0; b < 2; b++) if (sp.op_alloc[i][b] >= 0) s->pool_buf[i][b] = s->owned[sp.op_alloc[i][b]].as<uint64_t>();
+    for (int v = 0; v < 2; v++) {
+      if (!sp.pool[i][v] || !sp.pool[i][v]->plan) continue;
+      SlabPool& sl = *sp.pool[i][v];
+      if (keys) {
+        HIPCHK(sl.plan->maps.alloc(sl.maps.size() * 4));
+        if (!sl.maps.empty()) HIPCHK(hipMemcpy(sl.plan->maps.p, sl.maps.data(), sl.maps.size() * 4, hipMemcpyHostToDevice));
+      }
+      (v == 0 ? s->pool[i] : s->pool_last[i]) = std::move(sl.plan);
+    }
+  }
+  s->slab = sp.slab; s->divided_group = sp.divided_group;
+  s->planned_bytes = sp.total();
+  if (!s->budget_bytes) s->undivided_bytes = sp.total();
+  // 5. the look-up scratch: one chunk as large as the largest batch of bootstraps, at most 16384
+  return keys && !keep_scratch ? alloc_lut_scratch(s->keys, sp.scratch_chunk, &s->lut) : 0;
+}
+static int session_plan_buffers(dctfhe_session* s, const std::vector<int>* slab = nullptr, bool keep_scratch = false) {
+  const dctfhe_circuit* circ = s->circ;
+  const dctfhe_params* P = s->keys ? &s->keys->p : nullptr;
+  if (P)      // the layout follows the parameters' rule for the matrix-core key switch: the keys were built by the same one
+    for (const SiteOp& o : circ->ops) {
+      bool same = true;
+      for_each_bootstrap(o, *P, [&](int t, int, bool) { same = same && s->keys->tiers[t].mfma() == tier_ks_mfma(*P, t); });
+      if (!same) return fail("session plan: the keys' key-switch form differs from the parameters' rule");
+    }
+  std::vector<int> undivided;
+  for (const SlabGroup& G : circ->groups) undivided.push_back(G.channels);
+  SessionPlan sp;
+  PoolCut cut;
+  cut.on = s->shard_pool; cut.parts = (size_t)s->parts; cut.part = (size_t)s->part;
+  PoolCache cache;
+  CHK(plan_session(*circ, P, s->batch, cut, slab ? *slab : undivided, &sp, &cache, true));
+  return session_allocate(s, std::move(sp), keep_scratch);
+}
+
+// ---- memory budget (include/dctfhe.h): the planner from a blob and parameters alone, the session's switch, its getter
+static int fill_mem_plan(const CircuitPlan& circ, const SessionPlan& sp, size_t undivided, size_t budget, dctfhe_mem_plan* out) {
+  if (circ.groups.size() > DCTFHE_MAX_SLAB_GROUPS) return fail("memory plan: %zu slab groups, the record holds %d", circ.groups.size(), DCTFHE_MAX_SLAB_GROUPS);
+  memset(out, 0, sizeof *out);
+  out->bytes_undivided = undivided; out->bytes_planned = sp.total(); out->budget_bytes = budget;
+  out->bytes_buffers = sp.bytes_buffers; out->bytes_maps = sp.bytes_maps; out->bytes_scratch = sp.bytes_scratch + sp.bytes_flag;
+  out->n_groups = (int)circ.groups.size();
+  for (size_t g = 0; g < circ.groups.size(); g++) {
+    out->first_op[g] = circ.groups[g].first; out->end_op[g] = circ.groups[g].end; out->channels[g] = circ.groups[g].channels; out->slab[g] = sp.slab[g];
+  }
+  return 0;
+}
+extern "C" int dctfhe_memory_plan(const void* blob, size_t size, const dctfhe_params* params, int batch, size_t budget_bytes, dctfhe_mem_plan* out) {
+  if (!out) return fail("dctfhe_memory_plan: null argument");
+  if (batch < 1) return fail("dctfhe_memory_plan: batch must be >= 1");
+  CircuitPlan circ;
+  CHK(parse_circuit(blob, size, &circ));
+  if (params) { CHK(dctfhe_params_check(params)); CHK(circuit_check_tiers(circ, *params)); }
+  SessionPlan sp;
+  size_t undivided = 0;
+  CHK(plan_under_budget(circ, params, batch, budget_bytes, &sp, &undivided));
+  return fill_mem_plan(circ, sp, undivided, budget_bytes, out);
+}
+static int budget_allowed(const dctfhe_session* s, const char* who) {
+  if (!s) return fail("%s: null session", who);
+  if (s->has_run) return fail("%s: the session has run; set the budget before its first run", who);
+  if (s->parts > 1 || s->shard_pool) return fail("%s: the session is part %d of %d of a sharded run, and a budgeted session stays unsharded", who, s->part, s->parts);
+  if (s->d_audit_key.p) return fail("%s: the margin audit is on, and it runs undivided: turn it off first", who);
+  return 0;
+}
+// re-plan a session that has not run at these slab heights, with the trees of its divided pools, and allocate.  budget: what the session
+// records as its budget (nullptr: exactly the plan's bytes, 0 at the undivided heights); expect: the bytes the sizing pass promised (0:
+// none).  A refusal here has touched nothing.
+static int session_replan(dctfhe_session* s, const char* who, const std::vector<int>& heights, size_t undivided, const size_t* budget, size_t expect) {
+  HIPCHK(hipSetDevice(s->ctx->device));
+  SessionPlan sp;
+  PoolCache cache;
+  CHK(plan_session(*s->circ, s->keys ? &s->keys->p : nullptr, s->batch, PoolCut{}, heights, &sp, &cache, true));
+  if (expect && sp.total() != expect) return fail("%s: the plan with its trees needs %zu bytes, the sizing pass said %zu", who, sp.total(), expect);
+  s->undivided_bytes = undivided;
+  s->budget_bytes = budget ? *budget : heights == s->circ_heights() ? 0 : sp.total();
+  return session_allocate(s, std::move(sp), false);
+}
+// the plan at slab heights given by hand, one per slab group: what the planner would pick under SOME budget is its business; this is how a
+// test or an experiment runs a group at a height of its choosing.  It counts as a budget of exactly the plan's bytes.
+extern "C" int dctfhe_session_set_slab_heights(dctfhe_session* s, const int32_t* slab, int n_groups) {
+  CHK(budget_allowed(s, "dctfhe_session_set_slab_heights"));
+  if (!slab || n_groups != (int)s->circ->groups.size()) return fail("dctfhe_session_set_slab_heights: %d heights for a circuit of %zu slab groups", n_groups, s->circ->groups.size());
+  SessionPlan whole;
+  PoolCache cache;
+  CHK(plan_session(*s->circ, s->keys ? &s->keys->p : nullptr, s->batch, PoolCut{}, s->circ_heights(), &whole, &cache, false));
+  return session_replan(s, "dctfhe_session_set_slab_heights", std::vector<int>(slab, slab + n_groups), whole.total(), nullptr, 0);
+}
+extern "C" int dctfhe_session_set_memory_budget(dctfhe_session* s, size_t bytes) {
+  CHK(budget_allowed(s, "dctfhe_session_set_memory_budget"));
+  SessionPlan sp;
+  size_t undivided = 0;
+  CHK(plan_under_budget(*s->circ, s->keys ? &s->keys->p : nullptr, s->batch, bytes, &sp, &undivided));      // refused: nothing was touched
+  return session_replan(s, "dctfhe_session_set_memory_budget", sp.slab, undivided, &bytes, sp.total());
+}
+extern "C" int dctfhe_session_memory_plan(dctfhe_session* s, dctfhe_mem_plan* out) {
+  if (!s || !out) return fail("dctfhe_session_memory_plan: null argument");
+  SessionPlan sp;      // the heights in force; the byte figures are the session's own
+  sp.slab = s->slab;
+  CHK(fill_mem_plan(*s->circ, sp, s->undivided_bytes, s->budget_bytes, out));
+  out->bytes_planned = s->planned_bytes;
+  out->bytes_buffers = out->bytes_maps = out->bytes_scratch = 0;
+  return 0;
 }
 
 extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctfhe_keys* keys, int batch, dctfhe_session** out) {
@@ -2486,11 +2775,9 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   std::unique_ptr<dctfhe_session> s(new dctfhe_session);
   s->ctx = ctx; s->circ = circ; s->keys = keys; s->batch = batch;
   s->D = keys ? keys->p.D : 0;
-  if (keys) CHK(session_check_keys(s.get()));
+  if (keys) CHK(circuit_check_tiers(*circ, keys->p));
   if (keys) CHK(session_conv_packs(s.get()));
-  CHK(session_row_layout(s.get()));
   CHK(session_plan_buffers(s.get()));
-  if (keys) CHK(session_lut_scratch(s.get()));
   HIPCHK(s->d_overflow.alloc(sizeof(int)));
   HIPCHK(hipMemset(s->d_overflow.p, 0, sizeof(int)));
   s->whole.assign(circ->tensors.size(), 1);
@@ -2715,6 +3002,7 @@ extern "C" int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* C)
   if (!C) { s->audit_off(); return 0; }
   if (!s->keys) return fail("dctfhe_session_set_audit: a clear-mode session holds phases, not ciphertexts: there is no decision noise to measure");
   if (s->parts > 1) return fail("dctfhe_session_set_audit: this session is part %d of %d; the margin audit stays unsharded", s->part, s->parts);
+  if (s->budget_bytes) return fail("dctfhe_session_set_audit: the session has a memory budget (%zu bytes); the margin audit runs undivided", s->budget_bytes);
   const dctfhe_params &P = s->keys->p, &Q = C->p;
   if (C->ctx->device != s->ctx->device) return fail("dctfhe_session_set_audit: the client key lives on device %d, the session on %d", C->ctx->device, s->ctx->device);
   if (P.D != Q.D || P.n_max != Q.n_max || P.n_tiers != Q.n_tiers)
@@ -2782,6 +3070,7 @@ extern "C" int dctfhe_session_set_shard(dctfhe_session* s, int part, int parts) 
   CHK(dctfhe_shard_rows(0, parts, part, &f, &n));
   if (s->has_run) return fail("dctfhe_session_set_shard: the session has run; shard it before its first run");
   if (s->d_audit_key.p && parts > 1) return fail("dctfhe_session_set_shard: the margin audit is on, and it stays unsharded: turn it off first");
+  if (s->budget_bytes && parts > 1) return fail("dctfhe_session_set_shard: the session has a memory budget (%zu bytes), and a budgeted session stays unsharded", s->budget_bytes);
   if (s->shard_pool) return fail("dctfhe_session_set_shard: the max pools are divided for part %d of %d: turn that off first (dctfhe_session_set_shard_pool)", s->part, s->parts);
   s->part = part; s->parts = parts; s->shard_set = true;
   return 0;
@@ -2815,7 +3104,7 @@ extern "C" int dctfhe_session_set_shard_pool(dctfhe_session* s, int on) {
   if (want == s->shard_pool) return 0;
   HIPCHK(hipSetDevice(s->ctx->device));
   s->shard_pool = want;
-  return session_plan_buffers(s);      // the pools' trees and level buffers for this part (or the whole op again); the input's buffer stays
+  return session_plan_buffers(s, nullptr, true);      // the pools' trees and level buffers for this part (or the whole op again); the input's buffer and the look-up scratch stay
 }
 // the first rows of [first, first + count) of tensor t that this session does not hold: neither its own part's nor marked.  false: none
 static bool rows_missing(const dctfhe_session* s, int t, size_t first, size_t count, size_t* g0, size_t* g1) {
@@ -2963,52 +3252,33 @@ static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_t
   const bool audit = s->d_audit_key.p != nullptr;
   if (audit && first_op == 0 && !s->audit_slots.empty())      // every run starts from zeroed slots
     HIPCHK(hipMemsetAsync(s->d_audit.p, 0, s->audit_slots.size() * sizeof(margin_slot), st));
-  for (size_t i = (size_t)first_op; i < (size_t)end_op; i++) {
+  // one op on the rows it is given.  src / dst point at the first row read / written; r0 is that row's number in the WHOLE tensor (tables
+  // per channel and `simulate` noise go by it), rn the rows.  A convolution: conv_batch images from src, output window `window`.  A max
+  // pool: the tree `plan` (its maps count from src), or in clear mode the element bases of src and dst.
+  struct OpCall { const uint64_t* src; uint64_t* dst; size_t r0, rn; int conv_batch; const ConvWindow* window; const PoolPlan* plan; size_t in_base, out_base; };
+  auto run_op = [&](size_t i, const OpCall& call) -> int {
     const SiteOp& o = c->ops[i];
-    // this part's rows of an element-wise op (all of them in an unsharded session); any other op reads whole tensors
-    size_t r0 = 0, rn = (size_t)B * c->tensors[o.dst].elems();
-    if (op_runs_sliced(o)) {
-      CHK(dctfhe_shard_rows(rn, s->parts, s->part, &r0, &rn));
-      s->whole[o.dst] = !sharded;
-      s->marked[o.dst].clear();
-    } else if (o.type == OP_MAXPOOL && s->shard_pool) {      // a divided pool: the part's outputs, from the need range of its source
-      const PoolPlan& pp = *s->pool[i];
-      size_t g0 = 0, g1 = 0;
-      if (rows_missing(s, o.src0, pp.in_first, pp.in_count, &g0, &g1))
-        return fail("op %zu (max pool) reads rows %zu .. %zu of tensor %d, and part %d of %d lacks rows %zu .. %zu: bring them in and call dctfhe_session_mark_rows first",
-                    i, pp.in_first, pp.in_first + pp.in_count, o.src0, s->part, s->parts, g0, g1);
-      r0 = pp.out_first; rn = pp.out_count;
-      s->whole[o.dst] = 0;
-      s->marked[o.dst].clear();
-    } else {
-      if (!s->whole[o.src0])
-        return fail("op %zu needs tensor %d whole, and it holds only the rows of part %d of %d: exchange the other parts' rows and call dctfhe_session_mark_whole first",
-                    i, o.src0, s->part, s->parts);
-      s->whole[o.dst] = 1;
-      s->marked[o.dst].clear();
-    }
-    s->pool_pairs_run[i] = 0;
-    if (rn == 0) continue;      // an empty part of a small tensor
     const MarginProbe probe_i = audit ? MarginProbe{s->d_audit_key.as<uint8_t>(), s->d_audit.as<margin_slot>() + s->audit_first[i]} : MarginProbe{};
     const MarginProbe* probe = audit ? &probe_i : nullptr;
     const TensorShape& a = c->tensors[o.src0];
     const TensorShape& d = c->tensors[o.dst];
-    uint64_t* src = s->d_tensor[o.src0];
-    uint64_t* dst = s->d_tensor[o.dst];
+    const uint64_t* src = call.src;
+    uint64_t* dst = call.dst;
+    const size_t r0 = call.r0, rn = call.rn;
     const size_t Ls = s->t_L[o.src0], Ld = s->t_L[o.dst], ds = s->t_deff[o.src0];
     const double sg = i < s->sim_sigma.size() ? s->sim_sigma[i] : 0.0;      // clear mode: the noise `simulate` injects at this op
     switch (o.type) {
       case OP_CONV: {
         const int h = tm.begin(CAT_LINEAR);
-        CHK(dev_conv2d(s->ctx, src, B, a.C, a.H, a.W, Ls, ds, c->d_payload[i].as<int8_t>(), &c->conv[i], o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride, o.conv.pad, dst, Ld));
+        CHK(dev_conv2d(s->ctx, src, call.conv_batch, a.C, a.H, a.W, Ls, ds, c->d_payload[i].as<int8_t>(), &c->conv[i], o.conv.Cout, o.conv.KH, o.conv.KW, o.conv.stride,
+                       o.conv.pad, dst, Ld, call.window));
         tm.end(h);
         break;
       }
       case OP_ADD: {
         const int h = tm.begin(CAT_LINEAR);
         const size_t Lb = s->t_L[o.src1];
-        hipLaunchKernelGGL(k_add, dim3(ew_grid(rn * Ld)), dim3(256), 0, st, src + r0 * Ls, Ls, ds, s->d_tensor[o.src1] + r0 * Lb, Lb, s->t_deff[o.src1], dst + r0 * Ld, Ld,
-                           rn);
+        hipLaunchKernelGGL(k_add, dim3(ew_grid(rn * Ld)), dim3(256), 0, st, src, Ls, ds, s->d_tensor[o.src1] + r0 * Lb, Lb, s->t_deff[o.src1], dst, Ld, rn);
         HIPCHK(hipGetLastError());
         tm.end(h);
         break;
@@ -3025,7 +3295,7 @@ static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_t
         const LutSite& L = o.lut;
         const size_t E = rn;
         const int hw = a.H * a.W;
-        src += r0 * Ls; dst += r0 * Ld;      // the slice; r0 goes along wherever the element's number in the tensor is meant
+        // (src / dst: the slice; r0 goes along wherever the element's number in the tensor is meant)
         const int64_t* halves = c->d_split[i].as<int64_t>();      // [S | Dt] of a parity split, else nullptr
         const int64_t* half_d = halves ? halves + ((size_t)L.ntab << (L.w - 1)) : nullptr;
         if (!K) {
@@ -3061,20 +3331,98 @@ static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_t
       }
       case OP_MAXPOOL: {
         const PoolSite& S = o.pool;
+        const PoolPlan& pp = *call.plan;
         if (!K) {
           const int h = tm.begin(CAT_LINEAR);
-          const PoolPlan& pp = *s->pool[i];
           CHK(clear_max_pool(st, src, s->pool_buf[i][0], dst, B, a.C, a.H, a.W, S.k, S.stride, S.pad, S.shift, S.body_add, S.p_d, c->d_payload[i].as<int64_t>(), sg,
-                             s->sim_seed, (1ULL << 40) | ((uint64_t)(0x51D0000 + (s->sim_run << 12) + i) << 1), pp.mid_first, pp.mid_count, pp.out_first, pp.out_count));
+                             s->sim_seed, (1ULL << 40) | ((uint64_t)(0x51D0000 + (s->sim_run << 12) + i) << 1), pp.mid_first, pp.mid_count, pp.out_first, pp.out_count,
+                             call.in_base, call.out_base));
           tm.end(h);
         } else {
+          size_t launched = 0;
           uint64_t* const bufs[2] = {s->pool_buf[i][0], s->pool_buf[i][1]};
-          CHK(dev_max_pool(K, S, *s->pool[i], src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], c->d_payload[i].as<int64_t>(), sc, &tm, probe, &s->pool_pairs_run[i]));
+          CHK(dev_max_pool(K, S, pp, src, Ls, ds, bufs, dst, Ld, s->t_deff[o.dst], c->d_payload[i].as<int64_t>(), sc, &tm, probe, &launched));
+          s->pool_pairs_run[i] += launched;
         }
         break;
       }
       default: return fail("op %zu: unknown type %d", i, o.type);
     }
+    return 0;
+  };
+  for (size_t i = (size_t)first_op; i < (size_t)end_op; i++) {
+    const SiteOp& o = c->ops[i];
+    if (s->divided_group[i] >= 0) {
+      // a divided slab group (memory budget): per image and per slab of S channels, the windowed convolution into the slab's buffer, then
+      // every op behind it on the slab's rows; the last op writes its rows into the whole destination at their place.  All channels of a
+      // slab are whole, so a max pool has no halo.  (dctfhe_session_run_span admits whole groups only; never sharded, never audited.)
+      const SlabGroup& G = c->groups[s->divided_group[i]];
+      const int S = s->slab[s->divided_group[i]];
+      for (int j = G.first; j < G.end; j++) { s->whole[c->ops[j].dst] = 1; s->marked[c->ops[j].dst].clear(); s->pool_pairs_run[j] = 0; }
+      const TensorShape& in_t = c->tensors[o.src0];
+      for (int b = 0; b < B; b++)
+        for (int c0 = 0; c0 < G.channels; c0 += S) {
+          const int c1 = std::min(c0 + S, G.channels);
+          const ConvWindow window{c0, c1};
+          for (int j = G.first; j < G.end; j++) {
+            const SiteOp& oj = c->ops[j];
+            const TensorShape& a = c->tensors[oj.src0];
+            const TensorShape& d = c->tensors[oj.dst];
+            const bool last = j == G.end - 1;
+            // the slab's first row in the whole source / destination; a transient buffer holds the slab from its row 0
+            const size_t in_row = ((size_t)b * G.channels + c0) * a.H * a.W, out_row = ((size_t)b * G.channels + c0) * d.H * d.W;
+            OpCall call{};
+            call.src = j == G.first ? s->d_tensor[oj.src0] + (size_t)b * in_t.elems() * s->t_L[oj.src0] : s->d_tensor[oj.src0];
+            call.dst = s->d_tensor[oj.dst] + (last ? out_row * s->t_L[oj.dst] : 0);
+            call.r0 = out_row; call.rn = (size_t)(c1 - c0) * d.H * d.W;
+            call.conv_batch = 1; call.window = &window;
+            PoolPlan clear_range;      // clear mode: the slab's intermediates and outputs by their numbers in the whole op
+            if (oj.type == OP_MAXPOOL) {
+              call.plan = (c1 - c0 == S ? s->pool[j] : s->pool_last[j]).get();
+              if (!K) {
+                clear_range.mid_first = ((size_t)b * G.channels + c0) * a.H * d.W; clear_range.mid_count = (size_t)(c1 - c0) * a.H * d.W;
+                clear_range.out_first = out_row; clear_range.out_count = call.rn;
+                call.plan = &clear_range;
+                call.in_base = in_row; call.out_base = last ? 0 : out_row;
+                call.dst = s->d_tensor[oj.dst];      // ... the kernel places the rows itself
+              }
+            }
+            CHK(run_op((size_t)j, call));
+          }
+        }
+      i = (size_t)G.end - 1;
+      continue;
+    }
+    // this part's rows of an element-wise op (all of them in an unsharded session); any other op reads whole tensors
+    size_t r0 = 0, rn = (size_t)B * c->tensors[o.dst].elems();
+    if (op_runs_sliced(o)) {
+      CHK(dctfhe_shard_rows(rn, s->parts, s->part, &r0, &rn));
+      s->whole[o.dst] = !sharded;
+      s->marked[o.dst].clear();
+    } else if (o.type == OP_MAXPOOL && s->shard_pool) {      // a divided pool: the part's outputs, from the need range of its source
+      const PoolPlan& pp = *s->pool[i];
+      size_t g0 = 0, g1 = 0;
+      if (rows_missing(s, o.src0, pp.in_first, pp.in_count, &g0, &g1))
+        return fail("op %zu (max pool) reads rows %zu .. %zu of tensor %d, and part %d of %d lacks rows %zu .. %zu: bring them in and call dctfhe_session_mark_rows first",
+                    i, pp.in_first, pp.in_first + pp.in_count, o.src0, s->part, s->parts, g0, g1);
+      r0 = pp.out_first; rn = pp.out_count;
+      s->whole[o.dst] = 0;
+      s->marked[o.dst].clear();
+    } else {
+      if (!s->whole[o.src0])
+        return fail("op %zu needs tensor %d whole, and it holds only the rows of part %d of %d: exchange the other parts' rows and call dctfhe_session_mark_whole first",
+                    i, o.src0, s->part, s->parts);
+      s->whole[o.dst] = 1;
+      s->marked[o.dst].clear();
+    }
+    s->pool_pairs_run[i] = 0;
+    if (rn == 0) continue;      // an empty part of a small tensor
+    OpCall call{};
+    const bool sliced = o.type == OP_LUT || o.type == OP_ADD;      // their pointers are the slice's; every other op is given the whole tensors
+    call.src = s->d_tensor[o.src0] + (sliced ? r0 * s->t_L[o.src0] : 0);
+    call.dst = s->d_tensor[o.dst] + (sliced ? r0 * s->t_L[o.dst] : 0);
+    call.r0 = r0; call.rn = rn; call.conv_batch = B; call.plan = s->pool[i].get();
+    CHK(run_op(i, call));
   }
   if (end_op == (int)c->ops.size() && first_op < end_op) s->sim_run++;      // `simulate` draws afresh in every pass over the circuit (its last op ends one)
   HIPCHK(hipEventRecord(e1, st));
@@ -3104,6 +3452,12 @@ extern "C" int dctfhe_session_run_span(dctfhe_session* s, int first_op, int end_
   if (!s) return fail("dctfhe_session_run_span: null session");
   const int n = (int)s->circ->ops.size();
   if (first_op < 0 || end_op < first_op || end_op > n) return fail("dctfhe_session_run_span: ops [%d, %d) of a circuit of %d", first_op, end_op, n);
+  for (size_t g = 0; g < s->circ->groups.size(); g++) {      // a divided slab group runs slab by slab, all its ops per slab: whole or not at all
+    const SlabGroup& G = s->circ->groups[g];
+    if (s->slab[g] < G.channels && first_op < end_op && ((first_op > G.first && first_op < G.end) || (end_op > G.first && end_op < G.end)))
+      return fail("dctfhe_session_run_span: ops [%d, %d) cut the slab group of ops [%d, %d), which the memory budget divides into slabs of %d channels: a span holds it whole or not at all",
+                  first_op, end_op, G.first, G.end, s->slab[g]);
+  }
   return session_run_ops(s, first_op, end_op, timing);
 }
 extern "C" int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing) { return session_run_ops(s, 0, (int)s->circ->ops.size(), timing); }

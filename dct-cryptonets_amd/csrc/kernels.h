@@ -935,15 +935,17 @@ pbs_kernel(pbs_launch a) {
 // out[b][co][y][x][word] = sum_{ci,ky,kx} w[co][ci][ky][kx] * in[b][ci][y*s+ky-p][x*s+kx-p][word]  (mod 2^64)
 // Thread = one ciphertext word of one output pixel for a tile of COT output channels; lanes run over
 // words, so every load is a coalesced stream of one input ciphertext.
+// Output window (both kernels): channels [c0, c1) only, written to a buffer laid out [batch][c1 - c0][Ho][Wo] (relative to the window,
+// not to the whole tensor), and pixels from pix0 on, one per block of gridDim.y.  c0 = 0, c1 = Cout, pix0 = 0 is the whole output.
 template <int COT>
 __global__ void __launch_bounds__(256)
-k_conv2d(const uint64_t* __restrict__ in, int Cin, int H, int W, size_t Lin, size_t Deff, const int8_t* __restrict__ wgt, int Cout,
-         int KH, int KW, int stride, int pad, int Ho, int Wo, size_t Lout, uint64_t* __restrict__ out) {
+k_conv2d(const uint64_t* __restrict__ in, int Cin, int H, int W, size_t Lin, size_t Deff, const int8_t* __restrict__ wgt, int c0, int c1,
+         int pix0, int KH, int KW, int stride, int pad, int Ho, int Wo, size_t Lout, uint64_t* __restrict__ out) {
   // tensors are stored at their effective dimension: a row is Deff mask words (everything beyond is known to be zero and is
   // not stored) then the body; thread Deff of a pixel handles the body word
   const size_t word = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const int pix = blockIdx.y;           // b*Ho*Wo + y*Wo + x
-  const int co0 = blockIdx.z * COT;
+  const int pix = pix0 + blockIdx.y;    // b*Ho*Wo + y*Wo + x
+  const int co0 = c0 + blockIdx.z * COT;
   const int b = pix / (Ho * Wo), y = (pix / Wo) % Ho, x = pix % Wo;
   if (word >= Lout) return;
   const bool body = word == Lout - 1;
@@ -964,7 +966,7 @@ k_conv2d(const uint64_t* __restrict__ in, int Cin, int H, int W, size_t Lin, siz
 #pragma unroll
           for (int c = 0; c < COT; c++) {
             const int co = co0 + c;
-            const int8_t wv = (co < Cout) ? wgt[(((size_t)co * Cin + ci) * KH + ky) * KW + kx] : (int8_t)0;  // uniform
+            const int8_t wv = (co < c1) ? wgt[(((size_t)co * Cin + ci) * KH + ky) * KW + kx] : (int8_t)0;  // uniform
             acc[c] += (uint64_t)(int64_t)wv * v;
           }
         }
@@ -973,7 +975,7 @@ k_conv2d(const uint64_t* __restrict__ in, int Cin, int H, int W, size_t Lin, siz
 #pragma unroll
   for (int c = 0; c < COT; c++) {
     const int co = co0 + c;
-    if (co < Cout) out[((((size_t)b * Cout + co) * Ho + y) * Wo + x) * Lout + word] = acc[c];
+    if (co < c1) out[((((size_t)b * (c1 - c0) + (co - c0)) * Ho + y) * Wo + x) * Lout + word] = acc[c];
   }
 }
 
@@ -984,19 +986,20 @@ k_conv2d(const uint64_t* __restrict__ in, int Cin, int H, int W, size_t Lin, siz
 // GEMM for v_mfma_i32_32x32x32_i8 (|C| <= K * 127 * 128 < 2^31 for K <= 2^17) and out = sum_limb C_limb << 8 limb.
 // Workgroup = one output pixel x 32 ciphertext words x 64 output channels; K in steps of 32 (ci, ky, kx) triples; wave w owns
 // columns [64 w, 64 w + 64) = 8 words x 8 limbs.  Both operands K-contiguous in LDS (one ds_read_b128 per fragment).
+// The 64-channel tiles start at c0, so a tile may reach past the padded weight rows: rows at or past c1 are loaded as zeros.
 struct conv_tap { int32_t offset; int16_t dy, dx; };     // per k = (ci, ky, kx): ci*H*W (pixels; < 0: padding row of K), ky - pad, kx - pad
 
 __global__ void __launch_bounds__(256)
 k_conv2d_mfma(const uint64_t* __restrict__ in, int H, int W, size_t Lin, size_t Deff, const int8_t* __restrict__ wpack /* [Cout_pad64][Kpad] */,
-              const conv_tap* __restrict__ taps /* [Kpad], offset < 0: padding row */, int Kpad, int Cin_HW, int Cout, int stride, int Ho, int Wo,
-              size_t Lout, uint64_t* __restrict__ out) {
+              const conv_tap* __restrict__ taps /* [Kpad], offset < 0: padding row */, int Kpad, int Cin_HW, int c0, int c1, int pix0, int stride,
+              int Ho, int Wo, size_t Lout, uint64_t* __restrict__ out) {
   constexpr int BK = 32, LD = BK + 16;
   __shared__ __attribute__((aligned(16))) int8_t As[64 * LD];
   __shared__ __attribute__((aligned(16))) int8_t Bs[256 * LD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int pix = blockIdx.y;           // b*Ho*Wo + y*Wo + x
+  const int pix = pix0 + blockIdx.y;    // b*Ho*Wo + y*Wo + x
   const int b = pix / (Ho * Wo), y = (pix / Wo) % Ho, x = pix % Wo;
-  const int co0 = blockIdx.z * 64;
+  const int co0 = c0 + blockIdx.z * 64;
   // staging: thread = (word w of 32, group kq of 8): 4 consecutive k for one word
   const int sw = tid & 31, kq = tid >> 5;
   const size_t wg = (size_t)blockIdx.x * 32 + sw;                    // word of the output row this thread stages
@@ -1033,7 +1036,7 @@ k_conv2d_mfma(const uint64_t* __restrict__ in, int H, int W, size_t Lin, size_t 
       }
     }
     v4i ga = {0, 0, 0, 0};
-    if (tid < 128) ga = *reinterpret_cast<const v4i*>(wpack + (size_t)(co0 + (tid >> 1)) * Kpad + k0 + (tid & 1) * 16);
+    if (tid < 128 && co0 + (tid >> 1) < c1) ga = *reinterpret_cast<const v4i*>(wpack + (size_t)(co0 + (tid >> 1)) * Kpad + k0 + (tid & 1) * 16);
     __syncthreads();
 #pragma unroll
     for (int l = 0; l < 8; l++) *reinterpret_cast<uint32_t*>(&Bs[(sw * 8 + l) * LD + kq * 4]) = packed[l];
@@ -1063,7 +1066,7 @@ k_conv2d_mfma(const uint64_t* __restrict__ in, int H, int W, size_t Lin, size_t 
         v += __shfl_xor(v, 2);
         v += __shfl_xor(v, 4);
         const int co = co0 + a * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (limb == 0 && co < Cout && word < Lout) out[((((size_t)b * Cout + co) * Ho + y) * Wo + x) * Lout + word] = v;
+        if (limb == 0 && co < c1 && word < Lout) out[((((size_t)b * (c1 - c0) + (co - c0)) * Ho + y) * Wo + x) * Lout + word] = v;
       }
     }
 }

@@ -47,6 +47,24 @@ class MarginStats(C.Structure):
                 ("max_abs", C.c_int32), ("count", C.c_int64), ("sum", C.c_int64), ("sum_sq", C.c_uint64), ("hist", C.c_int64 * MARGIN_BINS)]
 
 
+MAX_SLAB_GROUPS = 64
+
+
+class MemPlan(C.Structure):
+    """dctfhe_mem_plan: planned session bytes and the slab height per slab group (include/dctfhe.h)"""
+    _fields_ = [("bytes_undivided", C.c_uint64), ("bytes_planned", C.c_uint64), ("budget_bytes", C.c_uint64),
+                ("bytes_buffers", C.c_uint64), ("bytes_maps", C.c_uint64), ("bytes_scratch", C.c_uint64),
+                ("n_groups", C.c_int32), ("reserved", C.c_int32),
+                ("first_op", C.c_int32 * MAX_SLAB_GROUPS), ("end_op", C.c_int32 * MAX_SLAB_GROUPS),
+                ("channels", C.c_int32 * MAX_SLAB_GROUPS), ("slab", C.c_int32 * MAX_SLAB_GROUPS)]
+
+    def record(self):
+        return dict(bytes_undivided=int(self.bytes_undivided), bytes_planned=int(self.bytes_planned), budget_bytes=int(self.budget_bytes),
+                    bytes_buffers=int(self.bytes_buffers), bytes_maps=int(self.bytes_maps), bytes_scratch=int(self.bytes_scratch),
+                    groups=[dict(first_op=int(self.first_op[g]), end_op=int(self.end_op[g]), channels=int(self.channels[g]), slab=int(self.slab[g]))
+                            for g in range(self.n_groups)])
+
+
 EXPORTS = [
     "dctfhe_last_error", "dctfhe_version", "dctfhe_ctx_create", "dctfhe_ctx_destroy", "dctfhe_ctx_set_stream",
     "dctfhe_ctx_synchronize", "dctfhe_keygen", "dctfhe_client_key_create", "dctfhe_client_key_destroy", "dctfhe_eval_keys_generate",
@@ -69,6 +87,7 @@ EXPORTS = [
     "dctfhe_shard_rows", "dctfhe_session_set_shard", "dctfhe_session_run_span", "dctfhe_session_shard_plan", "dctfhe_session_tensor",
     "dctfhe_session_mark_whole", "dctfhe_session_copy_rows",
     "dctfhe_shard_pool", "dctfhe_session_set_shard_pool", "dctfhe_session_mark_rows", "dctfhe_session_shard_plan_rows", "dctfhe_session_pool_pairs",
+    "dctfhe_conv2d_rows_window", "dctfhe_memory_plan", "dctfhe_session_set_memory_budget", "dctfhe_session_memory_plan", "dctfhe_session_set_slab_heights",
 ]
 
 _lib = None
@@ -121,6 +140,7 @@ def load():
     L.dctfhe_session_set_noise_split.argtypes = [vp, vp, i32]
     L.dctfhe_conv2d.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp]
     L.dctfhe_conv2d_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.dctfhe_conv2d_rows_window.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     L.dctfhe_add_rows.argtypes = [vp, vp, i32, i32, vp, i32, i32, sz, i32, vp]
     L.dctfhe_affine_rows.argtypes = [vp, vp, i32, i32, sz, i32, i32, u64, i32, vp]
     L.dctfhe_sum_pool_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
@@ -192,6 +212,10 @@ def load():
     L.dctfhe_session_mark_rows.argtypes = [vp, i32, sz, sz]
     L.dctfhe_session_shard_plan_rows.argtypes = [vp, vp, vp, vp, vp, i32, pi]
     L.dctfhe_session_pool_pairs.argtypes = [vp, i32, C.POINTER(sz)]
+    L.dctfhe_memory_plan.argtypes = [vp, sz, C.POINTER(Params), i32, sz, C.POINTER(MemPlan)]
+    L.dctfhe_session_set_memory_budget.argtypes = [vp, sz]
+    L.dctfhe_session_memory_plan.argtypes = [vp, C.POINTER(MemPlan)]
+    L.dctfhe_session_set_slab_heights.argtypes = [vp, vp, i32]
     _lib = L
     return L
 

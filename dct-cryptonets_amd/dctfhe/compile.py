@@ -376,8 +376,18 @@ class CompiledCircuit:
                 out.append((a, t) + shard_pool(batch, T.C, T.H, T.W, S.k, S.stride, S.pad, parts, part)[2:4])
         return out
 
-    def report(self):
-        """Text dump standing in for `fhe_circuit.mlir` (reference homomorphic_eval.py:309-311)."""
+    def memory_plan(self, params=None, batch=1, budget_bytes=None):
+        """The session planner's record for this circuit (include/dctfhe.h dctfhe_memory_plan -- the library's planner, not a restatement):
+        {bytes_undivided, bytes_planned, budget_bytes, ..., groups: [{first_op, end_op, channels, slab}]}.  params: a parameter set
+        (default: the circuit's own), or False for a clear-mode session.  Host only: no GPU."""
+        from .engine import memory_plan
+        ps = self.param_set if params is None else params
+        cp = None if ps is False else (ps if hasattr(ps, "_fields_") else P.to_c_params(ps))
+        return memory_plan(self.blob, cp, batch, budget_bytes)
+
+    def report(self, memory_budget_bytes=None, batch=1):
+        """Text dump standing in for `fhe_circuit.mlir` (reference homomorphic_eval.py:309-311).  memory_budget_bytes: also the planned
+        session bytes and slab heights under that budget (memory_plan)."""
         names = {OP_CONV: "conv2d", OP_ADD: "add", OP_SUMPOOL: "sum_pool", OP_LUT: "round_lut", OP_MAXPOOL: "max_pool2d"}
         ps = self.param_set
         lines = [f"// dctfhe circuit: {len(self.ops)} ops, max accumulator bit-width {self.max_bit_width}, D={ps.D}"]
@@ -408,6 +418,11 @@ class CompiledCircuit:
         lines.append(f"// expected table failures per image (noise model): {self.expected_failures_per_image:.2e}")
         if self.rounding_method == "approximate":
             lines.append(f"// approximate rounding: expected boundary flips per image: {self.expected_boundary_flips_per_image:.2e}")
+        if memory_budget_bytes:
+            m = self.memory_plan(batch=batch, budget_bytes=memory_budget_bytes)
+            lines.append(f"// device memory budget {memory_budget_bytes} bytes, batch {batch}: planned {m['bytes_planned']} bytes (undivided {m['bytes_undivided']})")
+            for g in m["groups"]:
+                lines.append(f"//   slab group ops [{g['first_op']}, {g['end_op']}): {g['slab']} of {g['channels']} channels at a time")
         return "\n".join(lines)
 
 

@@ -7,7 +7,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._lib import MarginStats, Params, Stats, Tier, Timing, check, ptr
+from ._lib import MarginStats, MemPlan, Params, Stats, Tier, Timing, check, ptr
 
 
 def make_params(D, n_max, tiers, input_sigma, input_dim=0):
@@ -128,6 +128,17 @@ class Context:
         Ho, Wo = (max(H + 2 * pad - KH, 0) // max(stride, 1) + 1, max(W + 2 * pad - KW, 0) // max(stride, 1) + 1)   # the library checks the geometry
         out = np.empty((B, Cout, Ho, Wo, max(dim_o, 0) + 1), np.uint64)
         check(self.L.dctfhe_conv2d_rows(self.h, ptr(x), L - 1, deff, B, Cin, H, W, ptr(weight), Cout, KH, KW, stride, pad, dim_o, ptr(out)))
+        return out
+
+    def conv2d_rows_window(self, x, deff, weight, stride, pad, dim_o, c0, c1):
+        """conv2d_rows for output channels [c0, c1) only -> [batch, c1 - c0, Ho, Wo, dim_o + 1] (include/dctfhe.h dctfhe_conv2d_rows_window:
+        launched in pixel chunks, so never refused for its pixel count)"""
+        x, weight = np.ascontiguousarray(x, np.uint64), np.ascontiguousarray(weight, np.int8)
+        B, Cin, H, W, L = x.shape
+        Cout, _, KH, KW = weight.shape
+        Ho, Wo = (max(H + 2 * pad - KH, 0) // max(stride, 1) + 1, max(W + 2 * pad - KW, 0) // max(stride, 1) + 1)   # the library checks the geometry
+        out = np.empty((B, max(c1 - c0, 0), Ho, Wo, max(dim_o, 0) + 1), np.uint64)
+        check(self.L.dctfhe_conv2d_rows_window(self.h, ptr(x), L - 1, deff, B, Cin, H, W, ptr(weight), Cout, KH, KW, stride, pad, dim_o, c0, c1, ptr(out)))
         return out
 
     def expand_seeded(self, sc, dim=None):
@@ -735,6 +746,15 @@ def shard_pool(batch, C_, H, W, k, s, pad, parts, part):
     return tuple(x.value for x in v)
 
 
+def memory_plan(blob, params=None, batch=1, budget_bytes=None):
+    """The session planner on the host (dctfhe_memory_plan; no context, no GPU): the bytes a session of `batch` images allocates for
+    itself, undivided and under `budget_bytes` (None: no budget), and per slab group its op range, channels and slab height.  params: a
+    ctypes Params (None: a clear-mode session).  Refused, naming an op, when one channel at a time everywhere still exceeds the budget."""
+    blob, m = bytes(blob), MemPlan()
+    check(_lib.load().dctfhe_memory_plan(blob, len(blob), None if params is None else C.byref(params), int(batch), int(budget_bytes or 0), C.byref(m)))
+    return m.record()
+
+
 class Circuit:
     def __init__(self, ctx, blob):
         self.ctx, self.L = ctx, ctx.L
@@ -813,6 +833,23 @@ class Session:
         t = Timing() if timing else None
         check(self.L.dctfhe_session_run(self.h, C.byref(t) if timing else None))
         return t
+
+    # -- bounded device memory (include/dctfhe.h dctfhe_session_set_memory_budget) ---------------------------------------------------
+    def set_memory_budget(self, budget_bytes):
+        """plan the session's buffers under `budget_bytes` (0 / None: no budget): slab groups are walked in channel slabs, no output word
+        changes.  Before the first run; never sharded, never with the margin audit; a refused budget leaves the session as it was"""
+        check(self.L.dctfhe_session_set_memory_budget(self.h, int(budget_bytes or 0)))
+
+    def set_slab_heights(self, heights):
+        """plan the session at these slab heights, one per slab group (dctfhe_session_set_slab_heights): for tests and experiments"""
+        h = np.ascontiguousarray(heights, np.int32)
+        check(self.L.dctfhe_session_set_slab_heights(self.h, ptr(h), h.size))
+
+    def memory_plan(self):
+        """the plan in force (dctfhe_session_memory_plan): planned bytes, undivided and as planned, and the slab height per group"""
+        m = MemPlan()
+        check(self.L.dctfhe_session_memory_plan(self.h, C.byref(m)))
+        return m.record()
 
     # -- sharded look-up sites (include/dctfhe.h dctfhe_session_set_shard): one image over several sessions, one per GPU ----------
     def set_shard(self, part, parts):

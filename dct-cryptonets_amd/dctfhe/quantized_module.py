@@ -33,7 +33,7 @@ class Configuration:
 
     def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
                  compress_evaluation_keys=False, compress_output_ciphertexts=False, result_packing_spec=None, public_key_inputs=False,
-                 public_input_spec=None, shard_image=False, shard_pool=False, **kwargs):
+                 public_input_spec=None, shard_image=False, shard_pool=False, device_memory_budget_gb=None, **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
         # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
         # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
@@ -64,7 +64,19 @@ class Configuration:
         self.shard_pool = bool(shard_pool)
         if self.shard_pool and not self.shard_image:
             raise ValueError("shard_pool divides the max pools of a sharded image: it needs shard_image=True")
+        # dctfhe addition: every session the module creates plans its buffers under this many GB (10^9 bytes) of device memory: a
+        # convolution and the look-ups / max pools behind it run in channel slabs, and no output word changes (DESIGN.md section 4.2;
+        # include/dctfhe.h dctfhe_session_set_memory_budget).  None: no budget.  A budgeted session stays unsharded.
+        self.device_memory_budget_gb = None if device_memory_budget_gb is None else float(device_memory_budget_gb)
+        if self.device_memory_budget_gb is not None and self.device_memory_budget_gb <= 0:
+            raise ValueError("device_memory_budget_gb must be positive (None: no budget)")
+        if self.device_memory_budget_gb is not None and self.shard_image:
+            raise ValueError("device_memory_budget_gb and shard_image exclude each other: a budgeted session stays unsharded")
         self.extra = kwargs
+
+    @property
+    def device_memory_budget_bytes(self):
+        return None if self.device_memory_budget_gb is None else int(self.device_memory_budget_gb * 1e9)
 
 
 _output_form = roles.output_form
@@ -212,7 +224,14 @@ class QuantizedModule:
             ctx = self._context()
             if mode == "execute" and self._keys is None:
                 self._keygen(None)
-            self._sessions[key] = Session(ctx, self._circuit, self._keys if mode == "execute" else None, batch)
+            sess = Session(ctx, self._circuit, self._keys if mode == "execute" else None, batch)
+            if self.configuration.device_memory_budget_bytes:
+                try:
+                    sess.set_memory_budget(self.configuration.device_memory_budget_bytes)
+                except Exception:
+                    sess.close()
+                    raise
+            self._sessions[key] = sess
         return self._sessions[key]
 
     def _shard_group(self):

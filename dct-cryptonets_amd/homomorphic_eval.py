@@ -69,7 +69,13 @@ def parse_args():
     e.add_argument("--shard_pool", action="store_true",
                    help="with --shard_image: divide the max pools too -- a rank computes its own pool outputs and receives only the rows "
                         "under its windows")
-    return parser.parse_args()
+    e.add_argument("--device_memory_budget_gb", default=None, type=float,
+                   help="plan every session under this many GB of device memory: convolutions and the look-ups / max pools behind them run "
+                        "in channel slabs; outputs are unchanged.  Not with --shard_image.  Default: no budget")
+    args = parser.parse_args()
+    if args.device_memory_budget_gb is not None and args.shard_image:
+        parser.error("--device_memory_budget_gb and --shard_image exclude each other: a budgeted session stays unsharded")
+    return args
 
 
 class AverageMeter:            # reference utils.py:74-89
@@ -133,7 +139,8 @@ def main():
     print("\nCompiling FHE Model (this can take up to 10 minutes for larger networks)...")
     configuration = Configuration(show_progress=False, progress_tag=True, progress_title="Evaluation: ",
                                   compress_output_ciphertexts=params.compress_outputs, public_key_inputs=params.public_key_inputs,
-                                  shard_image=params.shard_image, shard_pool=params.shard_pool)
+                                  shard_image=params.shard_image, shard_pool=params.shard_pool,
+                                  device_memory_budget_gb=params.device_memory_budget_gb)
     key_seed = None
     if params.shard_image and "RANK" in os.environ:      # one rank per GPU; every rank needs the same keys: rank 0's seed travels
         import torch.distributed as dist

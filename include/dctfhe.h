@@ -245,6 +245,43 @@ int dctfhe_sum_pool_rows(dctfhe_ctx* ctx, const uint64_t* in /* [batch][C][H][W]
 int dctfhe_conv2d_rows(dctfhe_ctx* ctx, const uint64_t* in /* [batch][Cin][H][W] rows of dim_in+1 */, int dim_in, int deff_in, int batch,
                        int Cin, int H, int W, const int8_t* weight /* [Cout][Cin][KH][KW] */, int Cout, int KH, int KW, int stride,
                        int pad, int dim_o, uint64_t* out /* [batch][Cout][Ho][Wo] rows of dim_o+1 */);
+/* dctfhe_conv2d_rows for a window of its output: channels [c0, c1) only, 0 <= c0 < c1 <= Cout, into a buffer that holds the window and
+ * nothing else.  The pixels go out in chunks of at most the device's launch-grid limit, so no pixel count is refused; c0 = 0, c1 = Cout
+ * computes what dctfhe_conv2d_rows computes.  The same kernels and the same weight pack: a session under a memory budget runs its
+ * convolutions through this path. */
+int dctfhe_conv2d_rows_window(dctfhe_ctx* ctx, const uint64_t* in /* [batch][Cin][H][W] rows of dim_in+1 */, int dim_in, int deff_in,
+                              int batch, int Cin, int H, int W, const int8_t* weight /* [Cout][Cin][KH][KW] */, int Cout, int KH, int KW,
+                              int stride, int pad, int dim_o, int c0, int c1, uint64_t* out /* [batch][c1-c0][Ho][Wo] rows of dim_o+1 */);
+
+/* ---- bounded device memory.  A slab group is a convolution and the maximal run of look-ups / max pools behind it
+ * in which each op reads exactly the destination of the op before it and nothing else reads that destination.  Under a budget a session
+ * holds `slab` channels of ONE image of a group's inner tensors at a time and walks the group slab by slab; the group's last destination
+ * is written whole.  slab = channels: the undivided group, byte for byte what runs without a budget.  No output word depends on the cut.
+ * The budget counts what a session allocates for itself: tensors, a max pool's level buffers and index maps, the parity work buffer, the
+ * look-up scratch and the overflow flag -- NOT keys, circuit payloads or convolution packs.
+ * dctfhe_memory_plan: host only (no context, no GPU), from a circuit blob, parameters (NULL: a clear-mode session) and batch.
+ * budget_bytes = 0: no budget.  It starts undivided and, while the plan exceeds the budget, lowers by one channel the slab height of the
+ * group that holds the largest inner tensor; it refuses, naming an op and the bytes of the smallest plan, when one channel at a time
+ * everywhere still does not fit.
+ * dctfhe_session_set_memory_budget: the same planner on a session, before its first run (an uploaded input stays where it is); refused once
+ * the session has run, on a sharded session and while the margin audit is on.  A budget the planner refuses leaves the session as it
+ * was: nothing is freed before the plan stands.  (An allocation that then fails on the device does not: destroy that session.)
+ * dctfhe_session_run_span refuses a span that begins or ends inside a divided group.  dctfhe_session_memory_plan: the plan in force. */
+#define DCTFHE_MAX_SLAB_GROUPS 64
+typedef struct {
+  uint64_t bytes_undivided, bytes_planned, budget_bytes;
+  uint64_t bytes_buffers, bytes_maps, bytes_scratch;      /* of bytes_planned (dctfhe_memory_plan; 0 from a session) */
+  int32_t n_groups, reserved;
+  int32_t first_op[DCTFHE_MAX_SLAB_GROUPS], end_op[DCTFHE_MAX_SLAB_GROUPS];      /* ops [first_op, end_op) */
+  int32_t channels[DCTFHE_MAX_SLAB_GROUPS], slab[DCTFHE_MAX_SLAB_GROUPS];        /* the group's channels; how many exist at a time */
+} dctfhe_mem_plan;
+int dctfhe_memory_plan(const void* blob, size_t size, const dctfhe_params* params, int batch, size_t budget_bytes, dctfhe_mem_plan* out);
+int dctfhe_session_set_memory_budget(dctfhe_session* s, size_t bytes);
+int dctfhe_session_memory_plan(dctfhe_session* s, dctfhe_mem_plan* out);
+/* The plan at slab heights given by hand, one per slab group in the order of the plan record, each from 1 to the group's channels, under
+ * the rules of dctfhe_session_set_memory_budget; it counts as a budget of exactly the plan's bytes.  For tests and experiments: which
+ * heights fit a budget is the planner's business. */
+int dctfhe_session_set_slab_heights(dctfhe_session* s, const int32_t* slab, int n_groups);
 
 /* max pool (circuit op 5), one piece at a time on host buffers.
  * keyswitch_diff: key switch of cts[ia[c]] - cts[ib[c]] (count rows of D + 1 words and count index pairs, indices < count), shifted

@@ -54,7 +54,10 @@ __device__ __forceinline__ int64_t gauss_torus(const rng_key& key, uint64_t stre
   const double u1 = ((double)(rnd64(key, stream, 2 * idx) >> 11) + 1.0) * (1.0 / 9007199254740992.0);
   const double u2 = ((double)(rnd64(key, stream, 2 * idx + 1) >> 11)) * (1.0 / 9007199254740992.0);
   const double g = sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
-  return (int64_t)rint(g * sigma * 18446744073709551616.0);
+  // a torus element: g sigma reduced to [-1/2, 1/2] before it is scaled, so that the conversion is defined for every sigma (x - rint(x)
+  // is exact, and the identity for |x| < 1/2: every draw of the key material and of an encryption is what it was)
+  const double x = g * sigma;
+  return (int64_t)rint((x - rint(x)) * 18446744073709551616.0);
 }
 
 // stream ids.  Masks are drawn from the PUBLIC key at stream s, the matching noise from the SECRET key at stream s + 1.

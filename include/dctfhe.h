@@ -341,7 +341,26 @@ int dctfhe_session_dims(dctfhe_session* s, int* in_dim, int* out_dim);
 /* synchronous.  The uploaded input stays resident: run may be called again without a fresh upload (same result). */
 int dctfhe_session_run(dctfhe_session* s, dctfhe_timing* timing /* may be NULL */);
 /* clear-mode sessions (keys == NULL) only: `simulate` with the noise model.  sigma_per_op[i] (fraction of the torus, 0 for
- * ops that are not look-ups) is added at the input of op i's table look-up, fresh draws every run; n_ops = 0 switches it off */
+ * ops that are not look-ups) is added at the input of op i's table look-up, fresh draws every run; n_ops = 0 switches it off.
+ * The definition (tests/simulate_ref.py is its numpy twin, compared word for word).  All words mod 2^64.
+ *   key      the dctfhe_rng_host key of words (seed & 0xffffffff, seed >> 32, 0x73696d75, 0, 0, 0, 0, 0), little-endian
+ *   draw     gauss(stream, idx, sigma) = (int64) rint(x 2^64), x = g sigma - rint(g sigma) (a torus element: exact, the identity for
+ *            |g sigma| < 1/2, defined for every sigma), g = sqrt(-2 ln u1) cospi(2 u2), u1 = ((word(2 idx) >> 11) + 1) 2^-53,
+ *            u2 = (word(2 idx + 1) >> 11) 2^-53; 0 where sigma <= 0
+ *   look-up  noisy_lookup(centre, w, T, idx, sigma): pos = centre + gauss + 2^(62-w); entry (pos >> (63-w)) & (2^w - 1) of T, negated when
+ *            bit 63 of pos is set
+ *   run R    counts, from the session's creation, the passes that reached the circuit's last op (a run_span that stops early does not
+ *            advance it; set_noise and uploads do not reset it)
+ *   OP_LUT i stream 0x51D0000 + (R << 12) + i; element g = its number in the whole [B][C][H][W] tensor, whatever slice or slab computes
+ *            it; v = (x << shift) + body_add, + 2^(63-p+r-1) when r > 0 except on an approximate site with sigma > 0; overflow when bit
+ *            63 of v is set; idx = the top w bits of v under the padding bit; table (g / hw) % ntab.  sigma = 0: T[idx], never negated.
+ *            Exact: centre idx << (63-w), draw g.  Approximate, r > 0: centre v + 2^(62-p), draw g.  Parity split: S[j] = ((T[2j] +
+ *            T[2j+1]) mod 2^64) >> 1, Dt[j] = T[2j] - S[j], centre (idx >> 1) << (64-w); S at width w-1, draw 2g, sigma, plus Dt with
+ *            (idx & 1) << 63 added to the centre, draw 2g+1, sigma2 (set_noise_split; sigma where 0 or absent)
+ *   OP_MAXPOOL i  streams P = 2^40 | ((0x51D0000 + (R << 12) + i) << 1) for the row pass, P + 1 for the column pass; an output folds its
+ *            in-range taps in tap order: m = x at the first, then d = ((x - m) << shift) + body_add and
+ *            m += noisy_lookup(top p_d bits of d, p_d, relu table, e 64 + taken, sigma), e the output's number in the whole pass, taken
+ *            the taps folded so far.  sigma = 0: the signed-word maximum */
 int dctfhe_session_set_noise(dctfhe_session* s, uint64_t seed, const double* sigma_per_op, int n_ops);
 /* parity-split look-ups run two table bootstraps: sigma_per_op is sampled at the first, sigma2_per_op[i] (> 0) at the second, whose input
  * also carries the parity bootstrap's output; without this call, or where the entry is 0, the second takes sigma_per_op[i] too */

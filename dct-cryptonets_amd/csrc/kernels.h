@@ -1266,7 +1266,8 @@ struct dct_args {
 };
 
 // libjpeg's accurate integer forward DCT ("islow": Loeffler-Ligtenberg-Moschytz, 13-bit constants, 2 extra bits carried out of the row
-// pass; jfdctint.c [K: restated from the published algorithm -- libjpeg-turbo is not in this environment, PARITY UNPINNED]) on one row
+// pass; jfdctint.c [K: restated from the published algorithm; pinned to the coefficients libjpeg-turbo wrote into quality-100 JPEG files,
+// tests/golden/jpeg_golden.npz, by tests/test_gpu_frontend_jpeg.py and, for the host twin, tests/test_jpeg_pin_host.py]) on one row
 // or column of 8 values, in place.  TurboJPEG picks this method at quality >= 96 (reference data/cvfunctional.py:24: quality=100).
 // first = 1: row pass (outputs scaled by 2^2 * sqrt(8)); first = 0: column pass (removes the 2^2; the 2-D result is 8x the DCT).
 __host__ __device__ inline void jfdct_islow_1d(int32_t* d, int first) {

@@ -177,7 +177,8 @@ def _round_half_away(x):
 
 
 # libjpeg's accurate integer DCT ("islow", jfdctint.c: Loeffler-Ligtenberg-Moschytz with 13-bit constants, two extra bits carried out of
-# the row pass) [K: restated from the published algorithm; libjpeg-turbo / TurboJPEG / jpeg2dct are absent -- PARITY UNPINNED].
+# the row pass) [K: restated from the published algorithm].  Pinned to libjpeg-turbo's own output: tests/test_jpeg_pin_host.py holds
+# jpeg_quantised_dct equal to the coefficients in JPEG files Pillow wrote at quality 100 (tests/golden/jpeg_golden.npz).
 # TurboJPEG selects it at quality >= 96 (reference data/cvfunctional.py:24 encodes at quality=100).
 _ISLOW = dict(F0_298=2446, F0_390=3196, F0_541=4433, F0_765=6270, F0_899=7373, F1_175=9633, F1_501=12299, F1_847=15137, F1_961=16069,
               F2_053=16819, F2_562=20995, F3_072=25172)
@@ -224,8 +225,11 @@ def jpeg_quantised_dct(plane_u8):
 
 def transform_dct_jpeg(img):
     """8x8 path of the reference (cvfunctional.py:21-26): TurboJPEG.encode(img, quality=100, jpeg_subsample=2) then
-    jpeg2dct.loads -> QUANTISED coefficients.  Restated from the JPEG/libjpeg definitions [K] -- PARITY UNPINNED, neither
-    library is available:
+    jpeg2dct.loads -> QUANTISED coefficients.  Restated from the JPEG/libjpeg definitions [K].  The colour conversion, the
+    down-sampler, the DCT and the quantiser are pinned: for the fixtures of tests/golden/jpeg_golden.npz this function returns exactly
+    the coefficients libjpeg-turbo (through Pillow, quality=100, subsampling=2, channels swapped) wrote into the JPEG file
+    (tests/test_jpeg_pin_host.py).  Still only restated, TurboJPEG and jpeg2dct being absent: that the encoder's default pixel format
+    is BGR, and jpeg2dct's return layout (natural order within a block, blocks row-major).
       * the encoder's default pixel format is BGR while the array is RGB, so red and blue trade places inside the JPEG;
       * JFIF full-range YCbCr (libjpeg jccolor, 16-bit fixed point, rounded);
       * 4:2:0: 2x2 box average with libjpeg's alternating bias 1,2,1,2 (h2v2_downsample);

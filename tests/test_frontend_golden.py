@@ -66,8 +66,9 @@ def test_full_transform_self_consistency():
 
 
 def test_jpeg_domain_dct_self_consistency():
-    """8x8 path (reference cvfunctional.py:21-26) -- PARITY UNPINNED (TurboJPEG / jpeg2dct absent): checks the JPEG
-    definitions the restatement follows, not the libraries."""
+    """8x8 path (reference cvfunctional.py:21-26): properties that follow from the JPEG definitions.  The arithmetic itself (colour
+    conversion, 4:2:0 down-sampler, islow DCT, quantiser) is held to libjpeg's own coefficients in tests/test_jpeg_pin_host.py; what
+    stays restated only (TurboJPEG / jpeg2dct absent) is the encoder's BGR default, checked here by its sign, and jpeg2dct's layout."""
     from dctfhe import frontend
     rng = np.random.default_rng(5)
     img = rng.integers(0, 256, (32, 48, 3), dtype=np.uint8)
@@ -134,8 +135,8 @@ def test_subset_patterns_square_triangle_learned():
 
 
 def test_jpeg_integer_dct_restatement():
-    """libjpeg's integer forward DCT + quality-100 quantiser (frontend.jpeg_quantised_dct; PARITY UNPINNED -- TurboJPEG / jpeg2dct absent):
-    integers only; within libjpeg's documented accuracy of the exact DCT (the scaled-by-8 result is good to about one unit, i.e. 1/8 here,
+    """libjpeg's integer forward DCT + quality-100 quantiser (frontend.jpeg_quantised_dct; equal to libjpeg-turbo's own coefficients on the
+    fixtures of tests/test_jpeg_pin_host.py).  Here its properties: integers only; within libjpeg's documented accuracy of the exact DCT (the scaled-by-8 result is good to about one unit, i.e. 1/8 here,
     before the quantiser rounds); exact on constant blocks; linear in the DC term."""
     from dctfhe import frontend
     rng = np.random.default_rng(9)

@@ -206,6 +206,7 @@ class PoolSite:
     levels: int               # tree levels of both passes
     shift: int = 0            # of the differences, up to 63 - p_d
     tier: int = -1            # of the relu table
+    quiet: bool = False       # moved to the catalogue's quiet pool tier (ParamSet.pool_tier_fallback_for_w; pool_policy "exact")
 
 
 @dataclass
@@ -274,6 +275,7 @@ class CompiledCircuit:
     rounding_method: str = "exact"
     expected_boundary_flips_per_image: float = 0.0    # approximate rounding only
     tier_policy: str = "exact"
+    pool_policy: str = "coarse"
     calib_out: np.ndarray = None                      # the compile-time integer forward: outputs [B, n_out] on the calibration batch
 
     @property
@@ -701,7 +703,7 @@ class _Builder:
 
 
 def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=None, range_margin=0.05, p_error=None,
-                  rounding_method="exact", tier_policy="exact"):
+                  rounding_method="exact", tier_policy="exact", pool_policy="coarse"):
     """-> CompiledCircuit.  calib: float [B, C, H, W] calibration inputs (reference: first training batch,
     homomorphic_eval.py:258-261).
     tier_policy "exact" (default): the exact-evaluation catalogue of dctfhe/params.py for the model's bit width
@@ -711,7 +713,17 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
     fail with probability <= p_error each -- stochastic outputs, like the reference's.
     rounding_method "approximate" (README.md:95-114 of the reference, rounding_threshold_bits={"n_bits":..,"method":
     "approximate"}): no one-bit rounding steps, the table bootstrap rounds; inputs next to a rounding boundary may land on
-    the neighbouring table entry."""
+    the neighbouring table entry.
+    pool_policy "coarse" (default): a max pool's relu table runs on the coarse tier of its width, whatever its price.  "exact": a pool
+    that leaves the budget on that tier, or pushes the look-up that reads it out, moves to the catalogue's quiet pool tier
+    (ParamSet.pool_tier_fallback_for_w), all its tree levels together.  Without a param_set the catalogue gains that tier
+    (params.default_params_5bit_pool) only for a circuit that moves a pool: every other circuit compiles to the blob, the parameters and
+    the evaluation keys of the default policy."""
+    if pool_policy not in ("coarse", "exact"):
+        raise ValueError(f"pool_policy {pool_policy!r}")
+    if pool_policy == "exact" and tier_policy == "p_error":
+        raise ValueError("pool_policy 'exact' needs tier_policy='exact': the p_error catalogue has no quiet pool tier (its look-ups "
+                         "may each fail with probability p_error anyway)")
     if rounding_method not in ("exact", "approximate"):
         raise ValueError(f"rounding_method {rounding_method!r}")
     if tier_policy not in ("exact", "p_error"):
@@ -831,7 +843,42 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
     circ = CompiledCircuit(tensors=bld.tensors, ops=bld.ops, input_tensor=t_in, output_tensor=out.tid, in_scale=s_in, in_bits=bits,
                            out_scale=s_f, out_bits=bits, max_bit_width=bld.max_bits, param_set=ps,
                            rounding_threshold_bits=rounding_threshold_bits, n_bits=n_bits, rounding_method=rounding_method,
-                           tier_policy=tier_policy, calib_out=out.q.reshape(out.q.shape[0], -1))
+                           tier_policy=tier_policy, pool_policy=pool_policy, calib_out=out.q.reshape(out.q.shape[0], -1))
+    _settle(circ)
+    if pool_policy == "exact":
+        budget = getattr(ps, "p_budget", 1e-12)
+        if own_catalogue and _pools_over_budget(circ, budget):
+            # the circuit needs a quiet pool tier: the same catalogue with it appended (the other indices unchanged), priced from scratch
+            quiet = P.params_for_bit_width(model.bit_width, pool_policy="exact")
+            if quiet.pool_tier_fallback_for_w:
+                ps = circ.param_set = quiet
+                _settle(circ)
+        # like the quiet twin of a parity split (_settle): a pool moves where it, or the look-up that reads its noisier output, leaves the
+        # budget; every tree level with it (level 1 alone on the coarse tier would leave level 2 near 1e-11)
+        while ps.pool_tier_fallback_for_w:
+            move = [o for o in _pools_over_budget(circ, budget) if not o.pool.quiet and o.pool.p_d in ps.pool_tier_fallback_for_w]
+            if not move:
+                break
+            for o in move:
+                o.pool.quiet = True
+            _settle(circ)
+    if own_catalogue and tier_policy == "exact" and circ.worst_site_failure > 1e-10:
+        import warnings
+        warnings.warn(f"dctfhe: a look-up site exceeds the exact-evaluation budget (p_fail/element {circ.worst_site_failure:.1e}); "
+                      "outputs may differ from the integer circuit -- see CompiledCircuit.report()")
+    circ.blob = _serialize(circ)
+    return circ
+
+
+def _pools_over_budget(circ, budget):
+    """the max pools whose worst pairwise maximum, or whose reading look-up, fails more often than `budget`"""
+    reader = {o.src0: o for o in circ.ops if o.type == OP_LUT}
+    return [o for o in circ.ops if o.type == OP_MAXPOOL and max(o.pfail, reader[o.dst].pfail if o.dst in reader else 0.0) > budget]
+
+
+def _settle(circ):
+    """encodings, tiers and prices (_price), then the quiet twins of the parity splits"""
+    ps = circ.param_set
     _price(circ)
     # parity-split sites: both look-ups on the site's (one-level) table tier where the budget holds; where the site's consumer -- the
     # refresh that reads the sum of two bootstrap outputs -- leaves it, the second look-up moves to the quiet twin, site by site
@@ -845,12 +892,6 @@ def compile_model(model, calib, rounding_threshold_bits=6, n_bits=5, param_set=N
         for o in move:
             o.lut.mode = LUT_SPLIT_QUIET
         _estimate_noise(circ)
-    if own_catalogue and tier_policy == "exact" and circ.worst_site_failure > 1e-10:
-        import warnings
-        warnings.warn(f"dctfhe: a look-up site exceeds the exact-evaluation budget (p_fail/element {circ.worst_site_failure:.1e}); "
-                      "outputs may differ from the integer circuit -- see CompiledCircuit.report()")
-    circ.blob = _serialize(circ)
-    return circ
 
 
 # ------------------------------------------------------------------------------------------ encodings
@@ -941,7 +982,7 @@ def _assign_encodings(circ):
             T[o.dst].e = T[o.src0].e
             S.shift = (63 - S.p_d) - T[o.src0].e
             assert S.shift >= 0
-            S.tier = ps.tier_for_width(S.p_d, coarse=not amplified[o.dst])
+            S.tier = ps.pool_tier_fallback_for_w[S.p_d] if S.quiet else ps.tier_for_width(S.p_d, coarse=not amplified[o.dst])
             if S.p_d > ps.tiers[S.tier].logN - 1:
                 raise ValueError("max-pool difference table wider than the ring")
             # the pairwise maxima accumulate a bootstrap output into the first kN words of a copy of `b`

@@ -140,14 +140,19 @@ def _params_tree(ps):
     out = {f.name: getattr(ps, f.name) for f in dataclasses.fields(ps) if f.name != "tiers"}
     for k in ("table_tier_for_w", "coarse_tier_for_w", "table_tier_fallback_for_w"):
         out[k] = pairs(out[k])
+    # a catalogue with a quiet pool tier says so; one without keeps the tree bundles have always carried
+    if out["pool_tier_fallback_for_w"] is None:
+        del out["pool_tier_fallback_for_w"]
+    else:
+        out["pool_tier_fallback_for_w"] = pairs(out["pool_tier_fallback_for_w"])
     out["tiers"] = [{n: getattr(t, n) for n in TIER_FIELDS} for t in ps.tiers]
     return out
 
 
 def _params_from_tree(t):
     t = dict(t)
-    for k in ("table_tier_for_w", "coarse_tier_for_w", "table_tier_fallback_for_w"):
-        t[k] = None if t[k] is None else {int(a): int(b) for a, b in t[k]}
+    for k in ("table_tier_for_w", "coarse_tier_for_w", "table_tier_fallback_for_w", "pool_tier_fallback_for_w"):
+        t[k] = None if t.get(k) is None else {int(a): int(b) for a, b in t[k]}
     t["tiers"] = [P.TierSpec(**tier) for tier in t["tiers"]]
     if len(t["tiers"]) > MAX_TIERS:
         raise ValueError(f"{len(t['tiers'])} tiers (at most {MAX_TIERS})")
@@ -184,7 +189,7 @@ def key_check_bits(ps):
     """per tier, the table precision the key check places its messages at: the widest table the catalogue gives the tier, 0 (a sign
     bootstrap) for the one-bit tiers and for a tier without a role"""
     w = [0] * len(ps.tiers)
-    for table in (ps.table_tier_for_w, ps.coarse_tier_for_w, ps.table_tier_fallback_for_w):
+    for table in (ps.table_tier_for_w, ps.coarse_tier_for_w, ps.table_tier_fallback_for_w, getattr(ps, "pool_tier_fallback_for_w", None)):
         for ww, ti in (table or {}).items():
             w[ti] = max(w[ti], int(ww))
     for ti in (ps.bit_tier, ps.bit_tier_coarse, ps.bit_tier_coarse2):
@@ -764,7 +769,8 @@ def _cmd_save(a):
     else:
         cfg = Configuration()
     rtb = a.rounding_threshold_bits if a.rounding_method == "exact" else {"n_bits": a.rounding_threshold_bits, "method": "approximate"}
-    qm = compile_fn(model, calib, rounding_threshold_bits=rtb, n_bits=a.n_bits, p_error=a.p_error, configuration=cfg, tier_policy=a.tier_policy, **kw)
+    qm = compile_fn(model, calib, rounding_threshold_bits=rtb, n_bits=a.n_bits, p_error=a.p_error, configuration=cfg, tier_policy=a.tier_policy,
+                    pool_policy=a.pool_policy, **kw)
     cls = None if model.classifier_w is None else (model.classifier_w, model.classifier_b)
     for p in save(qm, a.out, classifier=cls):
         print(f"wrote {p} ({os.path.getsize(p)} bytes)")
@@ -889,6 +895,7 @@ def _parser():
     p.add_argument("--p_error", default=0.01, type=float)
     p.add_argument("--rounding_method", default="exact", choices=["exact", "approximate"])
     p.add_argument("--tier_policy", default="exact", choices=["exact", "p_error"])
+    p.add_argument("--pool_policy", default="coarse", choices=["coarse", "exact"])
     p.add_argument("--seed", default=42, type=int, help="seed of the synthetic calibration images")
     p.add_argument("--test_params", action="store_true", help="the tiny, INSECURE test catalogue (trying the flow only)")
     p = cmd("keygen", _cmd_keygen, "client: make a key, write the key file and the exports")

@@ -58,6 +58,7 @@ class ParamSet:
     table_tier_for_w: dict             # table input width w -> tier index (outputs that feed a convolution / pooling)
     coarse_tier_for_w: dict = None     # same, for tables whose output only feeds an add or the circuit output (noisier is fine)
     table_tier_fallback_for_w: dict = None   # quieter (slower) tiers the compiler falls back to when a site leaves the budget
+    pool_tier_fallback_for_w: dict = None    # p_d -> the quieter tier a max pool moves to when it or its reader leaves the budget (pool_policy "exact")
     bit_tier_coarse: int = None        # one-level twin of the bit tier for the last rounding steps of a site
     bit_tier_coarse2: int = None       # a still cheaper (noisier) twin for the steps after those
     refresh_min_w: int = None          # tables this wide that feed a convolution are split: coarse look-up + small-ring refresh
@@ -289,10 +290,14 @@ def default_params():
                     input_dim=2048)
 
 
-def params_for_bit_width(bit_width):
+def params_for_bit_width(bit_width, pool_policy="coarse"):
     """Exact-evaluation catalogue for circuits of `bit_width`-bit weights and activations: the 5-bit one below for 5, default_params()
-    for every other width (that catalogue, its blob and its evaluation keys are what every 4-bit circuit depends on)."""
-    return default_params_5bit() if bit_width == 5 else default_params()
+    for every other width (that catalogue, its blob and its evaluation keys are what every 4-bit circuit depends on).
+    pool_policy "exact": the catalogue a circuit takes whose max pool has to move to a quiet tier -- default_params_5bit_pool() for 5
+    bits; no other width has such a tier (their pools sit far inside the budget: 1.5e-21 on T5a at 4 bits)."""
+    if bit_width == 5:
+        return default_params_5bit_pool() if pool_policy == "exact" else default_params_5bit()
+    return default_params()
 
 
 def default_params_5bit():
@@ -320,6 +325,23 @@ def default_params_5bit():
     # T5r: refresh of 5-bit tables that feed a convolution, four levels (csrc/pbs_core.h pack_digits: beta <= 10)
     t.append(TierSpec("T5r", n=856, k=1, logN=11, l=4, beta=10, lk=9, betak=2))
     ps.table_tier_for_w = {4: 6, 5: 9, 6: 0}
+    return ps
+
+
+def default_params_5bit_pool():
+    """default_params_5bit() plus T6p at index 10, the quiet tier of the stem max pool (compile_model(pool_policy="exact")); indices 0-9
+    are default_params_5bit()'s.
+
+    At 5 bits the pool's difference table has p_d = 6 and runs on T6a (one level, output sigma ~2^-12.4).  From the second tree level
+    on a candidate carries a T6a output and its key switch sums over 8192 mask words instead of 2048: sigma ~2^-10.2 against a 2^-8
+    half-box, 5.7e-5 per pairwise maximum.  T6p is T6a's ring with two levels of 15 bits and the one-bit rotation: output sigma
+    ~2^-20.2, six transforms per key bit where T6 has eight.  A longer key on one level does not help (n = 864: the pool at 8.7e-11, its
+    reader behind it at 2.4e-10).  n = 832 is the smallest multiple of 8 at which the pool and every other site of ResNet-18 3x128^2 and
+    3x224^2 stay under 1e-12 at rounding_threshold_bits 6 and 7 (tools/param_search.py --pool -> profiles/bw5_pool_param_search.log); it
+    differs from T6's 800, so T6p owns its key-switch key."""
+    ps = default_params_5bit()
+    ps.tiers.append(TierSpec("T6p", n=832, k=1, logN=13, l=2, beta=15, lk=9, betak=2))
+    ps.pool_tier_fallback_for_w = {6: 10}
     return ps
 
 

@@ -577,14 +577,15 @@ def _as_numpy(t):
 
 
 def compile_brevitas_qat_model(torch_model, torch_inputset, n_bits=5, configuration=None, rounding_threshold_bits=6, p_error=None,
-                               verbose=False, device=0, param_set=None, tier_policy="exact", **kwargs):
+                               verbose=False, device=0, param_set=None, tier_policy="exact", pool_policy="coarse", **kwargs):
     """Same keyword surface as the call at reference homomorphic_eval.py:276-285.  `torch_model` is what the reference
     passes -- the trunk `model.module.feature`, a torch.nn.Module walked by dctfhe.torch_import (duck-typed: the float
     `ResNetDCT` and, where Brevitas exists, `ResNetQDCT` import unchanged) -- or a dctfhe.models.ResNetQ description.
     `bit_width` (dctfhe addition): weight/activation width when the module does not say (`qconv_args`).
     rounding_threshold_bits: int (exact rounding) or {"n_bits": int, "method": "exact"|"approximate"} as the reference's
     README.md:95-114 suggests.  tier_policy: "exact" (default, outputs equal the integer circuit whatever p_error) or
-    "p_error" (cheaper tiers whose look-ups fail with probability <= p_error; dctfhe addition)."""
+    "p_error" (cheaper tiers whose look-ups fail with probability <= p_error; dctfhe addition).  pool_policy: "coarse" (default) or
+    "exact" (a max pool that leaves the budget on its coarse tier moves to the catalogue's quiet pool tier; dctfhe addition)."""
     method = "exact"
     if isinstance(rounding_threshold_bits, dict):
         method = str(rounding_threshold_bits.get("method", "exact")).lower().split(".")[-1]      # also accepts "Exactness.APPROXIMATE"
@@ -596,12 +597,13 @@ def compile_brevitas_qat_model(torch_model, torch_inputset, n_bits=5, configurat
     if torch_import.is_torch_module(torch_model):
         torch_model = torch_import.from_torch_module(torch_model, bit_width=bit_width or 4)
     compiled = cc.compile_model(torch_model, _as_numpy(torch_inputset), rounding_threshold_bits=rtb, n_bits=n_bits,
-                                param_set=param_set, p_error=p_error, rounding_method=method, tier_policy=tier_policy)
+                                param_set=param_set, p_error=p_error, rounding_method=method, tier_policy=tier_policy,
+                                pool_policy=pool_policy)
     return QuantizedModule(compiled, device=device, verbose=verbose, configuration=configuration)
 
 
 def compile_torch_model(torch_model, torch_inputset, n_bits=5, configuration=None, rounding_threshold_bits=6, p_error=None,
-                        verbose=False, device=0, param_set=None, tier_policy="exact", **kwargs):
+                        verbose=False, device=0, param_set=None, tier_policy="exact", pool_policy="coarse", **kwargs):
     """PTQ twin of the above (reference homomorphic_eval.py:287-295): a float torch trunk (`ResNetDCT`), every weight and
     activation quantised to `n_bits` post-training ([K] Concrete-ML's PTQ applies n_bits to all ops) unless `bit_width`
     says otherwise; the circuit builder is the same."""
@@ -609,4 +611,4 @@ def compile_torch_model(torch_model, torch_inputset, n_bits=5, configuration=Non
     if torch_import.is_torch_module(torch_model):
         kwargs.setdefault("bit_width", n_bits)
     return compile_brevitas_qat_model(torch_model, torch_inputset, n_bits, configuration, rounding_threshold_bits, p_error, verbose,
-                                      device, param_set, tier_policy, **kwargs)
+                                      device, param_set, tier_policy, pool_policy, **kwargs)

@@ -58,6 +58,9 @@ def parse_args():
                    help="exact = the reference's call (int rounding_threshold_bits); approximate = its README's suggested speed-up")
     e.add_argument("--tier_policy", default="exact", choices=["exact", "p_error"],
                    help="exact: outputs equal the integer circuit whatever --p_error; p_error: cheaper tiers failing with probability <= --p_error per look-up")
+    e.add_argument("--pool_policy", default="coarse", choices=["coarse", "exact"],
+                   help="coarse: a max pool's table on the coarse tier of its width; exact: a pool that leaves the exact-evaluation budget "
+                        "there (the 5-bit RGB trunks) moves to the quiet pool tier T6p -- one more evaluation key, a slower pool")
     e.add_argument("--compress_outputs", default="none", choices=["none", "rows", "ring"],
                    help="results on the way back: full rows; rows: key-switched 16-bit rows; ring: up to 2048 results in one GLWE "
                         "ciphertext (the client's packing key is made after keygen and loaded)")
@@ -154,7 +157,8 @@ def main():
     compile_fn = compile_brevitas_qat_model if quantization_type == "QAT" else compile_torch_model
     rtb = params.rounding_threshold_bits if params.rounding_method == "exact" else {"n_bits": params.rounding_threshold_bits, "method": "approximate"}
     q_module = compile_fn(model, calib_data, rounding_threshold_bits=rtb, n_bits=params.n_bits, p_error=params.p_error,
-                          configuration=configuration, verbose=params.verbose, device=params.device, tier_policy=params.tier_policy)
+                          configuration=configuration, verbose=params.verbose, device=params.device, tier_policy=params.tier_policy,
+                          pool_policy=params.pool_policy)
     print(f"Time for FHE compilation {time.time() - t:.2f}")
     bitwidth = q_module.fhe_circuit.graph.maximum_integer_bit_width()
     print(f"Max bit-width: {bitwidth} bits" + (" -> it works in FHE!!" if bitwidth <= 16 else " too high for FHE computation"))

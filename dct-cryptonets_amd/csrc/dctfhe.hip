@@ -698,14 +698,9 @@ static int gen_bsk_std_chunk(dctfhe_client_key* C, int tier, int i0, int ni, uin
   return 0;
 }
 
-// Precision of a key-switch key: the torus grid its words live on, 2^-(8 limbs).  The finest gadget level sits at 2^-(lk betak) and the
-// row noise (sigma_lwe >= 2^-19 on every shipped tier) at least 6 bits above the grid: limbs >= (lk betak + 6) / 8, as a power of two
-// (the matrix-core epilogue folds a word's limbs with lane shuffles).  Table tiers (9 levels of base 4): 4 limbs; one-bit tiers (5
-// levels): 2 limbs -- a half and a quarter of round 2's GEMM.
-static int ks_limbs(const dctfhe_tier& t) {
-  const int bits = t.lk * t.betak + 6;
-  return bits <= 16 ? 2 : bits <= 32 ? 4 : 8;
-}
+// Precision of a key-switch key: the torus grid its words live on, 2^-(8 limbs) (client_shared.h ks_limbs: the host client rounds its
+// key-switch bodies to the same grid)
+static int ks_limbs(const dctfhe_tier& t) { return dctfhe::ks_limbs(t.lk, t.betak); }
 
 // ---- evaluation keys ------------------------------------------------------------------------------
 static size_t tier_bsk_blocks(const dctfhe_tier& t) { return (size_t)(t.unroll == 2 ? 3 * t.n / 2 : t.n); }

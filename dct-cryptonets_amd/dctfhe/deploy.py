@@ -26,7 +26,7 @@ import numpy as np
 
 from . import params as P
 from . import roles
-from ._lib import MAX_TIERS
+from ._lib import MAX_TIERS, DctfheError
 from .engine import (Circuit, ClientKey, Context, EvalKeys, PackKey, PackedCiphertexts, PackedRing, PublicInputs, PublicKey, SeededCiphertexts,
                      Session, blob_params, seed_bytes)
 
@@ -419,15 +419,32 @@ def _unpack_key_check(magic, blob, digest, whose):
 
 
 # ------------------------------------------------------------------------------------------ roles
+HOST = "host"                                  # device="host": the role runs on libdctfhe_client.so, no GPU (dctfhe.host_client)
 KEY_MAGIC = b"DKEY"
 _KEYFILE = struct.Struct("<4sI32s32s")        # magic, version, circuit digest, the 32-byte key seed
 
 
+def device_arg(v):
+    """a role's device: a GPU index, or the string host (clients and data owners only)"""
+    if isinstance(v, str) and v.strip().lower() == HOST:
+        return HOST
+    try:
+        return int(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"device {v!r}: a GPU index or 'host'") from None
+
+
 class _Role:
     def __init__(self, spec, device):
-        self.spec, self.device, self._ctx = spec, device, None
+        self.spec, self.device, self._ctx = spec, device_arg(device), None
+
+    @property
+    def on_host(self):
+        return self.device == HOST
 
     def _context(self):
+        if self.on_host:
+            raise DctfheError("this role runs on the host: it has no GPU context (this engine has no CPU path for anything that needs one)")
         if self._ctx is None:
             self._ctx = Context(self.device)
         return self._ctx
@@ -453,7 +470,8 @@ class _Role:
 
 
 class Client(_Role):
-    """The key owner, started from client.dctfhe: makes the keys, encrypts with the secret key, decrypts results."""
+    """The key owner, started from client.dctfhe: makes the keys, encrypts with the secret key, decrypts results.
+    device: a GPU index, or "host" -- the same role on the host library, no GPU (compressed evaluation keys only)."""
 
     def __init__(self, path, device=0):
         super().__init__(load_client_spec(path), device)
@@ -469,7 +487,11 @@ class Client(_Role):
         seed = seed_bytes(seed)
         if self._key is not None:
             self._key.close()
-        self._key = ClientKey(self._context(), self.spec.c_params(), seed)
+        if self.on_host:
+            from .host_client import HostClientKey
+            self._key = HostClientKey(self.spec.c_params(), seed)
+        else:
+            self._key = ClientKey(self._context(), self.spec.c_params(), seed)
 
     def save_key(self, path):
         """the key file: the 32-byte key seed (key material is a pure function of the parameters and the seed), bound to the circuit
@@ -499,6 +521,9 @@ class Client(_Role):
         key = self._need_key()
         if compressed:
             return key.export_eval_keys_compressed()
+        if self.on_host:
+            raise ValueError('export_evaluation_keys(compressed=False): the full (Fourier) keys are made on the GPU; a client on device="host" '
+                             "ships the compressed form, which the server transforms on import")
         ek = key.generate_eval_keys()
         try:
             return ek.to_blob()
@@ -570,7 +595,8 @@ class Client(_Role):
 
 
 class DataOwner(_Role):
-    """A party with inputs and no secret, started from the same client.dctfhe: encrypts with the client's public key."""
+    """A party with inputs and no secret, started from the same client.dctfhe: encrypts with the client's public key.
+    device: a GPU index, or "host" -- the same role on the host library, no GPU."""
 
     def __init__(self, path, device=0):
         super().__init__(load_client_spec(path), device)
@@ -578,7 +604,11 @@ class DataOwner(_Role):
 
     def load_public_key(self, blob):
         plan = self.spec.public_input_plan()
-        pk = PublicKey(self._context(), blob)
+        if self.on_host:
+            from .host_client import HostPublicKey
+            pk = HostPublicKey(blob)
+        else:
+            pk = PublicKey(self._context(), blob)
         try:
             roles.check_public_key(plan, pk)
         except RuntimeError:
@@ -608,6 +638,8 @@ class Server(_Role):
     """The evaluator, started from server.dctfhe: holds the circuit and evaluation keys, never a secret."""
 
     def __init__(self, path, device=0):
+        if device_arg(device) == HOST:
+            raise DctfheError('Server(device="host"): circuits are evaluated on the GPU -- this engine has no CPU path for the server')
         super().__init__(load_server_bundle(path), device)
         self._circuit, self._keys, self._pack_key, self._sessions = None, None, None, {}
         self.sim_seed = 977
@@ -875,7 +907,9 @@ def _parser():
     def cmd(name, fn, help_):
         p = sub.add_parser(name, help=help_)
         p.set_defaults(fn=fn)
-        p.add_argument("--device", default=0, type=int, help="GPU index")
+        p.add_argument("--device", default=0, type=device_arg,
+                       help="GPU index; 'host' runs the client and owner sub-commands (keygen, encrypt, owner-encrypt, decrypt, key-check make / verify) "
+                            "without a GPU")
         return p
     p = cmd("save", _cmd_save, "compile a model and write client.dctfhe and server.dctfhe (no GPU)")
     p.add_argument("--out", required=True, help="directory for the two files")

@@ -1339,7 +1339,9 @@ static int dev_ms_center(dctfhe_keys* K, int tier, uint64_t* d_small, size_t cou
 // the one of element e_offset + c of a tensor with hw elements per channel.  The defaults mean one table.
 struct PbsLut { const int64_t* tables = nullptr; int w = 0; const int32_t* idx = nullptr; int hw = 1, nchan = 1; size_t e_offset = 0; };
 // Where its result goes: rows of L words, stored or added to what the rows hold, body_add on the body.
-struct PbsOut { uint64_t* rows = nullptr; size_t L = 0; bool accumulate = false; uint64_t body_add = 0; };
+// sink: L words for the padded groups of the last workgroup, which redo the last ciphertext in store mode (kernels.h pbs_kernel); nullptr: the
+// keys' own D + 1 words, which rows of at most D + 1 words fit.
+struct PbsOut { uint64_t* rows = nullptr; size_t L = 0; bool accumulate = false; uint64_t body_add = 0; uint64_t* sink = nullptr; };
 static int dev_pbs(dctfhe_keys* K, int tier, const uint64_t* d_small, size_t count, const PbsLut& lut, const PbsOut& out, Timers* tm) {
   const dctfhe_tier& t = K->p.tiers[tier];
   pbs_launch a;
@@ -1348,7 +1350,8 @@ static int dev_pbs(dctfhe_keys* K, int tier, const uint64_t* d_small, size_t cou
   a.tables = lut.tables; a.w = lut.w; a.table_idx = lut.idx; a.hw = lut.hw; a.nchan = lut.nchan; a.e_offset = lut.e_offset;
   const int ring = t.k << t.logN;
   if (out.L < (size_t)ring + 1) return fail("bootstrap output rows of %zu words cannot hold a ring of %d", out.L, ring);
-  a.out = out.rows; a.D_out = (int)out.L - 1; a.accumulate = out.accumulate; a.body_add = out.body_add; a.dummy = K->d_dummy.as<uint64_t>(); a.bsk_wrap = 0;
+  if (out.L > (size_t)K->p.D + 1 && !out.sink) return fail("bootstrap output rows of %zu words exceed the sink of the padded groups (%d words)", out.L, K->p.D + 1);
+  a.out = out.rows; a.D_out = (int)out.L - 1; a.accumulate = out.accumulate; a.body_add = out.body_add; a.dummy = out.sink ? out.sink : K->d_dummy.as<uint64_t>(); a.bsk_wrap = 0;
   // L2 warm-up: each workgroup touches 1/pf_parts of the next key blocks; the paired two-bit kernel at N = 2048 measures 3 % better
   // without (profiles/r02_exp_ablations.log: 22.5 vs 23.2 ms), every other barrier-coupled kernel better with (T4r 82.4 vs 86.3, T5a 25.7
   // vs 26.6).  The parts are dealt by blockIdx / 8, i.e. per XCD: with one 512-thread workgroup per CU an XCD holds 32 of them, and 32
@@ -2199,6 +2202,109 @@ extern "C" int dctfhe_keyswitch_diff(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int t
   in.source = KS_DIFF; in.ia = d_ia.as<int32_t>(); in.ib = d_ib.as<int32_t>();
   CHK(dev_keyswitch(K, tier, in, count, sc, nullptr));
   HIPCHK(sc.d_small.download(cts_small, count * (size_t)(t.n + 1) * 8, ctx->stream));
+  return 0;
+}
+
+// ---- the seams of a look-up site one launch at a time on host buffers (include/dctfhe.h): the bootstrap in the write-back modes that
+// dev_round_lut / dev_max_pool launch it in, the key switch of a row sum, and the two streaming kernels of a split site and a max pool.
+extern "C" int dctfhe_pbs_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts_small, size_t count, const int64_t* tables, int ntab, int w,
+                               const int32_t* table_idx, int hw, int nchan, size_t e_offset, uint64_t* rows_io, size_t n_rows, size_t row0, int dim_out,
+                               int accumulate, uint64_t body_add) {
+  if (!ctx || !K) return fail("dctfhe_pbs_rows: null handle");
+  if (!tables || !rows_io || (count && !cts_small)) return fail("dctfhe_pbs_rows: null argument");
+  if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  if (ntab < 1 || w < 0) return fail("dctfhe_pbs_rows: need at least one table and w >= 0");
+  if (hw < 1) return fail("dctfhe_pbs_rows: hw = %d elements per channel (at least 1)", hw);
+  if (nchan < 1 || nchan > ntab) return fail("dctfhe_pbs_rows: %d per-channel tables of the %d given (1 <= nchan <= ntab)", nchan, ntab);
+  if (row0 > n_rows || count > n_rows - row0) return fail("dctfhe_pbs_rows: rows [%zu, %zu) outside the %zu rows of the buffer", row0, row0 + count, n_rows);
+  if (dim_out < 1 || dim_out > (1 << 16)) return fail("dctfhe_pbs_rows: rows of %d mask words (1 .. 2^16)", dim_out);
+  const dctfhe_tier& t = K->p.tiers[tier];
+  if (w > t.logN - 1) return fail("table of 2^%d entries does not fit N = 2^%d", w, t.logN);
+  if (table_idx)
+    for (size_t i = 0; i < count; i++)
+      if (table_idx[i] < 0 || table_idx[i] >= ntab) return fail("table_idx[%zu] = %d out of range (%d tables)", i, table_idx[i], ntab);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t L = (size_t)dim_out + 1;
+  DevBuf d_small, d_rows, d_tab, d_idx, d_sink;
+  HIPCHK(d_small.upload(cts_small, count * (size_t)(t.n + 1) * 8));
+  HIPCHK(d_rows.upload(rows_io, n_rows * L * 8));
+  HIPCHK(d_tab.upload(tables, ((size_t)ntab << w) * 8));
+  if (table_idx) HIPCHK(d_idx.upload(table_idx, count * 4));
+  HIPCHK(d_sink.alloc(L * 8));
+  PbsLut lut;
+  lut.tables = d_tab.as<int64_t>(); lut.w = w; lut.idx = d_idx.as<int32_t>(); lut.hw = hw; lut.nchan = nchan; lut.e_offset = e_offset;
+  PbsOut out{d_rows.as<uint64_t>() + row0 * L, L, accumulate != 0, body_add, d_sink.as<uint64_t>()};
+  CHK(dev_pbs(K, tier, d_small.as<uint64_t>(), count, lut, out, nullptr));
+  HIPCHK(d_rows.download(rows_io, n_rows * L * 8, ctx->stream));
+  return 0;
+}
+
+// key switch of rows_a[c] + rows_b[c] (rows of dim_a + 1 and dim_b + 1 words; a word of b at or beyond dim_b counts as zero), shifted left
+// by `shift`, body_add on the body: what the second look-up of a parity-split site reads (dev_round_lut); deff as dctfhe_keyswitch_prefix
+extern "C" int dctfhe_keyswitch_sum(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* rows_a, int dim_a, const uint64_t* rows_b, int dim_b,
+                                    size_t count, int shift, uint64_t body_add, int deff, uint64_t* cts_small) {
+  if (!ctx || !K || (count && (!rows_a || !rows_b || !cts_small))) return fail("dctfhe_keyswitch_sum: null argument");
+  if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  if (dim_a < 1 || dim_a > K->p.D) return fail("dctfhe_keyswitch_sum: rows of %d mask words, the key has %d", dim_a, K->p.D);
+  if (dim_b < 0 || dim_b > (1 << 16)) return fail("dctfhe_keyswitch_sum: second rows of %d mask words (0 .. 2^16)", dim_b);
+  if (deff < 0 || deff > dim_a) return fail("deff out of range");
+  if (shift < 0 || shift > 63) return fail("shift out of range");
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const dctfhe_tier& t = K->p.tiers[tier];
+  const size_t La = (size_t)dim_a + 1, Lb = (size_t)dim_b + 1;
+  DevBuf d_a, d_b;
+  HIPCHK(d_a.upload(rows_a, count * La * 8));
+  HIPCHK(d_b.upload(rows_b, count * Lb * 8));
+  LutScratch sc;      // what dev_keyswitch uses of it, sized by the rows: digits of dim_a words per ciphertext
+  sc.chunk = count;
+  HIPCHK(sc.d_digits.alloc(count * (size_t)dim_a * t.lk));
+  HIPCHK(sc.d_bodies.alloc(count * 8));
+  HIPCHK(sc.d_small.alloc(count * (size_t)(t.n + 1) * 8));
+  KsInput in;
+  in.rows = d_a.as<uint64_t>(); in.L = La; in.deff = deff; in.shift = shift; in.body_add = body_add;
+  in.source = KS_SUM; in.rows_b = d_b.as<uint64_t>(); in.Lb = Lb;
+  CHK(dev_keyswitch(K, tier, in, count, sc, nullptr));
+  HIPCHK(sc.d_small.download(cts_small, count * (size_t)(t.n + 1) * 8, ctx->stream));
+  return 0;
+}
+
+// o += b on the first nwords mask words and the body (k_acc_rows): the sum of the two look-ups of a parity-split site
+extern "C" int dctfhe_acc_rows(dctfhe_ctx* ctx, uint64_t* o_io, int dim_o, const uint64_t* b, int dim_b, size_t count, int nwords) {
+  if (!ctx || !o_io || !b) return fail("dctfhe_acc_rows: null argument");
+  if (dim_o < 0 || dim_o > (1 << 16) || dim_b < 0 || dim_b > (1 << 16)) return fail("dctfhe_acc_rows: rows of %d and %d mask words (0 .. 2^16)", dim_o, dim_b);
+  if (nwords < 0 || nwords > std::min(dim_o, dim_b)) return fail("dctfhe_acc_rows: %d words do not fit rows of %d and %d mask words", nwords, dim_o, dim_b);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t Lo = (size_t)dim_o + 1, Lb = (size_t)dim_b + 1;
+  DevBuf d_o, d_b;
+  HIPCHK(d_o.upload(o_io, count * Lo * 8)); HIPCHK(d_b.upload(b, count * Lb * 8));
+  hipLaunchKernelGGL(k_acc_rows, dim3(ew_grid(count * ((size_t)nwords + 1))), dim3(256), 0, ctx->stream, d_o.as<uint64_t>(), Lo, d_b.as<uint64_t>(), Lb, count,
+                     (size_t)nwords);
+  HIPCHK(hipGetLastError());
+  HIPCHK(d_o.download(o_io, count * Lo * 8, ctx->stream));
+  return 0;
+}
+
+// dst[r] = src[map[r]] at another row stride (k_pool_gather, one tree level of a max pool): mask words from deff_s on are written as zeros
+extern "C" int dctfhe_gather_rows(dctfhe_ctx* ctx, const uint64_t* src, int dim_s, int deff_s, size_t n_src, const int32_t* map, size_t count, int dim_d,
+                                  uint64_t* dst) {
+  if (!ctx || !src || (count && (!map || !dst))) return fail("dctfhe_gather_rows: null argument");
+  CHK(rows_ok("dctfhe_gather_rows", dim_s, deff_s));
+  if (dim_d < deff_s || dim_d > (1 << 16)) return fail("dctfhe_gather_rows: output rows of %d mask words cannot hold the source's %d", dim_d, deff_s);
+  if (n_src < 1 || n_src > (size_t)INT32_MAX) return fail("dctfhe_gather_rows: %zu source rows (1 .. 2^31 - 1)", n_src);
+  for (size_t r = 0; r < count; r++)
+    if (map[r] < 0 || (size_t)map[r] >= n_src) return fail("dctfhe_gather_rows: map[%zu] = %d out of range (%zu source rows)", r, map[r], n_src);
+  if (count == 0) return 0;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t Ls = (size_t)dim_s + 1, Ld = (size_t)dim_d + 1;
+  DevBuf d_s, d_m, d_d;
+  HIPCHK(d_s.upload(src, n_src * Ls * 8)); HIPCHK(d_m.upload(map, count * 4)); HIPCHK(d_d.alloc(count * Ld * 8));
+  hipLaunchKernelGGL(k_pool_gather, dim3(ew_grid(count * Ld)), dim3(256), 0, ctx->stream, d_s.as<uint64_t>(), Ls, (size_t)deff_s, d_m.as<int32_t>(), d_d.as<uint64_t>(), Ld,
+                     count);
+  HIPCHK(hipGetLastError());
+  HIPCHK(d_d.download(dst, count * Ld * 8, ctx->stream));
   return 0;
 }
 

@@ -88,6 +88,7 @@ EXPORTS = [
     "dctfhe_session_mark_whole", "dctfhe_session_copy_rows",
     "dctfhe_shard_pool", "dctfhe_session_set_shard_pool", "dctfhe_session_mark_rows", "dctfhe_session_shard_plan_rows", "dctfhe_session_pool_pairs",
     "dctfhe_conv2d_rows_window", "dctfhe_memory_plan", "dctfhe_session_set_memory_budget", "dctfhe_session_memory_plan", "dctfhe_session_set_slab_heights",
+    "dctfhe_pbs_rows", "dctfhe_keyswitch_sum", "dctfhe_acc_rows", "dctfhe_gather_rows",
 ]
 
 _lib = None
@@ -167,6 +168,10 @@ def load():
     L.dctfhe_eval_keys_export_compressed.argtypes = [vp, vp, sz, C.POINTER(sz)]
     L.dctfhe_eval_keys_decompress_bsk.argtypes = [vp, vp, sz, i32, vp]
     L.dctfhe_keyswitch_diff.argtypes = [vp, vp, i32, vp, sz, vp, vp, i32, u64, i32, vp]
+    L.dctfhe_pbs_rows.argtypes = [vp, vp, i32, vp, sz, vp, i32, i32, vp, i32, i32, sz, vp, sz, sz, i32, i32, u64]
+    L.dctfhe_keyswitch_sum.argtypes = [vp, vp, i32, vp, i32, vp, i32, sz, i32, u64, i32, vp]
+    L.dctfhe_acc_rows.argtypes = [vp, vp, i32, vp, i32, sz, i32]
+    L.dctfhe_gather_rows.argtypes = [vp, vp, i32, i32, sz, vp, sz, i32, vp]
     L.dctfhe_max_pool_rows.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]
     L.dctfhe_session_download_packed.argtypes = [vp, i32, vp]
     L.dctfhe_keyswitch_pack.argtypes = [vp, vp, i32, vp, sz, i32, i32, vp]

@@ -89,6 +89,21 @@ class Context:
         check(self.L.dctfhe_affine_rows(self.h, ptr(a), a.shape[1] - 1, deff_a, a.shape[0], nwords, shift, C.c_uint64(body_add), out.shape[1] - 1, ptr(out)))
         return out
 
+    def acc_rows(self, o, b, nwords):
+        """o + b on the first nwords mask words and the body of rows [count, dim + 1], the other words of o as they were (dctfhe_acc_rows)"""
+        out, b = np.ascontiguousarray(o, np.uint64).copy(), np.ascontiguousarray(b, np.uint64)
+        if out.shape[0] != b.shape[0]:
+            raise ValueError("acc_rows takes one row of b per row of o")
+        check(self.L.dctfhe_acc_rows(self.h, ptr(out), out.shape[1] - 1, ptr(b), b.shape[1] - 1, out.shape[0], int(nwords)))
+        return out
+
+    def gather_rows(self, src, deff_s, row_map, dim_d):
+        """rows src[row_map] of [n_src, dim + 1] at effective dimension deff_s, as rows [len(row_map), dim_d + 1] (dctfhe_gather_rows)"""
+        src, m = np.ascontiguousarray(src, np.uint64), np.ascontiguousarray(row_map, np.int32)
+        out = np.empty((m.size, int(dim_d) + 1), np.uint64)
+        check(self.L.dctfhe_gather_rows(self.h, ptr(src), src.shape[1] - 1, int(deff_s), src.shape[0], ptr(m), m.size, int(dim_d), ptr(out)))
+        return out
+
     def sum_pool_rows(self, x, deff, K, dim_o):
         """x [batch, C, H, W, dim + 1] -> [batch, C, H // K, W // K, dim_o + 1]"""
         x = np.ascontiguousarray(x, np.uint64)
@@ -477,6 +492,30 @@ class EvalKeys:
                                 None if idx is None else ptr(idx), ptr(out)))
         return out
 
+    def pbs_rows(self, tier, cts_small, tables, w, rows, row0=0, table_idx=None, hw=1, nchan=1, e_offset=0, accumulate=False, body_add=0):
+        """the bootstrap in the library's write-back modes (dctfhe_pbs_rows): the results of cts_small go to rows [row0, row0 + count) of a
+        copy of `rows` [n_rows, dim_out + 1], stored or accumulated; the whole buffer comes back"""
+        cts_small = np.ascontiguousarray(cts_small, np.uint64)
+        tables = np.ascontiguousarray(tables, np.int64).reshape(-1, 1 << w)
+        idx = None if table_idx is None else np.ascontiguousarray(table_idx, np.int32)
+        if idx is not None and idx.size != cts_small.shape[0]:
+            raise ValueError("pbs_rows takes one table index per ciphertext")
+        out = np.ascontiguousarray(rows, np.uint64).copy()
+        check(self.L.dctfhe_pbs_rows(self.ctx.h, self.h, tier, ptr(cts_small), cts_small.shape[0], ptr(tables), tables.shape[0], w,
+                                     None if idx is None else ptr(idx), int(hw), int(nchan), C.c_size_t(int(e_offset)), ptr(out), out.shape[0], int(row0),
+                                     out.shape[1] - 1, int(bool(accumulate)), C.c_uint64(int(body_add))))
+        return out
+
+    def keyswitch_sum(self, tier, rows_a, rows_b, shift=0, body_add=0, deff=0):
+        """key switch of rows_a[c] + rows_b[c], rows [count, dim_a + 1] and [count, dim_b + 1] (dctfhe_keyswitch_sum)"""
+        a, b = np.ascontiguousarray(rows_a, np.uint64), np.ascontiguousarray(rows_b, np.uint64)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("keyswitch_sum takes one row of b per row of a")
+        out = np.empty((a.shape[0], self.tier(tier).n + 1), np.uint64)
+        check(self.L.dctfhe_keyswitch_sum(self.ctx.h, self.h, tier, ptr(a), a.shape[1] - 1, ptr(b), b.shape[1] - 1, a.shape[0], shift,
+                                          C.c_uint64(int(body_add)), deff, ptr(out)))
+        return out
+
     def round_lut(self, bit_tier, tab_tier, cts, p, r, tables, w, table_idx=None):
         cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, self.D + 1)
         tables = np.ascontiguousarray(tables, np.int64).reshape(-1, 1 << w)
@@ -528,7 +567,7 @@ class Keys:
                     "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed", "margin_probe", "export_pack_key", "decrypt_ring",
                     "export_public_key"):
             return getattr(self.client, name)
-        if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "modswitch_center", "pbs", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
+        if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "keyswitch_sum", "modswitch_center", "pbs", "pbs_rows", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
             return getattr(self.eval, name)
         raise AttributeError(name)
 

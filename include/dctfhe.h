@@ -297,6 +297,32 @@ int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, cons
                          int deff_in, int batch, int C, int H, int W, int k, int s, int p, int p_d, const int64_t* table, int dim_o,
                          uint64_t* out /* [batch][C][Ho][Wo] rows */);
 
+/* The seams a look-up site is stitched from, one launch at a time on host buffers (tests).  Nothing stays on the device afterwards.
+ * pbs_rows: dctfhe_pbs in the write-back modes the library itself launches.  rows_io holds n_rows rows of dim_out + 1 words (dim_out >= the
+ * tier's ring k N, at most 2^16); the bootstraps of the count small ciphertexts go to rows [row0, row0 + count).  accumulate = 0: mask words
+ * [0, k N) and the body are stored, words [k N, dim_out) zeroed; accumulate != 0: the result is ADDED to mask words [0, k N) and to the body,
+ * the words in between are left as they are.  body_add goes on the body in both modes.  Rows outside [row0, row0 + count) come back as they
+ * went in.  table_idx == NULL: ciphertext c takes table ((e_offset + c) / hw) % nchan of the first nchan tables (nchan = 1: table 0).
+ * Refused: row0 + count > n_rows, hw < 1, nchan < 1, nchan > ntab, a table_idx entry outside [0, ntab), w > logN - 1, dim_out < k N.
+ * keyswitch_sum: key switch of rows_a[c] + rows_b[c] (rows of dim_a + 1 and dim_b + 1 words, 1 <= dim_a <= D; a mask word of b at or beyond
+ * dim_b counts as zero), shifted left by `shift`, body_add on the body: what the second look-up of a parity split reads.  deff as
+ * dctfhe_keyswitch_prefix, for the SUM: 0 <= deff <= dim_a.
+ * acc_rows: o += b on the first nwords mask words and on the body of every row (rows of dim_o + 1 and dim_b + 1 words, nwords <=
+ * min(dim_o, dim_b)); the other words of o stay.
+ * gather_rows: dst[r] = row map[r] of src (n_src rows of dim_s + 1 words whose mask words from deff_s on count as zero) as a row of
+ * dim_d + 1 >= deff_s + 1 words: words [deff_s, dim_d) zero, the body last.  A map entry outside [0, n_src) is refused. */
+int dctfhe_pbs_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, const uint64_t* cts_small, size_t count,
+                    const int64_t* tables /* [ntab][2^w] */, int ntab, int w, const int32_t* table_idx /* may be NULL */, int hw, int nchan,
+                    size_t e_offset, uint64_t* rows_io /* n_rows x (dim_out+1) */, size_t n_rows, size_t row0, int dim_out, int accumulate,
+                    uint64_t body_add);
+int dctfhe_keyswitch_sum(dctfhe_ctx* ctx, dctfhe_eval_keys* keys, int tier, const uint64_t* rows_a /* count x (dim_a+1) */, int dim_a,
+                         const uint64_t* rows_b /* count x (dim_b+1) */, int dim_b, size_t count, int shift, uint64_t body_add, int deff,
+                         uint64_t* cts_small /* count x (n+1) */);
+int dctfhe_acc_rows(dctfhe_ctx* ctx, uint64_t* o_io /* count x (dim_o+1) */, int dim_o, const uint64_t* b /* count x (dim_b+1) */, int dim_b,
+                    size_t count, int nwords);
+int dctfhe_gather_rows(dctfhe_ctx* ctx, const uint64_t* src /* n_src x (dim_s+1) */, int dim_s, int deff_s, size_t n_src, const int32_t* map,
+                       size_t count, int dim_d, uint64_t* dst /* count x (dim_d+1) */);
+
 /* K10, client side, plaintext: the DCT front-end of reference data/cvfunctional.py:37-74 + data/cvtransforms.py:56-64,117-208 on
  * uint8 planes (luma [batch][fs*S][fs*S]; two chroma slots [batch][fs*Sc][fs*Sc], Sc = S/2 for the 4:2:0 paths or S):
  * blockwise orthonormal DCT-II of (pixel - 128), only the kept coefficients idx_* (row-major u*fs+v), chroma grids

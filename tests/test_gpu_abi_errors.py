@@ -72,6 +72,25 @@ def test_primitive_errors(kit):
     x = np.zeros((1, 2, 2, 2, 5), np.uint64)
     _fails(L, L.dctfhe_conv2d(ctx.h, 4, p(x), 1, 2, 2, 2, p(w), 2, 3, 3, 1, 0, p(x)), "kernel larger")
     _fails(L, L.dctfhe_conv2d(ctx.h, 4, p(x), 1, 2, 2, 2, p(w), 2, 3, 3, 0, 1, p(x)), "bad geometry")
+    # the seams of a look-up site: dctfhe_pbs_rows refuses each of its bad arguments by message, the other three one each
+    rows_io = np.zeros((4, D + 1), np.uint64)
+    pbs_rows = lambda count=3, ntab=2, w=4, ix=None, hw=1, nchan=1, n_rows=4, row0=1, dim_out=D, tier=0: L.dctfhe_pbs_rows(
+        ctx.h, keys.eval.h, tier, p(small), count, p(tab), ntab, w, ix, hw, nchan, 0, p(rows_io), n_rows, row0, dim_out, 1, 5)
+    _fails(L, pbs_rows(row0=2), "outside the 4 rows")
+    _fails(L, pbs_rows(hw=0), "hw = 0")
+    _fails(L, pbs_rows(nchan=0), "per-channel tables")
+    _fails(L, pbs_rows(nchan=3), "per-channel tables")
+    _fails(L, pbs_rows(ix=p(idx)), "table_idx[1]")
+    _fails(L, pbs_rows(ntab=1, w=12), "does not fit")
+    ring = ps.tiers[0].k << ps.tiers[0].logN
+    _fails(L, pbs_rows(dim_out=ring - 1), "cannot hold a ring")
+    _fails(L, pbs_rows(tier=7), "tier out of range")
+    assert not rows_io.any()
+    _fails(L, L.dctfhe_keyswitch_sum(ctx.h, keys.eval.h, 0, p(cts), D, p(cts), D, 3, 0, 0, D + 1, p(out_small)), "deff out of range")
+    _fails(L, L.dctfhe_keyswitch_sum(ctx.h, keys.eval.h, 0, p(cts), D + 1, p(cts), D, 3, 0, 0, 0, p(out_small)), "the key has")
+    _fails(L, L.dctfhe_acc_rows(ctx.h, p(big), D, p(cts), D, 3, D + 1), "do not fit")
+    gmap = np.array([0, 3, 1], np.int32)
+    _fails(L, L.dctfhe_gather_rows(ctx.h, p(cts), D, D, 3, p(gmap), 3, D, p(big)), "map[1] = 3 out of range")
     # the handles still work after all that
     assert np.array_equal((keys.decrypt(cts) + np.uint64(1 << 56)) >> np.uint64(57), (np.arange(3, dtype=np.uint64) << np.uint64(1)))
 

@@ -143,6 +143,10 @@ def test_primitives_hold_nothing(gpu_ctx):
             "keyswitch_diff": lambda: keys.keyswitch_diff(0, cts, ia, ib, 0, 1 << 62),
             "modswitch_center": lambda: keys.modswitch_center(0, small),
             "pbs": lambda: keys.pbs(0, small, np.zeros((1, 16), np.int64), 4),
+            "pbs_rows": lambda: keys.pbs_rows(0, small, np.zeros((2, 16), np.int64), 4, np.zeros((5, D + 4), np.uint64), row0=1, hw=2, nchan=2, accumulate=True),
+            "keyswitch_sum": lambda: keys.keyswitch_sum(1, narrow, narrow[:, D - 512:], deff=512),
+            "acc_rows": lambda: ctx.acc_rows(cts, narrow, 512),
+            "gather_rows": lambda: ctx.gather_rows(narrow, 512, ia, D),
             "round_lut": lambda: keys.round_lut(1, 0, cts, 6, 2, np.zeros((1, 16), np.int64), 4),
             "round_lut_split": lambda: keys.round_lut_split(1, 0, 0, cts, 8, 1, np.zeros((1, 128), np.int64), 7),
             "conv2d": lambda: ctx.conv2d(D, img, 1, 1, 2, 2, np.ones((1, 1, 1, 1), np.int8), 1, 0),

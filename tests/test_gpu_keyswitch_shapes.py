@@ -4,7 +4,10 @@ crosses and tests/test_gpu_primitives.py (n <= 40, two column blocks) does not:
     early return of the workgroups past the last column block), the two-limb epilogue, two row blocks of which the second holds two rows;
   * a trailing half K-step: rows used R = deff lk = 64 (mod 128), where the staging of the last step reads zeros for its upper half;
   * the grid-stride loop of k_ks_decompose (its grid is capped at 65 536 workgroups of 256 words), for plain rows and for the row
-    differences of a max pool (ks_src_diff; ks_src_sum has no entry point of its own and is covered by tests/test_gpu_lut7.py)."""
+    differences of a max pool (ks_src_diff) and for the row sums of a parity-split site (ks_src_sum);
+  * the summed source (ks_src_sum, dctfhe_keyswitch_sum) at the shipped gadget shapes: two row strides, the second row set narrower
+    than the first (a word of b at or beyond its width counts as zero), bodies whose sum wraps, and the prefix path at effective
+    dimensions on either side of b's width."""
 import math
 
 import numpy as np
@@ -89,6 +92,69 @@ def test_trailing_half_k_step_bit_exact(shape_keys, oracle, tier, deff):
     assert np.array_equal(full, ref), np.argwhere(full != ref)[:8]
 
 
+# ------------------------------------------------------------------------------------------ the summed source
+def _dense(r, dim, D):
+    """the ciphertexts that rows of dim mask words + body stand for, at D mask words: the words a row lacks are zero"""
+    out = np.zeros((r.shape[0], D + 1), np.uint64)
+    out[:, :dim] = r[:, :dim]
+    out[:, D] = r[:, -1]
+    return out
+
+
+def _sum_reference(oracle, a, dim_a, b, dim_b, shift, body_add, ksk, betak):
+    D = ksk.shape[0]
+    host = (_dense(a, dim_a, D) + _dense(b, dim_b, D)) << np.uint64(shift)
+    host[:, D] += np.uint64(body_add)
+    return oracle.keyswitch(host, ksk, betak)
+
+
+# (dim_b, deff, the first zero mask word of a): equal strides; b narrower, without and with the prefix path ending at b's width; a prefix
+# that ends inside b's width (576 lk is a multiple of 64 for every lk, so each shape takes the cached column sums of 576 lk key rows)
+SUM_CASES = [(1024, 0, 1024), (512, 0, 1024), (512, 512, 512), (640, 576, 576)]
+SUM_BODY_ADD = (1 << 64) - (1 << 62)          # the -2^62 of the parity bootstrap
+
+
+@pytest.fixture(scope="module")
+def sum_inputs(shape_inputs):
+    """two row sets from the wild rows (every digit value, the carry chains), the second in another order; every other pair of bodies wraps"""
+    _, _, wild = shape_inputs
+    a, b = wild.copy(), wild[::-1].copy()
+    a[0::2, -1] |= np.uint64(1 << 63)
+    b[0::2, -1] |= np.uint64(1 << 63)
+    assert ((a[:, -1] + b[:, -1]) < a[:, -1]).sum() >= 65 and ((a[:, -1] + b[:, -1]) >= a[:, -1]).any()
+    return a, b
+
+
+@pytest.mark.parametrize("dim_b,deff,zero_from", SUM_CASES, ids=["db%d-deff%d" % c[:2] for c in SUM_CASES])
+@pytest.mark.parametrize("tier", range(len(SHAPES)), ids=SHAPE_IDS)
+def test_summed_source_bit_exact(shape_keys, sum_inputs, oracle, tier, dim_b, deff, zero_from):
+    """dctfhe_keyswitch_sum == the oracle's key switch of ((a + b) << shift) + body_add made on the host"""
+    sh = SHAPES[tier]
+    assert deff == 0 or (deff * sh["lk"]) % 64 == 0         # else the library falls back to the full width: not the path this case is about
+    a, b = sum_inputs
+    a = a.copy()
+    a[:, zero_from:D_SHAPES] = 0
+    b = np.ascontiguousarray(np.concatenate([b[:, :dim_b], b[:, -1:]], axis=1))
+    b[:, min(zero_from, dim_b):dim_b] = 0                   # the caller's promise covers the sum: nothing beyond deff in either
+    assert deff == 0 or not (_dense(a, D_SHAPES, D_SHAPES) + _dense(b, dim_b, D_SHAPES))[:, deff:D_SHAPES].any()
+    ksk = shape_keys.export_ksk(tier)
+    for shift in (0, 3):
+        ref = _sum_reference(oracle, a, D_SHAPES, b, dim_b, shift, SUM_BODY_ADD, ksk, sh["betak"])
+        dev = shape_keys.keyswitch_sum(tier, a, b, shift=shift, body_add=SUM_BODY_ADD, deff=deff)
+        assert np.array_equal(dev, ref), (SHAPE_IDS[tier], dim_b, deff, shift, np.argwhere(dev != ref)[:8])
+
+
+@pytest.mark.parametrize("tier", range(len(SHAPES)), ids=SHAPE_IDS)
+def test_summed_source_with_a_zero_second_operand_is_the_plain_key_switch(shape_keys, sum_inputs, tier):
+    a, _ = sum_inputs
+    narrow = a.copy()
+    narrow[:, 512:D_SHAPES] = 0
+    for rows, deff in ((a, 0), (narrow, 512)):
+        for shift in (0, 3):
+            got = shape_keys.keyswitch_sum(tier, rows, np.zeros((rows.shape[0], 512 + 1), np.uint64), shift=shift, deff=deff)
+            assert np.array_equal(got, shape_keys.keyswitch(tier, rows, shift=shift, deff=deff)), (SHAPE_IDS[tier], deff, shift)
+
+
 # ------------------------------------------------------------------------------------------ grid-stride decompose
 D_BIG, ROWS_BIG = 8192, 2112          # 2112 x 8192 words > 65 536 x 256: the decompose grid walks its loop twice (the seam is at row 2048)
 
@@ -131,3 +197,26 @@ def test_decompose_grid_stride_row_differences(big, oracle):
     host[:, D_BIG] += np.uint64(body_add)
     ref = oracle.keyswitch(host, ksk, 4)              # the oracle on the differences made on the host, all rows
     assert np.array_equal(dev, ref), np.unique(np.argwhere(dev != ref)[:, 0])[:16]
+
+
+ROWS_SUM, DIM_SUM_A, DIM_SUM_B, DEFF_SUM = 70000, 320, 128, 256     # 70 000 x 256 words > 65 536 x 256: the seam is at row 65 536
+
+
+def test_decompose_grid_stride_row_sums(big, oracle):
+    """ks_src_sum through the same loop, at a narrow effective dimension: rows of 320 and 128 mask words, the first 256 switched"""
+    keys, _, ksk = big
+    assert ROWS_SUM * DEFF_SUM > 65536 * 256 and (DEFF_SUM * 4) % 64 == 0
+    rng = np.random.default_rng(11)
+    a = rng.integers(0, 2 ** 64, (ROWS_SUM, DIM_SUM_A + 1), dtype=np.uint64)
+    a[:, DEFF_SUM:DIM_SUM_A] = 0
+    b = rng.integers(0, 2 ** 64, (ROWS_SUM, DIM_SUM_B + 1), dtype=np.uint64)
+    body_add = 1 << 62
+    whole = keys.keyswitch_sum(0, a, b, shift=1, body_add=body_add, deff=DEFF_SUM)
+    half = ROWS_SUM // 2                  # each half stays under the grid cap: no loop
+    assert half * DEFF_SUM <= 65536 * 256
+    for c0 in (0, half):
+        part = keys.keyswitch_sum(0, a[c0:c0 + half], b[c0:c0 + half], shift=1, body_add=body_add, deff=DEFF_SUM)
+        assert np.array_equal(whole[c0:c0 + half], part), (c0, np.unique(np.argwhere(whole[c0:c0 + half] != part)[:, 0])[:16])
+    sample = np.concatenate([np.arange(0, 16), np.arange(65536 - 16, 65536 + 16), np.arange(ROWS_SUM - 16, ROWS_SUM)])
+    ref = _sum_reference(oracle, a[sample], DIM_SUM_A, b[sample], DIM_SUM_B, 1, body_add, ksk, 4)
+    assert np.array_equal(whole[sample], ref), np.unique(np.argwhere(whole[sample] != ref)[:, 0])[:16]

@@ -7,6 +7,14 @@ checks
   (b) 65 noisy ciphertexts against the oracle's bootstrap of the same inputs under the same key: decoded values, the rms of the
       difference and the largest error;
   (c) that a ciphertext's result does not depend on its place in a launch: shuffled and alone, bit for bit the rows of (b).
+On the first 37 inputs of (b), through dctfhe_pbs_rows, the write-back modes in which the library itself launches these kernels (the one-bit
+steps, the parity bootstrap, a max pool's maxima, the chunks and shards of a site); exact, resting on (c):
+  (d) store mode: the rows of (b); and into rows of D + 3 mask words between two guard rows, over garbage, with a body offset: the ring's
+      words and the body as in (b) plus the offset, zeros between the ring and the body, the guard rows untouched;
+  (e) accumulate mode at both widths, once and again on its own output: added on the ring's words and the body (the offset each time), the
+      words in between and the guard rows untouched -- the padded groups of the partial last workgroup accumulate nowhere; and, not
+      through store mode, onto fresh encryptions of known phases: every phase is the sum, within the model's bound plus six input sigmas;
+  (f) per-channel tables, table ((e_offset + c) / hw) % nchan, at an offset below and one beyond 2^32, against the explicit index.
 The bounds are the project's noise model at these shapes (tests/pbs_matrix_ref.py); nothing is taken from the kernels under test.
 The model was calibrated at n = 560 .. 856 (tests/test_gpu_noise.py); the measured ratios are printed and, with DCTFHE_MEASURE_DIR set,
 written to pbs_matrix.json (profiles/pbs_matrix.json is such a run)."""
@@ -87,6 +95,34 @@ def _pbs_odd_slices(keys, small, tables, w, idx, D):
     return np.concatenate(outs)
 
 
+# (d) .. (f): 37 ciphertexts leave a partial last workgroup whether a kernel packs 2, 4, 8 or 16 ciphertexts per workgroup
+WB_COUNT, WB_BODY_ADD = 37, 0x9E3779B97F4A7C15
+
+
+def _written(pre, dv, kN, D, body_add, reps):
+    """what rows [1, 1 + len(dv)) of the buffer `pre` must hold after the bootstraps whose store-mode rows are dv (D + 1 words) were stored
+    (reps = 0) or accumulated reps times with body_add on the body; every other row as it was"""
+    want = pre.copy()
+    rows = want[1:1 + dv.shape[0]]
+    if reps == 0:
+        rows[:, :kN] = dv[:, :kN]
+        rows[:, kN:-1] = 0
+        rows[:, -1] = dv[:, D] + np.uint64(body_add)
+    for _ in range(reps):
+        rows[:, :kN] += dv[:, :kN]
+        rows[:, -1] += dv[:, D] + np.uint64(body_add)
+    return want
+
+
+def _same_rows(got, want, kN, what):
+    """word for word, named by part: the guard rows, the ring's mask words, the words between the ring and the body, the body"""
+    assert got.shape == want.shape, what
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[-1], want[-1]), (what, "a row outside the launch was written")
+    assert np.array_equal(got[:, :kN], want[:, :kN]), (what, "mask words of the ring", np.flatnonzero((got[:, :kN] != want[:, :kN]).any(axis=1)))
+    assert np.array_equal(got[:, kN:-1], want[:, kN:-1]), (what, "words between the ring and the body", np.flatnonzero((got[:, kN:-1] != want[:, kN:-1]).any(axis=1)))
+    assert np.array_equal(got[:, -1], want[:, -1]), (what, "body", np.flatnonzero(got[:, -1] != want[:, -1]))
+
+
 # ------------------------------------------------------------------------------------------ host: the list is complete
 def test_matrix_lists_every_instantiation():
     """the literal list above == what the PBS_CASES / PBS_MB_CASES text of csrc/dctfhe.hip and the two general two-bit forms yield (a new
@@ -121,7 +157,8 @@ def _run_case(gpu_ctx, oracle, logN, k, l, unroll, beta, D, name):
     model = R.tier_spec(n, k, logN, l, beta, unroll, tier["glwe_sigma"])
     sigma, bound_max, bound_diff = R.sigma_model(model), R.max_bound(model), R.diff_bound(model)
     rec = dict(D=D, beta=beta, log2_sigma_model=math.log2(sigma), max_bound_over_sigma=bound_max / sigma)
-    keys = Keys(gpu_ctx, make_params(D, n, [tier], 2.0 ** (-62 if logN >= 12 else -50)), seed=41 + logN)
+    input_sigma = 2.0 ** (-62 if logN >= 12 else -50)
+    keys = Keys(gpu_ctx, make_params(D, n, [tier], input_sigma), seed=41 + logN)
     try:
         S, s = keys.export_secret()
         s = s[:n].copy()
@@ -181,6 +218,47 @@ def _run_case(gpu_ctx, oracle, logN, k, l, unroll, beta, D, name):
         assert np.array_equal(keys.pbs(0, small[perm], tables, w, idx[perm]), dev[perm]), (name, "a result depends on its place in the launch")
         for c in (0, count - 1):
             assert np.array_equal(keys.pbs(0, small[c:c + 1], tables, w, idx[c:c + 1]), dev[c:c + 1]), (name, c, "a batch of one differs")
+
+        # (d) .. (f): the write-back modes, on the first 37 inputs of (b).  By (c) their store-mode rows are dev[:37] whatever the launch.
+        m, kN = WB_COUNT, k * N
+        sm, ix, dv = small[:m], idx[:m], dev[:m]
+        garbage = lambda dim: rng.integers(0, 2 ** 64, (m + 2, dim + 1), dtype=np.uint64)      # a guard row either side of the launched rows
+        wide = dict(row0=1, table_idx=ix, body_add=WB_BODY_ADD)
+
+        # (d) store mode
+        assert np.array_equal(keys.pbs_rows(0, sm, tables, w, garbage(D)[:m], table_idx=ix), dv), (name, "store mode through pbs_rows differs from pbs")
+        pre = garbage(D + 3)
+        _same_rows(keys.pbs_rows(0, sm, tables, w, pre, **wide), _written(pre, dv, kN, D, WB_BODY_ADD, 0), kN, (name, "store, rows of D + 3 mask words"))
+        rec["step_d"] = True
+
+        # (e) accumulate mode, once and again on its own output
+        for dim in (D, D + 3):
+            pre = garbage(dim)
+            once = keys.pbs_rows(0, sm, tables, w, pre, accumulate=True, **wide)
+            _same_rows(once, _written(pre, dv, kN, D, WB_BODY_ADD, 1), kN, (name, "accumulate, rows of %d mask words" % dim))
+            twice = keys.pbs_rows(0, sm, tables, w, once, accumulate=True, **wide)
+            _same_rows(twice, _written(pre, dv, kN, D, WB_BODY_ADD, 2), kN, (name, "accumulate twice, rows of %d mask words" % dim))
+        # ... and against the reference, not through store mode: onto fresh encryptions of known phases
+        pre_ph = rng.integers(0, 2 ** 64, m, dtype=np.uint64)
+        acc = keys.pbs_rows(0, sm, tables, w, keys.encrypt(pre_ph), table_idx=ix, accumulate=True, body_add=WB_BODY_ADD)
+        want_ph = pre_ph + R.message_expected(tables, ix, w, msgs[:m]) + np.uint64(WB_BODY_ADD)
+        err = np.abs(R.cent(oracle.lwe_phase(S, D, acc) - want_ph)).max()
+        print(name, "accumulate onto encryptions: max error %.2f sigma_model" % (err / sigma))
+        assert err < bound_max + 6 * input_sigma, (name, "accumulate onto encryptions", err, bound_max, input_sigma)
+        rec["step_e"] = True
+
+        # (f) per-channel tables: element e_offset + c of a tensor with hw elements per channel, nchan channels
+        hw, nchan = 5, 3
+        for e_offset in (7, (1 << 33) + 4):
+            chan = np.array([((e_offset + c) // hw) % nchan for c in range(m)], np.int32)         # Python integers
+            if e_offset >> 32:            # an offset cut to 32 bits picks other tables
+                assert any(((e_offset % (1 << 32) + c) // hw) % nchan != chan[c] for c in range(m))
+            by_rule = keys.pbs_rows(0, sm, tables, w, garbage(D)[:m], hw=hw, nchan=nchan, e_offset=e_offset)
+            by_index = keys.pbs_rows(0, sm, tables, w, garbage(D)[:m], table_idx=chan)
+            assert np.array_equal(by_rule, by_index), (name, "per-channel tables at e_offset", e_offset, np.flatnonzero((by_rule != by_index).any(axis=1)))
+        one = keys.pbs_rows(0, sm, tables, w, garbage(D)[:m], hw=hw, nchan=1, e_offset=7)
+        assert np.array_equal(one, keys.pbs_rows(0, sm, tables, w, garbage(D)[:m], table_idx=np.zeros(m, np.int32))), (name, "nchan = 1 must take table 0")
+        rec["step_f"] = True
     finally:
         keys.close()
         MEASURED[name] = rec

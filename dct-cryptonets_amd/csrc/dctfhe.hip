@@ -455,6 +455,34 @@ constexpr int groups_for() {
   return g;
 }
 
+// The duo tier: the general two-bit form at N = 2048, k = 1, three levels (T4r2) runs two ciphertexts per group of M / 4 threads
+// (pbs_kernel_duo), so its transforms -- the bootstrap's and the key's -- keep P = 4 points per thread and the device holds its
+// Fourier key in the P = 4 order.  The evaluation-key blob keeps the one documented order (include/dctfhe.h: P = 8 for this shape):
+// export and import permute the entries of each polynomial, frequency for frequency.
+static bool tier_duo(const dctfhe_tier& t) { return t.logN == 11 && t.k == 1 && t.l == 3 && t.unroll == 2; }
+constexpr int DUO_LOGN = 11, DUO_P = 4, DUO_BLOB_P = 8, DUO_M = 1 << (DUO_LOGN - 1);
+// blob entry (j T + t of the P = 8 transform) -> device entry (of the P = 4 transform) that holds the same frequency
+static const std::vector<uint16_t>& duo_entry_map() {
+  static const std::vector<uint16_t> map = [] {
+    std::vector<uint16_t> by_freq(DUO_M), m(DUO_M);
+    constexpr int T4 = DUO_M / DUO_P, T8 = DUO_M / DUO_BLOB_P;
+    for (int e = 0; e < DUO_M; e++) by_freq[spectrum_freq<DUO_LOGN - 1, DUO_P>(DUO_P * (e % T4) + e / T4)] = (uint16_t)e;
+    for (int e = 0; e < DUO_M; e++) m[e] = by_freq[spectrum_freq<DUO_LOGN - 1, DUO_BLOB_P>(DUO_BLOB_P * (e % T8) + e / T8)];
+    return m;
+  }();
+  return map;
+}
+// npoly polynomials of M entries: blob order -> device order (to_device) or back; src and dst must not overlap
+static void duo_permute(const cplx* src, cplx* dst, size_t npoly, bool to_device) {
+  const std::vector<uint16_t>& m = duo_entry_map();
+  for (size_t q = 0; q < npoly; q++) {
+    const cplx* a = src + q * DUO_M;
+    cplx* b = dst + q * DUO_M;
+    if (to_device) for (int e = 0; e < DUO_M; e++) b[m[e]] = a[e];
+    else           for (int e = 0; e < DUO_M; e++) b[e] = a[m[e]];
+  }
+}
+
 static int tier_ppt(const dctfhe_tier& t) {
 #define X(LN, K_, L_, P_) if (t.logN == LN && t.k == K_ && t.l == L_) return P_;
   PBS_CASES(X)
@@ -486,6 +514,18 @@ static int launch_pbs_as(const pbs_launch& a, hipStream_t st) {
   return 0;
 }
 
+// the duo form: DUOS groups of two ciphertexts per workgroup
+template <int LN, int K, int L, int P, int DUOS>
+static int launch_pbs_as_duo(const pbs_launch& a, hipStream_t st) {
+  const size_t lds = pbs_duo_lds_bytes<LN, K, L, P>(DUOS);
+  static_assert(pbs_duo_lds_bytes<LN, K, L, P>(DUOS) <= 160 * 1024, "LDS of one CU");
+  SET_LDS_ATTR((pbs_kernel_duo<LN, K, L, P, DUOS>), lds);
+  const unsigned grid = (unsigned)((a.count + 2 * DUOS - 1) / (2 * DUOS));
+  hipLaunchKernelGGL((pbs_kernel_duo<LN, K, L, P, DUOS>), dim3(grid), dim3(pbs_geom<LN, K, L, P, 1>::T * DUOS), lds, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 static int launch_pbs(const dctfhe_tier& t, const pbs_launch& a, hipStream_t st) {
   if (a.count == 0) return 0;
   // the kernel's L2 warm-up contract (pbs_core.h): callers pad the key by PBS_PF_DIST iterations (eval_alloc does)
@@ -504,14 +544,22 @@ static int launch_pbs(const dctfhe_tier& t, const pbs_launch& a, hipStream_t st)
   // the general form of the two-bit rotation (one polynomial at a time, monomial factors rebuilt per gadget row), four
   // ciphertexts per 512-thread workgroup so that they share their key lines: 74.2 ms per 4096 against 82.3 for the one-bit
   // chain of the same tier (profiles/r02_exp_ablations.log); its output is 0.7 bit noisier, so the compiler only uses it
-  // where the circuit's budget allows (dctfhe/params.py T4r2)
-  if (t.logN == 11 && t.k == 1 && t.l == 3 && t.unroll == 2) return launch_pbs_as<11, 1, 3, 8, 4, 1>(a, st);
+  // where the circuit's budget allows (dctfhe/params.py T4r2).  As two duos: every loaded key value is folded into two
+  // ciphertexts (pbs_core.h pbs_thread_duo; profiles/t4r2_duo_ab.json).  pbs_kernel<11, 1, 3, 8, 4, 1>, the form it replaces,
+  // still builds in tools/exp_pbs.hip.
+  static_assert(DUO_LOGN == 11 && DUO_P == 4, "tier_duo names this kernel's shape");
+  if (t.logN == 11 && t.k == 1 && t.l == 3 && t.unroll == 2) return launch_pbs_as_duo<11, 1, 3, 4, 2>(a, st);
   // general two-bit rotation for the one-level bit tier (Ba2): one wave per ciphertext, four per workgroup
   if (t.logN == 10 && t.k == 2 && t.l == 1 && t.unroll == 2) return launch_pbs_as<10, 2, 1, 8, 4, 1>(a, st);
   return fail("no bootstrap kernel instantiated for logN=%d k=%d l=%d unroll=%d", t.logN, t.k, t.l, t.unroll);
 }
 
 static int make_twiddles(const dctfhe_tier& t, std::vector<cplx>& tw) {
+  if (tier_duo(t)) {
+    tw.resize(fft_geom<DUO_LOGN - 1, DUO_P>::TW_ELEMS);
+    fill_twiddles<DUO_LOGN - 1, DUO_P>(tw.data());
+    return 0;
+  }
 #define X(LN, K_, L_, P_)                                        \
   if (t.logN == LN && t.k == K_ && t.l == L_) {                  \
     tw.resize(fft_geom<LN - 1, P_>::TW_ELEMS);                   \
@@ -524,6 +572,14 @@ static int make_twiddles(const dctfhe_tier& t, std::vector<cplx>& tw) {
 }
 
 static int launch_bsk_fourier(const dctfhe_tier& t, const uint64_t* polys, size_t npoly, const cplx* tw, cplx* out, hipStream_t st) {
+  if (tier_duo(t)) {      // straight into the device order of the duo kernel: one polynomial per workgroup of M / 4 threads
+    using F = fft_geom<DUO_LOGN - 1, DUO_P>;
+    const size_t lds = (size_t)F::TW_ELEMS * 16 + (size_t)F::EXCH_ELEMS * 16;
+    SET_LDS_ATTR((k_bsk_fourier<DUO_LOGN, DUO_P, 1>), lds);
+    hipLaunchKernelGGL((k_bsk_fourier<DUO_LOGN, DUO_P, 1>), dim3((unsigned)npoly), dim3(F::T), lds, st, polys, npoly, tw, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
 #define X(LN, K_, L_, P_)                                                                            \
   if (t.logN == LN && t.k == K_ && t.l == L_) {                                                      \
     using F = fft_geom<LN - 1, P_>;                                                                  \
@@ -876,7 +932,13 @@ extern "C" int dctfhe_eval_keys_export(dctfhe_eval_keys* E, void* buf, size_t ca
       HIPCHK(hipMemcpy(q, E->ksk[ti].ksk.p, tier_ksk_words(E->p, t) * 8, hipMemcpyDeviceToHost));
       q += tier_ksk_words(E->p, t) * 8;
     }
-    HIPCHK(hipMemcpy(q, E->tiers[ti].bsk.p, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyDeviceToHost));
+    if (tier_duo(t)) {      // device order -> the blob's order
+      std::vector<cplx> dev(tier_bsk_elems(t));
+      HIPCHK(hipMemcpy(dev.data(), E->tiers[ti].bsk.p, dev.size() * sizeof(cplx), hipMemcpyDeviceToHost));
+      duo_permute(dev.data(), (cplx*)q, dev.size() / DUO_M, false);
+    } else {
+      HIPCHK(hipMemcpy(q, E->tiers[ti].bsk.p, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyDeviceToHost));
+    }
     q += tier_bsk_elems(t) * sizeof(cplx);
   }
   return 0;
@@ -1065,7 +1127,13 @@ extern "C" int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t 
       HIPCHK(hipMemcpy(E->ksk[ti].ksk.p, q, tier_ksk_words(h.params, t) * 8, hipMemcpyHostToDevice));
       q += tier_ksk_words(h.params, t) * 8;
     }
-    HIPCHK(hipMemcpy(E->tiers[ti].bsk.p, q, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyHostToDevice));
+    if (tier_duo(t)) {      // the blob's order -> device order
+      std::vector<cplx> dev(tier_bsk_elems(t));
+      duo_permute((const cplx*)q, dev.data(), dev.size() / DUO_M, true);
+      HIPCHK(hipMemcpy(E->tiers[ti].bsk.p, dev.data(), dev.size() * sizeof(cplx), hipMemcpyHostToDevice));
+    } else {
+      HIPCHK(hipMemcpy(E->tiers[ti].bsk.p, q, tier_bsk_elems(t) * sizeof(cplx), hipMemcpyHostToDevice));
+    }
     q += tier_bsk_elems(t) * sizeof(cplx);
   }
   CHK(eval_finish(E.get()));

@@ -148,7 +148,7 @@ HD void fused_bf(const cplx a, const cplx b, const double tr, const double ti, c
 template <int R, int S, int LV>
 struct fused_idft {
   static HD void run(const cplx* x, cplx* y, const cplx* pw, const cplx cw8) {
-    static_assert(R == 2 || R == 4 || R == 8, "radix 8 passes");
+    static_assert(R == 2 || R == 4 || R == 8, "radix 4 and radix 8 passes");
     if constexpr (R == 2) {
       fused_bf(x[0], x[S], pw[LV].re, pw[LV].im, y[0], y[1]);
     } else {
@@ -222,7 +222,17 @@ struct fft_geom {
   // (M = 512, one wave per ciphertext: a single gather would gain and the second set of addresses costs the k = 2 kernels registers they
   //  do not have -- 60-84 bytes of scratch per lane, +1 / +4 % time: profiles/r03_exp_lds_image.log -- so those keep `skew` throughout)
   static constexpr bool swz_reader(int i) { return P == 8 && LOGM >= 10 && geom_radix(LOGM, P, i) == P && geom_weight(LOGM, P, i) >= 16; }
-  template <int IR> static HD int ex(int idx) { if constexpr (swz_reader(IR)) return swz(idx); else return skew(idx); }   // IR: the pass that gathers
+  // P = 4 (five radix-4 passes at M = 1024): `skew` serves the gathers of passes 0 - 2 three- and two-way and their scatters two-way
+  // (tools/lds_model.py).  Chosen per exchange E (the one between passes E and E + 1, whichever direction it runs) instead:
+  //   E < 2   no image at all: the patterns of passes 0 - 2 (strides of 256, 64 and 16 elements, lane-contiguous) are conflict-free as they are;
+  //   E >= 2  x4: bits 0-1 XORed with bits 2-3 and bits 2-3 with bits 4-5 -- conflict-free for the patterns of passes 2, 3 and 4.
+  // Both stay inside a wave's own 256 elements, so the wave-local exchanges never touch another wave's slots.
+  static HD int x4(int idx) { return idx ^ ((idx >> 2) & 3) ^ (((idx >> 4) & 3) << 2); }
+  template <int IR, int E> static HD int ex(int idx) {   // IR: the pass that gathers; E: the exchange
+    if constexpr (P == 4) { if constexpr (E < 2) return idx; else return x4(idx); }
+    else if constexpr (swz_reader(IR)) return swz(idx);
+    else return skew(idx);
+  }
   static constexpr int EXCH_ELEMS = M + (M >> geom_logp(P));
 };
 
@@ -288,9 +298,9 @@ HD void fft_forward(cplx* v, int t, const cplx* tw, const cplx twist, cplx* exch
       // The gather itself, and everything a wave-local exchange touches, stays inside the wave's own block,
       // where program order (the LDS queue of a wave is in order) is enough.
       if constexpr (W <= 64) wsync(); else sync();
-      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; exch[G::template ex<i + 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
+      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; exch[G::template ex<i + 1, i>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
       if constexpr (W <= 64) wsync(); else sync();
-      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[j] = exch[G::template ex<i + 1>(pass_addr<LOGM, P, i + 1>(t, j))]; });
+      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[j] = exch[G::template ex<i + 1, i>(pass_addr<LOGM, P, i + 1>(t, j))]; });
     } else {
       static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[j] = y[j]; });
     }
@@ -307,7 +317,7 @@ HD void fft_inverse(cplx* v, int t, const cplx* tw, const cplx twist, cplx* exch
     constexpr int i = S - 1 - decltype(Irev)::value;
     constexpr int R = G::radix(i);
     constexpr int W = G::weight(i);
-    constexpr bool FUSED = i > 0 && i < S - 1 && R == P && P == 8;     // middle passes: fused butterflies (fused_idft)
+    constexpr bool FUSED = i > 0 && i < S - 1 && R == P && (P == 8 || P == 4);     // middle passes: fused butterflies (fused_idft)
     if constexpr (i < S - 1 && !FUSED) {
       const cplx b = tw[G::tw_offset(i) + (t % W)];
       {
@@ -328,9 +338,9 @@ HD void fft_inverse(cplx* v, int t, const cplx* tw, const cplx twist, cplx* exch
     }
     if constexpr (i > 0) {
       constexpr int Wp = G::weight(i - 1);   // exchange between pass i-1 and i: groups of W_{i-1} threads
-      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; exch[G::template ex<i - 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
+      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; exch[G::template ex<i - 1, i - 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
       if constexpr (Wp <= 64) wsync(); else sync();
-      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[j] = exch[G::template ex<i - 1>(pass_addr<LOGM, P, i - 1>(t, j))]; });
+      static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[j] = exch[G::template ex<i - 1, i - 1>(pass_addr<LOGM, P, i - 1>(t, j))]; });
       // after a cross-wave gather other waves may still be reading this wave's block: barrier before anyone writes again
       if constexpr (Wp <= 64) wsync(); else sync();
     } else {
@@ -380,7 +390,7 @@ HD void fft_forward_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       static_for<0, NP>([&](auto U) {
         constexpr int u = decltype(U)::value;
         cplx* ex = exch + u * G::EXCH_ELEMS;
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i + 1>(pass_addr<LOGM, P, i>(t, j))] = y[u][j]; });
+        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i + 1, i>(pass_addr<LOGM, P, i>(t, j))] = y[u][j]; });
       });
       if constexpr (W > 64) tick.template at<2>();        // phase 2: butterflies + twiddles + scatter of the cross-wave pass
       if constexpr (W <= 64) wsync(); else sync();
@@ -388,7 +398,7 @@ HD void fft_forward_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       static_for<0, NP>([&](auto U) {
         constexpr int u = decltype(U)::value;
         const cplx* ex = exch + u * G::EXCH_ELEMS;
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i + 1>(pass_addr<LOGM, P, i + 1>(t, j))]; });
+        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i + 1, i>(pass_addr<LOGM, P, i + 1>(t, j))]; });
       });
     } else {
       static_for<0, NP>([&](auto U) {
@@ -420,7 +430,7 @@ HD void fft_inverse_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       b = tw[G::tw_offset(i) + (t % W)];
       if constexpr (i == 0) run0 = twist;
     }
-    constexpr bool FUSED = i > 0 && i < S - 1 && R == P && P == 8;
+    constexpr bool FUSED = i > 0 && i < S - 1 && R == P && (P == 8 || P == 4);
     [[maybe_unused]] cplx pw[3], cw8;
     if constexpr (FUSED) fused_idft_factors(b, pw, cw8);
     if constexpr (i < S - 1 && !FUSED) {
@@ -444,7 +454,7 @@ HD void fft_inverse_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       }
       if constexpr (i > 0) {
         cplx* ex = exch + u * G::EXCH_ELEMS;
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i - 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
+        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; ex[G::template ex<i - 1, i - 1>(pass_addr<LOGM, P, i>(t, j))] = y[j]; });
       } else {
         static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = mul_root64<j*(64 / (4 * P)), -1>(y[j]); });
       }
@@ -457,7 +467,7 @@ HD void fft_inverse_n(cplx (&v)[NP][P], int t, const cplx* tw, const cplx twist,
       static_for<0, NP>([&](auto U) {
         constexpr int u = decltype(U)::value;
         const cplx* ex = exch + u * G::EXCH_ELEMS;
-        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i - 1>(pass_addr<LOGM, P, i - 1>(t, j))]; });
+        static_for<0, P>([&](auto J) { constexpr int j = decltype(J)::value; v[u][j] = ex[G::template ex<i - 1, i - 1>(pass_addr<LOGM, P, i - 1>(t, j))]; });
       });
       if constexpr (Wp > 64) tick.template at<9>();       // phase 9: the cross-wave gather
       if constexpr (Wp <= 64) wsync(); else sync();

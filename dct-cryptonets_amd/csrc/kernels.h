@@ -890,6 +890,60 @@ pbs_kernel(pbs_launch a) {
   }
 }
 
+// The duo form of the general two-bit bootstrap (pbs_thread_duo): DUOS groups of T = M / P threads per workgroup, two ciphertexts
+// each.  LDS per duo: the two exchange buffers (contiguous: fft_forward_n), then the LDS-resident accumulator polynomials of both.
+template <int LOGN, int K, int L, int P>
+constexpr size_t pbs_duo_lds_bytes(int duos) {
+  using G = pbs_geom<LOGN, K, L, P, 1>;
+  return (size_t)G::TW_BYTES + (size_t)duos * 2 * G::GROUP_BYTES;
+}
+
+template <int LOGN, int K, int L, int P, int DUOS>
+__global__ void __launch_bounds__((pbs_geom<LOGN, K, L, P, 1>::T * DUOS), ((pbs_geom<LOGN, K, L, P, 1>::T * DUOS) >= 512 ? 1 : 2))
+pbs_kernel_duo(pbs_launch a) {
+  using G = pbs_geom<LOGN, K, L, P, 1>;
+  constexpr int T = G::T;
+  static_assert(T >= 64 && T % 64 == 0, "a wave holds threads of one duo only");
+  static_assert(G::TWIST_LDS && G::SHARED_BYTES == G::EXCH_BYTES, "duo LDS layout");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  cplx* tw = reinterpret_cast<cplx*>(smem_raw);
+  unsigned char* per_duo = smem_raw + G::TW_BYTES;
+  for (int x = threadIdx.x; x < G::TW_LDS_ELEMS; x += blockDim.x) tw[x] = a.tw[x];
+  {     // root tables of the two-bit rotation: lo[j] = zeta^j, hi[j] = zeta^(j << ZLO)
+    cplx* zl = tw + G::TW_LDS_ELEMS;
+    for (int x = threadIdx.x; x < G::ZLUT_ELEMS; x += blockDim.x) zl[x] = x < (1 << G::ZLO) ? a.wtab[x] : a.wtab[(size_t)(x - (1 << G::ZLO)) << G::ZLO];
+  }
+  __syncthreads();
+  const int g = threadIdx.x / T, t = threadIdx.x % T;
+  unsigned char* mine = per_duo + (size_t)g * 2 * G::GROUP_BYTES;
+  cplx* exch = reinterpret_cast<cplx*>(mine);
+  uint64_t* accl = reinterpret_cast<uint64_t*>(mine + 2 * G::EXCH_BYTES);
+  pbs_args A2[2];
+#pragma unroll
+  for (int c = 0; c < 2; c++) {
+    size_t e = ((size_t)blockIdx.x * DUOS + g) * 2 + c;
+    const bool live = e < a.count;
+    if (!live) e = a.count - 1;  // padded slots redo the last ciphertext in store mode into the sink
+    pbs_args& A = A2[c];
+    A.ct_small = a.cts_small + e * (size_t)(a.n + 1);
+    A.n = a.n; A.beta = a.beta; A.bsk = a.bsk;
+    const size_t ti = a.table_idx ? (size_t)a.table_idx[e] : (a.nchan > 1 ? ((a.e_offset + e) / (size_t)a.hw) % (size_t)a.nchan : 0);
+    A.table = a.tables + (ti << a.w);
+    A.w = a.w;
+    A.out = live ? a.out + e * (size_t)(a.D_out + 1) : a.dummy;
+    A.D_out = a.D_out;
+    A.accumulate = live ? a.accumulate : 0;
+    A.body_add = a.body_add;
+    A.bsk_wrap = 0;
+    A.pf_parts = a.pf_parts;
+    A.wtab = a.wtab;
+    A.zlut = tw + G::TW_LDS_ELEMS;
+    A.twist = tw + G::F::TW_TOTAL;
+    A.pf_rank = (int)((blockIdx.x / 8) % (unsigned)(a.pf_parts > 0 ? a.pf_parts : 1));
+  }
+  pbs_thread_duo<LOGN, K, L, P>(A2, t, tw, exch, accl, nullptr, [] { __syncthreads(); }, [] { __builtin_amdgcn_wave_barrier(); });
+}
+
 // ------------------------------------------------------------------------------------------ K1 conv2d
 // out[b][co][y][x][word] = sum_{ci,ky,kx} w[co][ci][ky][kx] * in[b][ci][y*s+ky-p][x*s+kx-p][word]  (mod 2^64)
 // Thread = one ciphertext word of one output pixel for a tile of COT output channels; lanes run over

@@ -600,6 +600,216 @@ HD void pbs_thread(const pbs_args& A, int t, const cplx* tw, uint64_t* stage_raw
   }
 }
 
+// The general two-bit bootstrap (the MB && !PAIR form above) for TWO ciphertexts per group: a "duo".  One group of T = M / P threads
+// owns ciphertexts 0 and 1; thread t holds points t + T*j, j < P, of both, so with P = 4 the per-thread state (2P points per
+// ciphertext and polynomial) is that of the one-ciphertext form at P = 8.  What changes is who consumes a loaded key value: every
+// kk[w][q] is loaded once and folded twice, once per ciphertext with that ciphertext's own monomial factors -- the key bytes a CU
+// pulls through its vector L1 halve.  The transforms of the two ciphertexts run interleaved (fft_forward_n / fft_inverse_n, exchange
+// buffer c at exch + c * EXCH_ELEMS), so a pass's twiddle chain is computed once for both and one barrier pair serves both.
+// A wave holds threads of one duo only (T >= 64): both ciphertexts' mod-switched mask words stay wave-uniform.
+// A2[c]: the arguments of ciphertext c; n, beta, bsk, zlut / wtab, twist and the warm-up fields are read from A2[0] (the same for both).
+// accl_raw: NL polynomials of ciphertext 0, then NL of ciphertext 1.  bsk_wrap is not supported (as in every two-bit form).
+template <int LOGN, int K, int L, int P, class Sync, class WSync>
+HD void pbs_thread_duo(const pbs_args (&A2)[2], int t, const cplx* tw, cplx* exch, uint64_t* accl_raw, uint32_t* pf_dump, Sync&& sync, WSync&& wsync) {
+  using G = pbs_geom<LOGN, K, L, P, 1>;
+  static_assert(!G::PAIR && !G::ACC32, "the duo is the general two-bit form");
+  static_assert(G::NG == 1, "one small transform per thread in the last pass: a single monomial base per exponent");
+  constexpr int N = G::N, M = G::M, T = G::T, NL = G::NL;
+  using acc_t = typename G::acc_t;
+  const pbs_args& A = A2[0];
+  acc_t* const accl = reinterpret_cast<acc_t*>(accl_raw);
+  const int n = A.n;
+  const int msh = 64 - LOGN - 2;
+  const cplx twist = A.twist[t];
+
+  // L2 warm-up: the geometry and the contract of pbs_thread, with this group's T
+  constexpr int PF_LINES = (int)(G::KEY_BLOCKS * G::BSK_ELEMS_PER_KEYBIT * 16 / 128);
+  constexpr int PF_ROUNDS = (PF_LINES / 8 + T - 1) / T;
+  const char* pf_ptr;
+  const size_t pf_step = (size_t)G::KEY_BLOCKS * G::BSK_ELEMS_PER_KEYBIT * 16;
+  {
+    const int parts = A.pf_parts >= 8 ? A.pf_parts : PF_LINES;
+    const int per = (PF_LINES + parts - 1) / parts;
+    int line = A.pf_rank * per + (t < per ? t : per - 1);
+    if (line > PF_LINES - 1 - (PF_ROUNDS - 1) * T) line = PF_LINES - 1 - (PF_ROUNDS - 1) * T;
+    if (line < 0) line = 0;
+    pf_ptr = reinterpret_cast<const char*>(A.bsk) + (size_t)PBS_PF_DIST * pf_step + (size_t)line * 128;
+  }
+  acc_t acc[2][K + 1][2 * P];
+  static_for<0, 2>([&](auto Cc) {  // ACC = X^{-b~} * TV (trivial GLWE)
+    constexpr int c = decltype(Cc)::value;
+    const uint32_t bt = (uint32_t)(((A2[c].ct_small[n] >> msh) + 1) >> 1) & (2 * N - 1);
+    static_for<0, K>([&](auto Pp) {
+      constexpr int p = decltype(Pp)::value;
+      static_for<0, 2 * P>([&](auto R) {
+        constexpr int r = decltype(R)::value;
+        if constexpr (p < NL) accl[(c * NL + p) * N + t + T * r] = 0; else acc[c][p][r] = 0;
+      });
+    });
+    static_for<0, 2 * P>([&](auto R) {
+      constexpr int r = decltype(R)::value;
+      const uint32_t idx = ((uint32_t)(t + T * r) + bt) & (2 * N - 1);
+      const uint64_t v = testvec_coeff(A2[c].table, A2[c].w, N, (int)(idx & (N - 1)));
+      acc[c][K][r] = (acc_t)((idx & N) ? (uint64_t)0 - v : v);
+    });
+  });
+
+  // root exponent (1 - 4k) mod 2N of this thread's first point; point j sits at exponent ulow0 - j * (2N / P)
+  const uint32_t ulow0 = (uint32_t)(1 - 4 * spectrum_freq<G::LOGM, P>(P * t)) & (2 * N - 1);
+  auto zeta = [&](uint32_t m) -> cplx {
+#if defined(DCTFHE_DEVICE)
+    return cmul(A.zlut[(1 << G::ZLO) + (m >> G::ZLO)], A.zlut[m & ((1u << G::ZLO) - 1)]);
+#else
+    return A.zlut ? cmul(A.zlut[(1 << G::ZLO) + (m >> G::ZLO)], A.zlut[m & ((1u << G::ZLO) - 1)]) : A.wtab[m];
+#endif
+  };
+#if defined(__HIP_DEVICE_COMPILE__) && defined(DCTFHE_PHASE_TIMERS)
+  phase_clock tick;
+  tick.start();
+#else
+  no_tick tick;
+#endif
+  for (int i = 0; i < n; i += 2) {
+    uint32_t au[2], a2u[2], e1[2], e2[2];
+    static_for<0, 2>([&](auto Cc) {
+      constexpr int c = decltype(Cc)::value;
+      const uint32_t a = (uint32_t)(((A2[c].ct_small[i] >> msh) + 1) >> 1) & (2 * N - 1);
+      const uint32_t a2 = (uint32_t)(((A2[c].ct_small[i + 1] >> msh) + 1) >> 1) & (2 * N - 1);
+      au[c] = DCTFHE_UNIFORM(a); a2u[c] = DCTFHE_UNIFORM(a2);
+      e1[c] = a * ulow0; e2[c] = a2 * ulow0;
+    });
+    const cplx* key = A.bsk + (size_t)(3 * (i >> 1)) * G::BSK_ELEMS_PER_KEYBIT;     // blocks: b1 = s1(1-s2), b2 = (1-s1)s2, b12 = s1 s2
+    cplx out[K + 1][2][P];
+    static_for<0, K + 1>([&](auto Pp) {
+      constexpr int p = decltype(Pp)::value;
+      uint32_t packed[2][2 * P];
+      double first[2][2 * P];
+      static_for<0, 2>([&](auto Cc) {
+        constexpr int c = decltype(Cc)::value;
+        static_for<0, 2 * P>([&](auto R) {
+          constexpr int r = decltype(R)::value;
+          acc_t own;
+          if constexpr (p < NL) own = accl[(c * NL + p) * N + t + T * r]; else own = acc[c][p][r];
+          int32_t dg[L];
+          decompose<L>(own, A.beta, dg);
+          first[c][r] = (double)dg[0];
+          packed[c][r] = pack_digits<L>(dg);
+        });
+      });
+      static_for<0, L>([&](auto Lv) {
+        constexpr int lev = decltype(Lv)::value;
+        constexpr int row = p * L + lev;
+        cplx v[2][P];
+        static_for<0, 2>([&](auto Cc) {
+          constexpr int c = decltype(Cc)::value;
+          static_for<0, P>([&](auto J) {
+            constexpr int j = decltype(J)::value;
+            if constexpr (lev == 0) v[c][j] = cmk(first[c][j], first[c][P + j]);
+            else v[c][j] = cmk(unpack_digit<L, lev>(packed[c][j]), unpack_digit<L, lev>(packed[c][P + j]));
+          });
+        });
+        fft_forward_n<G::LOGM, P, 2>(v, t, tw, twist, exch, sync, wsync, tick);      // phases 0 - 4
+        cplx zb1[2], zb2[2];
+        static_for<0, 2>([&](auto Cc) {
+          constexpr int c = decltype(Cc)::value;
+          zb1[c] = zeta(e1[c] & (2 * N - 1));
+          zb2[c] = zeta(e2[c] & (2 * N - 1));
+        });
+        static_for<0, P>([&](auto J) {
+          constexpr int j = decltype(J)::value;
+          cplx kk[3][K + 1];
+          static_for<0, 3>([&](auto Ww) {
+            constexpr int w = decltype(Ww)::value;
+            static_for<0, K + 1>([&](auto Q) {
+              constexpr int q = decltype(Q)::value;
+              kk[w][q] = load_uniform_base(key + (((size_t)w * G::ROWS * (K + 1) + (size_t)row * (K + 1) + q) * M + j * T), (unsigned)t);    // uniform base + lane index
+            });
+          });
+          DCTFHE_SCHED_BARRIER();
+          static_for<0, 2>([&](auto Cc) {      // one delivery of the key values, two folds
+            constexpr int c = decltype(Cc)::value;
+            cplx z1 = zb1[c], z2 = zb2[c];
+            if constexpr (j > 0) {
+              z1 = cmul(z1, root8((0u - au[c] * (uint32_t)j) * (8 / P)));      // wave-uniform: scalar loads
+              z2 = cmul(z2, root8((0u - a2u[c] * (uint32_t)j) * (8 / P)));
+            }
+            const cplx m1 = cmk(z1.re - 1.0, z1.im), m2 = cmk(z2.re - 1.0, z2.im);
+            cplx m12 = cmul(z1, z2); m12.re -= 1.0;
+            static_for<0, K + 1>([&](auto Q) {
+              constexpr int q = decltype(Q)::value;
+              const cplx bundle = cfma(m12, kk[2][q], cfma(m2, kk[1][q], cmul(m1, kk[0][q])));
+              if constexpr (row == 0) out[q][c][j] = cmul(v[c][j], bundle); else out[q][c][j] = cfma(v[c][j], bundle, out[q][c][j]);
+            });
+          });
+          DCTFHE_SCHED_BARRIER();
+        });
+        tick.template at<5>();                            // phase 5: the products with the key of one gadget row
+      });
+    });
+
+    // L2 warm-up (see pbs_thread): straight-line, one dword per 128-byte line, PBS_PF_DIST iterations ahead
+    {
+      uint32_t acc_pf = 0;
+      static_for<0, PF_ROUNDS>([&](auto Rr) { acc_pf ^= *reinterpret_cast<const uint32_t*>(pf_ptr + (size_t)decltype(Rr)::value * T * 128); });
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" ::"v"(acc_pf));        // the touches only have to be issued
+#else
+      pf_dump[t] = acc_pf;
+#endif
+      pf_ptr += pf_step;
+    }
+    tick.template at<5>();
+
+    static_for<0, K + 1>([&](auto Q) {
+      constexpr int q = decltype(Q)::value;
+      fft_inverse_n<G::LOGM, P, 2>(out[q], t, tw, twist, exch, sync, wsync, tick);      // phases 6 - 10
+      static_for<0, 2>([&](auto Cc) {
+        constexpr int c = decltype(Cc)::value;
+        static_for<0, P>([&](auto J) {
+          constexpr int j = decltype(J)::value;
+          if constexpr (q < NL) {
+            acc_add(accl[(c * NL + q) * N + t + T * j], out[q][c][j].re);
+            acc_add(accl[(c * NL + q) * N + t + T * (P + j)], out[q][c][j].im);
+          } else {
+            acc_add(acc[c][q][j], out[q][c][j].re);
+            acc_add(acc[c][q][P + j], out[q][c][j].im);
+          }
+        });
+      });
+    });
+    tick.template at<11>();                               // phase 11: last inverse pass, accumulator update
+  }
+
+#if defined(__HIP_DEVICE_COMPILE__) && defined(DCTFHE_PHASE_TIMERS)
+  tick.template at<0>();
+  if (blockIdx.x == DCTFHE_PHASE_TIMERS && (threadIdx.x & 63) == 0)
+    for (int k = 0; k < 12; k++) dctfhe_phase_ticks[(threadIdx.x >> 6) * 12 + k] = tick.acc[k];
+#endif
+  // sample extract (coefficient 0) straight into the output LWE ciphertexts
+  static_for<0, 2>([&](auto Cc) {
+    constexpr int c = decltype(Cc)::value;
+    const pbs_args& B = A2[c];
+    uint64_t* o = B.out;
+    static_for<0, K>([&](auto Pp) {
+      constexpr int p = decltype(Pp)::value;
+      static_for<0, 2 * P>([&](auto R) {
+        constexpr int r = decltype(R)::value;
+        const int cf = t + T * r;
+        const int dst = p * N + (cf == 0 ? 0 : N - cf);
+        uint64_t av;
+        if constexpr (p < NL) av = acc_wide(accl[(c * NL + p) * N + cf]); else av = acc_wide(acc[c][p][r]);
+        const uint64_t v = (cf == 0) ? av : (uint64_t)0 - av;
+        if (B.accumulate) o[dst] += v; else o[dst] = v;
+      });
+    });
+    if (!B.accumulate)
+      for (int j = K * N + t; j < B.D_out; j += T) o[j] = 0;
+    if (t == 0) {
+      if (B.accumulate) o[B.D_out] += acc_wide(acc[c][K][0]) + B.body_add; else o[B.D_out] = acc_wide(acc[c][K][0]) + B.body_add;
+    }
+  });
+}
+
 // Forward transform of one standard-domain key polynomial into the device layout [j][t], with the 1/M of the inverse transform and
 // the 2^-64 that puts the accumulator updates in units of the whole torus (fft_core.h, f64_to_torus*) folded in -- both exact scalings.
 // Thread t of a T-thread group.

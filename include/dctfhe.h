@@ -119,6 +119,8 @@ int dctfhe_eval_keys_destroy(dctfhe_eval_keys* eval);
  * Entry j T + t (j < P, t < T) holds in-place position p = P t + j.  Its value is the polynomial, coefficients read as SIGNED 64-bit
  * integers, evaluated at e^{i pi (1 - 4k) / N} and multiplied by 2^-64 / M, where k = spectrum_freq(p) (csrc/fft_core.h): with
  * W_i = prod_{j > i} R_j, digit (p / W_i) mod R_i of the position is frequency digit k_i of weight R_0 ... R_{i-1}.
+ * (The blob's order is one rule for every shape.  On the device the general two-bit tier at logN 11, l 3 keeps its key in the order of a
+ * transform with 4 points per thread; export and import permute its entries frequency for frequency.)
  * tests/key_material_ref.py restates the rule; tests/test_gpu_key_material.py holds every shape's key to a long-double transform. */
 int dctfhe_eval_keys_export(dctfhe_eval_keys* eval, void* buf, size_t capacity, size_t* size);
 /* import accepts both blob forms: the one above and the compressed one below (told apart by the magic). */

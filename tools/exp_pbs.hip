@@ -5,12 +5,18 @@
 #include <vector>
 #include "../dct-cryptonets_amd/csrc/kernels.h"
 using namespace dctfhe;
+#ifndef EXP_REPS
+#define EXP_REPS 1
+#endif
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 
-template <int LOGN, int K, int L, int P, int GR, int MB = 0>
+// DUO: pbs_kernel_duo, GR duos (two ciphertexts each) per workgroup
+template <int LOGN, int K, int L, int P, int GR, int MB = 0, bool DUO = false>
 void run(int n, int beta, size_t count, int D, int wrap = 0, int pf = 0) {
   using G = pbs_geom<LOGN, K, L, P, MB>;
+  static_assert(!DUO || MB == 1, "the duo is a two-bit form");
   // every case announces itself BEFORE it launches: a fault then names its case (profiles/r01_exp_two_bit_rotation.log did not)
+  if (DUO) printf("duo ");
   printf("case mb=%d pf=%d wrap=%d N=%d k=%d l=%d P=%d groups=%d n=%d count=%zu ...\n", MB, pf, wrap, 1 << LOGN, K, L, P, GR, n, count);
   fflush(stdout);
   if (pf != 0 && pf < 8) { printf("pf_parts must be 0 or >= 8 (kernel contract, pbs_core.h)\n"); return; }
@@ -36,18 +42,33 @@ void run(int n, int beta, size_t count, int D, int wrap = 0, int pf = 0) {
   CK(hipMemcpy(d_small, small.data(), small.size() * 8, hipMemcpyHostToDevice)); CK(hipMemcpy(d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
   pbs_launch a; a.cts_small = d_small; a.count = count; a.n = n; a.beta = beta; a.bsk = d_bsk; a.tw = d_tw; a.wtab = d_wtab; a.tables = d_tab; a.w = 4; a.table_idx = nullptr;
   a.hw = 1; a.nchan = 1; a.e_offset = 0; a.out = d_out; a.D_out = D; a.accumulate = 0; a.body_add = 0; a.dummy = d_dummy; a.bsk_wrap = wrap; a.pf_parts = pf;
-  const size_t lds = pbs_lds_bytes<LOGN, K, L, P, MB>(GR);
-  CK(hipFuncSetAttribute((const void*)pbs_kernel<LOGN, K, L, P, GR, MB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const unsigned grid = (unsigned)((count + GR - 1) / GR);
+  size_t lds; unsigned grid; const void* fn;
+  if constexpr (DUO) {
+    lds = pbs_duo_lds_bytes<LOGN, K, L, P>(GR); grid = (unsigned)((count + 2 * GR - 1) / (2 * GR)); fn = (const void*)pbs_kernel_duo<LOGN, K, L, P, GR>;
+  } else {
+    lds = pbs_lds_bytes<LOGN, K, L, P, MB>(GR); grid = (unsigned)((count + GR - 1) / GR); fn = (const void*)pbs_kernel<LOGN, K, L, P, GR, MB>;
+  }
+  CK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  auto launch = [&] {
+    if constexpr (DUO) hipLaunchKernelGGL((pbs_kernel_duo<LOGN, K, L, P, GR>), dim3(grid), dim3(G::T * GR), lds, 0, a);
+    else hipLaunchKernelGGL((pbs_kernel<LOGN, K, L, P, GR, MB>), dim3(grid), dim3(G::T * GR), lds, 0, a);
+  };
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  hipLaunchKernelGGL((pbs_kernel<LOGN, K, L, P, GR, MB>), dim3(grid), dim3(G::T * GR), lds, 0, a);
+  launch();
   CK(hipDeviceSynchronize());
-  hipEventRecord(e0);
-  hipLaunchKernelGGL((pbs_kernel<LOGN, K, L, P, GR, MB>), dim3(grid), dim3(G::T * GR), lds, 0, a);
-  hipEventRecord(e1); CK(hipEventSynchronize(e1));
-  float ms; hipEventElapsedTime(&ms, e0, e1);
+  // EXP_REPS timed launches after the warm-up one; the mean is reported
+  float ms = 0;
+  for (int rep = 0; rep < EXP_REPS; rep++) {
+    hipEventRecord(e0);
+    launch();
+    hipEventRecord(e1); CK(hipEventSynchronize(e1));
+    float one; hipEventElapsedTime(&one, e0, e1);
+    printf("  launch %d: %.2f ms\n", rep, one);
+    ms += one / EXP_REPS;
+  }
   const double fft = 5.0 * M * log2((double)M);
   const double fl = n * ((K + 1) * L * fft + (K + 1) * fft + (double)(K + 1) * (K + 1) * L * M * 8.0);
+  if (DUO) printf("duo ");
   printf("mb=%d pf=%d wrap=%d N=%5d k=%d l=%d P=%2d groups=%d threads=%4d lds=%6zu: %zu cts %.1f ms -> %.0f PBS/s, %.2f TFLOP/s\n", MB, pf, wrap, N, K, L, P, GR, G::T * GR, lds, count, ms,
          count / (ms * 1e-3), fl * count / (ms * 1e-3) / 1e12);
   fflush(stdout);

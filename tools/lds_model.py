@@ -55,6 +55,7 @@ SKEWS = {
     "idx + idx/8 + idx/64": lambda i: i + (i >> 3) + (i >> 6),
     "idx + 2*(idx/16)": lambda i: i + 2 * (i >> 4),
     "idx + idx/4": lambda i: i + (i >> 2),
+    "x4: idx ^ ((idx>>2)&3) ^ (((idx>>4)&3)<<2)  (P = 4, exchanges 2 and 3)": lambda i: i ^ ((i >> 2) & 3) ^ (((i >> 4) & 3) << 2),
 }
 
 

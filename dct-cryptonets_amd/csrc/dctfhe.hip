@@ -158,6 +158,14 @@ struct dctfhe_eval_keys {
 };
 using dctfhe_keys = dctfhe_eval_keys;   // the server-side code below says K for the evaluation keys
 
+// What a handle is bound to (include/dctfhe.h): keys and sessions to the CONTEXT they were made on -- the device code launches on the
+// handle's context's stream while the entry point copies and synchronises on the caller's, and nothing orders two contexts' streams --
+// a circuit to its DEVICE.  Every entry point that is given a context and a handle calls this before it allocates, copies or launches.
+static int bound_to(const char* who, const dctfhe_ctx* ctx, const dctfhe_ctx* made_on, const char* what) {
+  if (ctx != made_on) return fail("%s: the %s belongs to another context than the one the call names", who, what);
+  return 0;
+}
+
 // a convolution's weights as the i8 MFMA kernel wants them: [Cout padded to 64][K padded to 32] K-contiguous, and per k the
 // input plane offset and the tap displacement (kernels.h k_conv2d_mfma)
 struct ConvPack {
@@ -205,12 +213,13 @@ static int build_conv_packs(const std::vector<const int8_t*>& w, const std::vect
 
 struct dctfhe_circuit : CircuitPlan {      // tensors, ops (one decoded SiteOp per record), input / output tensor
   dctfhe_ctx* ctx = nullptr;
+  int device = 0;                // a circuit belongs to a device, not to a context: its payload is uploaded once and read-only afterwards
   std::vector<DevBuf> d_payload; // per op, device copy of its payload (weights / tables)
   std::vector<DevBuf> d_split;   // per op: the half tables [S | Dt] of a parity-split look-up, each i64 [ntab][2^(w-1)] (empty for other ops)
   std::vector<ConvPack> conv;    // per op: the matrix-core form of a convolution's weights (empty for other ops)
   DevBuf conv_slab;              // ... all of them in one allocation, made when the first encrypted session is created
   std::vector<std::vector<int8_t>> conv_w;          // host copies of the convolution weights until then
-  ~dctfhe_circuit() { if (ctx) hipSetDevice(ctx->device); }
+  ~dctfhe_circuit() { if (ctx) hipSetDevice(device); }
 };
 
 // ---- max pool (OP_MAXPOOL): separable passes, rows then columns; each pass a log-depth tree of pairwise maxima
@@ -419,7 +428,11 @@ struct dctfhe_session {
   std::vector<std::unique_ptr<PoolPlan>> pool_last;
   size_t budget_bytes = 0, planned_bytes = 0, undivided_bytes = 0;
   std::vector<int> circ_heights() const { std::vector<int> h; for (const SlabGroup& G : circ->groups) h.push_back(G.channels); return h; }      // the undivided heights
-  void wipe_audit_key() { if (d_audit_key.p) hipMemset(d_audit_key.p, 0, d_audit_key.bytes); }      // the secret does not outlive the audit
+  void wipe_audit_key() {      // the secret does not outlive the audit: cleared on the context's stream, and done before the buffer is freed
+    if (!d_audit_key.p) return;
+    hipMemsetAsync(d_audit_key.p, 0, d_audit_key.bytes, ctx->stream);
+    hipStreamSynchronize(ctx->stream);
+  }
   void audit_off() {
     wipe_audit_key();
     d_audit_key.reset(); d_audit.reset();
@@ -494,12 +507,12 @@ static int tier_ppt(const dctfhe_tier& t) {
 // per process (a process with contexts on two GPUs would have failed on the second at every launch above 64 KB of LDS)
 #define SET_LDS_ATTR(kernel, bytes)                                                                  \
   do {                                                                                               \
-    static uint64_t done_mask = 0;                                                                   \
+    static std::atomic<uint64_t> done_mask{0};      /* contexts of several host threads launch through one call site */ \
     int dev_ = 0;                                                                                    \
     HIPCHK(hipGetDevice(&dev_));                                                                     \
-    if (dev_ < 0 || dev_ >= 64 || !((done_mask >> dev_) & 1)) {                                      \
+    if (dev_ < 0 || dev_ >= 64 || !((done_mask.load() >> dev_) & 1)) {                               \
       HIPCHK(hipFuncSetAttribute((const void*)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))); \
-      if (dev_ >= 0 && dev_ < 64) done_mask |= 1ull << dev_;                                         \
+      if (dev_ >= 0 && dev_ < 64) done_mask.fetch_or(1ull << dev_);                                  \
     }                                                                                                \
   } while (0)
 
@@ -1189,6 +1202,7 @@ extern "C" int dctfhe_rng_device(dctfhe_ctx* ctx, const uint8_t* key32, uint64_t
 // rows of `dim` mask words + body, input_dim <= dim <= D
 extern "C" int dctfhe_encrypt_rows(dctfhe_ctx* ctx, dctfhe_client_key* C, const uint64_t* phases, size_t count, int dim, uint64_t* cts) {
   if (!ctx || !C || (count && (!phases || !cts))) return fail("dctfhe_encrypt: null argument");
+  CHK(bound_to("dctfhe_encrypt", ctx, C->ctx, "client key"));
   const int D = C->p.D, dim_eff = C->p.input_dim > 0 ? C->p.input_dim : D;
   if (dim < dim_eff || dim > D) return fail("dctfhe_encrypt: rows of %d mask words; these parameters mask %d and the key has %d", dim, dim_eff, D);
   if (count == 0) return 0;
@@ -1227,6 +1241,7 @@ extern "C" int dctfhe_client_key_set_encrypt_nonce(dctfhe_client_key* C, const u
 }
 extern "C" int dctfhe_decrypt_rows(dctfhe_ctx* ctx, dctfhe_client_key* C, const uint64_t* cts, size_t count, int dim, uint64_t* phases) {
   if (!ctx || !C || (count && (!phases || !cts))) return fail("dctfhe_decrypt: null argument");
+  CHK(bound_to("dctfhe_decrypt", ctx, C->ctx, "client key"));
   if (dim < 0 || dim > C->p.D) return fail("dctfhe_decrypt: rows of %d mask words, the key has %d", dim, C->p.D);
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(ctx->device));
@@ -1248,6 +1263,7 @@ extern "C" int dctfhe_decrypt(dctfhe_ctx* ctx, dctfhe_client_key* C, const uint6
 // packed results (dctfhe_keyswitch_pack, dctfhe_session_download_packed): rows of n + 1 u16 under the first n bits of the small key
 extern "C" int dctfhe_decrypt_packed(dctfhe_ctx* ctx, dctfhe_client_key* C, int n, const uint16_t* rows, size_t count, uint64_t* phases) {
   if (!ctx || !C || (count && (!rows || !phases))) return fail("dctfhe_decrypt_packed: null argument");
+  CHK(bound_to("dctfhe_decrypt_packed", ctx, C->ctx, "client key"));
   if (n < 1 || n > C->p.n_max) return fail("dctfhe_decrypt_packed: rows of %d mask words, the small key has %d", n, C->p.n_max);
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(ctx->device));
@@ -1268,6 +1284,7 @@ extern "C" int dctfhe_decrypt_packed(dctfhe_ctx* ctx, dctfhe_client_key* C, int 
 extern "C" int dctfhe_encrypt_seeded(dctfhe_ctx* ctx, dctfhe_client_key* C, const uint64_t* phases, size_t count, uint8_t* mask_key,
                                      uint64_t* stream_out, uint64_t* bodies) {
   if (!ctx || !C || !mask_key || !stream_out || (count && (!phases || !bodies))) return fail("dctfhe_encrypt_seeded: null argument");
+  CHK(bound_to("dctfhe_encrypt_seeded", ctx, C->ctx, "client key"));
   const int D = C->p.D, dim_eff = C->p.input_dim > 0 ? C->p.input_dim : D;
   key_to_bytes(C->enc_pub, mask_key);
   if (count == 0) { *stream_out = 0; return 0; }    // nothing drawn: the counter stays, as in dctfhe_encrypt_rows
@@ -1650,6 +1667,7 @@ static int clear_max_pool(hipStream_t st, const uint64_t* in, uint64_t* mid, uin
 extern "C" int dctfhe_keyswitch_prefix(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, int shift, int deff,
                                        uint64_t* cts_small) {
   if (!ctx || !K) return fail("dctfhe_keyswitch: null handle");
+  CHK(bound_to("dctfhe_keyswitch", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   if (deff < 0 || deff > K->p.D) return fail("deff out of range");
   if (shift < 0 || shift > 63) return fail("shift out of range");
@@ -1694,6 +1712,7 @@ static int dev_keyswitch_pack(dctfhe_keys* K, int tier, const uint64_t* d_rows, 
 extern "C" int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, int dim, int deff,
                                      uint16_t* rows) {
   if (!ctx || !K || (count && (!cts || !rows))) return fail("dctfhe_keyswitch_pack: null argument");
+  CHK(bound_to("dctfhe_keyswitch_pack", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("dctfhe_keyswitch_pack: tier %d out of range (%d tiers)", tier, K->p.n_tiers);
   if (dim < 1 || dim > K->p.D) return fail("dctfhe_keyswitch_pack: rows of %d mask words, the key has %d", dim, K->p.D);
   if (deff < 0 || deff > dim) return fail("dctfhe_keyswitch_pack: effective dimension %d outside [0, dim = %d]", deff, dim);
@@ -1844,6 +1863,7 @@ extern "C" int dctfhe_ring_pack(dctfhe_ctx* ctx, dctfhe_pack_key* K, const uint6
 // CLIENT: phases of ring-packed results under the first 2^logN bits of the big key
 extern "C" int dctfhe_decrypt_ring(dctfhe_ctx* ctx, dctfhe_client_key* C, int logN, const uint16_t* words, size_t count, uint64_t* phases) {
   if (!ctx || !C || (count && (!words || !phases))) return fail("dctfhe_decrypt_ring: null argument");
+  CHK(bound_to("dctfhe_decrypt_ring", ctx, C->ctx, "client key"));
   if (logN < 5 || logN > 12) return fail("dctfhe_decrypt_ring: ring 2^%d outside 2^5 .. 2^12", logN);
   if ((1 << logN) > C->p.D) return fail("dctfhe_decrypt_ring: the ring key is a prefix of the big key: N_p = %d > D = %d", 1 << logN, C->p.D);
   if (count == 0) return 0;
@@ -2046,6 +2066,7 @@ extern "C" int dctfhe_ring_extract(dctfhe_ctx* ctx, int logN, const uint64_t* wo
 // the centred mod switch on host buffers (the scheduler applies it between every key switch and its bootstrap)
 extern "C" int dctfhe_modswitch_center(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, uint64_t* cts_small, size_t count) {
   if (!ctx || !K || (count && !cts_small)) return fail("dctfhe_modswitch_center: null argument");
+  CHK(bound_to("dctfhe_modswitch_center", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(ctx->device));
@@ -2060,6 +2081,7 @@ extern "C" int dctfhe_modswitch_center(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
 extern "C" int dctfhe_pbs(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts_small, size_t count, const int64_t* tables, int ntab,
                           int w, const int32_t* table_idx, uint64_t* cts_out) {
   if (!ctx || !K) return fail("dctfhe_pbs: null handle");
+  CHK(bound_to("dctfhe_pbs", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   if (ntab < 1 || w < 0) return fail("dctfhe_pbs: need at least one table and w >= 0");
   if (count == 0) return 0;
@@ -2087,6 +2109,7 @@ extern "C" int dctfhe_pbs(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const 
 extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int bit_tier, int tab_tier, int tab_tier2, const uint64_t* cts, size_t count,
                                       int p, int r, const int64_t* tables, int ntab, int w, const int32_t* table_idx, uint64_t* cts_out) {
   if (!ctx || !K) return fail("dctfhe_round_lut: null handle");
+  CHK(bound_to("dctfhe_round_lut", ctx, K->ctx, "evaluation keys"));
   const bool split = tab_tier2 >= 0;
   if (tab_tier < 0 || tab_tier >= K->p.n_tiers || tab_tier2 >= K->p.n_tiers || ((r > 0 || split) && (bit_tier < 0 || bit_tier >= K->p.n_tiers)))
     return fail("tier out of range");
@@ -2249,6 +2272,7 @@ extern "C" int dctfhe_sum_pool_rows(dctfhe_ctx* ctx, const uint64_t* in, int dim
 extern "C" int dctfhe_keyswitch_diff(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* cts, size_t count, const int32_t* ia,
                                      const int32_t* ib, int shift, uint64_t body_add, int deff, uint64_t* cts_small) {
   if (!ctx || !K || (count && (!cts || !ia || !ib || !cts_small))) return fail("dctfhe_keyswitch_diff: null argument");
+  CHK(bound_to("dctfhe_keyswitch_diff", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   if (deff < 0 || deff > K->p.D) return fail("deff out of range");
   if (shift < 0 || shift > 63) return fail("shift out of range");
@@ -2279,6 +2303,7 @@ extern "C" int dctfhe_pbs_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, c
                                const int32_t* table_idx, int hw, int nchan, size_t e_offset, uint64_t* rows_io, size_t n_rows, size_t row0, int dim_out,
                                int accumulate, uint64_t body_add) {
   if (!ctx || !K) return fail("dctfhe_pbs_rows: null handle");
+  CHK(bound_to("dctfhe_pbs_rows", ctx, K->ctx, "evaluation keys"));
   if (!tables || !rows_io || (count && !cts_small)) return fail("dctfhe_pbs_rows: null argument");
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   if (ntab < 1 || w < 0) return fail("dctfhe_pbs_rows: need at least one table and w >= 0");
@@ -2313,6 +2338,7 @@ extern "C" int dctfhe_pbs_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, c
 extern "C" int dctfhe_keyswitch_sum(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* rows_a, int dim_a, const uint64_t* rows_b, int dim_b,
                                     size_t count, int shift, uint64_t body_add, int deff, uint64_t* cts_small) {
   if (!ctx || !K || (count && (!rows_a || !rows_b || !cts_small))) return fail("dctfhe_keyswitch_sum: null argument");
+  CHK(bound_to("dctfhe_keyswitch_sum", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   if (dim_a < 1 || dim_a > K->p.D) return fail("dctfhe_keyswitch_sum: rows of %d mask words, the key has %d", dim_a, K->p.D);
   if (dim_b < 0 || dim_b > (1 << 16)) return fail("dctfhe_keyswitch_sum: second rows of %d mask words (0 .. 2^16)", dim_b);
@@ -2382,6 +2408,7 @@ extern "C" int dctfhe_gather_rows(dctfhe_ctx* ctx, const uint64_t* src, int dim_
 extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const uint64_t* in, int dim_in, int deff_in, int batch, int C,
                                     int H, int W, int k, int s, int p, int p_d, const int64_t* table, int dim_o, uint64_t* out) {
   if (!ctx || !in || !out) return fail("dctfhe_max_pool_rows: null argument");
+  if (K) CHK(bound_to("dctfhe_max_pool_rows", ctx, K->ctx, "evaluation keys"));
   if (batch < 1 || C < 1 || H < 1 || W < 1 || k < 1 || k > 32 || s < 1 || p < 0 || 2 * p > k || H + 2 * p < k || W + 2 * p < k)
     return fail("dctfhe_max_pool_rows: bad geometry (1 <= k <= 32, s >= 1, 0 <= p <= k/2, window inside the padded input)");
   if (p_d < 2 || p_d > 16) return fail("dctfhe_max_pool_rows: p_d %d out of range", p_d);
@@ -2472,7 +2499,7 @@ extern "C" int dctfhe_circuit_load(dctfhe_ctx* ctx, const void* blob, size_t siz
   std::unique_ptr<dctfhe_circuit> c(new dctfhe_circuit);
   CHK(parse_circuit(blob, size, c.get()));
   HIPCHK(hipSetDevice(ctx->device));
-  c->ctx = ctx;
+  c->ctx = ctx; c->device = ctx->device;
   c->d_payload.resize(c->ops.size());
   c->d_split.resize(c->ops.size());
   c->conv.assign(c->ops.size(), ConvPack{});
@@ -2939,7 +2966,10 @@ extern "C" int dctfhe_session_memory_plan(dctfhe_session* s, dctfhe_mem_plan* ou
 }
 
 extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctfhe_keys* keys, int batch, dctfhe_session** out) {
+  if (!ctx || !circ || !out) return fail("dctfhe_session_create: null argument");
   if (batch < 1) return fail("batch must be >= 1");
+  if (keys) CHK(bound_to("dctfhe_session_create", ctx, keys->ctx, "evaluation keys"));
+  if (circ->device != ctx->device) return fail("dctfhe_session_create: the circuit was loaded on device %d, the context runs on device %d", circ->device, ctx->device);
   HIPCHK(hipSetDevice(ctx->device));
   std::unique_ptr<dctfhe_session> s(new dctfhe_session);
   s->ctx = ctx; s->circ = circ; s->keys = keys; s->batch = batch;
@@ -2948,7 +2978,8 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   if (keys) CHK(session_conv_packs(s.get()));
   CHK(session_plan_buffers(s.get()));
   HIPCHK(s->d_overflow.alloc(sizeof(int)));
-  HIPCHK(hipMemset(s->d_overflow.p, 0, sizeof(int)));
+  HIPCHK(hipMemsetAsync(s->d_overflow.p, 0, sizeof(int), ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));      // the first run may come on another stream (dctfhe_ctx_set_stream)
   s->whole.assign(circ->tensors.size(), 1);
   s->marked.assign(circ->tensors.size(), {});
   s->pool_pairs_run.assign(circ->ops.size(), 0);
@@ -3173,7 +3204,7 @@ extern "C" int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* C)
   if (s->parts > 1) return fail("dctfhe_session_set_audit: this session is part %d of %d; the margin audit stays unsharded", s->part, s->parts);
   if (s->budget_bytes) return fail("dctfhe_session_set_audit: the session has a memory budget (%zu bytes); the margin audit runs undivided", s->budget_bytes);
   const dctfhe_params &P = s->keys->p, &Q = C->p;
-  if (C->ctx->device != s->ctx->device) return fail("dctfhe_session_set_audit: the client key lives on device %d, the session on %d", C->ctx->device, s->ctx->device);
+  CHK(bound_to("dctfhe_session_set_audit", s->ctx, C->ctx, "client key"));
   if (P.D != Q.D || P.n_max != Q.n_max || P.n_tiers != Q.n_tiers)
     return fail("dctfhe_session_set_audit: the client key (D = %d, n_max = %d, %d tiers) is of another parameter set than the session's keys (D = %d, n_max = %d, %d tiers)",
                 Q.D, Q.n_max, Q.n_tiers, P.D, P.n_max, P.n_tiers);
@@ -3202,10 +3233,13 @@ extern "C" int dctfhe_session_set_audit(dctfhe_session* s, dctfhe_client_key* C)
   DevBuf key, slot;
   HIPCHK(key.alloc((size_t)P.n_max));
   HIPCHK(slot.alloc(std::max<size_t>(1, slots.size()) * sizeof(margin_slot)));
-  HIPCHK(hipMemset(slot.p, 0, slot.bytes));
-  const hipError_t e = hipMemcpy(key.p, C->s(), key.bytes, hipMemcpyDeviceToDevice);
+  hipStream_t st = s->ctx->stream;
+  HIPCHK(hipMemsetAsync(slot.p, 0, slot.bytes, st));
+  hipError_t e = hipMemcpyAsync(key.p, C->s(), key.bytes, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {
-    hipMemset(key.p, 0, key.bytes);
+    hipMemsetAsync(key.p, 0, key.bytes, st);
+    hipStreamSynchronize(st);
     return fail("dctfhe_session_set_audit: copy of the small key -> %s", hipGetErrorString(e));
   }
   s->d_audit_key = std::move(key); s->d_audit = std::move(slot);
@@ -3613,7 +3647,11 @@ static int session_run_ops(dctfhe_session* s, int first_op, int end_op, dctfhe_t
   if (!K) {
     int ov = 0;
     HIPCHK(hipMemcpy(&ov, s->d_overflow.p, sizeof ov, hipMemcpyDeviceToHost));
-    if (ov) { HIPCHK(hipMemset(s->d_overflow.p, 0, sizeof(int))); return fail("clear run: a message left its padded range (calibration too tight)"); }
+    if (ov) {      // cleared on the run's stream and done before the caller is told: the next run starts from a clean flag on whatever stream it comes
+      HIPCHK(hipMemsetAsync(s->d_overflow.p, 0, sizeof(int), st));
+      HIPCHK(hipStreamSynchronize(st));
+      return fail("clear run: a message left its padded range (calibration too tight)");
+    }
   }
   return 0;
 }
@@ -3660,6 +3698,7 @@ extern "C" int dctfhe_margin_probe_host(const uint8_t* small_key, int n, int log
 extern "C" int dctfhe_margin_probe(dctfhe_ctx* ctx, dctfhe_client_key* C, int tier, const uint64_t* cts_small, size_t count, int table_bits, int32_t* err,
                                    dctfhe_margin_stats* stats) {
   if (!ctx || !C || (count && !cts_small)) return fail("dctfhe_margin_probe: null argument");
+  CHK(bound_to("dctfhe_margin_probe", ctx, C->ctx, "client key"));
   if (tier < 0 || tier >= C->p.n_tiers) return fail("dctfhe_margin_probe: tier %d out of range (%d tiers)", tier, C->p.n_tiers);
   const dctfhe_tier& t = C->p.tiers[tier];
   if (table_bits < 0 || t.logN - table_bits < 1)
@@ -3704,6 +3743,8 @@ extern "C" int dctfhe_fp64_peak(dctfhe_ctx* ctx, double* tflops) {
 }
 
 extern "C" int dctfhe_bench_pbs(dctfhe_ctx* ctx, dctfhe_keys* K, int tier, size_t count, int reps, double* ms_per_launch) {
+  if (!ctx || !K || !ms_per_launch) return fail("dctfhe_bench_pbs: null argument");
+  CHK(bound_to("dctfhe_bench_pbs", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
   HIPCHK(hipSetDevice(ctx->device));
   const dctfhe_tier& t = K->p.tiers[tier];

@@ -52,8 +52,11 @@ class Context:
         self.h = C.c_void_p()
         check(self.L.dctfhe_ctx_create(device, C.byref(self.h)))
 
-    def set_stream(self, stream_ptr):
-        check(self.L.dctfhe_ctx_set_stream(self.h, C.c_void_p(stream_ptr)))
+    def set_stream(self, stream):
+        """issue this context's work to `stream`: a raw HIP stream handle (int) or a torch.cuda.Stream (its .cuda_stream is taken); None, 0
+        or torch's default stream (the null stream) puts the context back on its own (include/dctfhe.h dctfhe_ctx_set_stream)"""
+        stream = getattr(stream, "cuda_stream", stream)
+        check(self.L.dctfhe_ctx_set_stream(self.h, C.c_void_p(stream or None)))
 
     def synchronize(self):
         check(self.L.dctfhe_ctx_synchronize(self.h))

@@ -18,7 +18,20 @@
  * the stub.  Conventions: opaque handles, int status (0 = OK, <0 = error, text through
  * dctfhe_last_error()), caller-allocated host buffers, no exceptions across the boundary.
  * A dctfhe_ctx is bound to one GPU and one host thread (one per rank); distinct contexts are
- * independent.  Ciphertext layout, encodings and key formats: DESIGN.md section 3.
+ * independent: each has a stream of its own, and nothing orders the streams of two contexts.
+ *
+ * WHAT A HANDLE IS BOUND TO.  Client keys, evaluation keys, packing keys, public keys and sessions belong to
+ * the CONTEXT they were made on: their work is issued to that context's stream.  Every entry point that takes
+ * a dctfhe_ctx together with such a handle refuses a handle of another context (the message says "context"),
+ * dctfhe_session_create refuses evaluation keys of another context and dctfhe_session_set_audit a client key
+ * of another context than the session's.  A refused call has allocated, copied and launched nothing: every
+ * handle stays usable and the caller's buffers are untouched.  A CIRCUIT belongs to a DEVICE: its payload is
+ * uploaded once by dctfhe_circuit_load and only read afterwards, so sessions of several contexts of that
+ * device may share one circuit handle (dctfhe_session_copy_rows expects it); dctfhe_session_create refuses a
+ * circuit of another device (the message says "device").  Key material is a pure function of (params, seed):
+ * a second context gets the same keys from the same seed.  One context, and the handles made on it, are used
+ * by one host thread at a time; two threads with a context each run side by side, and dctfhe_last_error() is
+ * per thread.  Ciphertext layout, encodings and key formats: DESIGN.md section 3.
  */
 #ifndef DCTFHE_H
 #define DCTFHE_H
@@ -86,7 +99,15 @@ int dctfhe_version(void);
 
 int dctfhe_ctx_create(int device_id, dctfhe_ctx** out);
 int dctfhe_ctx_destroy(dctfhe_ctx* ctx);
-/* use an existing HIP stream (e.g. torch's current stream) instead of the context's own; NULL resets */
+/* Issue the context's work to an existing HIP stream of the context's device -- a stream the caller made, e.g. a torch.cuda.Stream()
+ * (its .cuda_stream) -- instead of the context's own; NULL resets to the context's own stream.  Torch's DEFAULT stream is the null stream,
+ * whose handle is NULL: passing it resets the context, it does not put the library on the null stream.
+ * Guarantee: every copy, fill and kernel of a later call on this context or on a handle made on it goes to that stream (a handle follows
+ * its context's stream at call time, whenever it was made), so the library's work runs after whatever the caller had enqueued on the stream
+ * before the call, with no host synchronisation in between; dctfhe_ctx_synchronize waits for the stream that is set.
+ * Not guaranteed: asynchrony.  Every call still returns only when its own work is done (dctfhe_session_run is synchronous), and allocating
+ * or freeing device memory inside a call may wait for ALL streams of the device.  Blocking copies of host operands into buffers the call has
+ * just allocated do not wait for the stream; nothing reads them before the call's own launches.  The stream must outlive its use here. */
 int dctfhe_ctx_set_stream(dctfhe_ctx* ctx, void* hip_stream);
 int dctfhe_ctx_synchronize(dctfhe_ctx* ctx);
 

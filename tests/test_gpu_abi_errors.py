@@ -127,3 +127,54 @@ def test_circuit_and_session_errors(kit):
         _fails(L, L.dctfhe_session_set_noise(clear.h, 1, sg.ctypes.data_as(C.c_void_p), 3), "one sigma per op")
     finally:
         clear.close()
+
+
+def test_handles_of_another_context_are_refused(kit):
+    """keys and sessions belong to the context they were made on (include/dctfhe.h): a call that names another context is refused before
+    it allocates, copies or launches anything.  tests/test_gpu_contexts_streams.py has the case per entry point; here the ABI's answer."""
+    from dctfhe.engine import Context, Session, device_bytes_live
+    ctx, keys, circ, compiled, ps = kit
+    L = ctx.L
+    D = keys.D
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    cts = keys.encrypt(np.arange(3, dtype=np.uint64) << np.uint64(58))
+    small = np.zeros((3, ps.tiers[0].n + 1), np.uint64)
+    big = np.zeros((3, D + 1), np.uint64)
+    ph = np.zeros(3, np.uint64)
+    tab = np.zeros(16, np.int64)
+    h = C.c_void_p()
+    other = Context(0)
+    sess = Session(ctx, circ, keys, 1)
+    try:
+        held = device_bytes_live()
+        _fails(L, L.dctfhe_encrypt(other.h, keys.client.h, p(ph), 3, p(big)), "context")
+        _fails(L, L.dctfhe_decrypt(other.h, keys.client.h, p(cts), 3, p(ph)), "context")
+        _fails(L, L.dctfhe_keyswitch(other.h, keys.eval.h, 0, p(cts), 3, 0, p(small)), "context")
+        _fails(L, L.dctfhe_modswitch_center(other.h, keys.eval.h, 0, p(small), 3), "context")
+        _fails(L, L.dctfhe_pbs(other.h, keys.eval.h, 0, p(small), 3, p(tab), 1, 4, None, p(big)), "context")
+        _fails(L, L.dctfhe_round_lut(other.h, keys.eval.h, 1, 0, p(cts), 3, 8, 4, p(tab), 1, 4, None, p(big)), "context")
+        _fails(L, L.dctfhe_keyswitch_pack(other.h, keys.eval.h, 0, p(cts), 3, D, 0, p(small)), "context")
+        _fails(L, L.dctfhe_margin_probe(other.h, keys.client.h, 0, p(small), 3, 4, None, None), "context")
+        _fails(L, L.dctfhe_session_create(other.h, circ.h, keys.eval.h, 1, C.byref(h)), "context")
+        assert h.value is None and not big.any() and not small.any() and not ph.any()
+        assert device_bytes_live() == held
+        # a client key of another context at the margin audit; the session's own is accepted
+        from dctfhe import params as P
+        from dctfhe.engine import ClientKey
+        k2 = ClientKey(other, P.to_c_params(ps), seed=2)
+        try:
+            _fails(L, L.dctfhe_session_set_audit(sess.h, k2.h), "context")
+            sess.set_audit(keys)
+            sess.set_audit(None)
+        finally:
+            k2.close()
+        # a circuit is bound to its device, not to a context: a clear-mode session of the other context takes it
+        clear = Session(other, circ, None, 1)
+        clear.close()
+        assert device_bytes_live() == held
+        # the handles still work after all that
+        assert np.array_equal((keys.decrypt(cts) + np.uint64(1 << 56)) >> np.uint64(57), (np.arange(3, dtype=np.uint64) << np.uint64(1)))
+    finally:
+        sess.close()
+        other.close()
+

@@ -358,34 +358,66 @@ struct EvalBlobHeader { uint32_t magic, version; uint64_t total_bytes; dctfhe_pa
 static constexpr uint32_t EVAL_CBLOB_MAGIC = 0x43564544u /* 'DEVC' */, EVAL_CBLOB_VERSION = 1;
 static size_t tier_bsk_blocks(const dctfhe_tier& t) { return (size_t)(t.unroll == 2 ? 3 * t.n / 2 : t.n); }
 static size_t tier_bsk_body_words(const dctfhe_tier& t) { return tier_bsk_blocks(t) * (size_t)(t.k + 1) * t.l << t.logN; }
-static size_t eval_cblob_size(const dctfhe_params& p) {
-  size_t n = sizeof(EvalBlobHeader) + 32;
+// tier selections (include/dctfhe.h TIER SELECTIONS): the rules of dctfhe.hip closed_selection / eval_cblob_size, restated for the host
+static constexpr uint32_t EVAL_CBLOB_VERSION_PRUNED = 2;      // the masks follow pub[32]
+static int ksk_owner(const dctfhe_params& p, int tier) {
+  while (p.tiers[tier].ksk_share >= 0) tier = p.tiers[tier].ksk_share;
+  return tier;
+}
+static dctfhe_key_tiers key_tiers_full(const dctfhe_params& p) {
+  dctfhe_key_tiers s{0, 0};
+  for (int ti = 0; ti < p.n_tiers; ti++) {
+    s.bsk |= 1u << ti;
+    if (p.tiers[ti].ksk_share < 0) s.ksk |= 1u << ti;
+  }
+  return s;
+}
+static int closed_selection(const char* who, const dctfhe_params& p, const dctfhe_key_tiers* tiers, dctfhe_key_tiers* sel) {
+  if (!tiers) { *sel = key_tiers_full(p); return 0; }
+  *sel = *tiers;
+  if ((sel->bsk | sel->ksk) & (~0u << p.n_tiers))
+    return fail("%s: the tier selection names a tier at or beyond n_tiers = %d (bsk 0x%x, ksk 0x%x)", who, p.n_tiers, sel->bsk, sel->ksk);
+  for (int ti = 0; ti < p.n_tiers; ti++) {
+    if (((sel->ksk >> ti) & 1u) && p.tiers[ti].ksk_share >= 0)
+      return fail("%s: the tier selection asks for a key-switch key of tier %d, which has none of its own (it shares tier %d's)", who, ti, p.tiers[ti].ksk_share);
+    if ((sel->bsk >> ti) & 1u) sel->ksk |= 1u << ksk_owner(p, ti);
+  }
+  return 0;
+}
+static size_t eval_cblob_size(const dctfhe_params& p, const dctfhe_key_tiers& s) {
+  const dctfhe_key_tiers f = key_tiers_full(p);
+  size_t n = sizeof(EvalBlobHeader) + 32 + ((s.bsk == f.bsk && s.ksk == f.ksk) ? 0 : sizeof(dctfhe_key_tiers));
   for (int ti = 0; ti < p.n_tiers; ti++) {
     const dctfhe_tier& t = p.tiers[ti];
-    if (t.ksk_share < 0) n += (size_t)p.D * t.lk * 8;
-    n += tier_bsk_body_words(t) * 8;
+    if ((s.ksk >> ti) & 1u) n += (size_t)p.D * t.lk * 8;
+    if ((s.bsk >> ti) & 1u) n += tier_bsk_body_words(t) * 8;
   }
   return n;
 }
 
-extern "C" int dctfhe_host_eval_keys_export_compressed(dctfhe_host_client_key* C, void* buf, size_t capacity, size_t* size) {
+extern "C" int dctfhe_host_eval_keys_export_compressed_tiers(dctfhe_host_client_key* C, const dctfhe_key_tiers* tiers, void* buf, size_t capacity, size_t* size) {
   if (!C || !size) return fail("dctfhe_host_eval_keys_export_compressed: null argument");
   const dctfhe_params& P = C->p;
-  const size_t need = eval_cblob_size(P);
+  dctfhe_key_tiers sel;
+  if (closed_selection("dctfhe_host_eval_keys_export_compressed_tiers", P, tiers, &sel)) return -1;
+  const dctfhe_key_tiers all = key_tiers_full(P);
+  const bool full = sel.bsk == all.bsk && sel.ksk == all.ksk;
+  const size_t need = eval_cblob_size(P, sel);
   *size = need;
   if (!buf) return 0;                       // size query
   if (capacity < need) return fail("dctfhe_host_eval_keys_export_compressed: buffer of %zu bytes, %zu needed", capacity, need);
   return guarded("dctfhe_host_eval_keys_export_compressed", [&]() -> int {
     EvalBlobHeader h{};
-    h.magic = EVAL_CBLOB_MAGIC; h.version = EVAL_CBLOB_VERSION; h.total_bytes = need; h.params = P;
+    h.magic = EVAL_CBLOB_MAGIC; h.version = full ? EVAL_CBLOB_VERSION : EVAL_CBLOB_VERSION_PRUNED; h.total_bytes = need; h.params = P;
     char* q = (char*)buf;
     memcpy(q, &h, sizeof h); q += sizeof h;
     key_to_bytes(C->pub, (uint8_t*)q); q += 32;
+    if (!full) { memcpy(q, &sel, sizeof sel); q += sizeof sel; }
     const int nthr = omp_get_max_threads();
     const uint8_t *S = C->S.data(), *s = C->s.data();
     for (int ti = 0; ti < P.n_tiers; ti++) {
       const dctfhe_tier& t = P.tiers[ti];
-      if (t.ksk_share < 0) {      // k_ksk_gen, the body column: row = i lk + lev
+      if ((sel.ksk >> ti) & 1u) {      // k_ksk_gen, the body column: row = i lk + lev
         const int64_t rows = (int64_t)P.D * t.lk;
         const int n = t.n, drop = 64 - 8 * ks_limbs(t.lk, t.betak);
         const uint64_t mask = drop ? ~0ULL << drop : ~0ULL, half = drop ? 1ULL << (drop - 1) : 0;
@@ -406,6 +438,7 @@ extern "C" int dctfhe_host_eval_keys_export_compressed(dctfhe_host_client_key* C
         }
         q += (size_t)rows * 8;
       }
+      if (!((sel.bsk >> ti) & 1u)) continue;
       // k_bsk_gen_bodies: global row grow = block (k + 1) l + r, bodies [blocks (k + 1) l][N]
       const int N = 1 << t.logN, k = t.k, rows = (k + 1) * t.l;
       const int64_t nrow = (int64_t)tier_bsk_blocks(t) * rows;
@@ -438,6 +471,9 @@ extern "C" int dctfhe_host_eval_keys_export_compressed(dctfhe_host_client_key* C
     }
     return 0;
   });
+}
+extern "C" int dctfhe_host_eval_keys_export_compressed(dctfhe_host_client_key* C, void* buf, size_t capacity, size_t* size) {
+  return dctfhe_host_eval_keys_export_compressed_tiers(C, nullptr, buf, capacity, size);
 }
 
 // ------------------------------------------------------------------------------------------ packing key (ring-packed results)

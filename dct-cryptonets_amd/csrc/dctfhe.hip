@@ -153,6 +153,7 @@ struct dctfhe_eval_keys {
   dctfhe_params p{};
   KskKey ksk[DCTFHE_MAX_TIERS];  // per tier with a key-switch key of its own (ksk_share < 0)
   TierKeys tiers[DCTFHE_MAX_TIERS];
+  dctfhe_key_tiers sel{};        // which tiers' keys are held (closed; key_tiers_full: every one).  An absent key has no allocation at all
   DevBuf d_dummy;                // D+1 words, sink of padded bootstrap groups
   ~dctfhe_eval_keys() { if (ctx) hipSetDevice(ctx->device); }
 };
@@ -785,12 +786,117 @@ static int tier_bsk_chunk(const dctfhe_tier& t, int polys) {
   return std::max(1, (int)std::min(tier_bsk_blocks(t), ((size_t)64 << 20) / block_bytes));
 }
 
-// allocate every array of the evaluation keys and fill what depends on the parameters only (twiddles, root tables)
-static int eval_alloc(dctfhe_ctx* ctx, const dctfhe_params* params, std::unique_ptr<dctfhe_eval_keys>& E) {
+// ---- tier selections (include/dctfhe.h "TIER SELECTIONS"): host only ---------------------------------------
+// the tier whose key-switch key `tier` switches with: the end of its share chain
+static int ksk_owner(const dctfhe_params& p, int tier) {
+  while (p.tiers[tier].ksk_share >= 0) tier = p.tiers[tier].ksk_share;
+  return tier;
+}
+static dctfhe_key_tiers key_tiers_full(const dctfhe_params& p) {
+  dctfhe_key_tiers s{0, 0};
+  for (int ti = 0; ti < p.n_tiers; ti++) {
+    s.bsk |= 1u << ti;
+    if (p.tiers[ti].ksk_share < 0) s.ksk |= 1u << ti;
+  }
+  return s;
+}
+static bool key_tiers_is_full(const dctfhe_params& p, const dctfhe_key_tiers& s) {
+  const dctfhe_key_tiers f = key_tiers_full(p);
+  return s.bsk == f.bsk && s.ksk == f.ksk;
+}
+static bool has_bsk(const dctfhe_key_tiers& s, int tier) { return (s.bsk >> tier) & 1u; }
+static bool has_ksk(const dctfhe_key_tiers& s, int tier) { return (s.ksk >> tier) & 1u; }
+// what a selection must satisfy before anything is sized by it; `closed`: also that no owner is missing (what a blob must carry)
+static int key_tiers_check(const char* who, const dctfhe_params& p, const dctfhe_key_tiers& s, bool closed) {
+  const uint32_t beyond = p.n_tiers >= 32 ? 0u : ~0u << p.n_tiers;
+  if ((s.bsk | s.ksk) & beyond) return fail("%s: the tier selection names a tier at or beyond n_tiers = %d (bsk 0x%x, ksk 0x%x)", who, p.n_tiers, s.bsk, s.ksk);
+  for (int ti = 0; ti < p.n_tiers; ti++) {
+    if (has_ksk(s, ti) && p.tiers[ti].ksk_share >= 0)
+      return fail("%s: the tier selection asks for a key-switch key of tier %d, which has none of its own (it shares tier %d's)", who, ti, p.tiers[ti].ksk_share);
+    if (closed && has_bsk(s, ti) && !has_ksk(s, ksk_owner(p, ti)))
+      return fail("%s: the tier selection is not closed: tier %d bootstraps, the key-switch key of tier %d is not selected", who, ti, ksk_owner(p, ti));
+  }
+  return 0;
+}
+extern "C" int dctfhe_key_tiers_all(const dctfhe_params* params, dctfhe_key_tiers* out) {
+  if (!params || !out) return fail("dctfhe_key_tiers_all: null argument");
   CHK(check_params(params));
+  *out = key_tiers_full(*params);
+  return 0;
+}
+extern "C" int dctfhe_key_tiers_close(const dctfhe_params* params, dctfhe_key_tiers* io) {
+  if (!params || !io) return fail("dctfhe_key_tiers_close: null argument");
+  CHK(check_params(params));
+  CHK(key_tiers_check("dctfhe_key_tiers_close", *params, *io, false));
+  for (int ti = 0; ti < params->n_tiers; ti++)
+    if (has_bsk(*io, ti)) io->ksk |= 1u << ksk_owner(*params, ti);
+  return 0;
+}
+// The closed selection a circuit needs, and for the refusals an op that needs each key (-1: none does).  One enumeration, that of
+// circuit_stats: a tier is selected exactly when its count there is positive.
+struct CircuitKeyUse { dctfhe_key_tiers sel{0, 0}; int bsk_op[DCTFHE_MAX_TIERS], ksk_op[DCTFHE_MAX_TIERS]; };
+static void circuit_key_use(const CircuitPlan& c, const dctfhe_params& P, CircuitKeyUse* u) {
+  for (int i = 0; i < DCTFHE_MAX_TIERS; i++) u->bsk_op[i] = u->ksk_op[i] = -1;
+  u->sel = dctfhe_key_tiers{0, 0};
+  for (size_t i = 0; i < c.ops.size(); i++) {
+    const SiteOp& o = c.ops[i];
+    if (o.type == OP_MAXPOOL) {
+      const TensorShape& a = c.tensors[o.src0];
+      if (pool_pairs(a.C, a.H, a.W, o.pool.k, o.pool.stride, o.pool.pad) <= 0) continue;
+    }
+    for_each_bootstrap(o, P, [&](int tier, int, bool own_ks) {
+      if (tier < 0 || tier >= P.n_tiers) return;
+      if (!has_bsk(u->sel, tier)) { u->sel.bsk |= 1u << tier; u->bsk_op[tier] = (int)i; }
+      const int owner = ksk_owner(P, tier);
+      if (own_ks && !has_ksk(u->sel, owner)) { u->sel.ksk |= 1u << owner; u->ksk_op[owner] = (int)i; }
+    });
+  }
+  // closing: a bootstrap that reuses another's small ciphertext still belongs to a tier that a closed selection gives a key-switch key
+  for (int ti = 0; ti < P.n_tiers; ti++)
+    if (has_bsk(u->sel, ti) && !has_ksk(u->sel, ksk_owner(P, ti))) { u->sel.ksk |= 1u << ksk_owner(P, ti); u->ksk_op[ksk_owner(P, ti)] = u->bsk_op[ti]; }
+}
+static int circuit_check_tiers(const CircuitPlan& circ, const dctfhe_params& P);
+extern "C" int dctfhe_key_tiers_for_circuit(const void* blob, size_t size, const dctfhe_params* params, dctfhe_key_tiers* out) {
+  if (!blob || !params || !out) return fail("dctfhe_key_tiers_for_circuit: null argument");
+  CHK(check_params(params));
+  CircuitPlan c;
+  CHK(parse_circuit(blob, size, &c));
+  CHK(circuit_check_tiers(c, *params));
+  CircuitKeyUse u;
+  circuit_key_use(c, *params, &u);
+  *out = u.sel;
+  return 0;
+}
+// bytes of the two blob forms under a selection: the header (and the public generator key), the two masks unless everything is selected,
+// then the kept sections.  The caller has checked the selection.
+static size_t eval_blob_size(const dctfhe_params& p, const dctfhe_key_tiers& s);
+static size_t eval_cblob_size(const dctfhe_params& p, const dctfhe_key_tiers& s);
+extern "C" int dctfhe_key_tiers_blob_bytes(const dctfhe_params* params, const dctfhe_key_tiers* tiers, int compressed, size_t* out) {
+  if (!params || !tiers || !out) return fail("dctfhe_key_tiers_blob_bytes: null argument");
+  CHK(check_params(params));
+  CHK(key_tiers_check("dctfhe_key_tiers_blob_bytes", *params, *tiers, true));
+  *out = compressed ? eval_cblob_size(*params, *tiers) : eval_blob_size(*params, *tiers);
+  return 0;
+}
+// The one refusal of a call that needs a key the handle does not hold (like bound_to: before any allocation, copy or launch).
+// need_bsk: the bootstrap key of `tier`; need_ksk: the key-switch key `tier` switches with.
+static int keys_hold(const char* who, const dctfhe_eval_keys* K, int tier, bool need_bsk, bool need_ksk) {
+  if (need_bsk && !has_bsk(K->sel, tier)) return fail("%s: the evaluation keys hold no bootstrap key of tier %d (tier selection bsk 0x%x, ksk 0x%x)", who, tier, K->sel.bsk, K->sel.ksk);
+  if (need_ksk && !has_ksk(K->sel, ksk_owner(K->p, tier))) {
+    const int owner = ksk_owner(K->p, tier);
+    if (owner == tier) return fail("%s: the evaluation keys hold no key-switch key of tier %d (tier selection bsk 0x%x, ksk 0x%x)", who, tier, K->sel.bsk, K->sel.ksk);
+    return fail("%s: the evaluation keys hold no key-switch key of tier %d, which tier %d switches with (tier selection bsk 0x%x, ksk 0x%x)", who, owner, tier, K->sel.bsk, K->sel.ksk);
+  }
+  return 0;
+}
+
+// allocate every array of the selected evaluation keys and fill what depends on the parameters only (twiddles, root tables)
+static int eval_alloc(dctfhe_ctx* ctx, const dctfhe_params* params, const dctfhe_key_tiers& sel, std::unique_ptr<dctfhe_eval_keys>& E) {
+  CHK(check_params(params));
+  CHK(key_tiers_check("evaluation keys", *params, sel, true));
   HIPCHK(hipSetDevice(ctx->device));
   E.reset(new dctfhe_eval_keys);
-  E->ctx = ctx; E->p = *params;
+  E->ctx = ctx; E->p = *params; E->sel = sel;
   hipStream_t st = ctx->stream;
   const int D = params->D;
   HIPCHK(E->d_dummy.alloc((size_t)(D + 1) * 8));
@@ -800,6 +906,8 @@ static int eval_alloc(dctfhe_ctx* ctx, const dctfhe_params* params, std::unique_
     tk.t = t;
     if (t.ksk_share >= 0) {
       tk.ks = E->tiers[t.ksk_share].ks;
+    } else if (!has_ksk(sel, ti)) {
+      tk.ks = &E->ksk[ti];      // stays empty: keys_hold refuses every call that would read it
     } else {
       KskKey& ks = E->ksk[ti];
       tk.ks = &ks;
@@ -814,6 +922,7 @@ static int eval_alloc(dctfhe_ctx* ctx, const dctfhe_params* params, std::unique_
         HIPCHK(ks.kskT.alloc((size_t)ks.ncol_pad * rows));
       }
     }
+    if (!has_bsk(sel, ti)) continue;      // no twiddles, no root table, no key
     std::vector<cplx> tw;
     CHK(make_twiddles(t, tw));
     HIPCHK(tk.tw.alloc(tw.size() * sizeof(cplx)));
@@ -849,7 +958,7 @@ static int eval_finish(dctfhe_eval_keys* E) {
   hipStream_t st = E->ctx->stream;
   for (int ti = 0; ti < E->p.n_tiers; ti++) {
     const dctfhe_tier& t = E->p.tiers[ti];
-    if (t.ksk_share >= 0) continue;
+    if (t.ksk_share >= 0 || !has_ksk(E->sel, ti)) continue;
     KskKey& ks = E->ksk[ti];
     const size_t rows = (size_t)E->p.D * t.lk;
     hipLaunchKernelGGL(k_ksk_colsum, dim3((t.n + 256) / 256), dim3(256), 0, st, ks.ksk.as<uint64_t>(), (int)rows, t.n, ks.colsum.as<uint64_t>());
@@ -871,20 +980,32 @@ static int eval_finish(dctfhe_eval_keys* E) {
   return 0;
 }
 
-extern "C" int dctfhe_eval_keys_generate(dctfhe_client_key* C, dctfhe_eval_keys** out) {
+// a selection given by the caller: in range, no key-switch bit on a sharing tier, then closed
+static int closed_selection(const char* who, const dctfhe_params& p, const dctfhe_key_tiers* tiers, dctfhe_key_tiers* sel) {
+  if (!tiers) { *sel = key_tiers_full(p); return 0; }
+  *sel = *tiers;
+  CHK(key_tiers_check(who, p, *sel, false));
+  for (int ti = 0; ti < p.n_tiers; ti++)
+    if (has_bsk(*sel, ti)) sel->ksk |= 1u << ksk_owner(p, ti);
+  return 0;
+}
+extern "C" int dctfhe_eval_keys_generate_tiers(dctfhe_client_key* C, const dctfhe_key_tiers* tiers, dctfhe_eval_keys** out) {
   if (!C || !out) return fail("dctfhe_eval_keys_generate: null argument");
+  dctfhe_key_tiers sel;
+  CHK(closed_selection("dctfhe_eval_keys_generate_tiers", C->p, tiers, &sel));
   std::unique_ptr<dctfhe_eval_keys> E;
-  CHK(eval_alloc(C->ctx, &C->p, E));
+  CHK(eval_alloc(C->ctx, &C->p, sel, E));
   hipStream_t st = C->ctx->stream;
   const int D = C->p.D;
   for (int ti = 0; ti < C->p.n_tiers; ti++) {
     const dctfhe_tier& t = C->p.tiers[ti];
     TierKeys& tk = E->tiers[ti];
-    if (t.ksk_share < 0) {
+    if (t.ksk_share < 0 && has_ksk(sel, ti)) {
       hipLaunchKernelGGL(k_ksk_gen, dim3((unsigned)((size_t)D * t.lk)), dim3(256), 0, st, C->S(), C->s(), t.n, t.lk, t.betak, ks_limbs(t), t.lwe_sigma, C->pub, C->sec,
                          (uint64_t)(STREAM_KSK + 2 * ti), tk.ks->ksk.as<uint64_t>());
       HIPCHK(hipGetLastError());
     }
+    if (!has_bsk(sel, ti)) continue;
     const int N = 1 << t.logN, M = N / 2;
     const size_t per_bit_polys = (size_t)(t.k + 1) * t.l * (t.k + 1);
     const int blocks = (int)tier_bsk_blocks(t), chunk = tier_bsk_chunk(t, t.k + 1);
@@ -899,6 +1020,12 @@ extern "C" int dctfhe_eval_keys_generate(dctfhe_client_key* C, dctfhe_eval_keys*
   }
   CHK(eval_finish(E.get()));
   *out = E.release();
+  return 0;
+}
+extern "C" int dctfhe_eval_keys_generate(dctfhe_client_key* C, dctfhe_eval_keys** out) { return dctfhe_eval_keys_generate_tiers(C, nullptr, out); }
+extern "C" int dctfhe_eval_keys_tiers(dctfhe_eval_keys* E, dctfhe_key_tiers* out) {
+  if (!E || !out) return fail("dctfhe_eval_keys_tiers: null argument");
+  *out = E->sel;
   return 0;
 }
 
@@ -918,33 +1045,49 @@ extern "C" int dctfhe_eval_keys_destroy(dctfhe_eval_keys* E) { delete E; return 
 // version 3: the key-switch keys live on the 2^-(8 ks_limbs) torus grid (version-2 keys used all 64 bits and would lose their low bytes)
 static constexpr uint32_t EVAL_BLOB_VERSION = 3;
 struct EvalBlobHeader { uint32_t magic, version; uint64_t total_bytes; dctfhe_params params; };
-static size_t eval_blob_size(const dctfhe_params& p) {
-  size_t n = sizeof(EvalBlobHeader);
+// A PRUNED blob (a tier selection that is not everything) is the next version of its form: the two masks (u32 bsk, u32 ksk) follow the
+// header -- in the compressed form the public generator key -- and then come the kept sections in tier order.  Everything selected writes
+// the version above, byte for byte what it was.
+static constexpr uint32_t EVAL_BLOB_VERSION_PRUNED = 4;
+static size_t eval_blob_size(const dctfhe_params& p, const dctfhe_key_tiers& s) {
+  size_t n = sizeof(EvalBlobHeader) + (key_tiers_is_full(p, s) ? 0 : sizeof(dctfhe_key_tiers));
   for (int ti = 0; ti < p.n_tiers; ti++) {
     const dctfhe_tier& t = p.tiers[ti];
-    if (t.ksk_share < 0) n += tier_ksk_words(p, t) * 8;
-    n += tier_bsk_elems(t) * sizeof(cplx);
+    if (has_ksk(s, ti)) n += tier_ksk_words(p, t) * 8;
+    if (has_bsk(s, ti)) n += tier_bsk_elems(t) * sizeof(cplx);
   }
   return n;
 }
+// the masks of a blob of either form whose header names `pruned_version`: read and checked before anything is sized by them
+static int blob_selection(const char* what, const EvalBlobHeader& h, uint32_t pruned_version, const void* masks_at, size_t bytes_left, dctfhe_key_tiers* sel) {
+  if (h.version != pruned_version) { *sel = key_tiers_full(h.params); return 0; }
+  if (bytes_left < sizeof *sel) return fail("%s too short for its tier selection", what);
+  memcpy(sel, masks_at, sizeof *sel);
+  CHK(key_tiers_check(what, h.params, *sel, true));
+  if (key_tiers_is_full(h.params, *sel)) return fail("%s: a blob that selects every tier is written in the unpruned version", what);
+  return 0;
+}
 extern "C" int dctfhe_eval_keys_export(dctfhe_eval_keys* E, void* buf, size_t capacity, size_t* size) {
   if (!E || !size) return fail("dctfhe_eval_keys_export: null argument");
-  const size_t need = eval_blob_size(E->p);
+  const size_t need = eval_blob_size(E->p, E->sel);
   *size = need;
   if (!buf) return 0;                       // size query
   if (capacity < need) return fail("dctfhe_eval_keys_export: buffer of %zu bytes, %zu needed", capacity, need);
   HIPCHK(hipSetDevice(E->ctx->device));
   HIPCHK(hipStreamSynchronize(E->ctx->stream));
+  const bool full = key_tiers_is_full(E->p, E->sel);
   EvalBlobHeader h{};
-  h.magic = 0x4b564544u /* 'DEVK' */; h.version = EVAL_BLOB_VERSION; h.total_bytes = need; h.params = E->p;
+  h.magic = 0x4b564544u /* 'DEVK' */; h.version = full ? EVAL_BLOB_VERSION : EVAL_BLOB_VERSION_PRUNED; h.total_bytes = need; h.params = E->p;
   char* q = (char*)buf;
   memcpy(q, &h, sizeof h); q += sizeof h;
+  if (!full) { memcpy(q, &E->sel, sizeof E->sel); q += sizeof E->sel; }
   for (int ti = 0; ti < E->p.n_tiers; ti++) {
     const dctfhe_tier& t = E->p.tiers[ti];
-    if (t.ksk_share < 0) {
+    if (has_ksk(E->sel, ti)) {
       HIPCHK(hipMemcpy(q, E->ksk[ti].ksk.p, tier_ksk_words(E->p, t) * 8, hipMemcpyDeviceToHost));
       q += tier_ksk_words(E->p, t) * 8;
     }
+    if (!has_bsk(E->sel, ti)) continue;
     if (tier_duo(t)) {      // device order -> the blob's order
       std::vector<cplx> dev(tier_bsk_elems(t));
       HIPCHK(hipMemcpy(dev.data(), E->tiers[ti].bsk.p, dev.size() * sizeof(cplx), hipMemcpyDeviceToHost));
@@ -963,12 +1106,13 @@ extern "C" int dctfhe_eval_keys_export(dctfhe_eval_keys* E, void* buf, size_t ca
 // term sits in a mask polynomial (p < k) are shipped in body form (k_bsk_gen_bodies): they decompress to the same phase, not the same
 // words.  Key-switch keys and the rows with p = k decompress bit for bit.
 static constexpr uint32_t EVAL_CBLOB_MAGIC = 0x43564544u /* 'DEVC' */, EVAL_CBLOB_VERSION = 1;
-static size_t eval_cblob_size(const dctfhe_params& p) {
-  size_t n = sizeof(EvalBlobHeader) + 32;
+static constexpr uint32_t EVAL_CBLOB_VERSION_PRUNED = 2;      // the masks follow pub[32]
+static size_t eval_cblob_size(const dctfhe_params& p, const dctfhe_key_tiers& s) {
+  size_t n = sizeof(EvalBlobHeader) + 32 + (key_tiers_is_full(p, s) ? 0 : sizeof(dctfhe_key_tiers));
   for (int ti = 0; ti < p.n_tiers; ti++) {
     const dctfhe_tier& t = p.tiers[ti];
-    if (t.ksk_share < 0) n += (size_t)p.D * t.lk * 8;
-    n += tier_bsk_body_words(t) * 8;
+    if (has_ksk(s, ti)) n += (size_t)p.D * t.lk * 8;
+    if (has_bsk(s, ti)) n += tier_bsk_body_words(t) * 8;
   }
   return n;
 }
@@ -992,23 +1136,27 @@ static int launch_expand(const rng_key& key, uint64_t stream, uint64_t row0, uin
   return 0;
 }
 
-extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* buf, size_t capacity, size_t* size) {
+extern "C" int dctfhe_eval_keys_export_compressed_tiers(dctfhe_client_key* C, const dctfhe_key_tiers* tiers, void* buf, size_t capacity, size_t* size) {
   if (!C || !size) return fail("dctfhe_eval_keys_export_compressed: null argument");
   const dctfhe_params& P = C->p;
-  const size_t need = eval_cblob_size(P);
+  dctfhe_key_tiers sel;
+  CHK(closed_selection("dctfhe_eval_keys_export_compressed_tiers", P, tiers, &sel));
+  const size_t need = eval_cblob_size(P, sel);
   *size = need;
   if (!buf) return 0;                       // size query
   if (capacity < need) return fail("dctfhe_eval_keys_export_compressed: buffer of %zu bytes, %zu needed", capacity, need);
   HIPCHK(hipSetDevice(C->ctx->device));
   hipStream_t st = C->ctx->stream;
+  const bool full = key_tiers_is_full(P, sel);
   EvalBlobHeader h{};
-  h.magic = EVAL_CBLOB_MAGIC; h.version = EVAL_CBLOB_VERSION; h.total_bytes = need; h.params = P;
+  h.magic = EVAL_CBLOB_MAGIC; h.version = full ? EVAL_CBLOB_VERSION : EVAL_CBLOB_VERSION_PRUNED; h.total_bytes = need; h.params = P;
   char* q = (char*)buf;
   memcpy(q, &h, sizeof h); q += sizeof h;
   key_to_bytes(C->pub, (uint8_t*)q); q += 32;
+  if (!full) { memcpy(q, &sel, sizeof sel); q += sizeof sel; }
   for (int ti = 0; ti < P.n_tiers; ti++) {
     const dctfhe_tier& t = P.tiers[ti];
-    if (t.ksk_share < 0) {     // the generated key itself (k_ksk_gen), of which only the body column leaves the device
+    if (has_ksk(sel, ti)) {     // the generated key itself (k_ksk_gen), of which only the body column leaves the device
       const size_t rows = (size_t)P.D * t.lk;
       DevBuf d_ksk;
       HIPCHK(d_ksk.alloc(rows * (t.n + 1) * 8));
@@ -1019,6 +1167,7 @@ extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* bu
       HIPCHK(hipMemcpy2D(q, 8, d_ksk.as<uint64_t>() + t.n, (size_t)(t.n + 1) * 8, 8, rows, hipMemcpyDeviceToHost));
       q += rows * 8;
     }
+    if (!has_bsk(sel, ti)) continue;
     const int N = 1 << t.logN, rows = (t.k + 1) * t.l;
     const int blocks = (int)tier_bsk_blocks(t), chunk = tier_bsk_chunk(t, 1);
     const uint8_t* bits = t.unroll == 2 ? C->d_spair[ti].as<uint8_t>() : C->s();
@@ -1037,16 +1186,24 @@ extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* bu
   }
   return 0;
 }
+extern "C" int dctfhe_eval_keys_export_compressed(dctfhe_client_key* C, void* buf, size_t capacity, size_t* size) {
+  return dctfhe_eval_keys_export_compressed_tiers(C, nullptr, buf, capacity, size);
+}
 
-// a compressed blob's header and pub key, checked against its size
-static int parse_cblob(const void* buf, size_t size, EvalBlobHeader* h, rng_key* pub) {
+// a compressed blob's header, pub key and tier selection, checked against its size; *sections: where the first kept section begins
+static int parse_cblob(const void* buf, size_t size, EvalBlobHeader* h, rng_key* pub, dctfhe_key_tiers* sel, const char** sections) {
   if (size < sizeof(EvalBlobHeader) + 32) return fail("compressed evaluation-key blob too short");
   memcpy(h, buf, sizeof *h);
-  if (h->magic != EVAL_CBLOB_MAGIC || h->version != EVAL_CBLOB_VERSION) return fail("bad compressed evaluation-key blob magic/version");
+  if (h->magic != EVAL_CBLOB_MAGIC || (h->version != EVAL_CBLOB_VERSION && h->version != EVAL_CBLOB_VERSION_PRUNED))
+    return fail("bad compressed evaluation-key blob magic/version");
   CHK(check_params(&h->params));
-  if (h->total_bytes != size || eval_cblob_size(h->params) != size)
-    return fail("compressed evaluation-key blob is %zu bytes, its parameters need %zu", size, eval_cblob_size(h->params));
+  const size_t head = sizeof *h + 32;
+  CHK(blob_selection("compressed evaluation-key blob", *h, EVAL_CBLOB_VERSION_PRUNED, (const char*)buf + head, size - head, sel));
+  if (h->total_bytes != size || eval_cblob_size(h->params, *sel) != size)
+    return fail(h->version == EVAL_CBLOB_VERSION_PRUNED ? "compressed evaluation-key blob is %zu bytes, its parameters and tier selection need %zu"
+                                                        : "compressed evaluation-key blob is %zu bytes, its parameters need %zu", size, eval_cblob_size(h->params, *sel));
   *pub = key_from_bytes((const uint8_t*)buf + sizeof *h);
+  *sections = (const char*)buf + head + (h->version == EVAL_CBLOB_VERSION_PRUNED ? sizeof *sel : 0);
   return 0;
 }
 // standard-domain bootstrap-key blocks [i0, i0 + ni) of tier ti from their host bodies: masks regenerated, bodies copied in
@@ -1061,15 +1218,16 @@ static int expand_bsk_chunk(const rng_key& pub, int ti, const dctfhe_tier& t, in
 static int import_compressed(dctfhe_ctx* ctx, const void* buf, size_t size, dctfhe_eval_keys** out) {
   EvalBlobHeader h;
   rng_key pub;
-  CHK(parse_cblob(buf, size, &h, &pub));
+  dctfhe_key_tiers sel;
+  const char* q = nullptr;
+  CHK(parse_cblob(buf, size, &h, &pub, &sel, &q));
   std::unique_ptr<dctfhe_eval_keys> E;
-  CHK(eval_alloc(ctx, &h.params, E));
+  CHK(eval_alloc(ctx, &h.params, sel, E));
   hipStream_t st = ctx->stream;
-  const char* q = (const char*)buf + sizeof h + 32;
   for (int ti = 0; ti < h.params.n_tiers; ti++) {
     const dctfhe_tier& t = h.params.tiers[ti];
     TierKeys& tk = E->tiers[ti];
-    if (t.ksk_share < 0) {
+    if (has_ksk(sel, ti)) {
       const size_t rows = (size_t)h.params.D * t.lk;
       DevBuf d_b;
       HIPCHK(d_b.alloc(rows * 8));
@@ -1079,6 +1237,7 @@ static int import_compressed(dctfhe_ctx* ctx, const void* buf, size_t size, dctf
       HIPCHK(hipStreamSynchronize(st));
       q += rows * 8;
     }
+    if (!has_bsk(sel, ti)) continue;
     const int N = 1 << t.logN, M = N / 2, rows = (t.k + 1) * t.l;
     const size_t per_bit_polys = (size_t)rows * (t.k + 1);
     const int blocks = (int)tier_bsk_blocks(t), chunk = tier_bsk_chunk(t, t.k + 1);
@@ -1102,16 +1261,18 @@ extern "C" int dctfhe_eval_keys_decompress_bsk(dctfhe_ctx* ctx, const void* buf,
   if (!ctx || !buf || !out) return fail("dctfhe_eval_keys_decompress_bsk: null argument");
   EvalBlobHeader h;
   rng_key pub;
-  CHK(parse_cblob(buf, size, &h, &pub));
+  dctfhe_key_tiers sel;
+  const char* q = nullptr;
+  CHK(parse_cblob(buf, size, &h, &pub, &sel, &q));
   if (tier < 0 || tier >= h.params.n_tiers) return fail("tier out of range");
-  const char* q = (const char*)buf + sizeof h + 32;
+  if (!has_bsk(sel, tier)) return fail("dctfhe_eval_keys_decompress_bsk: the blob holds no bootstrap key of tier %d (tier selection bsk 0x%x, ksk 0x%x)", tier, sel.bsk, sel.ksk);
   for (int ti = 0; ti < tier; ti++) {
     const dctfhe_tier& t = h.params.tiers[ti];
-    if (t.ksk_share < 0) q += (size_t)h.params.D * t.lk * 8;
-    q += tier_bsk_body_words(t) * 8;
+    if (has_ksk(sel, ti)) q += (size_t)h.params.D * t.lk * 8;
+    if (has_bsk(sel, ti)) q += tier_bsk_body_words(t) * 8;
   }
   const dctfhe_tier& t = h.params.tiers[tier];
-  if (t.ksk_share < 0) q += (size_t)h.params.D * t.lk * 8;
+  if (has_ksk(sel, tier)) q += (size_t)h.params.D * t.lk * 8;
   HIPCHK(hipSetDevice(ctx->device));
   const size_t body_bytes = tier_bsk_body_words(t) * 8;
   DevBuf d_b, d_std;
@@ -1128,18 +1289,23 @@ extern "C" int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t 
   EvalBlobHeader h;
   memcpy(&h, buf, sizeof h);
   if (h.magic == EVAL_CBLOB_MAGIC) return import_compressed(ctx, buf, size, out);
-  if (h.magic != 0x4b564544u || h.version != EVAL_BLOB_VERSION) return fail("bad evaluation-key blob magic/version");
+  if (h.magic != 0x4b564544u || (h.version != EVAL_BLOB_VERSION && h.version != EVAL_BLOB_VERSION_PRUNED)) return fail("bad evaluation-key blob magic/version");
   CHK(check_params(&h.params));
-  if (h.total_bytes != size || eval_blob_size(h.params) != size) return fail("evaluation-key blob is %zu bytes, its parameters need %zu", size, eval_blob_size(h.params));
+  dctfhe_key_tiers sel;
+  CHK(blob_selection("evaluation-key blob", h, EVAL_BLOB_VERSION_PRUNED, (const char*)buf + sizeof h, size - sizeof h, &sel));
+  if (h.total_bytes != size || eval_blob_size(h.params, sel) != size)
+    return fail(h.version == EVAL_BLOB_VERSION_PRUNED ? "evaluation-key blob is %zu bytes, its parameters and tier selection need %zu"
+                                                      : "evaluation-key blob is %zu bytes, its parameters need %zu", size, eval_blob_size(h.params, sel));
   std::unique_ptr<dctfhe_eval_keys> E;
-  CHK(eval_alloc(ctx, &h.params, E));
-  const char* q = (const char*)buf + sizeof h;
+  CHK(eval_alloc(ctx, &h.params, sel, E));
+  const char* q = (const char*)buf + sizeof h + (h.version == EVAL_BLOB_VERSION_PRUNED ? sizeof sel : 0);
   for (int ti = 0; ti < h.params.n_tiers; ti++) {
     const dctfhe_tier& t = h.params.tiers[ti];
-    if (t.ksk_share < 0) {
+    if (has_ksk(sel, ti)) {
       HIPCHK(hipMemcpy(E->ksk[ti].ksk.p, q, tier_ksk_words(h.params, t) * 8, hipMemcpyHostToDevice));
       q += tier_ksk_words(h.params, t) * 8;
     }
+    if (!has_bsk(sel, ti)) continue;
     if (tier_duo(t)) {      // the blob's order -> device order
       std::vector<cplx> dev(tier_bsk_elems(t));
       duo_permute((const cplx*)q, dev.data(), dev.size() / DUO_M, true);
@@ -1163,6 +1329,7 @@ extern "C" int dctfhe_client_key_export_secret(dctfhe_client_key* C, uint8_t* bi
 }
 extern "C" int dctfhe_eval_keys_export_ksk(dctfhe_eval_keys* K, int tier, uint64_t* out) {
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_eval_keys_export_ksk", K, tier, false, true));
   const dctfhe_tier& t = K->p.tiers[tier];
   HIPCHK(hipSetDevice(K->ctx->device));
   HIPCHK(hipMemcpy(out, K->tiers[tier].ks->ksk.p, (size_t)K->p.D * t.lk * (t.n + 1) * 8, hipMemcpyDeviceToHost));
@@ -1669,6 +1836,7 @@ extern "C" int dctfhe_keyswitch_prefix(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
   if (!ctx || !K) return fail("dctfhe_keyswitch: null handle");
   CHK(bound_to("dctfhe_keyswitch", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_keyswitch", K, tier, false, true));
   if (deff < 0 || deff > K->p.D) return fail("deff out of range");
   if (shift < 0 || shift > 63) return fail("shift out of range");
   if (count == 0) return 0;
@@ -1714,6 +1882,7 @@ extern "C" int dctfhe_keyswitch_pack(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int t
   if (!ctx || !K || (count && (!cts || !rows))) return fail("dctfhe_keyswitch_pack: null argument");
   CHK(bound_to("dctfhe_keyswitch_pack", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("dctfhe_keyswitch_pack: tier %d out of range (%d tiers)", tier, K->p.n_tiers);
+  CHK(keys_hold("dctfhe_keyswitch_pack", K, tier, false, true));
   if (dim < 1 || dim > K->p.D) return fail("dctfhe_keyswitch_pack: rows of %d mask words, the key has %d", dim, K->p.D);
   if (deff < 0 || deff > dim) return fail("dctfhe_keyswitch_pack: effective dimension %d outside [0, dim = %d]", deff, dim);
   if (count == 0) return 0;
@@ -2068,6 +2237,7 @@ extern "C" int dctfhe_modswitch_center(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int
   if (!ctx || !K || (count && !cts_small)) return fail("dctfhe_modswitch_center: null argument");
   CHK(bound_to("dctfhe_modswitch_center", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_modswitch_center", K, tier, true, false));      // it rounds to the levels of this tier's bootstrap
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(ctx->device));
   const size_t bytes = count * (size_t)(K->p.tiers[tier].n + 1) * 8;
@@ -2083,6 +2253,7 @@ extern "C" int dctfhe_pbs(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, const 
   if (!ctx || !K) return fail("dctfhe_pbs: null handle");
   CHK(bound_to("dctfhe_pbs", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_pbs", K, tier, true, false));
   if (ntab < 1 || w < 0) return fail("dctfhe_pbs: need at least one table and w >= 0");
   if (count == 0) return 0;
   HIPCHK(hipSetDevice(ctx->device));
@@ -2113,6 +2284,9 @@ extern "C" int dctfhe_round_lut_split(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int 
   const bool split = tab_tier2 >= 0;
   if (tab_tier < 0 || tab_tier >= K->p.n_tiers || tab_tier2 >= K->p.n_tiers || ((r > 0 || split) && (bit_tier < 0 || bit_tier >= K->p.n_tiers)))
     return fail("tier out of range");
+  CHK(keys_hold("dctfhe_round_lut", K, tab_tier, true, true));
+  if (split) CHK(keys_hold("dctfhe_round_lut", K, tab_tier2, true, true));
+  if (r > 0 || split) CHK(keys_hold("dctfhe_round_lut", K, bit_tier, true, true));
   if (p < 1 || p > 62 || r < 0 || r >= p) return fail("need 1 <= p <= 62 and 0 <= r < p");
   if (w != p - r) return fail("w must equal p - r");
   if (split && w < 2) return fail("a parity split needs a table of at least 2 input bits");
@@ -2274,6 +2448,7 @@ extern "C" int dctfhe_keyswitch_diff(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int t
   if (!ctx || !K || (count && (!cts || !ia || !ib || !cts_small))) return fail("dctfhe_keyswitch_diff: null argument");
   CHK(bound_to("dctfhe_keyswitch_diff", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_keyswitch_diff", K, tier, false, true));
   if (deff < 0 || deff > K->p.D) return fail("deff out of range");
   if (shift < 0 || shift > 63) return fail("shift out of range");
   for (size_t c = 0; c < count; c++)
@@ -2306,6 +2481,7 @@ extern "C" int dctfhe_pbs_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int tier, c
   CHK(bound_to("dctfhe_pbs_rows", ctx, K->ctx, "evaluation keys"));
   if (!tables || !rows_io || (count && !cts_small)) return fail("dctfhe_pbs_rows: null argument");
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_pbs_rows", K, tier, true, false));
   if (ntab < 1 || w < 0) return fail("dctfhe_pbs_rows: need at least one table and w >= 0");
   if (hw < 1) return fail("dctfhe_pbs_rows: hw = %d elements per channel (at least 1)", hw);
   if (nchan < 1 || nchan > ntab) return fail("dctfhe_pbs_rows: %d per-channel tables of the %d given (1 <= nchan <= ntab)", nchan, ntab);
@@ -2340,6 +2516,7 @@ extern "C" int dctfhe_keyswitch_sum(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   if (!ctx || !K || (count && (!rows_a || !rows_b || !cts_small))) return fail("dctfhe_keyswitch_sum: null argument");
   CHK(bound_to("dctfhe_keyswitch_sum", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_keyswitch_sum", K, tier, false, true));
   if (dim_a < 1 || dim_a > K->p.D) return fail("dctfhe_keyswitch_sum: rows of %d mask words, the key has %d", dim_a, K->p.D);
   if (dim_b < 0 || dim_b > (1 << 16)) return fail("dctfhe_keyswitch_sum: second rows of %d mask words (0 .. 2^16)", dim_b);
   if (deff < 0 || deff > dim_a) return fail("deff out of range");
@@ -2426,6 +2603,7 @@ extern "C" int dctfhe_max_pool_rows(dctfhe_ctx* ctx, dctfhe_eval_keys* K, int ti
   }
   if (!table) return fail("dctfhe_max_pool_rows: null table");
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_max_pool_rows", K, tier, true, true));
   const dctfhe_tier& t = K->p.tiers[tier];
   if (p_d > t.logN - 1) return fail("dctfhe_max_pool_rows: table of 2^%d entries does not fit tier %d", p_d, tier);
   CHK(rows_ok("dctfhe_max_pool_rows", dim_in, deff_in));
@@ -2975,6 +3153,18 @@ extern "C" int dctfhe_session_create(dctfhe_ctx* ctx, dctfhe_circuit* circ, dctf
   s->ctx = ctx; s->circ = circ; s->keys = keys; s->batch = batch;
   s->D = keys ? keys->p.D : 0;
   if (keys) CHK(circuit_check_tiers(*circ, keys->p));
+  if (keys) {      // every key the circuit reads is held: the first missing tier, and an op that needs it
+    CircuitKeyUse u;
+    circuit_key_use(*circ, keys->p, &u);
+    for (int ti = 0; ti < keys->p.n_tiers; ti++) {
+      if (has_bsk(u.sel, ti) && !has_bsk(keys->sel, ti))
+        return fail("dctfhe_session_create: op %d bootstraps on tier %d, and the evaluation keys hold no bootstrap key of tier %d (tier selection bsk 0x%x, ksk 0x%x; the circuit needs bsk 0x%x, ksk 0x%x)",
+                    u.bsk_op[ti], ti, ti, keys->sel.bsk, keys->sel.ksk, u.sel.bsk, u.sel.ksk);
+      if (has_ksk(u.sel, ti) && !has_ksk(keys->sel, ti))
+        return fail("dctfhe_session_create: op %d key-switches with tier %d, and the evaluation keys hold no key-switch key of tier %d (tier selection bsk 0x%x, ksk 0x%x; the circuit needs bsk 0x%x, ksk 0x%x)",
+                    u.ksk_op[ti], ti, ti, keys->sel.bsk, keys->sel.ksk, u.sel.bsk, u.sel.ksk);
+    }
+  }
   if (keys) CHK(session_conv_packs(s.get()));
   CHK(session_plan_buffers(s.get()));
   HIPCHK(s->d_overflow.alloc(sizeof(int)));
@@ -3140,6 +3330,7 @@ extern "C" int dctfhe_session_download_packed(dctfhe_session* s, int tier, uint1
   if (!s || !rows) return fail("dctfhe_session_download_packed: null argument");
   if (!s->keys) return fail("dctfhe_session_download_packed: a clear-mode session holds phases, not ciphertexts (dctfhe_session_download)");
   if (tier < 0 || tier >= s->keys->p.n_tiers) return fail("dctfhe_session_download_packed: tier %d out of range (%d tiers)", tier, s->keys->p.n_tiers);
+  CHK(keys_hold("dctfhe_session_download_packed", s->keys, tier, false, true));
   CHK(output_whole(s, "dctfhe_session_download_packed"));
   HIPCHK(hipSetDevice(s->ctx->device));
   const int t = s->circ->output_tensor;
@@ -3153,6 +3344,7 @@ extern "C" int dctfhe_session_download_ring(dctfhe_session* s, int tier, dctfhe_
   if (!s->keys) return fail("dctfhe_session_download_ring: a clear-mode session holds phases, not ciphertexts (dctfhe_session_download)");
   if (K->ctx != s->ctx || s->keys->ctx != s->ctx) return fail("dctfhe_session_download_ring: session, evaluation keys and packing key must share one context");
   if (tier < 0 || tier >= s->keys->p.n_tiers) return fail("dctfhe_session_download_ring: tier %d out of range (%d tiers)", tier, s->keys->p.n_tiers);
+  CHK(keys_hold("dctfhe_session_download_ring", s->keys, tier, false, true));
   const int n = s->keys->p.tiers[tier].n;
   if (n > K->n_max) return fail("dctfhe_session_download_ring: tier %d has n = %d, the packing key covers n_max = %d", tier, n, K->n_max);
   if ((1 << K->logN) > s->keys->p.D) return fail("dctfhe_session_download_ring: the ring key is a prefix of the big key: N_p = %d > D = %d", 1 << K->logN, s->keys->p.D);
@@ -3746,6 +3938,7 @@ extern "C" int dctfhe_bench_pbs(dctfhe_ctx* ctx, dctfhe_keys* K, int tier, size_
   if (!ctx || !K || !ms_per_launch) return fail("dctfhe_bench_pbs: null argument");
   CHK(bound_to("dctfhe_bench_pbs", ctx, K->ctx, "evaluation keys"));
   if (tier < 0 || tier >= K->p.n_tiers) return fail("tier out of range");
+  CHK(keys_hold("dctfhe_bench_pbs", K, tier, true, false));
   HIPCHK(hipSetDevice(ctx->device));
   const dctfhe_tier& t = K->p.tiers[tier];
   const size_t L = (size_t)K->p.D + 1;

@@ -47,6 +47,20 @@ class MarginStats(C.Structure):
                 ("max_abs", C.c_int32), ("count", C.c_int64), ("sum", C.c_int64), ("sum_sq", C.c_uint64), ("hist", C.c_int64 * MARGIN_BINS)]
 
 
+class KeyTiers(C.Structure):
+    """dctfhe_key_tiers: which tiers' bootstrap keys (bsk) and own key-switch keys (ksk) a set of evaluation keys holds (include/dctfhe.h)"""
+    _fields_ = [("bsk", C.c_uint32), ("ksk", C.c_uint32)]
+
+    def __eq__(self, other):
+        return isinstance(other, KeyTiers) and (self.bsk, self.ksk) == (other.bsk, other.ksk)
+
+    def __hash__(self):
+        return hash((int(self.bsk), int(self.ksk)))
+
+    def __repr__(self):
+        return "KeyTiers(bsk=0x%x, ksk=0x%x)" % (self.bsk, self.ksk)
+
+
 MAX_SLAB_GROUPS = 64
 
 
@@ -89,6 +103,8 @@ EXPORTS = [
     "dctfhe_shard_pool", "dctfhe_session_set_shard_pool", "dctfhe_session_mark_rows", "dctfhe_session_shard_plan_rows", "dctfhe_session_pool_pairs",
     "dctfhe_conv2d_rows_window", "dctfhe_memory_plan", "dctfhe_session_set_memory_budget", "dctfhe_session_memory_plan", "dctfhe_session_set_slab_heights",
     "dctfhe_pbs_rows", "dctfhe_keyswitch_sum", "dctfhe_acc_rows", "dctfhe_gather_rows",
+    "dctfhe_key_tiers_all", "dctfhe_key_tiers_close", "dctfhe_key_tiers_for_circuit", "dctfhe_key_tiers_blob_bytes",
+    "dctfhe_eval_keys_generate_tiers", "dctfhe_eval_keys_export_compressed_tiers", "dctfhe_eval_keys_tiers",
 ]
 
 _lib = None
@@ -221,6 +237,14 @@ def load():
     L.dctfhe_session_set_memory_budget.argtypes = [vp, sz]
     L.dctfhe_session_memory_plan.argtypes = [vp, C.POINTER(MemPlan)]
     L.dctfhe_session_set_slab_heights.argtypes = [vp, vp, i32]
+    pk = C.POINTER(KeyTiers)
+    L.dctfhe_key_tiers_all.argtypes = [C.POINTER(Params), pk]
+    L.dctfhe_key_tiers_close.argtypes = [C.POINTER(Params), pk]
+    L.dctfhe_key_tiers_for_circuit.argtypes = [vp, sz, C.POINTER(Params), pk]
+    L.dctfhe_key_tiers_blob_bytes.argtypes = [C.POINTER(Params), pk, i32, C.POINTER(sz)]
+    L.dctfhe_eval_keys_generate_tiers.argtypes = [vp, pk, C.POINTER(vp)]
+    L.dctfhe_eval_keys_export_compressed_tiers.argtypes = [vp, pk, vp, sz, C.POINTER(sz)]
+    L.dctfhe_eval_keys_tiers.argtypes = [vp, pk]
     _lib = L
     return L
 

@@ -25,12 +25,17 @@ class Params(C.Structure):
                 ("input_sigma", C.c_double), ("tiers", Tier * MAX_TIERS)]
 
 
+class KeyTiers(C.Structure):
+    """dctfhe_key_tiers (include/dctfhe.h); the layout of dctfhe._lib.KeyTiers"""
+    _fields_ = [("bsk", C.c_uint32), ("ksk", C.c_uint32)]
+
+
 EXPORTS = [
     "dctfhe_host_last_error", "dctfhe_host_version", "dctfhe_host_threads",
     "dctfhe_host_client_key_create", "dctfhe_host_client_key_destroy", "dctfhe_host_client_key_export_secret",
     "dctfhe_host_client_key_set_encrypt_counter", "dctfhe_host_client_key_set_encrypt_nonce", "dctfhe_host_client_key_public_keys",
     "dctfhe_host_encrypt_rows", "dctfhe_host_encrypt_seeded", "dctfhe_host_decrypt_rows", "dctfhe_host_decrypt_packed", "dctfhe_host_decrypt_ring",
-    "dctfhe_host_eval_keys_export_compressed", "dctfhe_host_pack_key_export", "dctfhe_host_public_key_export",
+    "dctfhe_host_eval_keys_export_compressed", "dctfhe_host_eval_keys_export_compressed_tiers", "dctfhe_host_pack_key_export", "dctfhe_host_public_key_export",
     "dctfhe_host_public_key_import", "dctfhe_host_public_key_destroy", "dctfhe_host_public_key_info", "dctfhe_host_public_key_set_encrypt_seed",
     "dctfhe_host_public_key_draws", "dctfhe_host_encrypt_public",
 ]
@@ -65,6 +70,7 @@ def load():
     L.dctfhe_host_decrypt_packed.argtypes = [vp, i32, vp, sz, vp]
     L.dctfhe_host_decrypt_ring.argtypes = [vp, i32, vp, sz, vp]
     L.dctfhe_host_eval_keys_export_compressed.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    L.dctfhe_host_eval_keys_export_compressed_tiers.argtypes = [vp, C.POINTER(KeyTiers), vp, sz, C.POINTER(sz)]
     L.dctfhe_host_pack_key_export.argtypes = [vp, i32, i32, i32, C.c_double, vp, sz, C.POINTER(sz)]
     L.dctfhe_host_public_key_export.argtypes = [vp, i32, C.c_double, vp, sz, C.POINTER(sz)]
     L.dctfhe_host_public_key_import.argtypes = [vp, sz, C.POINTER(vp)]

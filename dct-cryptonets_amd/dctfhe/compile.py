@@ -35,6 +35,7 @@ import torch
 import torch.nn.functional as F
 
 from . import params as P
+from .params import KeyTierSelection, key_blob_bytes, key_section_bytes, ksk_owner  # noqa: F401 (tier selections: defined beside the tiers, used here)
 
 OP_CONV, OP_ADD, OP_SUMPOOL, OP_LUT = 1, 2, 3, 4
 OP_MAXPOOL = 5            # not 9: the ABI tests use 9 as the unknown type
@@ -335,6 +336,38 @@ class CompiledCircuit:
                 nm = ps.tiers[tier].name
                 out[nm] = out.get(nm, 0) + self._decisions(o)
         return out
+
+    def key_tiers(self, output=None, spec=None):
+        """The evaluation keys this circuit reads, as a closed tier selection (include/dctfhe.h TIER SELECTIONS; the library's
+        dctfhe_key_tiers_for_circuit computes the same from the blob): the bootstrap key of every tier an op bootstraps on and the
+        key-switch key at the end of that tier's share chain.  output "rows" / "ring": plus the key-switch key of the tier that
+        output_compaction(self, output, spec) picks, so that packed results under the pruned keys are those under the full set."""
+        ps = self.param_set
+        bsk = ksk = 0
+        for o in self.ops:
+            if o.type not in (OP_LUT, OP_MAXPOOL) or self._decisions(o) <= 0:
+                continue
+            for _, tier, _, _ in for_each_bootstrap(o, ps):
+                bsk |= 1 << tier
+                ksk |= 1 << ksk_owner(ps, tier)
+        if output is not None:
+            ksk |= 1 << output_compaction(self, output, spec).tier
+        return KeyTierSelection.from_masks(ps, bsk, ksk)
+
+    def key_report(self, output=None, spec=None):
+        """Per tier: which of its keys key_tiers(output, spec) keeps and the bytes of each in the two blob forms (full: the Fourier
+        bootstrap key and the whole key-switch key; compressed: their bodies), with the totals of the blobs for every tier and for the
+        selection (header, public generator key and masks included: the figures of dctfhe_key_tiers_blob_bytes)."""
+        ps, sel = self.param_set, self.key_tiers(output, spec)
+        tiers = []
+        for i, t in enumerate(ps.tiers):
+            b = key_section_bytes(ps, t)
+            tiers.append(dict(tier=i, name=t.name, bsk=t.name in sel.bsk, ksk=t.name in sel.ksk, ksk_owner=ps.tiers[ksk_owner(ps, i)].name,
+                              bootstraps_per_image=self.pbs_counts().get(t.name, 0), **b))
+        every = KeyTierSelection.all(ps)
+        return dict(tiers=tiers, selection=dict(bsk=sorted(sel.bsk), ksk=sorted(sel.ksk), bsk_mask=sel.bsk_mask, ksk_mask=sel.ksk_mask),
+                    all=dict(full_bytes=key_blob_bytes(ps, every, False), compressed_bytes=key_blob_bytes(ps, every, True)),
+                    selected=dict(full_bytes=key_blob_bytes(ps, sel, False), compressed_bytes=key_blob_bytes(ps, sel, True)))
 
     def shard_plan(self, rows=False, part=0, parts=1, batch=1):
         """The exchange points of a run whose look-up sites are sharded over several GPUs (include/dctfhe.h dctfhe_session_shard_plan, the

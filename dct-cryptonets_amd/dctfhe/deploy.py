@@ -26,9 +26,10 @@ import numpy as np
 
 from . import params as P
 from . import roles
+from .params import KeyTierSelection
 from ._lib import MAX_TIERS, DctfheError
 from .engine import (Circuit, ClientKey, Context, EvalKeys, PackKey, PackedCiphertexts, PackedRing, PublicInputs, PublicKey, SeededCiphertexts,
-                     Session, blob_params, seed_bytes)
+                     Session, blob_key_tiers, blob_params, key_tiers_for_circuit, seed_bytes)
 
 FILE_MAGIC, FORMAT_VERSION = b"DCTFHEDP", 1
 _FILE_HDR = struct.Struct("<8sIIQ")           # magic, format version, JSON header bytes, total file bytes; then the header, then the arrays
@@ -38,6 +39,9 @@ BOUNDARY_KEYS = ("input_shape", "in_scale", "in_bits", "e_in", "n_out", "e_out",
 # the client spec's keys: a fixed whitelist (tests/test_deploy_host.py); nothing of the model beyond its boundary
 CLIENT_KEYS = ("digest", "boundary", "param_set", "output_compaction", "public_input_plan", "has_classifier", "classifier_w", "classifier_b")
 SERVER_KEYS = ("digest", "boundary", "param_set", "output_compaction", "public_input_plan", "blob", "simulation_sigmas", "simulation_sigmas_split")
+# fields either file may carry and a default save() does not write.  key_tiers: dict(bsk, ksk), the bit masks of a PRUNED bundle's tier
+# selection (include/dctfhe.h TIER SELECTIONS); absent: every tier, which is how files from before the field load
+OPTIONAL_KEYS = ("key_tiers",)
 
 
 # ------------------------------------------------------------------------------------------ container
@@ -199,7 +203,20 @@ def key_check_bits(ps):
 
 
 # ------------------------------------------------------------------------------------------ save
-def bundle_trees(q_module, classifier=None):
+def bundle_key_tiers(q_module, key_tiers="all"):
+    """the tier selection a bundle records: None for "all"; for "circuit" CompiledCircuit.key_tiers at the output form (and packing spec)
+    of the module's Configuration -- None again where that is every tier"""
+    if key_tiers not in ("all", "circuit"):
+        raise ValueError(f"key_tiers {key_tiers!r} (all or circuit)")
+    if key_tiers == "all":
+        return None
+    cfg, c = q_module.configuration, q_module.compiled
+    form = cfg.compress_output_ciphertexts
+    sel = c.key_tiers("ring", cfg.result_packing_spec) if form == "ring" else c.key_tiers("rows" if form else None)
+    return None if sel.is_all(c.param_set) else sel
+
+
+def bundle_trees(q_module, classifier=None, key_tiers="all"):
     """(client tree, server tree) of a compiled module; the priced records at the specs its Configuration carries now"""
     c = q_module.compiled
     ps = c.param_set
@@ -212,6 +229,9 @@ def bundle_trees(q_module, classifier=None):
                   output_compaction=dict(rows=_priced(lambda: q_module.output_compaction("rows")),
                                          ring=_priced(lambda: q_module.output_compaction("ring"))),
                   public_input_plan=_priced(q_module.public_input_plan))
+    sel = bundle_key_tiers(q_module, key_tiers)
+    if sel is not None:
+        common["key_tiers"] = dict(bsk=int(sel.bsk_mask), ksk=int(sel.ksk_mask))
     client = dict(common, has_classifier=classifier is not None)
     if classifier is not None:
         w, b = classifier
@@ -223,10 +243,12 @@ def bundle_trees(q_module, classifier=None):
     return client, server
 
 
-def save(q_module, directory, classifier=None):
+def save(q_module, directory, classifier=None, key_tiers="all"):
     """Writes client.dctfhe and server.dctfhe for a compiled QuantizedModule into `directory`; needs no GPU.  classifier: (w, b) of the
-    clear nn.Linear the client applies to the decrypted features (optional).  Returns the two paths."""
-    client, server = bundle_trees(q_module, classifier)
+    clear nn.Linear the client applies to the decrypted features (optional).  key_tiers: "all" (default: the files of before) or
+    "circuit": both files record the tier selection the circuit reads, and the client makes and ships only those evaluation keys.
+    Returns the two paths."""
+    client, server = bundle_trees(q_module, classifier, key_tiers)
     os.makedirs(directory, exist_ok=True)
     paths = os.path.join(directory, CLIENT_FILE), os.path.join(directory, SERVER_FILE)
     write_container(paths[0], "client", client)
@@ -240,8 +262,8 @@ class Spec:
 
     def __init__(self, tree, keys, path="<tree>"):
         required = {"digest", "boundary", "param_set", "output_compaction", "public_input_plan"}
-        if set(tree) - set(keys) or not required <= set(tree):
-            raise ValueError(f"{path}: unexpected or missing fields {sorted((set(tree) - set(keys)) | (required - set(tree)))}")
+        if set(tree) - set(keys) - set(OPTIONAL_KEYS) or not required <= set(tree):
+            raise ValueError(f"{path}: unexpected or missing fields {sorted((set(tree) - set(keys) - set(OPTIONAL_KEYS)) | (required - set(tree)))}")
         self.tree = tree
         self.digest = bytes(np.asarray(tree["digest"], np.uint8).tobytes())
         if len(self.digest) != 32:
@@ -255,6 +277,12 @@ class Spec:
         self._n_out, self.in_dim, self.out_dim = int(b["n_out"]), int(b["in_dim"]), int(b["out_dim"])
         self.param_set = _params_from_tree(tree["param_set"])
         self.classifier = (tree["classifier_w"], tree["classifier_b"]) if tree.get("has_classifier") else None
+        # the bundle's tier selection (params.KeyTierSelection); a file without the field selects every tier
+        kt = tree.get("key_tiers")
+        if kt is not None and (not isinstance(kt, dict) or set(kt) != {"bsk", "ksk"}):
+            raise ValueError(f"{path}: key_tiers holds the two masks bsk and ksk")
+        self.key_tiers = KeyTierSelection.all(self.param_set) if kt is None else KeyTierSelection.from_masks(self.param_set, int(kt["bsk"]), int(kt["ksk"]))
+        self.pruned = kt is not None
 
     def n_in(self):
         return int(np.prod(self.input_shape))
@@ -519,12 +547,13 @@ class Client(_Role):
     def export_evaluation_keys(self, compressed=True):
         """the evaluation keys as a blob for the server (no secret inside): compressed (bodies + the public mask key) or full"""
         key = self._need_key()
+        tiers = self.spec.key_tiers if self.spec.pruned else None      # a pruned bundle ships only its selection
         if compressed:
-            return key.export_eval_keys_compressed()
+            return key.export_eval_keys_compressed(tiers)
         if self.on_host:
             raise ValueError('export_evaluation_keys(compressed=False): the full (Fourier) keys are made on the GPU; a client on device="host" '
                              "ships the compressed form, which the server transforms on import")
-        ek = key.generate_eval_keys()
+        ek = key.generate_eval_keys(tiers)
         try:
             return ek.to_blob()
         finally:
@@ -561,17 +590,22 @@ class Client(_Role):
     def make_key_check(self):
         """per tier a few fresh encryptions of known messages at the tier's table precision (compact rows), for Server.answer_key_check"""
         key, dim = self._need_key(), self.spec.in_dim
-        entries = [(ti, w, key.encrypt(key_check_messages(w) << np.uint64(63 - w), dim)) for ti, w in enumerate(key_check_bits(self.spec.param_set))]
+        entries = [(ti, w, key.encrypt(key_check_messages(w) << np.uint64(63 - w), dim)) for ti, w in self._key_check_tiers()]
         return _pack_key_check(KCQ_MAGIC, self.spec.digest, entries)
+
+    def _key_check_tiers(self):
+        """(tier, table bits) of the key check: the tiers whose bootstrap key the bundle's selection holds (a closed selection holds their
+        key-switch keys too)"""
+        return [(ti, w) for ti, w in enumerate(key_check_bits(self.spec.param_set)) if (self.spec.key_tiers.bsk_mask >> ti) & 1]
 
     def verify_key_check(self, answer):
         """decrypts what the server bootstrapped and compares with the identity table's entries; KeyCheckError names the first tier that
         differs.  Proves that the server's keys bootstrap correctly under this client's secret; says nothing about security."""
         key, ps = self._need_key(), self.spec.param_set
         entries = _unpack_key_check(KCA_MAGIC, answer, self.spec.digest, "this client's spec is")
-        bits = key_check_bits(ps)
-        if [(t, w) for t, w, _ in entries] != list(enumerate(bits)):
-            raise KeyCheckError(f"key check: the answer covers tiers {[(t, w) for t, w, _ in entries]}, this client asked for {list(enumerate(bits))}")
+        asked = self._key_check_tiers()
+        if [(t, w) for t, w, _ in entries] != asked:
+            raise KeyCheckError(f"key check: the answer covers tiers {[(t, w) for t, w, _ in entries]}, this client asked for {asked}")
         for ti, w, rows in entries:
             msgs = key_check_messages(w)
             if rows.shape != (msgs.size, ps.D + 1):
@@ -674,6 +708,13 @@ class Server(_Role):
         if fields(got) != fields(want):
             raise ValueError("these evaluation keys were made for another ParamSet than this bundle's (D, tiers or noise differ): "
                              "client.dctfhe and server.dctfhe are not of one save()")
+        # coverage before anything is imported: what the circuit itself reads (a full bundle refuses pruned keys only where a tier is
+        # really missing); the key that packs results is checked when a packed form is asked for (evaluate)
+        need = key_tiers_for_circuit(self.spec.blob, want)
+        held = KeyTierSelection.from_masks(self.spec.param_set, *blob_key_tiers(blob))
+        need = KeyTierSelection.from_masks(self.spec.param_set, need.bsk, need.ksk)
+        if not held.covers(need):
+            raise ValueError(f"these evaluation keys do not cover this bundle's circuit: they lack the {held.missing(need)}")
         keys = EvalKeys.from_blob(self._context(), blob)
         self._drop_sessions("execute")
         if self._keys is not None:
@@ -710,6 +751,10 @@ class Server(_Role):
             tier, pack_key = roles.ring_plan(self.spec.output_compaction("ring"), self._pack_key)
         elif packed:
             tier = self.spec.output_compaction("rows").tier
+        if tier is not None and self._keys is not None and not (self._keys.tiers.ksk >> tier) & 1:
+            raise ValueError(f"packed={packed!r}: results are packed with the key-switch key of tier {tier} ({self.spec.param_set.tiers[tier].name}), "
+                             "which these evaluation keys do not hold (a bundle saved with key_tiers=\"circuit\" covers the output form of "
+                             "the module's Configuration)")
         out = roles.evaluate_encrypted(self._session("execute", batch), self._keys, cts, dim, packed, tier, pack_key)
         if packed == "ring":
             return pack_response(self.spec.digest, batch, FORM_RING, out.to_bytes())
@@ -739,8 +784,11 @@ class Server(_Role):
         keys, D = self._keys, self._keys.D
         entries = _unpack_key_check(KCQ_MAGIC, blob, self.spec.digest, "this server's bundle is")
         out = []
+        held = keys.tiers
         for tier, w, rows in entries:
             dim = rows.shape[1] - 1
+            if 0 <= tier < keys.params.n_tiers and not (held.bsk >> tier) & 1:
+                raise ValueError(f"key check: these evaluation keys hold no bootstrap key of tier {tier} ({self.spec.param_set.tiers[tier].name})")
             if not 0 <= tier < keys.params.n_tiers or dim > D or w >= keys.tier(tier).logN:
                 raise ValueError(f"key check: tier {tier}, {w} table bits, rows of {dim} mask words do not fit these keys")
             full = np.zeros((rows.shape[0], D + 1), np.uint64)
@@ -804,7 +852,7 @@ def _cmd_save(a):
     qm = compile_fn(model, calib, rounding_threshold_bits=rtb, n_bits=a.n_bits, p_error=a.p_error, configuration=cfg, tier_policy=a.tier_policy,
                     pool_policy=a.pool_policy, **kw)
     cls = None if model.classifier_w is None else (model.classifier_w, model.classifier_b)
-    for p in save(qm, a.out, classifier=cls):
+    for p in save(qm, a.out, classifier=cls, key_tiers=a.key_tiers):
         print(f"wrote {p} ({os.path.getsize(p)} bytes)")
 
 
@@ -930,6 +978,8 @@ def _parser():
     p.add_argument("--rounding_method", default="exact", choices=["exact", "approximate"])
     p.add_argument("--tier_policy", default="exact", choices=["exact", "p_error"])
     p.add_argument("--pool_policy", default="coarse", choices=["coarse", "exact"])
+    p.add_argument("--key_tiers", default="all", choices=["all", "circuit"],
+                   help="circuit: the bundle records the tiers the circuit reads, and the client makes and ships only their evaluation keys")
     p.add_argument("--seed", default=42, type=int, help="seed of the synthetic calibration images")
     p.add_argument("--test_params", action="store_true", help="the tiny, INSECURE test catalogue (trying the flow only)")
     p = cmd("keygen", _cmd_keygen, "client: make a key, write the key file and the exports")

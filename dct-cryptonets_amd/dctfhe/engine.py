@@ -7,7 +7,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from ._lib import MarginStats, MemPlan, Params, Stats, Tier, Timing, check, ptr
+from ._lib import KeyTiers, MarginStats, MemPlan, Params, Stats, Tier, Timing, check, ptr
 from .wire import PackedCiphertexts, PackedRing, PublicInputs, SeededCiphertexts, _as_u8, seed_bytes  # noqa: F401 (re-exported)
 
 
@@ -197,12 +197,63 @@ class Context:
             self.h = C.c_void_p()
 
 
+def key_tiers_arg(tiers):
+    """a tier selection as the library's struct: a compile.KeyTierSelection (.bsk_mask / .ksk_mask), a KeyTiers of either binding or a
+    (bsk, ksk) pair of bit masks"""
+    bsk, ksk = (tiers.bsk_mask, tiers.ksk_mask) if hasattr(tiers, "bsk_mask") else (tiers.bsk, tiers.ksk) if hasattr(tiers, "bsk") else tiers
+    return KeyTiers(int(bsk), int(ksk))
+
+
+def key_tiers_all(params):
+    """every key of a parameter set (dctfhe_key_tiers_all; host-only)"""
+    t = KeyTiers()
+    check(_lib.load().dctfhe_key_tiers_all(C.byref(params), C.byref(t)))
+    return t
+
+
+def key_tiers_close(params, tiers):
+    """the closed selection: the owner of the key-switch key of every tier that bootstraps is added (dctfhe_key_tiers_close; host-only).
+    Refused: a bit at or beyond n_tiers, a ksk bit on a tier that shares its key-switch key."""
+    t = key_tiers_arg(tiers)
+    check(_lib.load().dctfhe_key_tiers_close(C.byref(params), C.byref(t)))
+    return t
+
+
+def key_tiers_for_circuit(blob, params):
+    """the closed selection a circuit blob needs under `params` (dctfhe_key_tiers_for_circuit; host-only)"""
+    blob, t = bytes(blob), KeyTiers()
+    check(_lib.load().dctfhe_key_tiers_for_circuit(blob, len(blob), C.byref(params), C.byref(t)))
+    return t
+
+
+def key_tiers_blob_bytes(params, tiers, compressed):
+    """bytes of the full-form (compressed False) or compressed evaluation-key blob under a closed selection (host-only)"""
+    n = C.c_size_t()
+    check(_lib.load().dctfhe_key_tiers_blob_bytes(C.byref(params), C.byref(key_tiers_arg(tiers)), int(bool(compressed)), C.byref(n)))
+    return n.value
+
+
 def blob_params(blob):
     """the parameters in an evaluation-key blob's header (magic, version, total_bytes, params: both the full and the compressed form)"""
     blob = _as_u8(blob)
     if blob.size < 16 + C.sizeof(Params):
         raise _lib.DctfheError("evaluation-key blob too short")
     return Params.from_buffer_copy(blob[16:16 + C.sizeof(Params)].tobytes())
+
+
+def blob_key_tiers(blob):
+    """(bsk mask, ksk mask) of an evaluation-key blob of any of the four kinds, read from its header alone (no library call, no check:
+    dctfhe_eval_keys_import validates).  The unpruned versions hold every key of their parameters."""
+    blob = _as_u8(blob)
+    params = blob_params(blob)
+    magic, version = struct.unpack_from("<4sI", blob[:8].tobytes())
+    pruned, at = {b"DEVK": (4, 16 + C.sizeof(Params)), b"DEVC": (2, 16 + C.sizeof(Params) + 32)}.get(magic, (None, 0))
+    if version == pruned:
+        if blob.size < at + 8:
+            raise _lib.DctfheError("evaluation-key blob too short for its tier selection")
+        return struct.unpack_from("<II", blob[at:at + 8].tobytes())
+    n = max(0, min(int(params.n_tiers), _lib.MAX_TIERS))
+    return (1 << n) - 1, sum(1 << i for i in range(n) if params.tiers[i].ksk_share < 0)
 
 
 class PackKey:
@@ -304,9 +355,13 @@ class ClientKey:
     def tier(self, i):
         return self.params.tiers[i]
 
-    def generate_eval_keys(self):
+    def generate_eval_keys(self, tiers=None):
+        """tiers: a tier selection (key_tiers_arg); None: every tier.  Unselected keys are not generated at all."""
         h = C.c_void_p()
-        check(self.L.dctfhe_eval_keys_generate(self.h, C.byref(h)))
+        if tiers is None:
+            check(self.L.dctfhe_eval_keys_generate(self.h, C.byref(h)))
+        else:
+            check(self.L.dctfhe_eval_keys_generate_tiers(self.h, C.byref(key_tiers_arg(tiers)), C.byref(h)))
         return EvalKeys(self.ctx, self.params, h)
 
     def export_secret(self):
@@ -354,12 +409,14 @@ class ClientKey:
         check(self.L.dctfhe_encrypt_seeded(self.ctx.h, self.h, ptr(phases), phases.size, key, C.byref(stream), ptr(bodies)))
         return SeededCiphertexts(key.raw, stream.value, self.D, self.input_dim, bodies)
 
-    def export_eval_keys_compressed(self):
-        """the evaluation keys as a compressed blob (bodies + the public mask key; EvalKeys.from_blob reads it)"""
+    def export_eval_keys_compressed(self, tiers=None):
+        """the evaluation keys as a compressed blob (bodies + the public mask key; EvalKeys.from_blob reads it).
+        tiers: a tier selection (key_tiers_arg); None: every tier, today's bytes"""
+        sel = None if tiers is None else C.byref(key_tiers_arg(tiers))
         n = C.c_size_t()
-        check(self.L.dctfhe_eval_keys_export_compressed(self.h, None, 0, C.byref(n)))
+        check(self.L.dctfhe_eval_keys_export_compressed_tiers(self.h, sel, None, 0, C.byref(n)))
         out = np.empty(n.value, np.uint8)
-        check(self.L.dctfhe_eval_keys_export_compressed(self.h, ptr(out), out.size, C.byref(n)))
+        check(self.L.dctfhe_eval_keys_export_compressed_tiers(self.h, sel, ptr(out), out.size, C.byref(n)))
         return out
 
     def decrypt(self, cts, dim=None):
@@ -434,7 +491,15 @@ class EvalKeys:
         check(ctx.L.dctfhe_eval_keys_import(ctx.h, ptr(blob), blob.size, C.byref(h)))
         return cls(ctx, params, h)
 
+    @property
+    def tiers(self):
+        """the tier selection this handle holds (KeyTiers: bsk and ksk bit masks over the tier indices)"""
+        t = KeyTiers()
+        check(self.L.dctfhe_eval_keys_tiers(self.h, C.byref(t)))
+        return t
+
     def to_blob(self):
+        """the full-form blob; of a pruned handle, a pruned blob"""
         n = C.c_size_t()
         check(self.L.dctfhe_eval_keys_export(self.h, None, 0, C.byref(n)))
         out = np.empty(n.value, np.uint8)
@@ -553,10 +618,15 @@ class Keys:
     """Both halves in one process (tests, benchmarks, the reference's single-machine flow homomorphic_eval.py:313-317):
     `.client` (ClientKey) and `.eval` (EvalKeys); every method is the half's own."""
 
-    def __init__(self, ctx, params, seed=None, client=None, evalk=None):
+    def __init__(self, ctx, params, seed=None, client=None, evalk=None, tiers=None):
         self.ctx, self.params = ctx, params
         self.client = client if client is not None else ClientKey(ctx, params, seed)
-        self.eval = evalk if evalk is not None else self.client.generate_eval_keys()
+        self.eval = evalk if evalk is not None else self.client.generate_eval_keys(tiers)
+
+    @classmethod
+    def generate(cls, ctx, params, seed=None, tiers=None):
+        """both halves from a seed; tiers: a tier selection for the evaluation keys (key_tiers_arg; None: every tier)"""
+        return cls(ctx, params, seed=seed, tiers=tiers)
 
     @property
     def D(self):
@@ -570,7 +640,7 @@ class Keys:
                     "encrypt_seeded", "export_eval_keys_compressed", "decrypt_packed", "margin_probe", "export_pack_key", "decrypt_ring",
                     "export_public_key"):
             return getattr(self.client, name)
-        if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "keyswitch_sum", "modswitch_center", "pbs", "pbs_rows", "round_lut", "round_lut_split", "bench_pbs", "to_blob"):
+        if name in ("export_ksk", "keyswitch", "keyswitch_pack", "keyswitch_diff", "keyswitch_sum", "modswitch_center", "pbs", "pbs_rows", "round_lut", "round_lut_split", "bench_pbs", "to_blob", "tiers"):
             return getattr(self.eval, name)
         raise AttributeError(name)
 

@@ -153,9 +153,14 @@ class HostClientKey:
         check(self.L.dctfhe_host_decrypt_ring(self.h, ring.logN, ptr(ring.words), len(ring), ptr(out)))
         return out
 
-    def export_eval_keys_compressed(self):
-        """the evaluation keys as a compressed blob (bodies + the public mask key; engine.EvalKeys.from_blob reads it on the server)"""
-        return _export(self.L.dctfhe_host_eval_keys_export_compressed, self.h)
+    def export_eval_keys_compressed(self, tiers=None):
+        """the evaluation keys as a compressed blob (bodies + the public mask key; engine.EvalKeys.from_blob reads it on the server).
+        tiers: a tier selection -- a compile.KeyTierSelection, a KeyTiers of either binding or a (bsk mask, ksk mask) pair; None: every
+        tier.  The library closes it."""
+        if tiers is None:
+            return _export(self.L.dctfhe_host_eval_keys_export_compressed, self.h)
+        bsk, ksk = (tiers.bsk_mask, tiers.ksk_mask) if hasattr(tiers, "bsk_mask") else (tiers.bsk, tiers.ksk) if hasattr(tiers, "bsk") else tiers
+        return _export(self.L.dctfhe_host_eval_keys_export_compressed_tiers, self.h, C.byref(_lib_client.KeyTiers(int(bsk), int(ksk))))
 
     def export_pack_key(self, spec):
         """the packing key for ring-packed results as its seeded blob; spec: params.PackSpec"""

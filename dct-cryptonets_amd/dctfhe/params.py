@@ -83,6 +83,69 @@ class ParamSet:
         raise ValueError(f"no tier for a table of {w} input bits")
 
 
+# ------------------------------------------------------------------------------------------ tier selections
+def ksk_owner(ps, tier):
+    """the tier whose key-switch key `tier` switches with: the end of its share chain"""
+    while ps.tiers[tier].ksk_share >= 0:
+        tier = ps.tiers[tier].ksk_share
+    return tier
+
+
+@dataclass(frozen=True)
+class KeyTierSelection:
+    """A tier selection of one ParamSet by name and as the library's bit masks (include/dctfhe.h dctfhe_key_tiers): bsk, the tiers whose
+    bootstrap key is present; ksk, the tiers whose OWN key-switch key is present (a tier that shares has none)."""
+    bsk: frozenset
+    ksk: frozenset
+    bsk_mask: int
+    ksk_mask: int
+
+    @classmethod
+    def from_masks(cls, ps, bsk_mask, ksk_mask):
+        names = lambda m: frozenset(t.name for i, t in enumerate(ps.tiers) if (m >> i) & 1)
+        if (bsk_mask | ksk_mask) >> len(ps.tiers):
+            raise ValueError(f"tier selection names a tier at or beyond the {len(ps.tiers)} tiers of the parameter set")
+        return cls(names(bsk_mask), names(ksk_mask), int(bsk_mask), int(ksk_mask))
+
+    @classmethod
+    def all(cls, ps):
+        return cls.from_masks(ps, (1 << len(ps.tiers)) - 1, sum(1 << i for i, t in enumerate(ps.tiers) if t.ksk_share < 0))
+
+    def is_all(self, ps):
+        return self == KeyTierSelection.all(ps)
+
+    def covers(self, other):
+        return not (other.bsk_mask & ~self.bsk_mask) and not (other.ksk_mask & ~self.ksk_mask)
+
+    def missing(self, other):
+        """what `other` asks for and this selection lacks, as text (for refusals)"""
+        parts = [f"bootstrap key of {n}" for n in sorted(other.bsk - self.bsk)] + [f"key-switch key of {n}" for n in sorted(other.ksk - self.ksk)]
+        return ", ".join(parts)
+
+
+EVAL_BLOB_HEADER = 16 + 24 + 56 * 12      # u32 magic, u32 version, u64 total bytes, the dctfhe_params (12 tier slots)
+
+
+def key_section_bytes(ps, t):
+    """bytes of one tier's sections in the two evaluation-key blob forms (include/dctfhe.h): the Fourier bootstrap key and the whole
+    key-switch key; the compressed form's standard-domain bodies"""
+    blocks = 3 * t.n // 2 if t.unroll == 2 else t.n
+    own = t.ksk_share < 0
+    return dict(bsk_full_bytes=blocks * (t.k + 1) ** 2 * t.l * (t.N // 2) * 16, bsk_compressed_bytes=blocks * (t.k + 1) * t.l * t.N * 8,
+                ksk_full_bytes=ps.D * t.lk * (t.n + 1) * 8 if own else 0, ksk_compressed_bytes=ps.D * t.lk * 8 if own else 0)
+
+
+def key_blob_bytes(ps, sel, compressed):
+    """bytes of an evaluation-key blob under a closed selection: header (+ the 32-byte public generator key in the compressed form), the
+    two masks unless everything is selected, the kept sections (dctfhe_key_tiers_blob_bytes is the library's figure)"""
+    n = EVAL_BLOB_HEADER + (32 if compressed else 0) + (0 if sel.is_all(ps) else 8)
+    form = "compressed" if compressed else "full"
+    for i, t in enumerate(ps.tiers):
+        b = key_section_bytes(ps, t)
+        n += b[f"ksk_{form}_bytes"] * ((sel.ksk_mask >> i) & 1) + b[f"bsk_{form}_bytes"] * ((sel.bsk_mask >> i) & 1)
+    return n
+
+
 # ------------------------------------------------------------------------------------------ variances
 def ks_limbs(t):
     """byte limbs kept per key-switch-key word (csrc/dctfhe.hip ks_limbs): the key lives on the 2^-(8 limbs) torus grid"""

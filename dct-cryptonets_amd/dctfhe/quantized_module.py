@@ -33,7 +33,7 @@ class Configuration:
 
     def __init__(self, show_progress=False, progress_tag=False, progress_title="", compress_input_ciphertexts=False,
                  compress_evaluation_keys=False, compress_output_ciphertexts=False, result_packing_spec=None, public_key_inputs=False,
-                 public_input_spec=None, shard_image=False, shard_pool=False, device_memory_budget_gb=None, **kwargs):
+                 public_input_spec=None, shard_image=False, shard_pool=False, device_memory_budget_gb=None, evaluation_key_tiers="all", **kwargs):
         self.show_progress, self.progress_tag, self.progress_title = show_progress, progress_tag, progress_title
         # Concrete's switches: fhe="execute" ships seeded inputs (bodies + a public mask key; include/dctfhe.h dctfhe_encrypt_seeded),
         # export_evaluation_keys() the compressed blob (dctfhe_eval_keys_export_compressed).  Both off by default.
@@ -72,6 +72,12 @@ class Configuration:
             raise ValueError("device_memory_budget_gb must be positive (None: no budget)")
         if self.device_memory_budget_gb is not None and self.shard_image:
             raise ValueError("device_memory_budget_gb and shard_image exclude each other: a budgeted session stays unsharded")
+        # dctfhe addition: "circuit" makes, exports and loads only the evaluation keys the compiled circuit reads (include/dctfhe.h TIER
+        # SELECTIONS; CompiledCircuit.key_tiers), plus the key-switch key that packs the results in the form compress_output_ciphertexts
+        # names.  "all" (default): every tier of the catalogue, the keys and blobs of before.  No output word depends on the choice.
+        if evaluation_key_tiers not in ("all", "circuit"):
+            raise ValueError(f"evaluation_key_tiers {evaluation_key_tiers!r} (all or circuit)")
+        self.evaluation_key_tiers = evaluation_key_tiers
         self.extra = kwargs
 
     @property
@@ -216,7 +222,17 @@ class QuantizedModule:
             for k in [k for k in self._sessions if k[0] == "execute"]:
                 self._sessions.pop(k).close()
             self._keys.close()
-        self._keys = Keys(ctx, P.to_c_params(self.compiled.param_set), seed)
+        self._keys = Keys(ctx, P.to_c_params(self.compiled.param_set), seed, tiers=self.key_tiers())
+
+    def key_tiers(self):
+        """the tier selection of this module's evaluation keys: None (every tier) under Configuration(evaluation_key_tiers="all"), under
+        "circuit" CompiledCircuit.key_tiers for the configuration's output form"""
+        if self.configuration.evaluation_key_tiers != "circuit":
+            return None
+        form = self.configuration.compress_output_ciphertexts
+        if form == "ring":
+            return self.compiled.key_tiers("ring", self.configuration.result_packing_spec)
+        return self.compiled.key_tiers("rows" if form else None)
 
     def _session(self, mode, batch):
         key = (mode, batch)
@@ -345,13 +361,18 @@ class QuantizedModule:
         if compressed:
             if not isinstance(self._keys, Keys):
                 raise RuntimeError("compressed evaluation keys are made by the client (its secret key); this module holds evaluation keys only")
-            return self._keys.client.export_eval_keys_compressed()
-        return self._keys.eval.to_blob()
+            return self._keys.client.export_eval_keys_compressed(self.key_tiers())
+        return self._keys.eval.to_blob()      # the handle's own selection (keygen made it with key_tiers())
 
     def load_evaluation_keys(self, blob):
         """server side: evaluate with keys a client generated elsewhere (either blob form: full or compressed); this module can
         then run `evaluate_encrypted` but can neither encrypt nor decrypt"""
-        from .engine import EvalKeys
+        from .engine import EvalKeys, blob_key_tiers
+        need = self.key_tiers()
+        if need is not None:      # refuse before anything is imported
+            held = cc.KeyTierSelection.from_masks(self.compiled.param_set, *blob_key_tiers(blob))
+            if not held.covers(need):
+                raise ValueError(f"the evaluation keys do not cover this circuit: they lack the {held.missing(need)}")
         ctx = self._context()
         for k in [k for k in self._sessions if k[0] == "execute"]:
             self._sessions.pop(k).close()

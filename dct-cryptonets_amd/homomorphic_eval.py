@@ -64,6 +64,9 @@ def parse_args():
     e.add_argument("--compress_outputs", default="none", choices=["none", "rows", "ring"],
                    help="results on the way back: full rows; rows: key-switched 16-bit rows; ring: up to 2048 results in one GLWE "
                         "ciphertext (the client's packing key is made after keygen and loaded)")
+    e.add_argument("--key_tiers", default="all", choices=["all", "circuit"],
+                   help="all: evaluation keys for every tier of the catalogue; circuit: only the tiers the compiled circuit reads (and the "
+                        "key that packs the results under --compress_outputs) -- fewer keys to make and hold, the same outputs")
     e.add_argument("--public_key_inputs", action="store_true",
                    help="encrypt the inputs without the secret key, through a public key made after keygen; the GPU extracts the rows")
     e.add_argument("--shard_image", action="store_true",
@@ -143,7 +146,7 @@ def main():
     configuration = Configuration(show_progress=False, progress_tag=True, progress_title="Evaluation: ",
                                   compress_output_ciphertexts=params.compress_outputs, public_key_inputs=params.public_key_inputs,
                                   shard_image=params.shard_image, shard_pool=params.shard_pool,
-                                  device_memory_budget_gb=params.device_memory_budget_gb)
+                                  device_memory_budget_gb=params.device_memory_budget_gb, evaluation_key_tiers=params.key_tiers)
     key_seed = None
     if params.shard_image and "RANK" in os.environ:      # one rank per GPU; every rank needs the same keys: rank 0's seed travels
         import torch.distributed as dist

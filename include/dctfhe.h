@@ -154,8 +154,46 @@ int dctfhe_eval_keys_import(dctfhe_ctx* ctx, const void* buf, size_t size, dctfh
  * for bit; the rows p < k are shipped in BODY FORM (a, b - s_i g S_p): the same phase and noise draw, another ciphertext.  About a
  * quarter of dctfhe_eval_keys_export's size for the default parameters.  buf == NULL: size query. */
 int dctfhe_eval_keys_export_compressed(dctfhe_client_key* client, void* buf, size_t capacity, size_t* size);
-/* test view: the standard-domain bootstrap key [blocks][(k+1)l][k+1][N] of `tier` as import rebuilds it from a compressed blob */
+/* test view: the standard-domain bootstrap key [blocks][(k+1)l][k+1][N] of `tier` as import rebuilds it from a compressed blob
+ * (refused for a tier whose bootstrap key a pruned blob does not hold) */
 int dctfhe_eval_keys_decompress_bsk(dctfhe_ctx* ctx, const void* buf, size_t size, int tier, uint64_t* out);
+
+/* TIER SELECTIONS: evaluation keys sized to a circuit.  A catalogue is one fixed list of tiers and a compiled
+ * circuit reads only some of their keys; a selection, carried BESIDE the parameters (tier indices are part of the circuit blob and of every
+ * key stream id, so the parameters themselves cannot shrink), says which keys are made, exported, imported and held.
+ *   bsk bit t: the bootstrap key of tier t is present.
+ *   ksk bit t: the key-switch key that tier t OWNS is present.  A tier with ksk_share >= 0 owns none: it needs the ksk bit of the owner at
+ *              the end of its share chain.
+ * CLOSING a selection sets the owner's ksk bit for every tier whose bsk bit is set.  Refused: a bit at or beyond n_tiers, a ksk bit on a
+ * tier that shares.  (A dropped bootstrap key whose key-switch key stays is the ordinary case: T6 next to T6a, which switches with T6's.)
+ * Everything selected -- dctfhe_key_tiers_all, and a NULL selection wherever one is taken -- is what the library did before selections
+ * existed: the same keys, the same blobs byte for byte.  The kept keys of any other selection are word for word those of the full set from
+ * the same seed (a key's draws depend on its tier index and nothing else), and the server draws nothing at random, so a run under pruned
+ * keys produces the output ciphertext words of the run under full keys.
+ * An absent key is not generated, transformed or allocated.
+ * Blobs: everything selected writes the version of each form documented above.  Any other selection writes the NEXT version of that form
+ * ('DEVK' version 4, 'DEVC' version 2): the two masks (u32 bsk, u32 ksk) follow the header -- in the compressed form the public generator
+ * key -- then the kept sections in tier order.  dctfhe_eval_keys_import reads all four kinds; it checks the masks before it sizes
+ * anything (a closed selection within n_tiers, not everything) and the total size against them.
+ * Refusals: every entry point that reads a key the handle lacks returns -1 before it allocates, copies or launches; the message names the
+ * tier and says "bootstrap key" or "key-switch key".  dctfhe_session_create names the first missing tier and an op that needs it.
+ * dctfhe_modswitch_center asks for the bootstrap key of its tier (it rounds to that bootstrap's levels).  dctfhe_margin_probe takes a client
+ * key, which holds no selection, and dctfhe_session_set_audit a session, whose keys dctfhe_session_create has already checked.
+ * all / close / for_circuit / blob_bytes run on the host without a GPU. */
+typedef struct { uint32_t bsk, ksk; } dctfhe_key_tiers;
+int dctfhe_key_tiers_all(const dctfhe_params* params, dctfhe_key_tiers* out);
+int dctfhe_key_tiers_close(const dctfhe_params* params, dctfhe_key_tiers* io);
+/* the closed selection of a circuit blob: every tier an op bootstraps on (rounding steps, table tiers, the second tier of a split site, the
+ * parity bootstrap, max-pool tiers) and the owner of every key-switch key an op switches with -- exactly the tiers whose pbs_count /
+ * ks_count in dctfhe_circuit_stats is positive.  Refused: a circuit that names a tier the parameters lack. */
+int dctfhe_key_tiers_for_circuit(const void* blob, size_t size, const dctfhe_params* params, dctfhe_key_tiers* out);
+/* bytes of dctfhe_eval_keys_export (compressed = 0) or dctfhe_eval_keys_export_compressed (!= 0) under a CLOSED selection */
+int dctfhe_key_tiers_blob_bytes(const dctfhe_params* params, const dctfhe_key_tiers* tiers, int compressed, size_t* out);
+/* tiers == NULL: everything.  The selection is closed first. */
+int dctfhe_eval_keys_generate_tiers(dctfhe_client_key* client, const dctfhe_key_tiers* tiers, dctfhe_eval_keys** out);
+int dctfhe_eval_keys_export_compressed_tiers(dctfhe_client_key* client, const dctfhe_key_tiers* tiers, void* buf, size_t capacity, size_t* size);
+/* the selection a handle holds (generated or imported); dctfhe_eval_keys_export of a pruned handle writes a pruned blob */
+int dctfhe_eval_keys_tiers(dctfhe_eval_keys* eval, dctfhe_key_tiers* out);
 
 /* test / client views */
 int dctfhe_client_key_export_secret(dctfhe_client_key* client, uint8_t* big_key /* D */, uint8_t* small_key /* n_max */);

@@ -66,6 +66,9 @@ int dctfhe_host_decrypt_ring(dctfhe_host_client_key* client, int logN, const uin
 /* dctfhe_eval_keys_export_compressed: the blob dctfhe_eval_keys_import reads (magic 'DEVC').  The heavy part: per bootstrap-key row a
  * negacyclic product of the mask polynomials with the binary GLWE key, shift-and-add over rows in parallel. */
 int dctfhe_host_eval_keys_export_compressed(dctfhe_host_client_key* client, void* buf, size_t capacity, size_t* size);
+/* the same under a tier selection (dctfhe.h TIER SELECTIONS; NULL: everything, the bytes of the call above): the selection is closed
+ * first, a pruned blob is 'DEVC' version 2 with the two masks behind the public generator key, and only the kept sections are computed. */
+int dctfhe_host_eval_keys_export_compressed_tiers(dctfhe_host_client_key* client, const dctfhe_key_tiers* tiers, void* buf, size_t capacity, size_t* size);
 int dctfhe_host_pack_key_export(dctfhe_host_client_key* client, int logN, int l_p, int beta_p, double sigma_p, void* buf, size_t capacity, size_t* size);
 int dctfhe_host_public_key_export(dctfhe_host_client_key* client, int logN, double sigma, void* buf, size_t capacity, size_t* size);
 

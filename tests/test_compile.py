@@ -38,6 +38,9 @@ def test_integer_circuit_reproduces_compile_time_values(tiny):
     assert not overflow
     vals = (out + (np.uint64(1) << np.uint64(c.e_out - 1))).view(np.int64) >> np.int64(c.e_out)
     assert vals.min() >= -8 and vals.max() <= 7 and len(np.unique(vals)) > 3
+    # ... and they ARE the compile-time integer forward, row for row of the calibration batch
+    assert vals.shape == c.calib_out.shape == (calib.shape[0], c.n_out())
+    assert np.array_equal(vals, c.calib_out), np.argwhere(vals != c.calib_out)[:5]
 
 
 def test_rounding_semantics_round_half_up():

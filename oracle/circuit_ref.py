@@ -50,13 +50,15 @@ def max_pool_words(x, k, s, p):
     out-of-range taps ignored)"""
     B, C, H, W = x.shape
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
-    xs = x.view(np.int64)
-    out = np.empty((B, C, Ho, Wo), np.int64)
-    for yo in range(Ho):
-        ys = [y for y in range(yo * s - p, yo * s - p + k) if 0 <= y < H]
-        for xo in range(Wo):
-            xs_ = [xx for xx in range(xo * s - p, xo * s - p + k) if 0 <= xx < W]
-            out[:, :, yo, xo] = xs[:, :, ys][:, :, :, xs_].max(axis=(2, 3))
+    # tap by tap over strided views of the input padded with the most negative word: an out-of-range tap never wins, and with
+    # p <= k / 2 every window holds an in-range tap (tests/test_grid_seams_host.py holds this to the window-by-window definition)
+    xp = np.full((B, C, H + 2 * p, W + 2 * p), np.iinfo(np.int64).min, np.int64)
+    xp[:, :, p:p + H, p:p + W] = np.ascontiguousarray(x, np.uint64).view(np.int64)
+    out = None
+    for ky in range(k):
+        for kx in range(k):
+            tap = xp[:, :, ky:ky + (Ho - 1) * s + 1:s, kx:kx + (Wo - 1) * s + 1:s]
+            out = tap.copy() if out is None else np.maximum(out, tap, out=out)
     return out.view(np.uint64)
 
 

@@ -15,6 +15,38 @@ def negamul_binary(K, u):
     return out
 
 
+def draws(key32, call, first, n, sigma, ft=np.float64):
+    """what call `call` of an encryptor whose generator key is `key32` draws at x in [first, first + n) (include/dctfhe.h, "Randomness"):
+    u[x] the top bit of generator word (key, 3 call, x), e1[x] the Gaussian draw (key, 3 call + 1, x), e2[x] the draw (key, 3 call + 2, x)
+    -> (u uint8, e1 int64, e2 int64), each of n values.  A range is made on its own (`first`): the generator is counter-based.  The caller
+    cuts e1 at groups N_e and e2 at count.  ft: the float type of the Gaussian (tests/simulate_ref.py gauss, the draw of the library)"""
+    import simulate_ref as R
+    x = np.arange(first, first + n, dtype=np.uint64)
+    u = (R.words_at(None, 3 * call, x, key32) >> U(63)).astype(np.uint8)
+    e1 = R.gauss(None, 3 * call + 1, x, sigma, ft, key=key32)
+    e2 = R.gauss(None, 3 * call + 2, x, sigma, ft, key=key32)
+    return u, e1, e2
+
+
+def draws_near_a_tie(key32, call, first, n, sigma):
+    """[x] in the range whose e1 or e2, before the final rounding to a torus word, lies so close to a half-integer that the last bit of
+    a math library could move it: within G = 256 times the largest |float64 - long double| of the unrounded draws of the range (the
+    guard of tests/simulate_ref.py, in units of 2^-64; at sigma = 2^-48 a draw is some 2^16 units and G some 2^-28 of one).  A
+    word-for-word comparison with the device asserts this empty for its seed first.  For |g sigma| < 1/2 only (asserted)"""
+    import simulate_ref as R
+    x = np.arange(first, first + n, dtype=np.uint64)
+    close = np.zeros(n, bool)
+    for stream in (3 * call + 1, 3 * call + 2):
+        y = [R._normal(None, stream, x, ft, key32) * ft(sigma) for ft in (np.float64, np.longdouble)]
+        assert (np.abs(y[1]) < 0.5).all()
+        y = [v * type(v[0])(18446744073709551616.0) for v in y]
+        G = 256 * float(np.abs(y[0].astype(np.longdouble) - y[1]).max())
+        assert G < 0.01, G
+        frac = y[1] - np.floor(y[1])
+        close |= np.asarray(np.abs(frac - np.longdouble(0.5)) < G)
+    return (first + np.flatnonzero(close)).tolist()
+
+
 def encrypt(rows, u, e1, e2, phases):
     """expanded key rows [2, N] (A, B), draws u [groups N] (0 / 1), e1 [groups N], e2 [count] (signed) and phases [count] -> the wire
     words: per group C_a = A u + e1 (N words), then C_b[i] = (B u)[i] + e2[i] + phase_i for its first m slots"""

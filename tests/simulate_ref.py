@@ -40,23 +40,23 @@ def sim_key(seed):
     return struct.pack("<8I", seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, 0x73696D75, 0, 0, 0, 0, 0)
 
 
-def words_at(seed, stream, idx):
-    """generator words `idx` (any integer array) of (key of `seed`, stream)"""
+def words_at(seed, stream, idx, key=None):
+    """generator words `idx` (any integer array) of (key of `seed`, stream); key: 32 generator-key bytes instead of a session's seed"""
     idx = np.asarray(idx, np.uint64)
     if idx.size == 0:
         return np.empty(idx.shape, np.uint64)
     lo, hi = int(idx.min()), int(idx.max())
     out = np.empty(hi - lo + 1, np.uint64)
-    rc = _lib().dctfhe_rng_host(sim_key(seed), C.c_uint64(stream), C.c_uint64(lo), C.c_size_t(out.size), out.ctypes.data_as(C.c_void_p))
+    rc = _lib().dctfhe_rng_host(sim_key(seed) if key is None else bytes(key), C.c_uint64(stream), C.c_uint64(lo), C.c_size_t(out.size), out.ctypes.data_as(C.c_void_p))
     assert rc == 0
     return out[(idx - U(lo)).astype(np.int64)]
 
 
-def _normal(seed, stream, idx, ft):
+def _normal(seed, stream, idx, ft, key=None):
     """the standard normal of draw `idx` in float type `ft`: Box-Muller on words 2 idx and 2 idx + 1.  cospi(2 u2) with the argument
     reduced exactly: 2 u2 is a multiple of 2^-52 in [0, 2), and so is every difference below, so only the last cos / sin rounds"""
     idx = np.asarray(idx, np.uint64)
-    w1, w2 = words_at(seed, stream, U(2) * idx), words_at(seed, stream, U(2) * idx + U(1))
+    w1, w2 = words_at(seed, stream, U(2) * idx, key), words_at(seed, stream, U(2) * idx + U(1), key)
     two53 = ft(9007199254740992.0)
     u1 = ((w1 >> U(11)).astype(ft) + ft(1)) / two53
     a = (w2 >> U(11)).astype(ft) / two53 * ft(2)          # [0, 2)
@@ -69,13 +69,13 @@ def _normal(seed, stream, idx, ft):
     return np.sqrt(ft(-2) * np.log(u1)) * c
 
 
-def gauss(seed, stream, idx, sigma, ft=np.float64, allow_wrap=False):
+def gauss(seed, stream, idx, sigma, ft=np.float64, allow_wrap=False, key=None):
     """draw `idx` of `stream`: rint(x 2^64) as int64 with x = g sigma reduced to [-1/2, 1/2] by x - rint(x) (the identity unless
     |g sigma| >= 1/2, which a caller must allow by name); 0 where sigma <= 0"""
     idx = np.asarray(idx, np.uint64)
     if sigma <= 0:
         return np.zeros(idx.shape, np.int64)
-    x = _normal(seed, stream, idx, ft) * ft(sigma)
+    x = _normal(seed, stream, idx, ft, key) * ft(sigma)
     assert allow_wrap or (np.abs(x) < 0.5).all(), "a draw of half the torus or more: |g sigma| >= 1/2"
     x = x - np.rint(x)
     assert (np.abs(x) < 0.5).all()
@@ -155,14 +155,20 @@ def pool_streams(run, op):
 
 def lut_site(x, p, r, w, shift, body_add, mode, tables, seed, stream, sigma, sigma2=0.0, trace=None, op=0):
     """x uint64 [B, C, H, W]; tables uint64 [ntab, 2^w] -> (outputs, overflow flag)"""
-    approx, split = mode == 1, mode in (2, 3)
     g = np.arange(x.size, dtype=np.uint64).reshape(x.shape)
+    return lut_elements(x, g, x.shape[2] * x.shape[3], p, r, w, shift, body_add, mode, tables, seed, stream, sigma, sigma2, trace, op)
+
+
+def lut_elements(x, g, hw, p, r, w, shift, body_add, mode, tables, seed, stream, sigma, sigma2=0.0, trace=None, op=0):
+    """the site on the words x of the elements numbered g in the whole tensor (uint64 arrays of one shape; a channel is hw elements):
+    table and draws go by g, so any range of a tensor can be evaluated on its own -> (outputs, overflow flag among these elements)"""
+    approx, split = mode == 1, mode in (2, 3)
     v = (x << U(shift)) + U(body_add % (1 << 64))
     if r > 0 and not (approx and sigma > 0):
         v = v + U(1 << (63 - p + r - 1))
     overflow = bool((v >> U(63)).any())
     idx = (v >> U(63 - w)) & U((1 << w) - 1)
-    hw, ntab = x.shape[2] * x.shape[3], tables.shape[0]
+    ntab = tables.shape[0]
     ti = ((g // U(hw)) % U(ntab)).astype(np.int64) if ntab > 1 else np.zeros(x.shape, np.int64)
     if sigma <= 0:
         return tables[ti, idx.astype(np.int64)], overflow
